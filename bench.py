@@ -11,6 +11,11 @@ top-k lists are all-gathered over RCCL and merged.  Corpus, queries and outputs 
 when the timed region starts.  Two batches are kept in flight (vf_index_search_begin / _end), as a
 serving loop would.  Rank 0 prints ONE JSON line.
 
+A plain run does only what that line's headline needs: set up, warm up, time the --steps steps and print the line (its roofline
+comes from HIP events of the timed steps themselves).  Everything described below -- the ordered pass, the CPU baseline, the
+oracle check of a multi-rank result and the other legs -- runs only with --full.  --dump-outputs DIR writes the last timed
+step's top-k ids and scores (inputs are seeded: two builds compare output for output).
+
 roofline: live HIP-event timing of the dominant kernel (the main scan: k_scan2r / k_scan2 -- whole-line LDS-DMA corpus loads -- for
 fp16 rows, k_scan for fp8 rows, k_scan_wide(8) above 128 queries; vf_search_stats.scan_kernel names it) inside the library, on the
 stream it runs on (vf_index_profile); algorithmic bytes = rows scanned x (d*2 + 4).  768-wide fp16 rows at every size (other rows
@@ -60,8 +65,8 @@ def parse():
     ap.add_argument("--no-rerank", action="store_true", help="skip every transformer leg (re-rank, embed, latency, llm, c4)")
     ap.add_argument("--no-llm", action="store_true", help="skip the gemma-2b-shape LLM re-ranker leg")
     ap.add_argument("--no-c4", action="store_true", help="skip the configs[3] end-to-end chain")
-    ap.add_argument("--no-startup", action="store_true", help="skip the corpus-file start-up leg of the default line")
-    ap.add_argument("--no-shard-legs", action="store_true", help="skip the configs[1] (c2) and 8-GPU-shard (shard8) legs of the default line")
+    ap.add_argument("--no-startup", action="store_true", help="skip the corpus-file start-up leg of the --full line at the default size")
+    ap.add_argument("--no-shard-legs", action="store_true", help="skip the configs[1] (c2) and 8-GPU-shard (shard8) legs of the --full line at the default size")
     ap.add_argument("--verify", action="store_true",
                     help="after the timed run push one bucket through the exchange path and compare the merged result "
                          "with per-batch searches (one rank) / with the CPU oracle run per shard (several ranks: on by default)")
@@ -86,6 +91,13 @@ def parse():
     ap.add_argument("--rerank-shape", default="xlmr-base", help="cross-encoder shape (tools/bench_rerank.py SHAPES)")
     ap.add_argument("--rerank-pairs", type=int, default=100)
     ap.add_argument("--rerank-tokens", type=int, default=512)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: the ordered-scan roofline pass, the oracle check of the merged "
+                         "result (N > 1), the host-buffer entry, the re-rank / embed / LLM / configs[3] / configs[4] legs, the CPU "
+                         "baseline, the start-up leg and the c2 / shard8 child runs (each still subject to its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's result (the top-k ids and scores a caller receives) "
+                         "to DIR/topk_ids.npy (float64) and DIR/topk_scores.npy (float32)")
     return ap.parse_args()
 
 
@@ -532,7 +544,7 @@ def small_shard_leg(rows, tag, with_exchange, steps=200, warm=20):
     profiles/r05_legs_in_process.log, r05_hw_queues.log).  The parent keeps its corpus in HBM meanwhile (17 of 288 GB); it launches
     nothing while the child runs."""
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--rows", str(rows), "--steps", str(steps), "--warmup", str(warm),
-           "--no-rerank", "--no-cpu-baseline", "--no-shard-legs"]
+           "--full", "--no-rerank", "--no-cpu-baseline", "--no-shard-legs"]
     env = dict(os.environ)
     if with_exchange:
         cmd.append("--verify")
@@ -1068,6 +1080,13 @@ def main():
         fence()
         elapsed = time.perf_counter() - t0
     import numpy as np
+    last_step = None
+    if args.dump_outputs and rank == 0:   # copied now: later passes reuse the result buffers
+        li, ls = merged[0]
+        if exchange:                      # the merged bucket holds E batches; the last step's batch sits at (steps - 1) % E
+            e = (args.steps - 1) % E
+            li, ls = li[e * args.batch:(e + 1) * args.batch], ls[e * args.batch:(e + 1) * args.batch]
+        last_step = (li.cpu().numpy().astype(np.float64), ls.cpu().numpy().astype(np.float32))
     gaps = np.diff(np.asarray([t0] + stamps)) * 1e3 if len(stamps) == args.steps else None
     p50_step_ms = None if gaps is None or len(gaps) < 3 else float(np.median(gaps[1:]))   # (the first gap holds the pipeline fill)
     torch.cuda.current_stream(device).wait_stream(side)
@@ -1081,10 +1100,11 @@ def main():
     # start on the CUs the previous one has finished with, so an event bracket around a launch contains the time it
     # shares the chip with its predecessor.  The roofline figure of the kernel is then taken in a second, ORDERED pass of
     # the same workload (scans serialised by events, as the timed region of the large-shard case runs anyway).
-    prof_timed = None
-    if stats.get("scans_overlap") and os.environ.get("VF_BENCH_NO_ISOLATED") == "1":
-        prof_timed = prof     # (profiling runs: the trace then holds the pipelined loop only; the isolated figure is absent from the line)
+    prof_timed, ordered_pass = None, False
+    if stats.get("scans_overlap") and (not args.full or os.environ.get("VF_BENCH_NO_ISOLATED") == "1"):
+        prof_timed = prof     # (plain and profiling runs: the pipelined loop only; the isolated figure is absent from the line)
     elif stats.get("scans_overlap"):
+        ordered_pass = True
         prof_timed = prof
         forced = stats.get("scan_kernel") == 5     # k_scan2r is the default only where scans overlap: name it for the ordered pass
         if forced:
@@ -1101,7 +1121,7 @@ def main():
         if forced:
             index.set_option("scan_impl", 2)
     verify_info, merged_equals_direct = None, None
-    if exchange and (args.verify or (world > 1 and not args.no_verify)):
+    if exchange and (args.verify or (world > 1 and args.full and not args.no_verify)):
         run(E)                      # exactly one full bucket: batches 0 .. E-1 of the query pool
         fence()
         mi, ms = merged[0]
@@ -1141,7 +1161,7 @@ def main():
     # queries copied in and the results copied out over PCIe, one call at a time (no overlap between calls).  Reported beside
     # `value`, never as it.
     host_entry = None
-    if world == 1 and not devs and rank == 0:
+    if args.full and world == 1 and not devs and rank == 0:
         try:
             qh = [q.cpu().numpy() for q in qpool]
             index.search(qh[0], args.k)
@@ -1158,13 +1178,13 @@ def main():
     # secondary legs: a failure here (environment, memory) must not take the main metric line down; it is reported in place
     rr_ms, rr_info, emb_info, rr_large, lat_info, llm_info, c4_info, c5_info = (None, None, None, None, None, None, None, None)
     texts_info, startup_info = None, None
-    if (world > 1 or (exchange and dist.is_initialized())) and not devs and not args.no_rerank:   # (the one-rank rehearsal takes it too)
+    if args.full and (world > 1 or (exchange and dist.is_initialized())) and not devs and not args.no_rerank:   # (the one-rank rehearsal takes it too)
         # N > 1: the re-rank leg is the data-parallel form (all ranks take part); the single-GPU legs are reported by the N = 1 run
         try:
             rr_ms, rr_info = rerank_p50_sharded(args, device)
         except Exception as e:  # noqa: BLE001
             rr_info = {"error": f"{type(e).__name__}: {e}"}
-    elif rank == 0 and not args.no_rerank:
+    elif args.full and rank == 0 and not args.no_rerank:
         try:
             rr_ms, rr_info = rerank_p50(args)
         except Exception as e:  # noqa: BLE001
@@ -1198,7 +1218,7 @@ def main():
             except Exception as e:  # noqa: BLE001
                 c4_info = {"error": f"{type(e).__name__}: {e}"}
         if world == 1 and not devs and args.corpus_dtype == "f16" and not args.no_c4 and (args.rows, args.dim) == (10_000_000, 768):
-            try:      # (the default line only: configs[4] at full size beside the headline)
+            try:      # (the --full line at the default size only: configs[4] at full size beside the headline)
                 c5_info = c5_leg(args, torch, vf, device)
             except Exception as e:  # noqa: BLE001
                 c5_info = {"error": f"{type(e).__name__}: {e}"}
@@ -1288,11 +1308,12 @@ def main():
                             measured_in=f"the timed region: consecutive launches OVERLAP on this shard size (CU split {stats.get('aux_cus', 0)}, "
                                         f"scans not ordered), so avg_launch_ms is the launch interval = makespan of the {n_l} timed launches "
                                         f"(first begin to last end, HIP events on the scan streams) / {n_l}; the per-launch event brackets "
-                                        f"average {prof_timed['scan_ms_total'] / n_l:.4f} ms because each contains its predecessor's tail",
-                            isolated_launch={"avg_launch_ms": round(iso_ms, 4), "achieved": round(iso_gbs, 1),
-                                             "frac": round(iso_gbs / HBM_PEAK_GBS, 4), "launches": prof["scan_launches"],
-                                             "what": "the same kernel in an ordered pass after the timed region (scans serialised by events, "
-                                                     "one launch per bracket, still on the scan partition's CUs)"})
+                                        f"average {prof_timed['scan_ms_total'] / n_l:.4f} ms because each contains its predecessor's tail")
+                if ordered_pass:
+                    roof["isolated_launch"] = {"avg_launch_ms": round(iso_ms, 4), "achieved": round(iso_gbs, 1),
+                                               "frac": round(iso_gbs / HBM_PEAK_GBS, 4), "launches": prof["scan_launches"],
+                                               "what": "the same kernel in an ordered pass after the timed region (scans serialised by events, "
+                                                       "one launch per bracket, still on the scan partition's CUs)"}
         line = {
             "metric": "queries/sec top-100 over 10Mx768 corpus" if (args.rows, args.dim, args.k) == (10_000_000, 768, 100)
                       else f"queries/sec top-{args.k} over {args.rows}x{args.dim} corpus", "value": round(qps, 1), "unit": "queries/s",
@@ -1333,7 +1354,7 @@ def main():
             "request_latency": lat_info,
             "host_entry": host_entry,
         }
-        if world == 1 and not args.no_cpu_baseline and corpus is not None:
+        if args.full and world == 1 and not args.no_cpu_baseline and corpus is not None:
             try:
                 gi, gs = index.search_device(qpool[0], args.k)
                 line["cpu_baseline"] = cpu_baseline(args, torch, vf, corpus, qpool[0], gi, gs)
@@ -1341,18 +1362,18 @@ def main():
             except Exception as e:  # noqa: BLE001
                 line["cpu_baseline"] = {"value": None, "unit": "queries/s", "cores": os.cpu_count(), "kind": "port",
                                         "sample": f"failed: {type(e).__name__}: {e}"}
-        # start-up: the corpus as a .vfc file -> searchable (the default line only; this process's own index is closed first)
+        # start-up: the corpus as a .vfc file -> searchable (the --full line at the default size only; this process's own index is closed first)
         index.close()
-        if world == 1 and not devs and corpus is not None and args.corpus_dtype == "f16" and not args.no_startup and \
+        if args.full and world == 1 and not devs and corpus is not None and args.corpus_dtype == "f16" and not args.no_startup and \
                 (args.rows, args.dim) == (10_000_000, 768):
             try:
                 line["startup"] = startup_leg(args, torch, vf, corpus)
             except Exception as e:  # noqa: BLE001
                 line["startup"] = {"error": f"{type(e).__name__}: {e}"}
-        # configs[1] and one rank's share of configs[2] (the default line only), each as a child process running this script on that
+        # configs[1] and one rank's share of configs[2] (the --full line at the default size only), each as a child process running this script on that
         # workload (small_shard_leg); last, with this process's index closed AND its corpus freed (round-5 advisor: the 15 GB stayed
         # resident behind the children)
-        run_legs = rank == 0 and world == 1 and not devs and corpus is not None and args.corpus_dtype == "f16" and not args.no_shard_legs and \
+        run_legs = rank == 0 and args.full and world == 1 and not devs and corpus is not None and args.corpus_dtype == "f16" and not args.no_shard_legs and \
             (args.rows, args.dim, args.batch, args.k) == (10_000_000, 768, 64, 100) and not dist.is_initialized()
         if run_legs:
             corpus = None
@@ -1370,6 +1391,10 @@ def main():
                 else:
                     shard8_info = info_
         line["c2"], line["shard8"] = c2_info, shard8_info
+        if last_step is not None:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "topk_ids.npy"), last_step[0])
+            np.save(os.path.join(args.dump_outputs, "topk_scores.npy"), last_step[1])
         print(json.dumps(line), flush=True)
     index.close()
     if dist.is_initialized():

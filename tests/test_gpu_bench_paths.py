@@ -52,7 +52,8 @@ def test_bench_four_ranks_share_the_one_gpu():
     oracle check of the merged result -- rehearsed on the one-GPU box: VF_BENCH_SHARE_DEVICE=1 puts every rank on device 0 and carries
     the collectives over gloo (RCCL refuses two ranks on one device; the pool allows six processes on a card, so four ranks + this
     process).  Nothing here is a performance figure."""
-    out, err = _bench(["--gpus", "4", "--rows", "500000", "--steps", "8", "--warmup", "2", "--rerank-pairs", "100", "--rerank-tokens", "64"],
+    out, err = _bench(["--gpus", "4", "--rows", "500000", "--steps", "8", "--warmup", "2", "--rerank-pairs", "100", "--rerank-tokens", "64",
+                       "--full"],
                       {"VF_BENCH_SHARE_DEVICE": "1"}, timeout=800)
     assert out["n_gpus"] == 4 and out["config"]["rows_per_gpu"] == [125_000] * 4 and out["config"]["batches_per_exchange"] == 4
     assert out["rccl"]["backend"] == "gloo" and out["rccl"]["world"] == 4 and len({d["pid"] for d in out["rccl"]["devices"]}) == 4

@@ -31,7 +31,9 @@ def test_host_side_of_the_c_abi_is_clean_under_asan_and_ubsan(tmp_path):
     # (the driver is plain C++: compiled on its own -- given a .cc beside objects, hipcc applies "-x hip" to the objects as well)
     subprocess.check_call([clangxx, "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
                            "-c", os.path.join(ROOT, "tools", "host_sanitize_check.cc"), "-o", drv_o])
-    subprocess.check_call([hipcc, f"--offload-arch={vf_build.ARCH}", "-fsanitize=address,undefined", drv_o, api_o] + objs + ["-o", exe])
+    # (the link takes the host sanitizer runtimes; -fno-gpu-sanitize keeps the device side uninstrumented, as the compiles above do)
+    subprocess.check_call([hipcc, f"--offload-arch={vf_build.ARCH}", "-fsanitize=address,undefined", "-fno-gpu-sanitize", drv_o, api_o] + objs +
+                          ["-o", exe])
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0:halt_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
     work = tmp_path / "files"
     work.mkdir()
