@@ -353,6 +353,27 @@ int vf_clip_text_create(vf_clip_text** out, const vf_clip_text_config* cfg, cons
 int vf_clip_text_forward(vf_clip_text* ct, const int32_t* ids, const int32_t* mask, int32_t b, int32_t t, float* out);
 int vf_clip_text_destroy(vf_clip_text* ct);
 
+/* ---- BM25 leg: replaces bm25s.BM25.retrieve over the index src/utils/bm25Retriever.py:10-20 writes ----------------------------
+ * The ensemble's third leg (src/utils/ensembleRetriever.py:188-190) scores every chunk and ranks all of them per request.  The
+ * index is bm25s's CSC layout: column c (one per vocabulary token) holds postings indptr[c] .. indptr[c+1]: document rows
+ * `indices` (strictly ascending within a column) and their precomputed float32 scores `data` (> 0: Lucene / Robertson-free
+ * methods; bm25l / bm25+ are not served).  The arrays are copied to HBM once.
+ * Scoring contract: score(doc) = fp32 sum of the doc's postings over the query's token columns, added left to right in query
+ * order from 0.0f -- bit-equal to bm25s's numpy scorer (np.add.at per token) on the same token ids.  Ranking: score descending,
+ * ties to the LOWER row, over all n_docs rows; untouched rows score 0 and follow the touched ones in ascending row order.
+ * Per-query scratch on the device: n_docs * 4 B of scores + n_docs / 8 B of bitmap, up to 64 queries in flight (as many as
+ * 3 GiB of it allows); k > 4096 also holds next_pow2(n_docs) * 8 B of sort keys and n_docs * 12 B of results. */
+typedef struct vf_bm25 vf_bm25;
+/* slots (may be NULL) = queries one device pass serves.  With indptr == NULL the call RELEASES the handle *out instead (all other
+ * arguments ignored; *out is set to NULL) -- the exported surface stays two entry points. */
+int vf_bm25_create(const int64_t* indptr, int64_t vocab, const int32_t* indices, const float* data, int64_t nnz,
+                   int64_t n_docs, int32_t device_id, vf_bm25** out, int32_t* slots);
+/* q_offsets [nq + 1] (q_offsets[0] = 0, non-decreasing), q_terms [q_offsets[nq]] token columns in query order (repeats count
+ * again; a query with no token ranks every row at score 0), 1 <= k <= n_docs (else VF_EINVAL)
+ * -> out_ids [nq, k] rows, out_scores [nq, k] (host) */
+int vf_bm25_search(vf_bm25* h, const int64_t* q_offsets, const int32_t* q_terms, int32_t nq, int32_t k, int64_t* out_ids,
+                   float* out_scores);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,8 @@ Drop-in names (same signatures as the reference):
 * ``HipEmbeddings`` / ``HipReranker``   -- ``HuggingFaceEmbeddings`` (``src/utils/ragManager.py:50``) /
                                             ``reranker.compute_score`` (``src/utils/vllmManager.py:451``)
 * ``EnsembleRetriever``                  -- ``src/utils/ensembleRetriever.py:19-232`` (candidate gathering around the search)
+* ``BM25Retriever``, ``load_from_chroma_and_save``
+                                         -- ``src/utils/bm25Retriever.py`` (the ensemble's BM25 leg, scored and ranked on the GPU)
 * ``ShardedRetriever``                   -- row-sharded multi-GPU search
 * ``ShardedScorer``                      -- data-parallel re-rank / embed: a replica per rank + one all-gather of the scores
 * ``HuggingFaceEmbeddings(model_name=...)`` / ``FlagLLMReranker(name, ...)`` / ``from_config(cfg)``
@@ -74,6 +76,8 @@ from .rank import rank_chunk  # noqa: F401
 from .vision import (HipClipTextEmbeddings, HipClipTextEncoder, HipImageEmbeddings, HipVisionEncoder, pack_hf_clip_text,  # noqa: F401
                      pack_hf_clip_vision)
 from .ensemble import EnsembleRetriever  # noqa: F401
+from .bm25 import (BM25Retriever, build_bm25_index, build_bm25_index_from_ids, load_bm25_index,  # noqa: F401
+                   load_from_chroma_and_save)
 from .stages import StageTimer, get_profiler, set_profiler  # noqa: F401
 from .pretrained import (FlagLLMReranker, FlagReranker, HuggingFaceEmbeddings, ReplicaSet, from_config, load_embeddings,  # noqa: F401
                          load_reranker, read_sentence_transformers_layout)

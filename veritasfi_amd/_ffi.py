@@ -119,6 +119,8 @@ SIGNATURES = {
     "vf_clip_text_create": (ctypes.c_int, [ctypes.POINTER(vp), ctypes.POINTER(ClipTextConfig), vp, c_i64, vp, c_i64, c_i32]),
     "vf_clip_text_forward": (ctypes.c_int, [vp, vp, vp, c_i32, c_i32, vp]),
     "vf_clip_text_destroy": (ctypes.c_int, [vp]),
+    "vf_bm25_create": (ctypes.c_int, [p_i64, c_i64, p_i32, p_f32, c_i64, c_i64, c_i32, ctypes.POINTER(vp), p_i32]),
+    "vf_bm25_search": (ctypes.c_int, [vp, p_i64, p_i32, c_i32, c_i32, p_i64, p_f32]),
 }
 
 _lib = None

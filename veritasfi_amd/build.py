@@ -23,7 +23,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, os.environ.get("VF_BUILD_LIB", "libveritasfi_hip.so"))   # VF_BUILD_LIB: name of an A/B variant
-SOURCES = ["vf_kernels.hip", "vf_api.hip", "vf_transformer.hip"]
+SOURCES = ["vf_kernels.hip", "vf_api.hip", "vf_transformer.hip", "vf_sparse.hip"]
 HEADERS = ["vf_internal.h", os.path.join("..", "..", "include", "veritasfi_hip.h")]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]

@@ -26,6 +26,33 @@ struct DeviceGuard {
     DeviceGuard& operator=(const DeviceGuard&) = delete;
 };
 
+// ---- device helpers shared by the kernel TUs (vf_kernels.hip, vf_sparse.hip) ----------------------
+// orderkey: float -> u32 whose unsigned order is the float order; a ranking key is (orderkey(score) << 32) | ~row
+__device__ __forceinline__ u32 orderkey(float f) {
+    f = f + 0.0f;  // -0 -> +0 so equal floats have equal keys
+    const u32 b = __float_as_uint(f);
+    return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+}
+__device__ __forceinline__ float unorderkey(u32 k) {
+    return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
+}
+
+// workgroup bitonic sort, descending, n a power of two, keys in LDS
+__device__ __forceinline__ void bitonic_sort_desc(u64* s, int n, int tid, int nthreads) {
+    for (int k = 2; k <= n; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < (n >> 1); i += nthreads) {
+                const int lo = ((i & ~(j - 1)) << 1) | (i & (j - 1));
+                const int hi = lo | j;
+                const bool desc = (lo & k) == 0;
+                const u64 a = s[lo], b = s[hi];
+                if ((a < b) == desc) { s[lo] = b; s[hi] = a; }
+            }
+            __syncthreads();
+        }
+    }
+}
+
 // ---- fixed design constants ------------------------------------------------------
 constexpr int kQueryTile = 32;        // queries per MFMA N-tile (v_mfma_f32_32x32x16_f16)
 constexpr int kMaxBatch = 64;         // queries per scan pass (2 N-tiles); larger nq loops

@@ -31,15 +31,6 @@ typedef int i8v __attribute__((ext_vector_type(8)));
 // ------------------------------------------------------------------------------------------------
 // small device helpers
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ u32 orderkey(float f) {
-    f = f + 0.0f;  // -0 -> +0 so equal floats have equal keys
-    const u32 b = __float_as_uint(f);
-    return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-__device__ __forceinline__ float unorderkey(u32 k) {
-    return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
-}
-
 // canonical 16-lane tree: acc[l] += acc[l+8]; += [l+4]; += [l+2]; acc[0] + acc[1]  (lane 0 of the group)
 __device__ __forceinline__ float group16_tree(float acc) {
     acc = acc + __shfl_down(acc, 8, 16);
@@ -84,22 +75,6 @@ __device__ __forceinline__ float bin_x(float s) { return __builtin_fmaf(s, 0.5f 
 __device__ __forceinline__ int bin_of_x(float x) {
     int b = (int)floorf(x);
     return b < 0 ? 0 : (b > kHistBins - 1 ? kHistBins - 1 : b);
-}
-
-// workgroup bitonic sort, descending, n a power of two, keys in LDS
-__device__ __forceinline__ void bitonic_sort_desc(u64* s, int n, int tid, int nthreads) {
-    for (int k = 2; k <= n; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < (n >> 1); i += nthreads) {
-                const int lo = ((i & ~(j - 1)) << 1) | (i & (j - 1));
-                const int hi = lo | j;
-                const bool desc = (lo & k) == 0;
-                const u64 a = s[lo], b = s[hi];
-                if ((a < b) == desc) { s[lo] = b; s[hi] = a; }
-            }
-            __syncthreads();
-        }
-    }
 }
 
 __device__ __forceinline__ int next_pow2(int n) {

@@ -9,9 +9,9 @@ through this package's ``FaissRetriever`` (GPU).  Output schema, ordering, the `
 neighbour expansion (score > 0.72, neighbours > 0.66 in the 2048-deep score map, at most 4 rows, ``:85-107``) and
 the running ``bundle_id`` counter are the reference's.
 
-BM25 itself is outside this path (CPU, sparse): the constructor does what the reference's does (``:37``) -- it builds the
-host application's own ``BM25Retriever(bm25_dir)`` -- unless an object with ``invoke(query, k) -> (ids, scores)``
-(``src/utils/bm25Retriever.py:50-87``) is handed in as ``bm25_retriever``.  When the BM25 branch is on (``bm25_k`` resolves
+BM25: the constructor does what the reference's does (``:37``) -- it builds the host application's own
+``BM25Retriever(bm25_dir)`` -- unless an object with ``invoke(query, k) -> (ids, scores)`` (``src/utils/bm25Retriever.py:50-87``)
+is handed in as ``bm25_retriever``; this package's GPU one is ``bm25_retriever=veritasfi_amd.BM25Retriever(bm25_dir)`` (bm25.py).  When the BM25 branch is on (``bm25_k`` resolves
 to > 0) and neither works, construction FAILS; the branch is never dropped silently.  The stores are anything with
 Chroma's ``get(include=[...])`` / ``get(ids=[...], include=[...])``.
 """
@@ -234,7 +234,13 @@ class EnsembleRetriever:
         return bundle_cnt
 
     def _bm25_branch(self, input, seen, out, bundle_cnt):
-        b_ids, b_scores = self.bm25_retriever.invoke(input, self.num_chunk)
+        # upstream ranks every chunk (:188) and reads the first bm25_k; a retriever whose ranking is a total order
+        # (exact_prefix, e.g. veritasfi_amd.BM25Retriever) returns exactly that prefix when asked for bm25_k rows -- min_score
+        # included, since it keeps a prefix of a descending ranking.  Others keep the upstream call.
+        depth = self.num_chunk
+        if getattr(self.bm25_retriever, "exact_prefix", False) is True:
+            depth = max(1, min(int(self.bm25_k), self.num_chunk))
+        b_ids, b_scores = self.bm25_retriever.invoke(input, depth)
         for row, score in zip(b_ids[:self.bm25_k], b_scores[:self.bm25_k]):
             if row in seen:
                 continue
