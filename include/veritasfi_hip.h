@@ -57,7 +57,8 @@ typedef struct vf_search_stats {
     int64_t aux_cus;         /* CUs the main scan left to the small kernels of the other slots (0 = no CU split) */
     int64_t scans_overlap;   /* 1 = main scans of consecutive slots were not ordered against each other */
     int64_t scan_kernel;     /* main-scan kernel of the call: 1 k_scan (register loads), 2 k_scan2 (whole-line LDS-DMA), 3 k_scan_wide, 4 k_scan_wide8 (fp8 matrix instruction), 5 k_scan2r (k_scan2, half the query image in registers) */
-    int64_t reserved[4];
+    int64_t scan_image;      /* 1 = the main scan read the int8 row image (option "scan_image"), 0 = the rows as stored */
+    int64_t reserved[3];
 } vf_search_stats;
 
 int vf_version(void);

@@ -54,7 +54,7 @@ class SearchStats(ctypes.Structure):
     _fields_ = [
         ("path", c_i64), ("n_queries", c_i64), ("candidates", c_i64), ("max_candidates", c_i64),
         ("uncertified", c_i64), ("overflowed", c_i64), ("exact_reruns", c_i64), ("wide_launches", c_i64), ("wide_queries", c_i64),
-        ("aux_cus", c_i64), ("scans_overlap", c_i64), ("scan_kernel", c_i64), ("reserved", c_i64 * 4),
+        ("aux_cus", c_i64), ("scans_overlap", c_i64), ("scan_kernel", c_i64), ("scan_image", c_i64), ("reserved", c_i64 * 3),
     ]
 
     def as_dict(self):

@@ -105,6 +105,7 @@ struct Slot {
     bool timed = false;
     int wide_launches = 0, wide_queries = 0;   // k_scan_wide main passes of the pending search / queries they served
     int scan_kernel = 0;                       // main-scan kernel of the pending search: 1 k_scan, 2 k_scan2, 3 k_scan_wide
+    int scan_image = 0;                        // 1: the pending search's scans read the int8 row image
     DevBuf qn, qimg, s0, cnt, tau, hist, hist_coarse, cand, flags, counts;   // fused-path state
     DevBuf dbg, wgbase, tilecnt, sib;
     DevBuf qimg8, epsq;                  // k_scan_wide8: hi / lo e4m3 query image, per-query certificate bounds
@@ -164,12 +165,17 @@ struct vf_index {
     float* norm = nullptr;            // canonical norms [n]
     float* inv_scan = nullptr;        // [n]
     float* cn_cache = nullptr;        // canonical normalised rows when n <= kSmallN
+    unsigned char* rows_img = nullptr;   // int8 row image [n][dp] (fp16 / fp32 rows, option scan_image): biased codes, k_prep_image
+    float* inv_img = nullptr;         // [n + 64] row scale / canonical norm: the image's approx score = acc x inv_img, then [n + 64] per-row
+                                      // score offsets off_img (k_prep_image; the scan adds them: DESIGN.md 4)
+    float rho_max = 0.0f;             // largest relative residual ||x - s code|| / ||x|| of a row of the image (rounded up)
+    float rho_mean = 0.0f;            // their average: sets the re-score band
     std::mutex mu;
     Slot slots[kSlots];
     // options
     int64_t force_path = -1, sample_rows = -1, margin = -1, cap_opt = 0, waves_opt = 0, scan_g = 0,
             refresh_every = 128, debug = 0, steal_opt = 0, wide_opt = 1, wide_sync = -1, wide_mfma = -1, wide8_waves = 8, wide8_stage = 0,
-            aux_cus = -1, sample_grid = -1, overlap_scans = -1, scan_impl = 2, sample_impl = -1;   // aux_cus / overlap_scans: -1 = auto (resolved_split)   // scan_impl: 1 = k_scan (register loads), 2 = k_scan2 (whole-line LDS-DMA) where it fits   // aux_cus: CUs the main scan leaves to the small kernels of the other slots (0 = no split)   // wide_sync: -1 siblings of a wide row group run free (default: fastest), >= 0 = the slack in super-tiles  // steal_opt: cross-workgroup tile pool in the main scan (measured slower: DESIGN.md 5)  // wide_opt: 0 never, 1 auto (nq >= 129), > 1 = from that many queries
+            aux_cus = -1, sample_grid = -1, overlap_scans = -1, scan_impl = 2, sample_impl = -1, scan_image = 1;   // aux_cus / overlap_scans: -1 = auto (resolved_split)   // scan_impl: 1 = k_scan (register loads), 2 = k_scan2 (whole-line LDS-DMA) where it fits   // aux_cus: CUs the main scan leaves to the small kernels of the other slots (0 = no split)   // wide_sync: -1 siblings of a wide row group run free (default: fastest), >= 0 = the slack in super-tiles  // steal_opt: cross-workgroup tile pool in the main scan (measured slower: DESIGN.md 5)  // wide_opt: 0 never, 1 auto (nq >= 129), > 1 = from that many queries
     vf_search_stats stats{};
     bool profile = false;
     double prof_scan_ms = 0.0, prof_pipe_ms = 0.0;
@@ -201,6 +207,8 @@ static int ensure_pinned(Slot& s, size_t nq_total) {
     return VF_OK;
 }
 
+static int build_image(vf_index* ix, int64_t mode);
+
 static int build_common(vf_index* ix) {
     hipDeviceProp_t prop;
     VF_HIP(hipGetDeviceProperties(&prop, ix->device));
@@ -227,6 +235,7 @@ static int build_common(vf_index* ix) {
         }
     }
     VF_HIP(launch_prep_rows(ix->rows_orig, dt, ix->n, ix->d, ix->dp, scan_out, ix->norm, ix->inv_scan, nullptr));
+    VF_TRY(build_image(ix, ix->scan_image));
     if (ix->n > 0 && ix->n <= kSmallN) {
         VF_HIP(hipMalloc((void**)&ix->cn_cache, (size_t)ix->n * ix->d * sizeof(float)));
         VF_HIP(launch_normalize_rows(ix->rows_orig, dt, 0, ix->n, ix->d, ix->norm, ix->cn_cache, nullptr));
@@ -266,6 +275,59 @@ static int64_t resolved_aux(const vf_index* ix) {
 }
 static bool resolved_overlap(const vf_index* ix) {
     return ix->overlap_scans >= 0 ? ix->overlap_scans != 0 : resolved_aux(ix) > 0;
+}
+
+// ---- the int8 row image ---------------------------------------------------------------------------------
+// fp16 / fp32 rows of 768 elements in a shard of at least kImageMinRows rows get a second copy at one byte per element (plus a float per
+// row): the main scan of a batch with k <= kImageMaxK reads 772 instead of 1 540 bytes per row (768 wide) and k_final's band re-score
+// keeps the results those of the canonical arithmetic.  Option scan_image: 0 off, 1 auto (default: only with kImageHeadroom of device
+// memory left over after it), 2 force.  A shard whose worst row leaves more than kImageMaxRho of residual keeps no image: its eps band
+// would hold a large part of the corpus (a row with one huge element and the rest near zero: tests/adversarial.py).
+// k and width limits: the band must fit k_final's 4 096-entry survivor area.  Measured with the first band (2 rho_max wide,
+// tests/test_gpu_scan_image.py): 4M x 768, k = 256 and 4M x 1024, k = 100 overflowed it for most queries; 768, k <= 128 did not
+constexpr int kImageMaxK = 128;
+constexpr int64_t kImageMinRows = 4'000'000;   // measured at 10M rows; the shards of a 4- or 8-GPU split (2.5M / 1.25M rows) keep the fp16 scan
+constexpr double kImageMaxRho = 1.0 / 64;
+constexpr size_t kImageHeadroom = (size_t)8 << 30;
+static bool image_eligible(const vf_index* ix) {
+    return ix->shards.empty() && (ix->dtype == VF_DTYPE_F16 || ix->dtype == VF_DTYPE_F32) && ix->n >= kImageMinRows &&
+           ix->n < (int64_t)0xFFFFFFFFll && ix->dp == 768 && scan2r_stage_cap(ix->dp, kMaxBatch, 2) >= 256;
+}
+static float* image_offsets(const vf_index* ix) { return ix->inv_img ? ix->inv_img + ix->n + 64 : nullptr; }
+static void free_image(vf_index* ix) {
+    if (ix->rows_img) (void)hipFree(ix->rows_img);
+    if (ix->inv_img) (void)hipFree(ix->inv_img);
+    ix->rows_img = nullptr; ix->inv_img = nullptr; ix->rho_max = ix->rho_mean = 0.0f;
+}
+static int build_image(vf_index* ix, int64_t mode) {
+    if (mode == 0 || ix->rows_img || !image_eligible(ix)) return VF_OK;
+    const size_t bytes = (size_t)ix->n * ix->dp, ibytes = 2 * ((size_t)ix->n + 64) * sizeof(float);   // inverses + offsets
+    if (mode == 1) {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return VF_OK; }
+        if (free_b < bytes + ibytes + kImageHeadroom) return VF_OK;   // auto: no room, the rows as stored are scanned
+    }
+    if (hipMalloc((void**)&ix->rows_img, bytes) != hipSuccess || hipMalloc((void**)&ix->inv_img, ibytes) != hipSuccess) {
+        (void)hipGetLastError();
+        free_image(ix);
+        return mode == 2 ? fail(VF_ENOMEM, "scan_image = 2: the int8 row image does not fit in device memory") : VF_OK;
+    }
+    u32* d_rho = nullptr;   // [0] largest rho (float bits), [1] sum of rho (float)
+    VF_HIP(hipMalloc((void**)&d_rho, 2 * sizeof(u32)));
+    VF_HIP(hipMemset(d_rho, 0, 2 * sizeof(u32)));
+    VF_HIP(hipMemset(ix->inv_img, 0, ibytes));
+    VF_HIP(launch_prep_image(ix->rows_orig, ix->dtype, ix->n, ix->d, ix->dp, ix->norm, ix->rows_img, ix->inv_img, image_offsets(ix), d_rho,
+                             (float*)(d_rho + 1), nullptr));
+    u32 bits[2] = {0u, 0u};
+    VF_HIP(hipMemcpy(bits, d_rho, sizeof(bits), hipMemcpyDeviceToHost));
+    (void)hipFree(d_rho);
+    float rho, sum;
+    memcpy(&rho, &bits[0], sizeof(rho));
+    memcpy(&sum, &bits[1], sizeof(sum));
+    if (!(rho <= kImageMaxRho)) { free_image(ix); return VF_OK; }   // (a NaN fails the test too)
+    ix->rho_max = rho;
+    ix->rho_mean = sum / (float)ix->n;
+    return VF_OK;
 }
 
 static int ensure_slot(vf_index* ix, Slot& s) {
@@ -346,6 +408,8 @@ static void destroy_index(vf_index* ix) {
     if (ix->norm) (void)hipFree(ix->norm);
     if (ix->inv_scan) (void)hipFree(ix->inv_scan);
     if (ix->cn_cache) (void)hipFree(ix->cn_cache);
+    if (ix->rows_img) (void)hipFree(ix->rows_img);
+    if (ix->inv_img) (void)hipFree(ix->inv_img);
     if (ix->ev_span) (void)hipEventDestroy(ix->ev_span);
     delete ix;
 }
@@ -628,6 +692,17 @@ extern "C" int vf_index_set_option(vf_index* ix, const char* name, int64_t value
     else if (s == "scan_impl") { if (!in_range(1, 5)) return fail(VF_EINVAL, "scan_impl must be 1 (k_scan), 2 (auto: k_scan2 for fp16 rows, k_scan2r where it measured faster), 3 (k_scan2 wherever it fits, e4m3 rows converted), 4 (k_scan2 for fp16 rows, never k_scan2r) or 5 (k_scan2r wherever a shape of it exists: fp16 rows of 384 / 512 / 768 / 1024 elements, e4m3 rows of 768 / 1024)"); ix->scan_impl = value; }
     else if (s == "sample_impl") { if (!in_range(-1, 1)) return fail(VF_EINVAL, "sample_impl must be -1 (auto: k_scan2r's operand path for the sample pass where it exists and the CU split is on), 0 (k_scan) or 1 (k_scan2r wherever it fits)"); ix->sample_impl = value; }
     else if (s == "overlap_scans") { if (!in_range(-1, 1)) return fail(VF_EINVAL, "overlap_scans must be -1 (auto), 0 or 1"); ix->overlap_scans = value; }
+    else if (s == "scan_image") {
+        if (!in_range(0, 2)) return fail(VF_EINVAL, "scan_image must be 0 (off), 1 (auto: when it fits with headroom) or 2 (force)");
+        if (!ix->shards.empty()) { ix->scan_image = value; return VF_OK; }   // (the shards have built or dropped theirs above)
+        for (const Slot& sl : ix->slots) if (sl.pending) return fail(VF_EINVAL, "scan_image cannot change while a search is pending");
+        DeviceGuard restore_callers_device;
+        VF_HIP(hipSetDevice(ix->device));
+        VF_HIP(hipDeviceSynchronize());
+        if (value == 0) free_image(ix);
+        else VF_TRY(build_image(ix, value));
+        ix->scan_image = value;
+    }
     else if (s == "debug") ix->debug = value;
     else if (s == "profile") {
         ix->profile = value != 0; ix->prof_scan_ms = ix->prof_pipe_ms = 0.0; ix->prof_launches = 0;
@@ -696,6 +771,8 @@ static int exact_search(vf_index* ix, Slot& s, const float* qn_dev, int nq, int 
 struct FusedPlan {
     int kprime, cap, total_waves, grid, samp;
     float eps;
+    bool image;              // the scans read the int8 row image: kprime = k, thresholds and the re-score follow the eps band
+    int tau_band, fine_band; // that band (2 eps, rounded up, + one bin) in threshold bins (1 / 1024) and in k_final's fine bins (1 / 16 384)
 };
 
 static int qn_tile_for(int nq_batch) { return nq_batch <= kQueryTile ? kQueryTile : kMaxBatch; }
@@ -714,8 +791,43 @@ static int batch_limit(const vf_index* ix) {
     return scan_lds_bytes(ix->dp, kMaxBatch) <= 160 * 1024 ? kMaxBatch : kQueryTile;
 }
 
-static FusedPlan make_plan(const vf_index* ix, int k) {
+// The int8 image's certificate.  The row the scan sees is s code / ||c|| = c / ||c|| + r with ||r|| = rho_row, so its
+// approximate score moves by |q16 . r| <= ||q16|| rho_row <= (1 + 2^-11)(1 + 2^-20) rho_row more than on the fp16 path, and the scan's
+// fp32 sum, whose terms now add up to at most 1 + rho_row, by d 2^-24 rho_row more: off_row (k_prep_image, rounded up).  The scan adds
+// off_row to every score it forms, so canonical <= key + eps holds for every row with the fp16 path's eps (+ 10^-7 for that addition's
+// rounding) -- the certificate k_final tests is the fp16 path's.  What the band must hold: the k-th canonical is ~ the k-th key minus
+// that row's off, so every row whose key is within eps + off of the k-th best key must be re-scored.  The band is eps + 1.5 rho_mean c
+// + 2^-9 (a top-k row up to ~1.75 x the average residual); a query whose rows lie further out fails the certificate and takes the exact
+// path.  Widths in threshold bins (1 / 1024) and fine bins (1 / 16 384), rounded up + one bin.
+static void image_bound(int d, int dtype, float rho_mean, float* eps, int* tau_band, int* fine_band) {
+    const double u16 = 1.0 / 2048.0;
+    const double base = u16 * (dtype == VF_DTYPE_F32 ? 2.0 : 1.0) + sqrt((double)d) * ldexp(1.0, -24) + 2.0 * d * ldexp(1.0, -24) + 1e-6;
+    const float e = (float)(base + 1e-7);
+    const double band = (double)e + 1.5 * rho_mean * (1.0 + u16) * (1.0 + ldexp(1.0, -20)) + ldexp(1.0, -9);
+    *eps = e;
+    *tau_band = (int)ceil(band * (kHistBins / 2)) + 1;
+    *fine_band = (int)ceil(band * (kHistBins / 2) * 16) + 1;
+}
+
+// Test hook (not in the public header; exported by the test build only): the bound and bands above, for tests/test_scan_image_model.py
+extern "C" int vf_debug_image_bound(int32_t d, int32_t dtype, float rho_mean, float* eps, int32_t* tau_band, int32_t* fine_band) {
+    if (!eps || !tau_band || !fine_band || d <= 0) return fail(VF_EINVAL, "vf_debug_image_bound: bad argument");
+    int tb = 0, fb = 0;
+    image_bound(d, dtype, rho_mean, eps, &tb, &fb);
+    *tau_band = tb; *fine_band = fb;
+    return VF_OK;
+}
+
+// the int8 image serves a fused batch when it exists, k is within kImageMaxK and the scans are k_scan2r's (the options that pick another
+// kernel, the tile pool or k_scan's sample pass keep the rows as stored); wide passes never reach it (wide_pass returns before)
+static bool image_serves(const vf_index* ix, int k, int qt) {
+    return ix->rows_img && k <= kImageMaxK && (ix->scan_impl == 2 || ix->scan_impl == 5) && !ix->steal_opt && ix->sample_impl != 0 &&
+           scan2r_stage_cap(ix->dp, qt, 2) >= 256;
+}
+
+static FusedPlan make_plan(const vf_index* ix, int k, bool image = false) {
     FusedPlan p;
+    p.image = image; p.tau_band = 0; p.fine_band = 0;
     // k' = k + margin, rounded up to a multiple of 32 (whole re-score rounds of 32 row groups)
     const int margin = ix->margin >= 0 ? (int)ix->margin : std::max(24, k / 4);
     p.kprime = ix->margin >= 0 ? k + margin : (k + margin + 31) / 32 * 32;
@@ -759,6 +871,14 @@ static FusedPlan make_plan(const vf_index* ix, int k) {
     const double u16 = 1.0 / 2048.0;
     p.eps = (float)(u16 * (ix->dtype == VF_DTYPE_F32 ? 2.0 : 1.0) + sqrt((double)ix->d) * ldexp(1.0, -24) +
                     2.0 * ix->d * ldexp(1.0, -24) + 1e-6);
+    if (image) {
+        image_bound(ix->d, ix->dtype, ix->rho_mean, &p.eps, &p.tau_band, &p.fine_band);
+        p.kprime = k;
+        // a list holds ~ (rows in the band) x (1 + ln(n / sample rows)) x the refresh lag -- several thousand per query on ordinary data
+        // (DESIGN.md 4): the largest list the fused path has, 256 KB per query, whatever the `cap` option says (that option sizes the
+        // count-based lists only); its length costs memory, not time (k_final reads what was written)
+        p.cap = 32768;
+    }
     return p;
 }
 
@@ -912,7 +1032,9 @@ static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq,
         return VF_OK;
     }
 
-    FusedPlan p = make_plan(ix, k);
+    const bool img = !wide_possible(ix, nq) && image_serves(ix, k, qn_tile_for(std::min(bl, nq)));
+    FusedPlan p = make_plan(ix, k, img);
+    s.scan_image = img ? 1 : 0;
     if (wide_possible(ix, nq)) {
         s.timed = ix->profile;
         if (s.timed) VF_HIP(hipEventRecord(s.ev_t[2], st));
@@ -950,8 +1072,9 @@ static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq,
         ScanArgs a{};
         a.rows = (const char*)ix->rows_scan; a.inv_scan = ix->inv_scan; a.qimg = s.qimg.as<_Float16>();
         a.n = ix->n; a.dp = ix->dp; a.row_bytes = (long long)ix->dp * (ix->dtype == VF_DTYPE_FP8_E4M3 ? 1 : 2); a.total_waves = p.total_waves; a.samp = p.samp;
+        if (p.image) { a.rows = (const char*)ix->rows_img; a.inv_scan = ix->inv_img; a.off_scan = image_offsets(ix); a.row_bytes = ix->dp; }   // every pass of the batch: sample, seed, main
         a.s0 = s.s0.as<float>(); a.wg_base = s.wgbase.as<long long>(); a.cnt = s.cnt.as<u32>(); a.tau_bin = s.tau.as<int>(); a.hist = s.hist.as<u32>();
-        a.cand = s.cand.as<u64>(); a.cap = p.cap; a.kprime = p.kprime;
+        a.cand = s.cand.as<u64>(); a.cap = p.cap; a.kprime = p.kprime; a.tau_band = p.tau_band;
         a.hist_coarse = s.hist_coarse.as<u32>(); a.stage_cap = scan_stage_cap(ix->dp, qt);
         a.tile_cnt = ix->steal_opt ? s.tilecnt.as<u32>() : nullptr; a.scan_grid = p.grid;
         a.dbg = nullptr;
@@ -974,16 +1097,16 @@ static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq,
         // Round 6: where k_scan2r's operand path is the default (scan2r_auto_width) the sample pass takes it too -- ONE workgroup per spare
         // CU, each walking the sample parts of p.grid / 32 ranges with six-segment rings: the pass is bound by what a CU keeps in flight
         // (k_scan's register-staged loads: 68-71 us for 8 rows per wave in four rounds of 128 workgroups).  sample_impl: -1 auto, 0 k_scan, 1 k_scan2r
-        const bool f8rows = ix->dtype == VF_DTYPE_FP8_E4M3;
+        const bool f8rows = ix->dtype == VF_DTYPE_FP8_E4M3 || p.image;   // (image rows: one byte per element, the e4m3 shapes)
         // e4m3 rows (768 / 1024 elements) take it wherever k_scan2r is their main scan (n > 1.1M: below), whole chip or split.
         const bool r_f8_auto = f8rows && ix->scan_impl == 2 && ix->n > kScan2rMinRows && !ix->steal_opt && scan2r_auto_width(ix->dp, true);
-        const bool sample_r = ix->sample_impl != 0 && ix->scan_impl != 1 && scan2r_stage_cap(ix->dp, qt, f8rows) >= 256 &&
-                              (ix->sample_impl == 1 || (!f8rows && s.scan_stream != s.stream && scan2r_auto_width(ix->dp, false)) || r_f8_auto);
+        const bool sample_r = p.image || (ix->sample_impl != 0 && ix->scan_impl != 1 && scan2r_stage_cap(ix->dp, qt, f8rows) >= 256 &&
+                              (ix->sample_impl == 1 || (!f8rows && s.scan_stream != s.stream && scan2r_auto_width(ix->dp, false)) || r_f8_auto));
         if (sample_r) {
             const int64_t sg_r = ix->sample_grid > 0 ? ix->sample_grid : (s.scan_stream != s.stream ? resolved_aux(ix) : p.grid);
             ScanArgs as = a;
             as.stage_cap = 0;
-            VF_HIP(launch_scan2r_sample(as, qt, (int)std::min<int64_t>(std::max<int64_t>(sg_r, 1), p.grid), f8rows, st));
+            VF_HIP(launch_scan2r_sample(as, qt, (int)std::min<int64_t>(std::max<int64_t>(sg_r, 1), p.grid), p.image ? 2 : (int)f8rows, st));
         } else {
         const int64_t sg_opt = ix->sample_grid >= 0 ? ix->sample_grid : (s.scan_stream != s.stream ? 4 * resolved_aux(ix) : 0);
         const int sgrid = sg_opt > 0 ? (int)std::min<int64_t>(sg_opt, p.grid) : p.grid;
@@ -1033,7 +1156,12 @@ static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq,
         const bool dbg_r = true;
 #endif
         const int capr = ((ix->scan_impl == 5 || r_auto) && !ix->steal_opt && dbg_r) ? scan2r_stage_cap(ix->dp, qt, f8) : 0;
-        if (capr >= 256) {
+        if (p.image) {   // the int8 row image (image_serves: k_scan2r's e4m3 shapes, stage >= 256)
+            ScanArgs a2 = a;
+            a2.stage_cap = scan2r_stage_cap(ix->dp, qt, 2);
+            VF_HIP(launch_scan2r(a2, qt, p.grid, 2, sst));
+            s.scan_kernel = 5;
+        } else if (capr >= 256) {
             ScanArgs a2 = a;
             a2.stage_cap = capr;
             VF_HIP(launch_scan2r(a2, qt, p.grid, f8, sst));
@@ -1060,13 +1188,14 @@ static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq,
             VF_HIP(hipEventRecord(s.ev_t[1], sst));
             const int64_t per_wave = ix->n / p.total_waves;
             const int64_t sampled = std::min<int64_t>(ix->n, (int64_t)p.total_waves * std::min<int64_t>(p.samp, per_wave));
-            ix->prof_bytes = (ix->n - sampled) * ((int64_t)ix->d * (ix->dtype == VF_DTYPE_FP8_E4M3 ? 1 : 2) + 4);
+            ix->prof_bytes = (ix->n - sampled) * (p.image ? (int64_t)ix->dp + 8 : (int64_t)ix->d * (ix->dtype == VF_DTYPE_FP8_E4M3 ? 1 : 2) + 4);
         }
         if (sst != st) VF_HIP(hipStreamWaitEvent(st, s.ev_scan, 0));
         FinalArgs f{};
         f.cnt = a.cnt; f.cand = a.cand; f.cap = p.cap; f.tau_bin = a.tau_bin; f.rows_orig = ix->rows_orig;
         f.orig_dtype = ix->dtype; f.orig_row_elems = ix->d; f.norm = ix->norm; f.qn = qn_b;
         f.d = ix->d; f.k = k; f.kprime = p.kprime; f.eps = p.eps; f.n_rows = ix->n; f.id_offset = ix->id_offset;
+        f.band = p.fine_band;
         f.out_ids = (long long*)(d_ids + (size_t)b0 * k); f.out_scores = d_scores + (size_t)b0 * k;
         f.flags = s.d_flags + b0; f.cand_count_out = s.d_counts + b0;
         f.dbg = nullptr;
@@ -1091,6 +1220,7 @@ static int end_impl(vf_index* ix, int slot_id) {
     stt.aux_cus = (s.path == 1 && s.scan_stream && s.scan_stream != s.stream) ? resolved_aux(ix) : 0;
     stt.scans_overlap = (s.path == 1 && resolved_overlap(ix)) ? 1 : 0;
     stt.scan_kernel = s.scan_kernel;
+    stt.scan_image = (s.path == 1) ? s.scan_image : 0;
     if (s.path == 1 && s.nq > 0 && s.k > 0) {
         if (s.timed) {
             float ms = 0.f;
@@ -1274,6 +1404,7 @@ static int group_end(vf_index* ix, int slot_id) {
                 tot.wide_launches = std::max(tot.wide_launches, st.wide_launches); tot.wide_queries = std::max(tot.wide_queries, st.wide_queries);
                 tot.aux_cus = std::max(tot.aux_cus, st.aux_cus); tot.scans_overlap = std::max(tot.scans_overlap, st.scans_overlap);
                 tot.scan_kernel = std::max(tot.scan_kernel, st.scan_kernel);
+                tot.scan_image = std::max(tot.scan_image, st.scan_image);
             }
         }
         if (r == VF_OK && !shard_is_staged(ix, g)) {

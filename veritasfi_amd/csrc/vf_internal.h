@@ -70,6 +70,7 @@ enum ScanMode { kModeSample = 0, kModeMain = 1 };
 struct ScanArgs {
     const char* rows;        // fp16 scan copy, row-major, row_bytes per row (dp * 2)
     const float* inv_scan;   // [n] 1 / (canonical norm * row scale): approx score = acc * inv_scan
+    const float* off_scan;   // int8 image only (k_scan2r, F8 = 2): [n + 64] per-row offset added to every approximate score; else null
     const _Float16* qimg;    // query image [dp/8][QN][8] fp16 (normalised queries, zero padded)
     long long n;             // rows in this shard
     int dp;                  // padded dim, multiple of 64
@@ -88,6 +89,7 @@ struct ScanArgs {
     u64* cand;               // [QN][cap] (orderkey(approx) << 32) | local row
     int cap;
     int kprime;              // k + margin: the threshold keeps >= kprime rows above it
+    int tau_band;            // bins every threshold is set below the one kprime rows reach (int8 image scan: 2 eps wide); 0 = none
     int refresh_every;       // recompute tau when a query's count crosses a multiple of this
     int nq;                  // real queries (<= QN); padded queries never pass
     u32* tile_cnt;           // [grid] pool counters: tiles claimed from the shared tail of each workgroup's row range (k_sel0 zeroes them); null = no stealing
@@ -109,6 +111,8 @@ struct FinalArgs {
     const float* qn;         // canonical normalised queries [nq][d] fp32
     int d; int k; int kprime; float eps;
     const float* eps_q;      // optional [nq] per-query certificate bound (k_scan_wide8: the query's own quantisation residual); null = eps
+    int band;                // > 0 (int8 image scan): re-score every candidate within `band` fine bins (1 / 16 384 each) of the k-th best
+                             // approximate score (kprime = k then); 0: the best kprime candidates
     long long n_rows;        // rows in the shard (certificate is moot when all were re-scored)
     long long id_offset;
     long long* out_ids; float* out_scores;   // [nq][k]
@@ -121,6 +125,9 @@ struct FinalArgs {
 hipError_t launch_prep_rows(const void* rows, int dt /* VF_DTYPE_* */, long long n, int d, int dp,
                             void* scan /*fp16 [n][dp] (fp8 rows: bytes [n][dp]); null when rows are used in place*/,
                             float* norm, float* inv_scan, hipStream_t s);
+// the int8 row image of fp16 / fp32 rows (after launch_prep_rows: it reads `norm`): bytes [n][dp], inv_img [n], max relative residual (float bits)
+hipError_t launch_prep_image(const void* rows, int dt, long long n, int d, int dp, const float* norm, unsigned char* img,
+                             float* inv_img, float* off_img, u32* rho_max_bits, float* rho_sum, hipStream_t s);
 hipError_t launch_prep_queries(const float* q, int nq, int d, int dp, int qn_tile /*32 or 64*/,
                                float* qn, _Float16* qimg, hipStream_t s);
 hipError_t launch_normalize_rows(const void* rows, int dt /* VF_DTYPE_* */, long long row0, long long nrows, int d,

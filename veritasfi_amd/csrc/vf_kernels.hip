@@ -129,6 +129,79 @@ __global__ __launch_bounds__(256) void k_prep_rows(const void* rows, int dt, lon
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// k_prep_image: the int8 row image of fp16 / fp32 rows -- one 16-lane group per row, after k_prep_rows (it reads the
+// canonical norm).  Per row: s = absmax / 127, code_j = rint(x_j / s) (|code| <= 127), stored as the byte code + 128 (cvt8_i8b undoes
+// it exactly), dp bytes with code 0 in the padding; inv_img = s / norm, so that the scan's approximate score stays acc x inv.
+// rho = ||x - s code|| / norm, summed in fp64 and rounded UP to a float, is the row's relative residual; the shard keeps the largest
+// (as float bits: a non-negative float orders like its bits; a non-finite row gives +inf or a NaN, both above every finite bound) and
+// the sum (the band's width).  off_img = rho (1 + 2^-11)(1 + 2^-20) + d 2^-24 rho, rounded up: what the row's
+// quantisation can move its score by, added to its approximate score by the scan (k_scan2r, F8 = 2) so that canonical <= key + eps.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_prep_image(const void* rows, int dt, long long n, int d, int dp, const float* norm,
+                                                     unsigned char* img, float* inv_img, float* off_img, u32* rho_max_bits, float* rho_sum) {
+    __shared__ u32 wg_max;
+    __shared__ float wg_sum;
+    if (threadIdx.x == 0) { wg_max = 0u; wg_sum = 0.0f; }
+    __syncthreads();
+    const int l = threadIdx.x & 15;
+    const long long r = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);
+    if (r < n) {   // (no early return: the whole block meets at the barrier below)
+        const long long base = r * (long long)d;
+        float mx = 0.0f;
+        for (int j = l; j < d; j += 16) mx = fmaxf(mx, fabsf(load_elem(rows, dt, base + j)));
+        for (int o = 8; o; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 16));
+        const bool finite = mx <= FLT_MAX;
+        const float sc = (finite && mx > 0.0f) ? mx / 127.0f : 1.0f;
+        double res = 0.0;
+        unsigned* out = (unsigned*)(img + r * (long long)dp);
+        for (int j0 = 4 * l; j0 < dp; j0 += 64) {   // four codes per lane per step: one 32-bit vector store
+            u32 w = 0u;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int j = j0 + e;
+                float code = 0.0f;
+                if (j < d) {
+                    const float x = load_elem(rows, dt, base + j);
+                    code = fminf(fmaxf(rintf(x / sc), -127.0f), 127.0f);
+                    const double dx = (double)x - (double)sc * (double)code;
+                    res += dx * dx;
+                }
+                w |= (u32)((int)code + 128) << (8 * e);
+            }
+            out[j0 >> 2] = w;
+        }
+        for (int o = 8; o; o >>= 1) res += __shfl_xor(res, o, 16);
+        if (l == 0) {
+            const float nm = norm[r];
+            inv_img[r] = (float)((double)sc / (double)nm);
+            float rho, off;
+            if (!finite) rho = off = INFINITY;
+            else {
+                const double rd = sqrt(res) / (double)nm;
+                rho = (float)rd;
+                if ((double)rho < rd) rho = nextafterf(rho, INFINITY);
+                const double od = rd * (1.0 + 0x1p-11) * (1.0 + 0x1p-20) + (double)d * 0x1p-24 * rd;
+                off = (float)od;
+                if ((double)off < od) off = nextafterf(off, INFINITY);
+            }
+            off_img[r] = off;
+            atomicMax(&wg_max, __float_as_uint(rho));
+            atomicAdd(&wg_sum, finite ? rho : 0.0f);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && wg_max) { atomicMax(rho_max_bits, wg_max); atomicAdd(rho_sum, wg_sum); }
+}
+
+hipError_t launch_prep_image(const void* rows, int dt, long long n, int d, int dp, const float* norm, unsigned char* img,
+                             float* inv_img, float* off_img, u32* rho_max_bits, float* rho_sum, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    const long long blocks = (n + 15) / 16;
+    hipLaunchKernelGGL(k_prep_image, dim3((unsigned)blocks), dim3(256), 0, s, rows, dt, n, d, dp, norm, img, inv_img, off_img, rho_max_bits, rho_sum);
+    return hipGetLastError();
+}
+
 hipError_t launch_prep_rows(const void* rows, int dt, long long n, int d, int dp, void* scan,
                             float* norm, float* inv_scan, hipStream_t s) {
     if (n <= 0) return hipSuccess;
@@ -588,6 +661,20 @@ __device__ __forceinline__ h8 cvt8_e4m3(u32 w0, u32 w1) {
     return r;
 }
 
+// int8 row image (k_prep_image): byte b = code + 128, code in [-127, 127].  v_perm_b32 puts b under a 0x64 high byte -- the fp16
+// value 1024 + b, exactly -- and one v_pk_add_f16 of -1152 per two codes leaves the code itself, exactly (every integer of magnitude
+// <= 2048 is an fp16 value): two VALU ops per two codes, no scale (the row's scale sits in its inverse norm)
+__device__ __forceinline__ h8 cvt8_i8b(u32 w0, u32 w1) {
+    const h2v off = {(_Float16)-1152.0f, (_Float16)-1152.0f};
+    const h2v a = __builtin_bit_cast(h2v, __builtin_amdgcn_perm(0x64646464u, w0, 0x04010400u)) + off;
+    const h2v b = __builtin_bit_cast(h2v, __builtin_amdgcn_perm(0x64646464u, w0, 0x04030402u)) + off;
+    const h2v c = __builtin_bit_cast(h2v, __builtin_amdgcn_perm(0x64646464u, w1, 0x04010400u)) + off;
+    const h2v d = __builtin_bit_cast(h2v, __builtin_amdgcn_perm(0x64646464u, w1, 0x04030402u)) + off;
+    h8 r;
+    r[0] = a[0]; r[1] = a[1]; r[2] = b[0]; r[3] = b[1]; r[4] = c[0]; r[5] = c[1]; r[6] = d[0]; r[7] = d[1];
+    return r;
+}
+
 template <int G>
 __device__ __forceinline__ void issue_loads_f8(uint4 (&buf)[2 * G], const char* rows, long long row_bytes, long long myrow,
                                                int ss, int h) {
@@ -694,6 +781,7 @@ struct EpiRegs {
     int tau_g[NT];
     bool sync_tau;
     const char* inv_lds = nullptr;   // k_scan2 / k_scan2r: the tile's 32 reciprocal norms as floats in LDS (the scratch half the DMA filled); nullptr: inv_lane
+    float off_lane = 0.0f;           // OFF (k_scan2r on the int8 image): lane r (and r + 32) holds row r's score offset; inv_lds + 128: the 32 offsets
 };
 
 // Wave-wide OR / sum of a 32-bit value, result uniform (an SGPR): four DPP row rotations leave every lane with its row's
@@ -731,7 +819,8 @@ __device__ __forceinline__ void epi_prefetch(EpiRegs<NT>& e, const ScanArgs& a, 
 // PUBLISH = false (k_scan2): the wave only STAGES its candidates; publishing completed blocks to the global histograms and
 // refreshing thresholds is the service wave's job (k_scan2_service), so that no global atomic or dependent load of this
 // path ever sits in a streaming wave's in-order memory queue.
-template <int NT, int MODE, bool PUBLISH = true, bool INV_LDS = false>
+// OFF (the int8 image): every score is acc x inv + the row's offset (ScanArgs::off_scan), in the sample pass as in the filter.
+template <int NT, int MODE, bool PUBLISH = true, bool INV_LDS = false, bool OFF = false>
 __device__ __forceinline__ void tile_epilogue(const ScanArgs& a, const f16v (&acc)[NT], const EpiRegs<NT>& e,
                                               long long t0, long long hi, long long s0_slot, int lane, char* ctl) {
     const int r31 = lane & 31, h = lane >> 5;
@@ -743,6 +832,12 @@ __device__ __forceinline__ void tile_epilogue(const ScanArgs& a, const f16v (&ac
         const float hi_half = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, e.inv_lane), r0 + 4));
         return h ? hi_half : lo_half;
     };
+    auto off_of = [&](int reg) {
+        const int r0 = (reg & 3) + 8 * (reg >> 2);
+        const float lo_half = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, e.off_lane), r0));
+        const float hi_half = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, e.off_lane), r0 + 4));
+        return h ? hi_half : lo_half;
+    };
     if (MODE == kModeSample) {
         const long long s0_stride = (long long)a.total_waves * a.samp;
 #pragma unroll
@@ -751,7 +846,11 @@ __device__ __forceinline__ void tile_epilogue(const ScanArgs& a, const f16v (&ac
 #pragma unroll
             for (int reg = 0; reg < 16; ++reg) {
                 const int rr = (reg & 3) + 8 * (reg >> 2) + 4 * h;
-                if (t0 + rr < hi) a.s0[(long long)q * s0_stride + s0_slot + rr] = acc[nt][reg] * inv_of(reg);
+                if constexpr (OFF) {
+                    if (t0 + rr < hi) a.s0[(long long)q * s0_stride + s0_slot + rr] = acc[nt][reg] * inv_of(reg) + off_of(reg);
+                } else {
+                    if (t0 + rr < hi) a.s0[(long long)q * s0_stride + s0_slot + rr] = acc[nt][reg] * inv_of(reg);
+                }
             }
         }
         return;
@@ -782,6 +881,15 @@ __device__ __forceinline__ void tile_epilogue(const ScanArgs& a, const f16v (&ac
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) inv16[reg] = inv_of(reg);
     }
+    float off16[16];
+    if constexpr (OFF) {
+        static_assert(INV_LDS, "the offsets ride in the scratch half the inverse norms' DMA fills");
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const float4 v = *(const float4*)(e.inv_lds + 128 + (8 * g + 4 * h) * 4);
+            off16[4 * g] = v.x; off16[4 * g + 1] = v.y; off16[4 * g + 2] = v.z; off16[4 * g + 3] = v.w;
+        }
+    }
     const long long left = hi - t0;
     const int lf = __builtin_amdgcn_readfirstlane((int)(left < kRowTile ? left : kRowTile));   // (wave-uniform by construction: a scalar branch)
     if (lf < kRowTile) {
@@ -802,7 +910,8 @@ __device__ __forceinline__ void tile_epilogue(const ScanArgs& a, const f16v (&ac
         float top = -INFINITY;
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {
-            m[nt * 16 + reg] = acc[nt][reg] * inv16[reg];
+            if constexpr (OFF) m[nt * 16 + reg] = acc[nt][reg] * inv16[reg] + off16[reg];
+            else m[nt * 16 + reg] = acc[nt][reg] * inv16[reg];
             top = fmaxf(top, m[nt * 16 + reg]);                        // (a NaN -- a row that does not exist -- never wins)
         }
         any |= bin_x(top) >= tb[nt];
@@ -883,7 +992,7 @@ __device__ __forceinline__ void tile_epilogue(const ScanArgs& a, const f16v (&ac
     if constexpr (!PUBLISH) return;
     if (need) {
         // (1) refresh one tau from what is published so far (two dependent L2 reads)
-        const int nb = wave_tau_two_level(a.hist_coarse + qq * 64, a.hist + (long long)qq * kHistBins, a.kprime, lane);
+        const int nb = wave_tau_two_level(a.hist_coarse + qq * 64, a.hist + (long long)qq * kHistBins, a.kprime, lane) - a.tau_band;
         if (lane == 0 && nb > 0) {
             atomicMax(a.tau_bin + qq, nb);
             atomicMax(tau_lds + qq, nb);
@@ -1275,7 +1384,7 @@ __device__ __forceinline__ void k_scan2_service(const ScanArgs& a, char* ctl, in
 #pragma unroll
             for (int o = 32; o; o >>= 1) qq = max(qq, __shfl_xor(qq, o));
             if (qq >= 0 && !(a.debug & 2)) {
-                const int nb = wave_tau_two_level(a.hist_coarse + qq * 64, a.hist + (long long)qq * kHistBins, a.kprime, lane);
+                const int nb = wave_tau_two_level(a.hist_coarse + qq * 64, a.hist + (long long)qq * kHistBins, a.kprime, lane) - a.tau_band;
                 if (lane == 0 && nb > 0) { atomicMax(a.tau_bin + qq, nb); atomicMax(tau_lds + qq, nb); }
             }
             continue;
@@ -1587,6 +1696,9 @@ __global__ __launch_bounds__(kScan2Threads) void k_scan2(ScanArgs a) {
 //   e4m3 rows, dp =  768: S =  6, RB = 3 (a segment is 128 elements: 16 KB of image, 64 registers), RING = 6
 //   e4m3 rows, dp = 1024: S =  8, RB = 3 (with the 32 accumulators the 256 accumulator registers hold no fourth), RING = 4
 // (e4m3 rows are converted in registers like k_scan2's F8 variant: every e4m3 value is an fp16 value, the image is shared.)
+// F8 = 2: the int8 row image of fp16 / fp32 rows of 768 elements (k_prep_image) -- one byte per element like e4m3 rows, so the e4m3
+// shape; the bytes are converted by cvt8_i8b (exact), the row's scale rides in its inverse norm and its quantisation bound is added to
+// every score (ScanArgs::off_scan).
 struct Scan2rShape { int S, RB, RING; };
 static Scan2rShape scan2r_shape(int dp, int f8) {
     if (!f8 && dp == 768) return {12, 6, 6};
@@ -1719,7 +1831,8 @@ __global__ __launch_bounds__(kScan2Waves * 64) void k_scan2r(ScanArgs a) {
     };
     auto issue_epi = [&](long long t0, bool sync_tau, int par) {
         par = __builtin_amdgcn_readfirstlane(par);
-        dma4(a.inv_scan + t0 + r31, scratch_l + par * 512 + 256);
+        // (int8 image: lanes 32..63 bring the 32 rows' score offsets instead of repeating their inverse norms; off_scan is padded like inv_scan)
+        dma4((F8 == 2 && h) ? a.off_scan + t0 + r31 : a.inv_scan + t0 + r31, scratch_l + par * 512 + 256);
         if (sync_tau) dma4(a.tau_bin + (lane < QN ? lane : QN - 1), scratch_l + par * 512);
     };
     int cur_tile = __builtin_amdgcn_readfirstlane(wid);                // (a scalar from here on: tile addresses stay in SGPRs)
@@ -1881,7 +1994,8 @@ __global__ __launch_bounds__(kScan2Waves * 64) void k_scan2r(ScanArgs a) {
                                 af = __builtin_bit_cast(h8, raw);
                             } else
 #endif
-                            af = (i & 1) ? cvt8_e4m3(w.z, w.w) : cvt8_e4m3(w.x, w.y);
+                            if constexpr (F8 == 2) af = (i & 1) ? cvt8_i8b(w.z, w.w) : cvt8_i8b(w.x, w.y);   // int8 image rows
+                            else af = (i & 1) ? cvt8_e4m3(w.z, w.w) : cvt8_e4m3(w.x, w.y);
 #pragma unroll
                             for (int nt = 0; nt < NT; ++nt)
                                 acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, sgc < 0 ? bl[4 * c + i][nt] : bfrag(4 * c + i, nt), acc[nt], 0, 0, 0);
@@ -1913,12 +2027,13 @@ __global__ __launch_bounds__(kScan2Waves * 64) void k_scan2r(ScanArgs a) {
             EpiRegs<NT> epi;
             epi.inv_lane = *(const float*)(sc + 256 + r31 * 4);
             epi.inv_lds = sc + 256;
+            if constexpr (F8 == 2) epi.off_lane = *(const float*)(sc + 384 + r31 * 4);
             epi.sync_tau = sync_now;
             if (sync_now) {
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) epi.tau_g[nt] = *(const int*)(sc + (nt * kQueryTile + r31) * 4);
             }
-            tile_epilogue<NT, MODE, true, true>(a, acc, epi, t0, t_hi, t_s0, lane, ctl);
+            tile_epilogue<NT, MODE, true, true, F8 == 2>(a, acc, epi, t0, t_hi, t_s0, lane, ctl);
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
@@ -2277,7 +2392,7 @@ __device__ __forceinline__ void wide_epilogue(const ScanArgs& a, const f16v (&ac
         m &= m - 1ull;
         const u32 blk0 = (u32)__shfl((int)myslot, leader) & ~Rm1;   // first entry of the completed block
         const int qq = qg0 + __shfl(myq, leader);
-        const int nb = wave_tau_two_level(a.hist_coarse + qq * 64, a.hist + (long long)qq * kHistBins, a.kprime, lane);
+        const int nb = wave_tau_two_level(a.hist_coarse + qq * 64, a.hist + (long long)qq * kHistBins, a.kprime, lane) - a.tau_band;
         if (lane == 0 && nb > 0) {
             atomicMax(a.tau_bin + qq, nb);
             atomicMax(tau_lds + (qq - qg0), nb);
@@ -3207,7 +3322,8 @@ hipError_t launch_scan2(const ScanArgs& a, int qn_tile, int grid, int rows_are_f
 }
 
 // every (query tile, mode, shape) instantiation of k_scan2r, as X(NT, MODE, F8, S, RB, RING)
-#define VF_SCAN2R_PRODUCT(X, NT, MODE) X(NT, MODE, 0, 12, 6, 6, 1) X(NT, MODE, 0, 16, 6, 4, 1) X(NT, MODE, 0, 8, 4, 6, 1) X(NT, MODE, 0, 6, 3, 6, 1) X(NT, MODE, 1, 6, 3, 6, 1) X(NT, MODE, 1, 8, 3, 4, 1)
+#define VF_SCAN2R_PRODUCT(X, NT, MODE) X(NT, MODE, 0, 12, 6, 6, 1) X(NT, MODE, 0, 16, 6, 4, 1) X(NT, MODE, 0, 8, 4, 6, 1) X(NT, MODE, 0, 6, 3, 6, 1) X(NT, MODE, 1, 6, 3, 6, 1) X(NT, MODE, 1, 8, 3, 4, 1) \
+    X(NT, MODE, 2, 6, 3, 6, 1)
 #ifdef VF_EXPERIMENTS
 #define VF_SCAN2R_SHAPES(X, NT, MODE) VF_SCAN2R_PRODUCT(X, NT, MODE) X(NT, MODE, 0, 12, 6, 6, 0) X(NT, MODE, 1, 6, 3, 4, 1)   // (+ the first form: debug bit 10; + a four-segment ring on e4m3 rows of 768: bit 11)
 #else
@@ -3217,7 +3333,7 @@ hipError_t launch_scan2(const ScanArgs& a, int qn_tile, int grid, int rows_are_f
 static hipError_t launch_scan2r_any(const ScanArgs& a, int qn_tile, int mode, int grid, int f8, size_t lds, hipStream_t s) {
     Scan2rShape sh = scan2r_shape(a.dp, f8);
 #ifdef VF_EXPERIMENTS
-    if (f8 && a.dp == 768 && (a.debug & 2048)) sh.RING = 4;   // timing experiment: is the scan bound by what a wave keeps in flight?  (LDS sized for six: harmless)
+    if (f8 == 1 && a.dp == 768 && (a.debug & 2048)) sh.RING = 4;   // timing experiment: is the scan bound by what a wave keeps in flight?  (LDS sized for six: harmless)
 #endif
     const int nt = qn_tile / kQueryTile;
     bool done = false;
@@ -3338,7 +3454,7 @@ __global__ __launch_bounds__(1024) void k_sel0(ScanArgs a) {
     __syncthreads();
     if (tid < 64) {
         const int nb = wave_tau_from_lds(lh, a.kprime, tid);
-        if (tid == 0) sbin = nb > 0 ? nb : 0;
+        if (tid == 0) sbin = nb - a.tau_band > 0 ? nb - a.tau_band : 0;   // (band: ScanArgs::tau_band)
     }
     __syncthreads();
     const int tb = sbin;
@@ -3600,7 +3716,10 @@ __global__ __launch_bounds__(kFinalThreads) void k_final(FinalArgs a) {
     for (int i = tid; i < n; i += kFinalThreads) atomicAdd(&lh[fine_bin(cq[i])], 1u);
     __syncthreads();
     if (tid < 64) {
-        const int nb = wave_tau_from_lds(lh, mwant > 0 ? mwant : 1, tid);
+        int nb = wave_tau_from_lds(lh, mwant > 0 ? mwant : 1, tid);
+        // band mode (int8 image scan, kprime = k): every candidate within 2 eps of the k-th best approximate score -- `band` fine bins
+        // of 1 / 16 384, or band / 16 threshold bins without a threshold -- but none below the scan's threshold (fine bin 0)
+        if (a.band > 0 && nb > 0) nb = max(nb - (tbin > 0 ? a.band : (a.band + 15) / 16), tbin > 0 ? 1 : 0);
         if (tid == 0) s_bin = nb > 0 ? nb : 0;
     }
     __syncthreads();
@@ -3680,7 +3799,12 @@ __global__ __launch_bounds__(kFinalThreads) void k_final(FinalArgs a) {
             if (a.k > m) flag = 1;
             else if (flag == 0) {
                 const float ck_k = unorderkey((u32)(ranked[a.k - 1] >> 32));
-                if (!(ck_k > approx_floor + (a.eps_q ? fmaxf(a.eps_q[q], a.eps) : a.eps))) flag = 1;
+                // band mode: what a row that was not re-scored can have is bounded by the cut itself -- its fine bin is below sbin, i.e.
+                // bin_x(s) < forig + (sbin - 1) / fscale (exact in fp32), so s < that edge mapped back + 2^-20 (bin_x's rounding) -- not by
+                // the smallest survivor, which a sparse band (k = 1) leaves far above the cut
+                float bound = approx_floor;
+                if (a.band > 0 && sbin > 0) bound = (forig + (float)(sbin - 1) / fscale - 0.5f * kHistBins) / (0.5f * kHistBins) + 0x1p-20f;
+                if (!(ck_k > bound + (a.eps_q ? fmaxf(a.eps_q[q], a.eps) : a.eps))) flag = 1;
             }
         }
         // flags / counts live in host-mapped pinned memory: no device-to-host copy kernel needed
@@ -3698,6 +3822,7 @@ hipError_t launch_final(FinalArgs a, int nq, hipStream_t s) {
     // does not fit is recomputed by the exact path).  Sized at 1.25 k' rounded up to a power of two: at k' = 1504 that is 2048 entries
     // instead of 4096 -- 40 instead of 57 KB of LDS per workgroup, four workgroups per CU instead of two for a latency-bound gather
     while (sc < a.kprime + a.kprime / 4 && sc < 4096) sc <<= 1;
+    if (a.band > 0) sc = 4096;   // band mode: the 2 eps band holds ~5-10 k rows on ordinary data; more is the exact path's
     a.sel_cap = sc > a.top_cap ? sc : a.top_cap;
     const size_t lds = ((size_t)a.top_cap + a.sel_cap) * 8 + ((size_t)a.d + 4 + kHistBins + 4) * 4;
     hipLaunchKernelGGL(k_final, dim3(nq), dim3(kFinalThreads), lds, s, a);
