@@ -1,0 +1,164 @@
+#!/usr/bin/env python3
+"""A/B of the search paths for rows of 2560 to 4096 padded elements, on ONE index in ONE process.
+
+    python tools/bench_wide_rows.py --n 1000000 --d 2560 --nq 4 --k 100 [--dtype f16|f32] [--scan-wide] [--verify 2]
+
+Settings: `path2` (option wide_rows = 0: the chunked exact path, what these rows took before k_scan_ksplit existed), `ksplit`
+(wide_rows = 2, wide = 0: the fused path on k_scan_ksplit, 32-query passes at every batch size) and, with --scan-wide, `scan_wide` (wide_rows = 2 and
+wide = 2: the batch goes to k_scan_wide's 256-query tiles; only for nq >= 2).  Every setting is warmed up; then timed windows
+of at least --window seconds each, the settings ALTERNATING, --rounds rounds; the spread over the rounds is printed.  Batches are
+pipelined two deep through the slots (vf_index_search_begin / _end) with resident inputs, as bench.py does; on the fused path
+HIP events around the main scan launches give the launch time (vf_index_profile) and the launch interval (vf_index_profile_span).
+One JSON line: ms per batch per setting (median, min, max over the rounds), the byte rate n (2 dp + 4) / launch interval of the
+ksplit setting as a fraction of 8 TB/s, and `verified`: ids and score bits of --verify queries against the CPU oracle."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=1_000_000)
+    ap.add_argument("--d", type=int, default=2560)
+    ap.add_argument("--nq", default="4", help="queries per batch; a comma list runs every value on the same index")
+    ap.add_argument("--k", default="100", help="results per query; a comma list runs every value")
+    ap.add_argument("--dtype", choices=["f16", "f32"], default="f16")
+    ap.add_argument("--scan-wide", action="store_true", help="also time k_scan_wide forced onto these rows (nq >= 2)")
+    ap.add_argument("--scan-wide-from", type=int, default=2, help="with --scan-wide: only for batches of at least this many queries")
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--window", type=float, default=1.0, help="seconds per timed window, at least")
+    ap.add_argument("--verify", type=int, default=2, help="queries checked against the CPU oracle (0 = none)")
+    ap.add_argument("--seed", type=int, default=1234)
+    args = ap.parse_args()
+
+    import torch
+    import veritasfi_amd as vf
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev)
+    g.manual_seed(args.seed)
+    tdt = torch.float16 if args.dtype == "f16" else torch.float32
+    corpus = torch.empty((args.n, args.d), dtype=tdt, device=dev)
+    for lo in range(0, args.n, 100_000):
+        hi = min(args.n, lo + 100_000)
+        corpus[lo:hi] = torch.randn((hi - lo, args.d), generator=g, device=dev, dtype=torch.float32).to(tdt)
+    dp = (args.d + 127) // 128 * 128
+    host = None
+
+    index = vf.DenseIndex(corpus)
+    ok_all = True
+    try:
+        for k in [int(x) for x in args.k.split(",")]:
+            for nq in [int(x) for x in args.nq.split(",")]:
+                out, host = cell(args, torch, vf, index, corpus, g, dev, dp, nq, k, host)
+                print(json.dumps(out), flush=True)
+                ok_all = ok_all and out.get("verified", out["settings_agree_bitwise"])
+    finally:
+        index.close()
+    return 0 if ok_all else 1
+
+
+def cell(args, torch, vf, index, corpus, g, dev, dp, nq, k, host):
+    qpool = [torch.randn((nq, args.d), generator=g, device=dev, dtype=torch.float32) for _ in range(2)]
+    ids = [torch.empty((nq, k), dtype=torch.int64, device=dev) for _ in range(2)]
+    sc = [torch.empty((nq, k), dtype=torch.float32, device=dev) for _ in range(2)]
+    settings = [("path2", {"wide_rows": 0, "wide": 1}), ("ksplit", {"wide_rows": 2, "wide": 0})]
+    if args.scan_wide and nq >= max(2, args.scan_wide_from):
+        settings.append(("scan_wide", {"wide_rows": 2, "wide": 2}))
+    out = {"n": args.n, "d": args.d, "dp": dp, "nq": nq, "k": k, "dtype": args.dtype, "rounds": args.rounds, "window_s": args.window, "settings": {}}
+    try:
+        stream = torch.cuda.Stream(device=dev)
+
+        def apply(opts):
+            for name, val in opts.items():
+                index.set_option(name, val)
+
+        def run(steps):
+            for i in range(steps + 1):
+                if i < steps:
+                    index.search_begin(i & 1, qpool[i & 1], k, ids[i & 1], sc[i & 1])
+                if i >= 1:
+                    index.search_end((i - 1) & 1)
+
+        per_step, stats, results = {}, {}, {}
+        with torch.cuda.stream(stream):
+            for name, opts in settings:          # warm-up of every setting; the step count of a window from a first timing
+                apply(opts)
+                run(2)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                run(4)
+                torch.cuda.synchronize()
+                per_step[name] = (time.perf_counter() - t0) / 4
+                stats[name] = index.stats()
+                results[name] = (ids[1].cpu().numpy().copy(), sc[1].cpu().numpy().copy())   # (4 steps: the last batch is qpool[1])
+            times = {name: [] for name, _ in settings}
+            launch = {name: [] for name, _ in settings}
+            interval = {name: [] for name, _ in settings}
+            for _ in range(args.rounds):
+                for name, opts in settings:
+                    apply(opts)
+                    steps = max(4, int(args.window / max(per_step[name], 1e-6)) + 1)
+                    run(2)
+                    torch.cuda.synchronize()
+                    index.set_option("profile", 1)
+                    t0 = time.perf_counter()
+                    run(steps)
+                    torch.cuda.synchronize()
+                    el = time.perf_counter() - t0
+                    prof = index.profile()
+                    index.set_option("profile", 0)
+                    times[name].append(1e3 * el / steps)
+                    if prof["scan_launches"] > 0:
+                        launch[name].append(prof["scan_ms_total"] / prof["scan_launches"])
+                        if prof["span_ms"] > 0:
+                            interval[name].append(prof["span_ms"] / prof["scan_launches"])
+        for name, _ in settings:
+            t = times[name]
+            rec = {"ms_per_batch": round(statistics.median(t), 4), "min": round(min(t), 4), "max": round(max(t), 4),
+                   "spread": round((max(t) - min(t)) / statistics.median(t), 4), "path": stats[name]["path"], "scan_kernel": stats[name]["scan_kernel"],
+                   "exact_reruns_last_batch": stats[name]["exact_reruns"], "overflowed_last_batch": stats[name]["overflowed"]}
+            if launch[name]:
+                rec["scan_launch_ms"] = round(statistics.median(launch[name]), 4)
+            if interval[name]:
+                iv = statistics.median(interval[name])
+                rec["launch_interval_ms"] = round(iv, 4)
+                # one pass reads the shard once, rows + reciprocal norms (k_scan_ksplit: a pass per 32 queries; the events bracket a
+                # batch's first pass, the interval is per batch)
+                passes = (nq + 31) // 32 if stats[name]["scan_kernel"] == 6 else 1
+                rec["passes_per_batch"] = passes
+                rec["bytes_per_pass"] = args.n * (2 * dp + 4)
+                rec["byte_rate_TBps"] = round(passes * args.n * (2 * dp + 4) / (iv * 1e-3) / 1e12, 3)
+                rec["frac_of_8TBps"] = round(passes * args.n * (2 * dp + 4) / (iv * 1e-3) / 8e12, 4)
+            out["settings"][name] = rec
+            print(f"# {name:9s} {rec['ms_per_batch']:9.4f} ms/batch (min {rec['min']:.4f} max {rec['max']:.4f}) path {rec['path']} kernel {rec['scan_kernel']}"
+                  + (f" launch {rec.get('scan_launch_ms')} ms interval {rec.get('launch_interval_ms')} ms {rec.get('frac_of_8TBps')} of 8 TB/s" if launch[name] else ""),
+                  file=sys.stderr, flush=True)
+        base = results["path2"]
+        same = all(np.array_equal(results[n_][0], base[0]) and np.array_equal(results[n_][1].view(np.uint32), base[1].view(np.uint32)) for n_, _ in settings)
+        out["settings_agree_bitwise"] = bool(same)
+        if args.verify > 0:
+            from oracle import canonical as oracle
+            oracle.build()
+            nv = min(args.verify, nq)
+            if host is None:
+                host = corpus.cpu().numpy()
+            wi, ws = oracle.search(host, qpool[1][:nv].cpu().numpy(), k)
+            out["verified"] = bool(same and all(np.array_equal(results[n_][0][:nv], wi) and np.array_equal(results[n_][1][:nv].view(np.uint32), ws.view(np.uint32))
+                                                for n_, _ in settings))
+            out["verified_queries"] = nv
+    finally:
+        for name, val in (("wide_rows", 1), ("wide", 1), ("profile", 0)):
+            index.set_option(name, val)
+    return out, host
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -175,7 +175,7 @@ struct vf_index {
     // options
     int64_t force_path = -1, sample_rows = -1, margin = -1, cap_opt = 0, waves_opt = 0, scan_g = 0,
             refresh_every = 128, debug = 0, steal_opt = 0, wide_opt = 1, wide_sync = -1, wide_mfma = -1, wide8_waves = 8, wide8_stage = 0,
-            aux_cus = -1, sample_grid = -1, overlap_scans = -1, scan_impl = 2, sample_impl = -1, scan_image = 1;   // aux_cus / overlap_scans: -1 = auto (resolved_split)   // scan_impl: 1 = k_scan (register loads), 2 = k_scan2 (whole-line LDS-DMA) where it fits   // aux_cus: CUs the main scan leaves to the small kernels of the other slots (0 = no split)   // wide_sync: -1 siblings of a wide row group run free (default: fastest), >= 0 = the slack in super-tiles  // steal_opt: cross-workgroup tile pool in the main scan (measured slower: DESIGN.md 5)  // wide_opt: 0 never, 1 auto (nq >= 129), > 1 = from that many queries
+            aux_cus = -1, sample_grid = -1, overlap_scans = -1, scan_impl = 2, sample_impl = -1, scan_image = 1, wide_rows = 1;   // aux_cus / overlap_scans: -1 = auto (resolved_split)   // scan_impl: 1 = k_scan (register loads), 2 = k_scan2 (whole-line LDS-DMA) where it fits   // aux_cus: CUs the main scan leaves to the small kernels of the other slots (0 = no split)   // wide_sync: -1 siblings of a wide row group run free (default: fastest), >= 0 = the slack in super-tiles  // steal_opt: cross-workgroup tile pool in the main scan (measured slower: DESIGN.md 5)  // wide_opt: 0 never, 1 auto (nq >= 129), > 1 = from that many queries
     vf_search_stats stats{};
     bool profile = false;
     double prof_scan_ms = 0.0, prof_pipe_ms = 0.0;
@@ -703,6 +703,7 @@ extern "C" int vf_index_set_option(vf_index* ix, const char* name, int64_t value
         else VF_TRY(build_image(ix, value));
         ix->scan_image = value;
     }
+    else if (s == "wide_rows") { if (!in_range(0, 2)) return fail(VF_EINVAL, "wide_rows must be 0 (rows of more than 2432 padded elements never take the fused path), 1 (auto: from 131 072 rows) or 2 (wherever k_scan_ksplit serves them)"); ix->wide_rows = value; }
     else if (s == "debug") ix->debug = value;
     else if (s == "profile") {
         ix->profile = value != 0; ix->prof_scan_ms = ix->prof_pipe_ms = 0.0; ix->prof_launches = 0;
@@ -777,17 +778,37 @@ struct FusedPlan {
 
 static int qn_tile_for(int nq_batch) { return nq_batch <= kQueryTile ? kQueryTile : kMaxBatch; }
 
-static bool fused_possible(const vf_index* ix, int k) {
+// Rows of 2560 to 4096 padded elements (fp16, or the fp16 scan copy of fp32 rows): a 32-query image does not fit the LDS, so k_scan cannot
+// serve them; k_scan_ksplit does (the contraction split over four waves, the image in registers + LDS).  Option wide_rows: 0 never, 2
+// wherever the kernel serves the rows, 1 (auto) from kWideRowsMinRows rows.
+// The count is measured (tools/bench_wide_rows.py, one box, the settings alternating, three windows of a second each;
+// profiles/r08_wide_rows_threshold.log): the chunked exact path against this one at 32 768 / 65 536 / 131 072 / 262 144 / 1 048 576 rows,
+// 1 / 4 / 64 queries, k = 100 / 2048.  At k = 100 the fused path wins everywhere (32 768 x 2560, one query: 0.139 against 0.329 ms).  At
+// k = 2048 with one or four queries k_final's re-score of k' = 2 560+ rows per query is the step, and the fused path LOSES at 32 768 rows
+// (2560: 0.579 / 0.619 against 0.357 / 0.479 ms; 4096: 0.912 / 0.975 against 0.520 / 0.571) and, for 4096-wide rows, at 65 536
+// (1.231 / 1.287 against 1.025 / 1.104; 2560-wide rows are 1 to 4 % ahead there: a tie); from 131 072 rows it wins every cell at both widths
+// (k = 2048, one query: 0.845 against 1.375 ms at 2560, 1.406 against 2.036 at 4096) and the margin grows with n (1M x 2560: 0.86
+// against 10.1 ms).  So: 131 072 for every width.  Below it the existing behaviour stays (tests/test_gpu_retrieval.py::
+// test_wide_rows_and_path_limits: 17 000 x 2560 on path 2).
+constexpr int64_t kWideRowsMinRows = 131072;
+static bool ksplit_width(const vf_index* ix) { return scan_lds_bytes(ix->dp, kQueryTile) > 160 * 1024; }   // no LDS-resident 32-query image: dp > 2432
+static bool ksplit_serves(const vf_index* ix, bool forced) {
+    if (ix->wide_rows == 0 || ix->dtype == VF_DTYPE_FP8_E4M3 || scan_ksplit_stage_cap(ix->dp) < 256) return false;
+    return forced || ix->wide_rows == 2 || ix->n >= kWideRowsMinRows;
+}
+
+static bool fused_possible(const vf_index* ix, int k, bool forced = false) {
     if (ix->n <= 1024 || k > kMaxKFused || k <= 0) return false;
     // corpora of up to kSmallN rows are built WITHOUT the scan copy and its inverse norms (they never take the fused path on their
     // own): forcing path 1 on one must be refused, not run on null operands (round 4: found by the option fuzz -- a memory fault)
     if (!ix->rows_scan || !ix->inv_scan) return false;
-    if (scan_lds_bytes(ix->dp, kQueryTile) > 160 * 1024) return false;
+    if (ksplit_width(ix)) return ix->n > kSmallN && ksplit_serves(ix, forced);
     return true;
 }
 
 static int batch_limit(const vf_index* ix) {
     // 64 queries need dp * 64 * 2 bytes of LDS; fall back to 32-query passes for wide rows
+    // (k_scan_ksplit's rows: 32 as well)
     return scan_lds_bytes(ix->dp, kMaxBatch) <= 160 * 1024 ? kMaxBatch : kQueryTile;
 }
 
@@ -829,7 +850,21 @@ static FusedPlan make_plan(const vf_index* ix, int k, bool image = false) {
     FusedPlan p;
     p.image = image; p.tau_band = 0; p.fine_band = 0;
     // k' = k + margin, rounded up to a multiple of 32 (whole re-score rounds of 32 row groups)
-    const int margin = ix->margin >= 0 ? (int)ix->margin : std::max(24, k / 4);
+    int margin = ix->margin >= 0 ? (int)ix->margin : std::max(24, k / 4);
+    // Rows only k_scan_ksplit serves (2560 to 4096 padded elements): the certificate needs the k-th canonical score to clear the k'-th
+    // approximate score by eps, and eps grows with d (2 d 2^-24: 4.9e-4 at d = 4096, beside 2^-11 per fp16 rounding) while the scores of
+    // isotropic rows crowd together like 1 / sqrt(d).  Around rank k such rows lie k z sqrt(d) to the unit of score (z = the normal
+    // quantile of k / n, <= sqrt(2 ln(n / k))), so k + k / 4 leaves a gap of 1.2 to 1.8 eps at d = 3072 .. 4096 and a fifth to a third of
+    // the queries of an N(0, 1) corpus failed the certificate (40 000 rows, k = 100; exact through the repair, at its price).  The margin
+    // is set for an expected gap of 2.5 eps on such rows -- the sum of `margin` spacings scatters by 1 / sqrt(margin) of itself, so 2.5 is
+    // four to five deviations at margin >= 40; real embeddings spread wider and need less.  A speed setting: results do not depend on it.
+    const double u16 = 1.0 / 2048.0;
+    const float eps_plan = (float)(u16 * (ix->dtype == VF_DTYPE_F32 ? 2.0 : 1.0) + sqrt((double)ix->d) * ldexp(1.0, -24) +
+                                   2.0 * ix->d * ldexp(1.0, -24) + 1e-6);
+    if (ix->margin < 0 && ksplit_width(ix)) {
+        const double z = sqrt(2.0 * log(std::max(3.0, (double)ix->n / k)));
+        margin = std::max(margin, (int)ceil(2.5 * eps_plan * k * z * sqrt((double)ix->d)));
+    }
     p.kprime = ix->margin >= 0 ? k + margin : (k + margin + 31) / 32 * 32;
     p.kprime = std::min(p.kprime, 4096);  // k_final ranks into a fixed 4096-entry LDS array (k <= kMaxKFused = 2048)
     int cap = kMaxCap;
@@ -868,9 +903,9 @@ static FusedPlan make_plan(const vf_index* ix, int k, bool image = false) {
     // dot product by <= 2^-11 * sum|q_j c_j| <= 2^-11 (Cauchy-Schwarz, both vectors of unit norm); rounding an fp32
     // corpus row to fp16 adds the same again.  Then the fp16 subnormal floor (2^-25 per element against a unit
     // vector: sqrt(d) * 2^-24 covers it twice) and the two fp32 dot products (d * 2^-24 each).
-    const double u16 = 1.0 / 2048.0;
-    p.eps = (float)(u16 * (ix->dtype == VF_DTYPE_F32 ? 2.0 : 1.0) + sqrt((double)ix->d) * ldexp(1.0, -24) +
-                    2.0 * ix->d * ldexp(1.0, -24) + 1e-6);
+    // (k_scan_ksplit adds a row's dp products per quarter, then across quarters: still one sum of the same terms with dp - 1 additions, and
+    // d 2^-24 times the sum of their magnitudes (<= 1 + 2^-11) bounds the error of ANY order -- tests/test_wide_rows_bound.py)
+    p.eps = eps_plan;
     if (image) {
         image_bound(ix->d, ix->dtype, ix->rho_mean, &p.eps, &p.tau_band, &p.fine_band);
         p.kprime = k;
@@ -884,7 +919,7 @@ static FusedPlan make_plan(const vf_index* ix, int k, bool image = false) {
 
 static int select_path(const vf_index* ix, int k) {
     if (ix->force_path >= 0) {
-        if (ix->force_path == 1 && !fused_possible(ix, k)) return -1;
+        if (ix->force_path == 1 && !fused_possible(ix, k, true)) return -1;
         return (int)ix->force_path;
     }
     if (ix->n <= kSmallN) return 0;
@@ -894,11 +929,19 @@ static int select_path(const vf_index* ix, int k) {
 // ---- wide passes (k_scan_wide): up to 1024 queries share ONE read of the shard --------------------------------------
 constexpr int kWideMinQueries = 129;   // e4m3 rows: below this the 64-query HBM-bound passes are faster (2 of them at most)
 constexpr int kWideMinQueries16 = 65;  // fp16 (and fp32 -> fp16 scan copy) rows: TWO 64-query passes cost two reads of the shard (5.2 ms at 10M x 768), one wide pass 4.2-4.3 ms (round 4, profiles/r04_wide_threshold.log)
+// rows of 2560 to 4096 padded elements: k_scan_ksplit reads the shard once per 32 queries, k_scan_wide (its query operand streams through
+// LDS in 32-KB chunks, so its LDS does not grow with dp; exact at these widths, checked against the oracle) once per 256 at the matrix
+// rate.  1M x 2560, k = 100, ms per batch, k_scan_ksplit / k_scan_wide: 4 queries 0.974 / 1.559, 32: 0.989 / 1.576, 64 (two passes): 1.739 /
+// 1.483, 128: 3.475 / 1.583; 1M x 4096: 32: 1.545 / 2.452, 64: 2.738 / 2.308, 128: 5.475 / 2.413; at 64 queries k_scan_wide is ahead at
+// every measured row count from 32 768 up and at k = 2048 too (profiles/r08_wide_rows_ab.log, r08_wide_rows_threshold.log).  So the
+// boundary is the second pass: up to 32 queries k_scan_ksplit, from 33 k_scan_wide.
+constexpr int kWideMinQueriesKsplit = 33;
 constexpr int kWideMaxQueries = 1024;  // 4 query tiles of 256 per pass: one workgroup per CU
 constexpr int kWideTile = 256;
 
 static bool wide_possible(const vf_index* ix, int nq) {
-    if (ix->wide_opt == 0 || nq < (ix->wide_opt > 1 ? (int)ix->wide_opt : (ix->dtype == VF_DTYPE_FP8_E4M3 ? kWideMinQueries : kWideMinQueries16))) return false;
+    const bool ks = ksplit_width(ix);   // rows only k_scan_ksplit holds an image of (32 queries per pass)
+    if (ix->wide_opt == 0 || nq < (ix->wide_opt > 1 ? (int)ix->wide_opt : ks ? kWideMinQueriesKsplit : (ix->dtype == VF_DTYPE_FP8_E4M3 ? kWideMinQueries : kWideMinQueries16))) return false;
     // a register stage is 2 k-chunks of fp8 rows / 1 of fp16 rows and a tile alternates two stages
     return ix->dp % (ix->dtype == VF_DTYPE_FP8_E4M3 ? 256 : 128) == 0;
 }
@@ -1032,7 +1075,8 @@ static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq,
         return VF_OK;
     }
 
-    const bool img = !wide_possible(ix, nq) && image_serves(ix, k, qn_tile_for(std::min(bl, nq)));
+    const bool ks = ksplit_width(ix);   // (path 1 on such rows: select_path found that k_scan_ksplit serves them)
+    const bool img = !ks && !wide_possible(ix, nq) && image_serves(ix, k, qn_tile_for(std::min(bl, nq)));
     FusedPlan p = make_plan(ix, k, img);
     s.scan_image = img ? 1 : 0;
     if (wide_possible(ix, nq)) {
@@ -1075,7 +1119,7 @@ static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq,
         if (p.image) { a.rows = (const char*)ix->rows_img; a.inv_scan = ix->inv_img; a.off_scan = image_offsets(ix); a.row_bytes = ix->dp; }   // every pass of the batch: sample, seed, main
         a.s0 = s.s0.as<float>(); a.wg_base = s.wgbase.as<long long>(); a.cnt = s.cnt.as<u32>(); a.tau_bin = s.tau.as<int>(); a.hist = s.hist.as<u32>();
         a.cand = s.cand.as<u64>(); a.cap = p.cap; a.kprime = p.kprime; a.tau_band = p.tau_band;
-        a.hist_coarse = s.hist_coarse.as<u32>(); a.stage_cap = scan_stage_cap(ix->dp, qt);
+        a.hist_coarse = s.hist_coarse.as<u32>(); a.stage_cap = ks ? scan_ksplit_stage_cap(ix->dp) : scan_stage_cap(ix->dp, qt);
         a.tile_cnt = ix->steal_opt ? s.tilecnt.as<u32>() : nullptr; a.scan_grid = p.grid;
         a.dbg = nullptr;
         if (ix->debug & 128) { VF_TRY(s.dbg.ensure((size_t)p.total_waves * ((ix->debug & 512) ? 72 : 4) * sizeof(u64))); a.dbg = s.dbg.as<u64>(); if (ix->debug & 512) VF_HIP(hipMemsetAsync(s.dbg.p, 0, s.dbg.bytes, st)); }
@@ -1102,7 +1146,9 @@ static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq,
         const bool r_f8_auto = f8rows && ix->scan_impl == 2 && ix->n > kScan2rMinRows && !ix->steal_opt && scan2r_auto_width(ix->dp, true);
         const bool sample_r = p.image || (ix->sample_impl != 0 && ix->scan_impl != 1 && scan2r_stage_cap(ix->dp, qt, f8rows) >= 256 &&
                               (ix->sample_impl == 1 || (!f8rows && s.scan_stream != s.stream && scan2r_auto_width(ix->dp, false)) || r_f8_auto));
-        if (sample_r) {
+        if (ks) {   // one workgroup per range: each loads its share of the image once and scores its range's sample part
+            VF_HIP(launch_scan_ksplit(a, kModeSample, p.grid, st));
+        } else if (sample_r) {
             const int64_t sg_r = ix->sample_grid > 0 ? ix->sample_grid : (s.scan_stream != s.stream ? resolved_aux(ix) : p.grid);
             ScanArgs as = a;
             as.stage_cap = 0;
@@ -1156,7 +1202,10 @@ static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq,
         const bool dbg_r = true;
 #endif
         const int capr = ((ix->scan_impl == 5 || r_auto) && !ix->steal_opt && dbg_r) ? scan2r_stage_cap(ix->dp, qt, f8) : 0;
-        if (p.image) {   // the int8 row image (image_serves: k_scan2r's e4m3 shapes, stage >= 256)
+        if (ks) {
+            VF_HIP(launch_scan_ksplit(a, kModeMain, p.grid, sst));
+            s.scan_kernel = 6;
+        } else if (p.image) {   // the int8 row image (image_serves: k_scan2r's e4m3 shapes, stage >= 256)
             ScanArgs a2 = a;
             a2.stage_cap = scan2r_stage_cap(ix->dp, qt, 2);
             VF_HIP(launch_scan2r(a2, qt, p.grid, 2, sst));

@@ -8,6 +8,8 @@
 
 #include <string>
 
+#include "vf_ksplit_geom.h"
+
 namespace vf {
 
 // records the thread-local message vf_last_error() returns; returns `code` (defined in vf_api.hip)
@@ -152,6 +154,11 @@ size_t scan2r_lds_bytes(int dp, int qn_tile, int stage_cap, int f8);
 int scan2r_stage_cap(int dp, int qn_tile, int f8);
 hipError_t launch_scan2r(const ScanArgs& a, int qn_tile, int grid, int f8, hipStream_t s);
 hipError_t launch_scan2r_sample(const ScanArgs& a, int qn_tile, int grid, int f8, hipStream_t s);
+// k_scan_ksplit: the fused scan of fp16 rows with 2560 <= dp <= 4096 (32 queries; the contraction split over the workgroup's four waves,
+// the query image in registers + LDS); scan_ksplit_stage_cap = 0: not this kernel
+hipError_t launch_scan_ksplit(const ScanArgs& a, int mode, int grid, hipStream_t s);
+size_t scan_ksplit_lds_bytes(int dp, int stage_cap);
+int scan_ksplit_stage_cap(int dp);
 hipError_t launch_scan_wide(const ScanArgs& a, int mode, int rows_are_fp8, hipStream_t s);
 size_t scan_wide_lds_bytes(int stage_cap);
 // k_scan_wide8: the wide main scan on the fp8 matrix instruction (e4m3 rows; a.qimg = the hi / lo code image of launch_prep_wide8)

@@ -1264,6 +1264,161 @@ __global__ __launch_bounds__(kScanThreads) void k_scan(ScanArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// k_scan_ksplit: the fused scan for rows of 2560 to 4096 padded elements (Qwen3-Embedding-4B / -8B, gte-Qwen2-7B), fp16 rows, 32 queries.
+//
+// A 32-query image of such rows is 160 to 256 KB: it does not fit the CU's 160 KB of LDS, so k_scan cannot hold it.  Here the
+// contraction is split ACROSS THE WORKGROUP'S FOUR WAVES (one per SIMD, 512 registers each): wave w owns segments
+// [S w / 4, S (w + 1) / 4) of every row (S = dp / 64 segments of 128 bytes; 10 to 16 per wave) and keeps the first kKsRegSegs = 10 of
+// its share of the image in registers (16 per segment: 160), the remaining 0 to 6 in LDS (4 waves x 6 x 4 KB = 96 KB at dp = 4096).
+// All four waves work on the SAME 32-row tile: each reads only its quarter of the rows' bytes (k_scan's lane map: lane (r, h) reads
+// 64 contiguous bytes of each segment of row r straight into A-operand registers, a ring of D segments in flight per wave, refilled
+// a segment at a time right behind the matrix instructions that consumed it), the four 32 x 32 partial accumulator tiles meet in LDS
+// (4 KB each, double-buffered by tile parity, ONE barrier per tile), and one wave -- wave (tile & 3), so the work rotates -- adds them
+// in a fixed order ((p0 + p1) + p2) + p3 and runs k_scan's epilogue (sample scores, or threshold filter + candidate stage) on the sum.
+// The barrier is a raw s_barrier behind an LDS-only wait: the ring's loads stay in flight across it.
+// The fp32 sum of a row now adds per quarter, then across quarters; it is still ONE sum of the same dp products with dp - 1 additions,
+// which the certificate's d 2^-24 term bounds for any order (make_plan; tests/test_wide_rows_bound.py models this order).
+// Row ranges, sample parts and sample slots are k_scan's (samp * 8 rows per range); the geometry lives in vf_ksplit_geom.h.
+// ------------------------------------------------------------------------------------------------
+template <int MODE, int P, int D>
+__global__ __launch_bounds__(kKsThreads) void k_scan_ksplit(ScanArgs a) {
+    static_assert(P >= kKsRegSegs && P <= 16 && P % D == 0, "segments per wave: 10..16, ring depth divides it");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int XS = P - kKsRegSegs;   // image segments per wave in LDS
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r31 = lane & 31, h = lane >> 5;
+    const int S = ks_segs(a.dp);
+    const int sbeg = ks_seg_begin(S, wid), send = ks_seg_begin(S, wid + 1);
+    const bool has_last = sbeg + P - 1 < send;   // (wave-uniform) the wave's P-th segment exists
+    const long long swg = (long long)a.samp * kKsSampWaves;
+    const KsPart part = ks_part(a.n, MODE == kModeSample ? a.scan_grid : gridDim.x, blockIdx.x, swg, MODE == kModeSample);
+    const int ntiles = ks_ntiles(part, swg, MODE == kModeSample);
+    char* qx = smem;                                       // [4 waves][XS] image segments
+    char* red = smem + (size_t)kKsWaves * XS * kKsSegBytes;   // [2][4 waves][4 KB]
+    char* ctl = red + kKsRedBytes;
+
+    h8 A[D * 4];
+    auto issue = [&](int slot, long long row, int j) {   // segment j of the wave's share of `row` -> ring slot
+        if (j == P - 1 && !has_last) return;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) A[slot * 4 + i] = stream_load((const h8*)(a.rows + ks_src(row, a.row_bytes, sbeg + j, h, i)));
+    };
+    long long row_cur = ks_row(part, a.n, 0, r31);
+    if (ntiles > 0) {
+#pragma unroll
+        for (int j = 0; j < D; ++j) issue(j, row_cur, j);
+    }
+    // the wave's share of the query image: registers, then LDS
+    h8 qr[kKsRegSegs * 4];
+#pragma unroll
+    for (int j = 0; j < kKsRegSegs; ++j)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            qr[j * 4 + i] = *(const h8*)(a.qimg + ((size_t)(8 * (sbeg + j) + 4 * h + i) * kQueryTile + r31) * 8);
+    if constexpr (XS > 0) {
+        for (int j = kKsRegSegs; j < send - sbeg; ++j) {
+            const uint4* src = (const uint4*)((const char*)a.qimg + (size_t)(sbeg + j) * kKsSegBytes);
+            uint4* dst = (uint4*)(qx + (size_t)(wid * XS + (j - kKsRegSegs)) * kKsSegBytes);
+#pragma unroll
+            for (int i = 0; i < kKsSegBytes / 16 / 64; ++i) dst[i * 64 + lane] = src[i * 64 + lane];
+        }
+    }
+    {
+        uint4* z = (uint4*)ctl;
+        const int nz = (MODE == kModeMain) ? (kCtlBytes / 16 + a.stage_cap) : 1;
+        for (int i = tid; i < nz; i += kKsThreads) z[i] = make_uint4(0u, 0u, 0u, 0u);
+    }
+    __syncthreads();
+    if (MODE == kModeMain && tid < kQueryTile) ((int*)(ctl + 16))[tid] = a.tau_bin[tid];
+    __syncthreads();
+    const char* qx_lane = qx + (size_t)wid * XS * kKsSegBytes + ((4 * h) * kQueryTile + r31) * 16;
+
+    EpiRegs<1> epi;
+    for (int t = 0; t < ntiles; ++t) {
+        const long long row_nxt = ks_row(part, a.n, t + 1 < ntiles ? t + 1 : ntiles - 1, r31);
+        const long long t0 = part.lo + (long long)t * kKsRowTile;
+        const bool reducer = (t & 3) == wid;
+        f16v acc[1];
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[0][e] = 0.0f;
+#pragma unroll
+        for (int j = 0; j < P; ++j) {
+            constexpr int kLast = P - 1;
+            if (j == kLast) {   // the epilogue's operands go out ahead of the last refill, so that waiting for them leaves the ring in flight
+                epi.inv_lane = a.inv_scan[ks_inv_index(t0, a.n, r31)];
+                epi.sync_tau = MODE == kModeMain && (t & 7) == wid;
+                if (MODE == kModeMain && epi.sync_tau)
+                    epi.tau_g[0] = __hip_atomic_load(a.tau_bin + r31, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            const int slot = j % D;
+            if (j < kLast || has_last) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    h8 b;
+                    if (j < kKsRegSegs) b = qr[(j < kKsRegSegs ? j : 0) * 4 + i];
+                    else b = *(const h8*)(qx_lane + (size_t)(j - kKsRegSegs) * kKsSegBytes + i * (kQueryTile * 16));
+                    acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[slot * 4 + i], b, acc[0], 0, 0, 0);
+                }
+            }
+            // refill the slot: segment j + D of this tile, or of the next (past the part's end: the last tile again, never consumed)
+            if (j + D < P) issue(slot, row_cur, j + D);
+            else issue(slot, row_nxt, j + D - P);
+        }
+        row_cur = row_nxt;
+        // partial tiles -> LDS, one barrier (LDS wait only: the ring's loads stay in flight), the tile's reducer adds them
+        char* rbuf = red + (size_t)(t & 1) * (kKsWaves * 4096);
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+            *(float4*)(rbuf + wid * 4096 + (g * 64 + lane) * 16) = make_float4(acc[0][4 * g], acc[0][4 * g + 1], acc[0][4 * g + 2], acc[0][4 * g + 3]);
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        if (reducer) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const float4 p0 = *(const float4*)(rbuf + 0 * 4096 + (g * 64 + lane) * 16);
+                const float4 p1 = *(const float4*)(rbuf + 1 * 4096 + (g * 64 + lane) * 16);
+                const float4 p2 = *(const float4*)(rbuf + 2 * 4096 + (g * 64 + lane) * 16);
+                const float4 p3 = *(const float4*)(rbuf + 3 * 4096 + (g * 64 + lane) * 16);
+                acc[0][4 * g] = ((p0.x + p1.x) + p2.x) + p3.x;
+                acc[0][4 * g + 1] = ((p0.y + p1.y) + p2.y) + p3.y;
+                acc[0][4 * g + 2] = ((p0.z + p1.z) + p2.z) + p3.z;
+                acc[0][4 * g + 3] = ((p0.w + p1.w) + p2.w) + p3.w;
+            }
+            tile_epilogue<1, MODE>(a, acc, epi, t0, part.hi, (long long)blockIdx.x * swg + (long long)t * kKsRowTile, lane, ctl);
+        }
+    }
+    if (MODE == kModeMain) {   // k_scan's flush: rank the staged entries per query, one returning atomic per non-empty query, write
+        __syncthreads();
+        const u32 staged = *(const u32*)ctl;
+        const u32 nst = staged < (u32)a.stage_cap ? staged : (u32)a.stage_cap;
+        uint4* ent = (uint4*)(ctl + kCtlBytes);
+        u32* qcnt = (u32*)red;          // the reduction area is dead now
+        u32* qbase = qcnt + kQueryTile;
+        if (tid < kQueryTile) qcnt[tid] = 0u;
+        __syncthreads();
+        for (u32 i = tid; i < nst; i += kKsThreads) {
+            const uint4 e = ent[i];
+            const u32 q = e.z & 0xFFu;
+            if (e.w != 1u || q >= (u32)kQueryTile) continue;
+            ent[i].w = 2u + atomicAdd(qcnt + q, 1u);
+        }
+        __syncthreads();
+        if (tid < kQueryTile) {
+            const u32 c = qcnt[tid];
+            qbase[tid] = c ? atomicAdd(a.cnt + tid * kCntStride, c) : 0u;
+        }
+        __syncthreads();
+        for (u32 i = tid; i < nst; i += kKsThreads) {
+            const uint4 e = ent[i];
+            if (e.w < 2u) continue;
+            const u32 q = e.z & 0xFFu;
+            const u32 gs = qbase[q] + (e.w - 2u);
+            if (gs < (u32)a.cap) a.cand[(long long)q * a.cap + gs] = ((u64)e.y << 32) | (u64)e.x;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // k_scan2: the main scan with WHOLE-LINE corpus loads (round 3).  fp16 rows, main mode.
 //
 // What round 3 measured (tools/ubench/stream_read.hip, profiles/r03_stream_read.log): k_scan's A-operand loads -- lane
@@ -3309,6 +3464,33 @@ hipError_t launch_scan(const ScanArgs& a, int mode, int qn_tile, int grid, int w
     return hipErrorInvalidValue;
 }
 
+// k_scan_ksplit: LDS = the image segments the registers do not hold + the reduction area + control block + (main mode) candidate stage
+#define VF_KSPLIT_SHAPES(X) X(10, 10) X(11, 11) X(12, 6) X(13, 13) X(14, 7) X(15, 5) X(16, 8)   // (segments per wave P, ring depth ks_D(P))
+size_t scan_ksplit_lds_bytes(int dp, int stage_cap) {
+    const int xs = ks_P(ks_segs(dp)) - kKsRegSegs;
+    return (size_t)kKsWaves * (xs > 0 ? xs : 0) * kKsSegBytes + kKsRedBytes + kCtlBytes + (size_t)stage_cap * 16;
+}
+int scan_ksplit_stage_cap(int dp) {
+    if (!ks_serves(dp)) return 0;
+    const size_t used = scan_ksplit_lds_bytes(dp, 0);
+    const size_t freeb = used < 160 * 1024 ? 160 * 1024 - used : 0;
+    return (int)((freeb < 32 * 1024 ? freeb : 32 * 1024) / 16);
+}
+// mode kModeSample: `grid` = a.scan_grid workgroups, one per range (each scores its range's sample part); kModeMain: a.stage_cap = scan_ksplit_stage_cap
+hipError_t launch_scan_ksplit(const ScanArgs& a, int mode, int grid, hipStream_t s) {
+    if (!ks_serves(a.dp) || a.row_bytes != (long long)a.dp * 2 || (mode == kModeSample && grid != a.scan_grid)) return hipErrorInvalidValue;
+    const int P = ks_P(ks_segs(a.dp));
+    const size_t lds = scan_ksplit_lds_bytes(a.dp, mode == kModeMain ? a.stage_cap : 0);
+#define VF_X(P_, D_) \
+    if (P == P_) { \
+        if (mode == kModeMain) hipLaunchKernelGGL((k_scan_ksplit<kModeMain, P_, D_>), dim3(grid), dim3(kKsThreads), lds, s, a); \
+        else hipLaunchKernelGGL((k_scan_ksplit<kModeSample, P_, D_>), dim3(grid), dim3(kKsThreads), lds, s, a); \
+        return hipGetLastError(); }
+    VF_KSPLIT_SHAPES(VF_X)
+#undef VF_X
+    return hipErrorInvalidValue;
+}
+
 hipError_t launch_scan2(const ScanArgs& a, int qn_tile, int grid, int rows_are_fp8, hipStream_t s) {
     const size_t lds = scan2_lds_bytes(a.dp, qn_tile, a.stage_cap);
     if (qn_tile == kQueryTile) {
@@ -3848,6 +4030,11 @@ hipError_t scan_configure() {
 #define VF_X(NT, MODE, F8, S_, RB_, RING_, AR_) \
     if ((e = hipFuncSetAttribute((const void*)k_scan2r<NT, MODE, F8, S_, RB_, RING_, AR_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
     VF_SCAN2R_ALL(VF_X)
+#undef VF_X
+#define VF_X(P_, D_) \
+    if ((e = hipFuncSetAttribute((const void*)k_scan_ksplit<kModeMain, P_, D_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e; \
+    if ((e = hipFuncSetAttribute((const void*)k_scan_ksplit<kModeSample, P_, D_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
+    VF_KSPLIT_SHAPES(VF_X)
 #undef VF_X
     if ((e = hipFuncSetAttribute((const void*)k_scan2<1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
     if ((e = hipFuncSetAttribute((const void*)k_scan2<2, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
