@@ -44,7 +44,8 @@ def draw_case(rng, max_work):
     if rng.random() < 0.35:      # the other tuning knobs: every one of them is a speed setting, none may change a result
         knobs = {"force_path": [0, 1, 2], "margin": [0, 1, 8, 64, 2048], "cap": [0, 256, 1024, 16384], "waves": [0, 64, 1024, 8192],
                  "scan_g": [0, 1, 2, 3, 4], "refresh_every": [1, 4, 128, 256], "steal": [0, 1], "wide": [0, 1, 16, 65, 200],
-                 "wide_sync": [-1, 0, 2, 8], "aux_cus": [0, 32, 64], "sample_grid": [0, 8, 64, 1024], "overlap_scans": [0, 1]}
+                 "wide_sync": [-1, 0, 2, 8], "aux_cus": [0, 32, 64], "sample_grid": [0, 8, 64, 1024], "overlap_scans": [0, 1],
+                 "image_mfma": [-1, 0, 1, 2]}
         for name in rng.choice(sorted(knobs), size=int(rng.integers(1, 4)), replace=False):
             opts[str(name)] = int(pick(knobs[str(name)]))
     shards = int(pick([1, 1, 1, 2, 3, 5])) if n >= 8 else 1      # > 1: one handle over that many row blocks, all on device 0

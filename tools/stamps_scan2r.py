@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Where a wave of k_scan2r spends a tile (debug bits 7 + 9: entry / image staged / first 64 tile starts / stream end / flushed on the
 100-MHz constant clock): ISOLATED launches (ordered scans, whole chip), fp16 or e4m3 rows, any option / debug experiment bit.
-usage: stamps_scan2r.py ROWS D f16|fp8 [opt=value ...]      (VF_DBG_EXTRA = experiment bits of the test variant)"""
+usage: stamps_scan2r.py ROWS D f16|fp8 [opt=value ...]      (VF_DBG_EXTRA = experiment bits of the test variant)
+The int8 row image (768-wide fp16 rows, >= 4M rows): image_mfma=0 is the fp16-instruction shape (F8 = 2), image_mfma=1 the int8-instruction
+shape with one query plane (F8 = 3), image_mfma=2 with two (F8 = 4) -- the cycle accounting (VF_DBG_EXTRA=4096) of the three side by side is DESIGN.md 4.1's table."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

@@ -108,7 +108,9 @@ struct Slot {
     int scan_image = 0;                        // 1: the pending search's scans read the int8 row image
     DevBuf qn, qimg, s0, cnt, tau, hist, hist_coarse, cand, flags, counts;   // fused-path state
     DevBuf dbg, wgbase, tilecnt, sib;
-    DevBuf qimg8, epsq;                  // k_scan_wide8: hi / lo e4m3 query image, per-query certificate bounds
+    DevBuf qimg8, epsq;                  // k_scan_wide8: hi / lo e4m3 query image, per-query certificate bounds (the image scan's int8 query plane: the same two)
+    DevBuf qscale, bandq;                // ... and that plane's code steps [64] and per-query bands [2][64] (launch_prep_q8)
+    int image_i8 = 0;                    // 1 / 2: the pending search's image scans run on the int8 matrix instruction with that many query planes
     int64_t wgbase_n = -1; int wgbase_grid = -1;
     DevBuf dense_s, cn_tmp, parts_ids, parts_sc, run_ids, run_sc, qsel; // exact-path scratch
     int* h_flags = nullptr;      // pinned, [max batches * 64]
@@ -175,7 +177,7 @@ struct vf_index {
     // options
     int64_t force_path = -1, sample_rows = -1, margin = -1, cap_opt = 0, waves_opt = 0, scan_g = 0,
             refresh_every = 128, debug = 0, steal_opt = 0, wide_opt = 1, wide_sync = -1, wide_mfma = -1, wide8_waves = 8, wide8_stage = 0,
-            aux_cus = -1, sample_grid = -1, overlap_scans = -1, scan_impl = 2, sample_impl = -1, scan_image = 1, wide_rows = 1;   // aux_cus / overlap_scans: -1 = auto (resolved_split)   // scan_impl: 1 = k_scan (register loads), 2 = k_scan2 (whole-line LDS-DMA) where it fits   // aux_cus: CUs the main scan leaves to the small kernels of the other slots (0 = no split)   // wide_sync: -1 siblings of a wide row group run free (default: fastest), >= 0 = the slack in super-tiles  // steal_opt: cross-workgroup tile pool in the main scan (measured slower: DESIGN.md 5)  // wide_opt: 0 never, 1 auto (nq >= 129), > 1 = from that many queries
+            aux_cus = -1, sample_grid = -1, overlap_scans = -1, scan_impl = 2, sample_impl = -1, scan_image = 1, wide_rows = 1, image_mfma = -1;   // aux_cus / overlap_scans: -1 = auto (resolved_split)   // scan_impl: 1 = k_scan (register loads), 2 = k_scan2 (whole-line LDS-DMA) where it fits   // aux_cus: CUs the main scan leaves to the small kernels of the other slots (0 = no split)   // wide_sync: -1 siblings of a wide row group run free (default: fastest), >= 0 = the slack in super-tiles  // steal_opt: cross-workgroup tile pool in the main scan (measured slower: DESIGN.md 5)  // wide_opt: 0 never, 1 auto (nq >= 129), > 1 = from that many queries
     vf_search_stats stats{};
     bool profile = false;
     double prof_scan_ms = 0.0, prof_pipe_ms = 0.0;
@@ -289,6 +291,7 @@ constexpr int kImageMaxK = 128;
 constexpr int64_t kImageMinRows = 4'000'000;   // measured at 10M rows; the shards of a 4- or 8-GPU split (2.5M / 1.25M rows) keep the fp16 scan
 constexpr double kImageMaxRho = 1.0 / 64;
 constexpr size_t kImageHeadroom = (size_t)8 << 30;
+constexpr int kImageMfmaAuto = 1;   // option image_mfma = -1
 static bool image_eligible(const vf_index* ix) {
     return ix->shards.empty() && (ix->dtype == VF_DTYPE_F16 || ix->dtype == VF_DTYPE_F32) && ix->n >= kImageMinRows &&
            ix->n < (int64_t)0xFFFFFFFFll && ix->dp == 768 && scan2r_stage_cap(ix->dp, kMaxBatch, 2) >= 256;
@@ -703,6 +706,7 @@ extern "C" int vf_index_set_option(vf_index* ix, const char* name, int64_t value
         else VF_TRY(build_image(ix, value));
         ix->scan_image = value;
     }
+    else if (s == "image_mfma") { if (!in_range(-1, 2)) return fail(VF_EINVAL, "image_mfma must be -1 (auto), 0 (the int8 row image on the fp16 matrix instruction, fp16 queries), 1 (on the int8 matrix instruction, the queries as one int8 plane) or 2 (as two planes, hi + lo: the band of 0)"); ix->image_mfma = value; }
     else if (s == "wide_rows") { if (!in_range(0, 2)) return fail(VF_EINVAL, "wide_rows must be 0 (rows of more than 2432 padded elements never take the fused path), 1 (auto: from 131 072 rows) or 2 (wherever k_scan_ksplit serves them)"); ix->wide_rows = value; }
     else if (s == "debug") ix->debug = value;
     else if (s == "profile") {
@@ -837,6 +841,25 @@ extern "C" int vf_debug_image_bound(int32_t d, int32_t dtype, float rho_mean, fl
     image_bound(d, dtype, rho_mean, eps, &tb, &fb);
     *tau_band = tb; *fine_band = fb;
     return VF_OK;
+}
+
+// Test hook (not in the public header; exported by the test build only): what a query's int8 plane adds (image_q8_bound / image_q8_eps, the formulas k_prep_q8 runs on the device),
+// for tests/test_scan_image_q8_model.py
+extern "C" int vf_debug_image_q8_bound(float rho_q, float eps_img, int32_t tau_band, int32_t fine_band, float* eps_q, int32_t* tau_band_q,
+                                       int32_t* fine_band_q) {
+    if (!eps_q || !tau_band_q || !fine_band_q) return fail(VF_EINVAL, "vf_debug_image_q8_bound: bad argument");
+    const Q8Bound b = image_q8_bound(rho_q);
+    *eps_q = image_q8_eps(eps_img, b.eps_add);
+    *tau_band_q = tau_band + b.tau_bins; *fine_band_q = fine_band + b.fine_bins;
+    return VF_OK;
+}
+
+// Which matrix instruction scans the image (option image_mfma): 1 = v_mfma_i32_32x32x32_i8 on the codes as they are, the
+// queries quantised to one int8 plane whose residual widens each query's certificate bound and band; 0 = the codes converted to fp16
+// 2 = the same on hi + lo planes (the residual quantised again at step / 254: rho_q < 10^-4, the band of 0, twice the instructions of 1)
+static int image_planes(const vf_index* ix, int qt) {   // 0: the fp16 instruction
+    const int m = ix->image_mfma < 0 ? kImageMfmaAuto : (int)ix->image_mfma;
+    return (m >= 1 && scan2r_stage_cap(ix->dp, qt, 2 + m) >= 256) ? m : 0;
 }
 
 // the int8 image serves a fused batch when it exists, k is within kImageMaxK and the scans are k_scan2r's (the options that pick another
@@ -1079,6 +1102,8 @@ static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq,
     const bool img = !ks && !wide_possible(ix, nq) && image_serves(ix, k, qn_tile_for(std::min(bl, nq)));
     FusedPlan p = make_plan(ix, k, img);
     s.scan_image = img ? 1 : 0;
+    s.image_i8 = img ? image_planes(ix, qn_tile_for(std::min(bl, nq))) : 0;
+    const int img_f8 = 2 + s.image_i8;   // k_scan2r's row type of the image scans
     if (wide_possible(ix, nq)) {
         s.timed = ix->profile;
         if (s.timed) VF_HIP(hipEventRecord(s.ev_t[2], st));
@@ -1112,9 +1137,19 @@ static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq,
         const int nb = std::min(bl, nq - b0);
         const int qt = qn_tile_for(nb);
         float* qn_b = s.qn.as<float>() + (size_t)b0 * ix->d;
-        VF_HIP(launch_prep_queries(d_queries + (size_t)b0 * ix->d, nb, ix->d, ix->dp, qt, qn_b, s.qimg.as<_Float16>(), st));
+        // (the int8 plane replaces the fp16 image: that one is not built)
+        VF_HIP(launch_prep_queries(d_queries + (size_t)b0 * ix->d, nb, ix->d, ix->dp, qt, qn_b, s.image_i8 ? nullptr : s.qimg.as<_Float16>(), st));
         ScanArgs a{};
         a.rows = (const char*)ix->rows_scan; a.inv_scan = ix->inv_scan; a.qimg = s.qimg.as<_Float16>();
+        if (s.image_i8) {
+            VF_TRY(s.qimg8.ensure((size_t)ix->dp * kMaxBatch * 2));
+            VF_TRY(s.epsq.ensure(kMaxBatch * sizeof(float)));
+            VF_TRY(s.qscale.ensure(kMaxBatch * sizeof(float)));
+            VF_TRY(s.bandq.ensure(2 * kMaxBatch * sizeof(int)));
+            VF_HIP(launch_prep_q8(qn_b, nb, ix->d, ix->dp, qt, s.image_i8, (signed char*)s.qimg8.p, s.qscale.as<float>(), s.epsq.as<float>(), s.bandq.as<int>(),
+                                  p.eps, p.tau_band, p.fine_band, st));
+            a.qimg = (const _Float16*)s.qimg8.p; a.q_scale = s.qscale.as<float>(); a.band_q = s.bandq.as<int>();
+        }
         a.n = ix->n; a.dp = ix->dp; a.row_bytes = (long long)ix->dp * (ix->dtype == VF_DTYPE_FP8_E4M3 ? 1 : 2); a.total_waves = p.total_waves; a.samp = p.samp;
         if (p.image) { a.rows = (const char*)ix->rows_img; a.inv_scan = ix->inv_img; a.off_scan = image_offsets(ix); a.row_bytes = ix->dp; }   // every pass of the batch: sample, seed, main
         a.s0 = s.s0.as<float>(); a.wg_base = s.wgbase.as<long long>(); a.cnt = s.cnt.as<u32>(); a.tau_bin = s.tau.as<int>(); a.hist = s.hist.as<u32>();
@@ -1152,7 +1187,7 @@ static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq,
             const int64_t sg_r = ix->sample_grid > 0 ? ix->sample_grid : (s.scan_stream != s.stream ? resolved_aux(ix) : p.grid);
             ScanArgs as = a;
             as.stage_cap = 0;
-            VF_HIP(launch_scan2r_sample(as, qt, (int)std::min<int64_t>(std::max<int64_t>(sg_r, 1), p.grid), p.image ? 2 : (int)f8rows, st));
+            VF_HIP(launch_scan2r_sample(as, qt, (int)std::min<int64_t>(std::max<int64_t>(sg_r, 1), p.grid), p.image ? img_f8 : (int)f8rows, st));
         } else {
         const int64_t sg_opt = ix->sample_grid >= 0 ? ix->sample_grid : (s.scan_stream != s.stream ? 4 * resolved_aux(ix) : 0);
         const int sgrid = sg_opt > 0 ? (int)std::min<int64_t>(sg_opt, p.grid) : p.grid;
@@ -1207,8 +1242,8 @@ static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq,
             s.scan_kernel = 6;
         } else if (p.image) {   // the int8 row image (image_serves: k_scan2r's e4m3 shapes, stage >= 256)
             ScanArgs a2 = a;
-            a2.stage_cap = scan2r_stage_cap(ix->dp, qt, 2);
-            VF_HIP(launch_scan2r(a2, qt, p.grid, 2, sst));
+            a2.stage_cap = scan2r_stage_cap(ix->dp, qt, img_f8);
+            VF_HIP(launch_scan2r(a2, qt, p.grid, img_f8, sst));
             s.scan_kernel = 5;
         } else if (capr >= 256) {
             ScanArgs a2 = a;
@@ -1245,6 +1280,7 @@ static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq,
         f.orig_dtype = ix->dtype; f.orig_row_elems = ix->d; f.norm = ix->norm; f.qn = qn_b;
         f.d = ix->d; f.k = k; f.kprime = p.kprime; f.eps = p.eps; f.n_rows = ix->n; f.id_offset = ix->id_offset;
         f.band = p.fine_band;
+        if (s.image_i8) { f.eps_q = s.epsq.as<float>(); f.band_q = s.bandq.as<int>() + qt; }
         f.out_ids = (long long*)(d_ids + (size_t)b0 * k); f.out_scores = d_scores + (size_t)b0 * k;
         f.flags = s.d_flags + b0; f.cand_count_out = s.d_counts + b0;
         f.dbg = nullptr;
@@ -1960,6 +1996,49 @@ extern "C" int vf_fuse_rank(const float* rerank_scores, const float* time_scores
     VF_HIP(launch_fuse_rank(a, b, n, o, ord, nullptr));
     VF_HIP(hipMemcpy(out_scores, o, (size_t)n * 4, hipMemcpyDeviceToHost));
     VF_HIP(hipMemcpy(out_order, ord, (size_t)n * 8, hipMemcpyDeviceToHost));
+    return VF_OK;
+}
+
+// Test hook (not in the public header): k_prep_q8 on a batch of up to 64 canonical queries (host pointers): the codes as stored
+// ([dp / 16][planes][64][16], dp = d padded to 128), the steps [64], the certificate bounds [64] and the bands [2][64], so that a test can hold
+// the DEVICE's residual and bands against the NumPy model
+extern "C" int vf_debug_prep_q8(const float* qn, int32_t nq, int32_t d, int32_t planes, float eps_img, int32_t tau_band, int32_t fine_band,
+                                signed char* codes, float* q_scale, float* eps_q, int32_t* band_q) {
+    DeviceGuard restore_callers_device;
+    if (!qn || !codes || !q_scale || !eps_q || !band_q || nq < 1 || nq > kMaxBatch || d < 1 || planes < 1 || planes > 2)
+        return fail(VF_EINVAL, "vf_debug_prep_q8: bad argument");
+    const int dp = (d + 127) / 128 * 128;
+    const size_t nimg = (size_t)dp * planes * kMaxBatch;
+    float* d_q = nullptr; char* d_out = nullptr;   // d_out: codes | steps | bounds | bands
+    VF_HIP(hipMalloc((void**)&d_q, (size_t)nq * d * sizeof(float)));
+    hipError_t e = hipMalloc((void**)&d_out, nimg + 4 * kMaxBatch * 4);
+    float* d_sc = (float*)(d_out + nimg);
+    if (e == hipSuccess) e = hipMemcpy(d_q, qn, (size_t)nq * d * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = launch_prep_q8(d_q, nq, d, dp, kMaxBatch, planes, (signed char*)d_out, d_sc, d_sc + kMaxBatch, (int*)(d_sc + 2 * kMaxBatch),
+                                            eps_img, tau_band, fine_band, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(codes, d_out, nimg, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(q_scale, d_sc, kMaxBatch * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(eps_q, d_sc + kMaxBatch, kMaxBatch * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(band_q, d_sc + 2 * kMaxBatch, 2 * kMaxBatch * 4, hipMemcpyDeviceToHost);
+    (void)hipFree(d_q); (void)hipFree(d_out);
+    if (e != hipSuccess) return fail(VF_EHIP, std::string("vf_debug_prep_q8: ") + hipGetErrorString(e));
+    return VF_OK;
+}
+
+// Test hook (not in the public header): C [32][32] = A [32][32] B [32][32]^T through ONE int8 matrix instruction fed the way k_scan2r's
+// int8 body feeds it (host pointers)
+extern "C" int vf_debug_mfma_i8(const signed char* A, const signed char* B, int32_t* C) {
+    DeviceGuard restore_callers_device;
+    if (!A || !B || !C) return fail(VF_EINVAL, "vf_debug_mfma_i8: bad argument");
+    signed char* d_in = nullptr; int* d_out = nullptr;
+    VF_HIP(hipMalloc((void**)&d_in, 2048));
+    hipError_t e = hipMalloc((void**)&d_out, 4096);
+    if (e == hipSuccess) e = hipMemcpy(d_in, A, 1024, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_in + 1024, B, 1024, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = launch_debug_mfma_i8(d_in, d_in + 1024, d_out, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(C, d_out, 4096, hipMemcpyDeviceToHost);
+    (void)hipFree(d_in); (void)hipFree(d_out);
+    if (e != hipSuccess) return fail(VF_EHIP, std::string("vf_debug_mfma_i8: ") + hipGetErrorString(e));
     return VF_OK;
 }
 

@@ -2,6 +2,7 @@
 // gfx950 only.  Not part of the public ABI (that is include/veritasfi_hip.h).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 
 #include "../../include/veritasfi_hip.h"  // VF_DTYPE_*
@@ -68,11 +69,34 @@ constexpr int kMaxKFused = 2048;      // largest k the fused path serves (k' <= 
 
 enum ScanMode { kModeSample = 0, kModeMain = 1 };
 
+// What a query quantised to ONE int8 plane adds to its certificate bound and to its bands (k_scan2r, F8 = 3).  The scan sees
+// q' = qn + r_q with ||r_q|| = rho_q against rows c' = c / ||c|| + r_row, ||c'|| <= 1 + rho_row <= 65 / 64 (an image exists only if
+// every rho_row <= 1 / 64), so |r_q . c'| <= rho_q 65 / 64: one constant per query.  It moves all of that query's keys together, so it
+// widens the query's certificate bound and its re-score band by itself, rounded up: in threshold bins (1 / 1024) and fine bins (1 / 16 384).
+struct Q8Bound { float eps_add; int tau_bins, fine_bins; };
+__host__ __device__ inline Q8Bound image_q8_bound(float rho_q) {
+    Q8Bound b;
+    if (!(rho_q < 1.0f)) { b.eps_add = INFINITY; b.tau_bins = kHistBins; b.fine_bins = 16 * kHistBins; return b; }   // (a NaN too)
+    const double c = (double)rho_q * (65.0 / 64.0);
+    b.eps_add = (float)c;
+    if ((double)b.eps_add < c) b.eps_add = nextafterf(b.eps_add, INFINITY);
+    b.tau_bins = (int)ceil(c * (kHistBins / 2));
+    b.fine_bins = (int)ceil(c * (kHistBins / 2) * 16);
+    return b;
+}
+// ... and the query's certificate bound: the image's + that term + 2^-20 -- the two fp32 multiplications (row inverse, query step) and the
+// offset addition that form a key of magnitude <= 1 + 2 / 64 round by 2^-24 of it each; every step here rounds up
+__host__ __device__ inline float image_q8_eps(float eps_img, float eps_add) {
+    const float e = nextafterf(eps_img + eps_add, INFINITY) + 0x1p-20f;
+    return nextafterf(e, INFINITY);
+}
+
 // Arguments of the fused scan kernel (k_scan).  Plain struct passed by value.
 struct ScanArgs {
     const char* rows;        // fp16 scan copy, row-major, row_bytes per row (dp * 2)
     const float* inv_scan;   // [n] 1 / (canonical norm * row scale): approx score = acc * inv_scan
-    const float* off_scan;   // int8 image only (k_scan2r, F8 = 2): [n + 64] per-row offset added to every approximate score; else null
+    const float* off_scan;   // int8 image only (k_scan2r, F8 = 2 / 3): [n + 64] per-row offset added to every approximate score; else null
+    const float* q_scale;    // int8 image on the int8 matrix instruction only (k_scan2r, F8 = 3): [QN] the queries' code steps s_q (launch_prep_q8); else null
     const _Float16* qimg;    // query image [dp/8][QN][8] fp16 (normalised queries, zero padded)
     long long n;             // rows in this shard
     int dp;                  // padded dim, multiple of 64
@@ -92,6 +116,7 @@ struct ScanArgs {
     int cap;
     int kprime;              // k + margin: the threshold keeps >= kprime rows above it
     int tau_band;            // bins every threshold is set below the one kprime rows reach (int8 image scan: 2 eps wide); 0 = none
+    const int* band_q;       // optional [QN] per-query tau_band (set for k_scan2r's int8 query planes only, F8 = 3 / 4: the plan's band + the query's own quantisation term); null = tau_band
     int refresh_every;       // recompute tau when a query's count crosses a multiple of this
     int nq;                  // real queries (<= QN); padded queries never pass
     u32* tile_cnt;           // [grid] pool counters: tiles claimed from the shared tail of each workgroup's row range (k_sel0 zeroes them); null = no stealing
@@ -115,6 +140,7 @@ struct FinalArgs {
     const float* eps_q;      // optional [nq] per-query certificate bound (k_scan_wide8: the query's own quantisation residual); null = eps
     int band;                // > 0 (int8 image scan): re-score every candidate within `band` fine bins (1 / 16 384 each) of the k-th best
                              // approximate score (kprime = k then); 0: the best kprime candidates
+    const int* band_q;       // optional [nq] per-query `band` (the int8 query plane: launch_prep_q8); null = band
     long long n_rows;        // rows in the shard (certificate is moot when all were re-scored)
     long long id_offset;
     long long* out_ids; float* out_scores;   // [nq][k]
@@ -145,6 +171,8 @@ hipError_t launch_scan(const ScanArgs& a, int mode, int qn_tile, int grid, int w
                        int rows_are_fp8, hipStream_t s);
 // test hook: the scan's hardware e4m3 -> fp16 conversion over `count` codes (device pointers)
 hipError_t launch_debug_cvt_e4m3(const unsigned char* in, float* out, int count, hipStream_t s);
+// test hook: one v_mfma_i32_32x32x32_i8 over A [32][32], B [32][32] int8 -> C [32][32] = A B^T with k_scan2r's operand map (device pointers)
+hipError_t launch_debug_mfma_i8(const signed char* A, const signed char* B, int* C, hipStream_t s);
 // k_scan2: the main scan with whole-line LDS-DMA corpus loads (fp16 or e4m3 rows); a.stage_cap = scan2_stage_cap(...) >= 256
 hipError_t launch_scan2(const ScanArgs& a, int qn_tile, int grid, int rows_are_fp8, hipStream_t s);
 size_t scan2_lds_bytes(int dp, int qn_tile, int stage_cap);
@@ -166,6 +194,12 @@ hipError_t launch_prep_wide8(const float* qn, int nq, int d, int dp, int qtot, u
 hipError_t launch_scan_wide8(const ScanArgs& a, int waves /* 8: 256-query tiles, one workgroup per CU; 4: 128-query tiles, two per CU */, hipStream_t s);
 int scan_wide8_stage_cap(int waves);
 int scan_wide8_occupancy(int waves, int stage_cap);
+// The int8 query plane of the image scan on the int8 matrix instruction (k_scan2r, F8 = 3): codes in the B-operand order
+// [dp / 16][qn_tile][16], the code step s_q, and per query what its own quantisation residual rho_q = ||qn - s_q code|| (fp64, rounded
+// up) adds: eps_q = eps_img + rho_q 65 / 64 + 2^-20 and the two bands widened by rho_q 65 / 64 in their bins (image_q8_bound).
+// band_q: [2][qn_tile] ints -- threshold bins, then k_final's fine bins.
+hipError_t launch_prep_q8(const float* qn, int nq, int d, int dp, int qn_tile, int planes /* 1, or 2: hi + lo, [dp / 16][2][qn_tile][16] */, signed char* img8, float* q_scale, float* eps_q, int* band_q,
+                          float eps_img, int tau_band, int fine_band, hipStream_t s);
 // k_scan2<NT, 2>: the narrow main scan on the fp8 matrix instruction (launch_scan2 with rows_are_fp8 = 2; a.qimg = this image)
 hipError_t launch_sel0(const ScanArgs& a, int qn_tile, hipStream_t s);
 hipError_t launch_final(FinalArgs a, int nq, hipStream_t s);

@@ -26,6 +26,8 @@ namespace vf {
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 typedef float f16v __attribute__((ext_vector_type(16)));
+typedef int i4v __attribute__((ext_vector_type(4)));     // A / B operand of v_mfma_i32_32x32x32_i8: 16 int8 codes
+typedef int i16v __attribute__((ext_vector_type(16)));   // its accumulator
 typedef int i8v __attribute__((ext_vector_type(8)));
 
 // ------------------------------------------------------------------------------------------------
@@ -241,9 +243,9 @@ __global__ __launch_bounds__(256) void k_prep_queries(const float* q, int nq, in
                 v = xs[j] * inv;
                 qn[(long long)slot * d + j] = v;
             }
-            qimg[((long long)(j >> 3) * QN + slot) * 8 + (j & 7)] = (_Float16)v;
+            if (qimg) qimg[((long long)(j >> 3) * QN + slot) * 8 + (j & 7)] = (_Float16)v;
         }
-    } else {
+    } else if (qimg) {
         for (int j = tid; j < dp; j += 256) qimg[((long long)(j >> 3) * QN + slot) * 8 + (j & 7)] = (_Float16)0.0f;
     }
 }
@@ -251,6 +253,67 @@ __global__ __launch_bounds__(256) void k_prep_queries(const float* q, int nq, in
 hipError_t launch_prep_queries(const float* q, int nq, int d, int dp, int qn_tile, float* qn, _Float16* qimg,
                                hipStream_t s) {
     hipLaunchKernelGGL(k_prep_queries, dim3(qn_tile), dim3(256), (size_t)d * sizeof(float), s, q, nq, d, dp, qn_tile, qn, qimg);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_prep_q8: the int8 query plane of the image scan on the int8 matrix instruction (k_scan2r, F8 = 3) -- block per query slot, after
+// k_prep_queries (it reads qn).  s_q = absmax / 127, code_j = rint(qn_j / s_q) (|code| <= 127) as two's complement bytes at
+// img8[((j / 16) QN + slot) 16 + j % 16]: a lane's 16 bytes ARE its B fragment of one K = 32 step.  rho_q = ||qn - s_q code|| is summed in
+// fp64 from the codes as stored and rounded UP, so the bound holds whatever the rounding of s_q or of the codes did; image_q8_bound
+// turns it into the query's certificate bound and bands.  Padding slots hold code 0 and step 0.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_prep_q8(const float* qn, int nq, int d, int dp, int QN, int planes, signed char* img8, float* q_scale,
+                                                  float* eps_q, int* band_q, float eps_img, int tau_band, int fine_band) {
+    __shared__ float red_f[256];
+    __shared__ double red_d[256];
+    const int slot = blockIdx.x, tid = threadIdx.x;
+    const bool live = slot < nq;
+    float mx = 0.0f;
+    if (live) for (int j = tid; j < d; j += 256) mx = fmaxf(mx, fabsf(qn[(long long)slot * d + j]));
+    red_f[tid] = mx;
+    __syncthreads();
+    for (int o = 128; o; o >>= 1) { if (tid < o) red_f[tid] = fmaxf(red_f[tid], red_f[tid + o]); __syncthreads(); }
+    mx = red_f[0];
+    bool finite = mx <= FLT_MAX;
+    const float sc = (finite && mx > 0.0f) ? mx / 127.0f : 1.0f;
+    const float sc2 = sc / 254.0f;                                     // two planes: the step of the lo plane (the residual quantised again)
+    double res = 0.0;
+    for (int j = tid; j < dp; j += 256) {
+        float code = 0.0f, lo = 0.0f;
+        if (live && j < d) {
+            const float x = qn[(long long)slot * d + j];
+            code = fminf(fmaxf(rintf(x / sc), -127.0f), 127.0f);
+            double dx = (double)x - (double)sc * (double)code;
+            if (planes == 2) {
+                lo = fminf(fmaxf(rintf((float)dx / sc2), -127.0f), 127.0f);
+                dx -= (double)sc2 * (double)lo;
+            }
+            res += dx * dx;
+        }
+        const long long at = (((long long)(j >> 4) * planes) * QN + slot) * 16 + (j & 15);
+        img8[at] = (signed char)(int)code;
+        if (planes == 2) img8[at + (long long)QN * 16] = (signed char)(int)lo;
+    }
+    red_d[tid] = res;
+    __syncthreads();
+    for (int o = 128; o; o >>= 1) { if (tid < o) red_d[tid] += red_d[tid + o]; __syncthreads(); }
+    if (tid == 0) {
+        const double rd = sqrt(red_d[0]);
+        float rho = (float)rd;
+        if ((double)rho < rd) rho = nextafterf(rho, INFINITY);
+        if (!finite || !(rd <= (double)FLT_MAX)) rho = INFINITY;       // (a NaN query element: no bound, the exact path)
+        const Q8Bound b = image_q8_bound(live ? rho : 0.0f);
+        q_scale[slot] = live ? (planes == 2 ? sc2 : sc) : 0.0f;   // what the scan multiplies its sum by (two planes: hi x 254 + lo)
+        eps_q[slot] = image_q8_eps(eps_img, b.eps_add);
+        band_q[slot] = tau_band + b.tau_bins;
+        band_q[QN + slot] = fine_band + b.fine_bins;
+    }
+}
+
+hipError_t launch_prep_q8(const float* qn, int nq, int d, int dp, int qn_tile, int planes, signed char* img8, float* q_scale, float* eps_q, int* band_q,
+                          float eps_img, int tau_band, int fine_band, hipStream_t s) {
+    hipLaunchKernelGGL(k_prep_q8, dim3(qn_tile), dim3(256), 0, s, qn, nq, d, dp, qn_tile, planes, img8, q_scale, eps_q, band_q, eps_img, tau_band, fine_band);
     return hipGetLastError();
 }
 
@@ -727,6 +790,25 @@ hipError_t launch_debug_cvt_e4m3(const unsigned char* in, float* out, int count,
     return hipGetLastError();
 }
 
+// Test hook: ONE v_mfma_i32_32x32x32_i8 with the operand map k_scan2r's int8 body assumes -- lane (r, h) holds bytes 16 h .. 16 h + 15 of
+// row r of A (32 rows x K = 32) and of row r of B (32 queries x K = 32); accumulator register e of lane (r, h) is C[(e & 3) + 8 (e >> 2)
+// + 4 h][r] -- so that a test can pin it with exact integers and an asymmetric B instead of trusting the documentation of the bf16 form.
+__global__ __launch_bounds__(64) void k_debug_mfma_i8(const signed char* A, const signed char* B, int* C) {
+    const int lane = threadIdx.x, r = lane & 31, h = lane >> 5;
+    const i4v a = *(const i4v*)(A + r * 32 + 16 * h), b = *(const i4v*)(B + r * 32 + 16 * h);
+    i16v acc;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[e] = 0;
+    acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b, acc, 0, 0, 0);
+#pragma unroll
+    for (int e = 0; e < 16; ++e) C[((e & 3) + 8 * (e >> 2) + 4 * h) * 32 + r] = acc[e];
+}
+
+hipError_t launch_debug_mfma_i8(const signed char* A, const signed char* B, int* C, hipStream_t s) {
+    hipLaunchKernelGGL(k_debug_mfma_i8, dim3(1), dim3(64), 0, s, A, B, C);
+    return hipGetLastError();
+}
+
 // Recompute tau for query q: the largest fine bin b with sum(fine[b..]) >= kprime, found in two
 // round trips through a two-level histogram (64 coarse bins of 32 fine bins): lane l reads coarse[l],
 // a suffix scan finds the coarse bin L where the count crosses kprime, then lanes 0..31 read the 32
@@ -992,7 +1074,7 @@ __device__ __forceinline__ void tile_epilogue(const ScanArgs& a, const f16v (&ac
     if constexpr (!PUBLISH) return;
     if (need) {
         // (1) refresh one tau from what is published so far (two dependent L2 reads)
-        const int nb = wave_tau_two_level(a.hist_coarse + qq * 64, a.hist + (long long)qq * kHistBins, a.kprime, lane) - a.tau_band;
+        const int nb = wave_tau_two_level(a.hist_coarse + qq * 64, a.hist + (long long)qq * kHistBins, a.kprime, lane) - (a.band_q ? a.band_q[qq] : a.tau_band);
         if (lane == 0 && nb > 0) {
             atomicMax(a.tau_bin + qq, nb);
             atomicMax(tau_lds + qq, nb);
@@ -1860,6 +1942,8 @@ static Scan2rShape scan2r_shape(int dp, int f8) {
     if (!f8 && dp == 1024) return {16, 6, 4};   // (bge-m3 / bge-large rows: the reference's own width, config/example.yaml:3)
     if (!f8 && dp == 512) return {8, 4, 6};
     if (!f8 && dp == 384) return {6, 3, 6};
+    if (f8 == 3) return dp == 768 ? Scan2rShape{6, 6, 6} : Scan2rShape{0, 0, 0};   // one int8 query plane: every B fragment in registers
+    if (f8 == 4) return dp == 768 ? Scan2rShape{6, 3, 6} : Scan2rShape{0, 0, 0};   // hi + lo planes: half in registers, half in LDS, as the fp16 image
     if (f8 && dp == 768) return {6, 3, 6};
     if (f8 && dp == 1024) return {8, 3, 4};
     return {0, 0, 0};
@@ -1890,10 +1974,14 @@ __global__ __launch_bounds__(kScan2Waves * 64) void k_scan2r(ScanArgs a) {
     const unsigned long long c_entry = (a.debug & 512) ? __builtin_amdgcn_s_memtime() : 0ull;   // shader cycles: the in-kernel clock = [71] / ([3] - [68]) x 100 MHz
     extern __shared__ __attribute__((aligned(1024))) char smem[];
     constexpr int QN = NT * kQueryTile, THREADS = kScan2Waves * 64;
-    constexpr int J = F8 ? 8 : 4;                       // B fragments (matrix instructions per query tile) per 128-byte row segment
+    constexpr bool I8 = F8 >= 3;                        // int8 image rows x int8 query planes on v_mfma_i32_32x32x32_i8
+    constexpr int PLANES = F8 == 4 ? 2 : 1;             // ... F8 = 3: one plane; F8 = 4: hi + lo planes (the residual quantised again at step / 254)
+    constexpr int J = I8 ? 4 * PLANES : F8 ? 8 : 4;     // B fragments (matrix instructions per query tile) per 128-byte row segment
     constexpr int SEGIMG = J * 2 * QN * 16;             // image bytes of a segment: 16 (e4m3: 128 elements) or 8 k-groups x QN x 16 B
-    // fragment j of a segment: k-group 8 sg + 4 h + j (fp16 rows) or 16 sg + 8 (j >> 2) + 4 h + (j & 3) (e4m3 rows: two 64-element chunks)
-    auto frag_off = [](int j) { return F8 ? ((j >> 2) * 8 + (j & 3)) * (QN * 16) : j * (QN * 16); };
+    // fragment j of a segment: k-group 8 sg + 4 h + j (fp16 rows) or 16 sg + 8 (j >> 2) + 4 h + (j & 3) (e4m3 rows: two 64-element chunks);
+    // I8: a k-group is 16 codes, the image is [dp / 16][PLANES][QN][16] and fragment j is plane j >> 2 of the K = 32 step j & 3: k-groups 8 sg + 2 (j & 3) + h
+    auto frag_off = [](int j) { return I8 ? (2 * (j & 3) * PLANES + (j >> 2)) * (QN * 16) : F8 ? ((j >> 2) * 8 + (j & 3)) * (QN * 16) : j * (QN * 16); };
+    static_assert(F8 != 3 || RB == S, "the single int8 plane lives in registers whole: no LDS part");
     static_assert(S >= RING && RB <= S && RB <= 6, "ring fill and the spelled-out register segments");
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int r31 = lane & 31, h = lane >> 5;
@@ -1932,7 +2020,7 @@ __global__ __launch_bounds__(kScan2Waves * 64) void k_scan2r(ScanArgs a) {
     // ---- the register part of the image: B fragments of segments 0 .. RB - 1 (query 32 nt + r31), loaded first
     h8 breg[RB][J][NT];
     {
-        const char* qb = (const char*)a.qimg + ((long long)(4 * h) * QN + r31) * 16;
+        const char* qb = (const char*)a.qimg + ((long long)((I8 ? PLANES : 4) * h) * QN + r31) * 16;
 #pragma unroll
         for (int sg = 0; sg < RB; ++sg)
 #pragma unroll
@@ -1941,6 +2029,9 @@ __global__ __launch_bounds__(kScan2Waves * 64) void k_scan2r(ScanArgs a) {
                 for (int nt = 0; nt < NT; ++nt)
                     breg[sg][j][nt] = *(const h8*)(qb + (long long)sg * SEGIMG + frag_off(j) + nt * (kQueryTile * 16));
     }
+    float sq[NT];                                       // I8: the code step of this lane's query of each tile (the accumulator's column)
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) sq[nt] = I8 ? a.q_scale[nt * kQueryTile + r31] : 1.0f;
     // LDS carve-up: four rings of RING segments | the LDS half of the image (segments RB .. S - 1) | scratch | control block | stage
     char* ring = smem + (size_t)wid * (RING * kSegBytes);
     char* img = smem + kScan2Waves * RING * kSegBytes;
@@ -1987,7 +2078,7 @@ __global__ __launch_bounds__(kScan2Waves * 64) void k_scan2r(ScanArgs a) {
     auto issue_epi = [&](long long t0, bool sync_tau, int par) {
         par = __builtin_amdgcn_readfirstlane(par);
         // (int8 image: lanes 32..63 bring the 32 rows' score offsets instead of repeating their inverse norms; off_scan is padded like inv_scan)
-        dma4((F8 == 2 && h) ? a.off_scan + t0 + r31 : a.inv_scan + t0 + r31, scratch_l + par * 512 + 256);
+        dma4((F8 >= 2 && h) ? a.off_scan + t0 + r31 : a.inv_scan + t0 + r31, scratch_l + par * 512 + 256);
         if (sync_tau) dma4(a.tau_bin + (lane < QN ? lane : QN - 1), scratch_l + par * 512);
     };
     int cur_tile = __builtin_amdgcn_readfirstlane(wid);                // (a scalar from here on: tile addresses stay in SGPRs)
@@ -2025,7 +2116,7 @@ __global__ __launch_bounds__(kScan2Waves * 64) void k_scan2r(ScanArgs a) {
         __syncthreads();
     }
 
-    const char* lds_lane = img + ((4 * h) * QN + r31) * 16;            // + (sg - RB) * SEGIMG + frag_off(j) + nt * (32 * 16)
+    const char* lds_lane = img + (((I8 ? PLANES : 4) * h) * QN + r31) * 16;            // + (sg - RB) * SEGIMG + frag_off(j) + nt * (32 * 16)
     const int asw = (r31 >> 1) & 7;
     const char* a_lane = ring + r31 * 128;
     const int dbg_rec = (a.debug & 512) ? 72 : 4;
@@ -2051,10 +2142,15 @@ __global__ __launch_bounds__(kScan2Waves * 64) void k_scan2r(ScanArgs a) {
     int tiles_done = 0;
     if (active) {
         f16v acc[NT];
+        i16v acci[PLANES][NT];                             // I8: the exact integer sums per plane (|sum| <= 768 x 127^2 < 2^24: their fp32 form is exact too)
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
-            for (int e = 0; e < 16; ++e) acc[nt][e] = 0.0f;
+            for (int e = 0; e < 16; ++e) {
+                acc[nt][e] = 0.0f;
+#pragma unroll
+                for (int pl = 0; pl < PLANES; ++pl) acci[pl][nt][e] = 0;
+            }
         int buf = 0;
         while (true) {
             VF_PC(pt0 = cyc())
@@ -2092,7 +2188,31 @@ __global__ __launch_bounds__(kScan2Waves * 64) void k_scan2r(ScanArgs a) {
                         return *(const h8*)(bb + frag_off(j) + nt * (kQueryTile * 16));
                     }
                 };
-                if constexpr (F8 == 0) {
+                if constexpr (I8) {
+                    // int8 image rows on the int8 instruction: lane (r, h)'s 16 bytes of K-step i (pieces 2 i + h of its row) ARE the A
+                    // fragment; the image stores code + 128, so one v_xor per dword flips the sign bit back (the VALU, beside the matrix pipe)
+                    i4v af[4];
+                    h8 bl[J][NT];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) af[i] = *(const i4v*)(ab + (((2 * i + h) ^ asw) << 4));
+                    if constexpr (sgc < 0) {
+#pragma unroll
+                        for (int j = 0; j < J; ++j)
+#pragma unroll
+                            for (int nt = 0; nt < NT; ++nt) bl[j][nt] = bfrag(j, nt);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const i4v ax = af[i] ^ (int)0x80808080;
+#pragma unroll
+                        for (int pl = 0; pl < PLANES; ++pl)
+#pragma unroll
+                            for (int nt = 0; nt < NT; ++nt)
+                                acci[pl][nt] = __builtin_amdgcn_mfma_i32_32x32x32_i8(ax, __builtin_bit_cast(i4v, sgc < 0 ? bl[4 * pl + i][nt] : bfrag(4 * pl + i, nt)),
+                                                                                     acci[pl][nt], 0, 0, 0);
+                    }
+                } else if constexpr (F8 == 0) {
                     if constexpr (AR) {
                         h8 af[4], bl[4][NT];
 #pragma unroll
@@ -2182,13 +2302,25 @@ __global__ __launch_bounds__(kScan2Waves * 64) void k_scan2r(ScanArgs a) {
             EpiRegs<NT> epi;
             epi.inv_lane = *(const float*)(sc + 256 + r31 * 4);
             epi.inv_lds = sc + 256;
-            if constexpr (F8 == 2) epi.off_lane = *(const float*)(sc + 384 + r31 * 4);
+            if constexpr (F8 >= 2) epi.off_lane = *(const float*)(sc + 384 + r31 * 4);
+            if constexpr (I8) {   // the exact sums, once per tile: v_cvt_f32_i32 (exact) x the query's code step; the row's step rides in its inverse
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) {
+                        float v = (float)acci[0][nt][e];
+                        // two planes: hi x 254 + lo in fp32 (the int32 sum would overflow); sq is the lo plane's step = the hi plane's / 254
+                        if constexpr (PLANES == 2) { v = v * 254.0f + (float)acci[1][nt][e]; acci[1][nt][e] = 0; }
+                        acc[nt][e] = v * sq[nt];
+                        acci[0][nt][e] = 0;
+                    }
+            }
             epi.sync_tau = sync_now;
             if (sync_now) {
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) epi.tau_g[nt] = *(const int*)(sc + (nt * kQueryTile + r31) * 4);
             }
-            tile_epilogue<NT, MODE, true, true, F8 == 2>(a, acc, epi, t0, t_hi, t_s0, lane, ctl);
+            tile_epilogue<NT, MODE, true, true, F8 >= 2>(a, acc, epi, t0, t_hi, t_s0, lane, ctl);
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
@@ -2211,7 +2343,7 @@ __global__ __launch_bounds__(kScan2Waves * 64) void k_scan2r(ScanArgs a) {
         const u32 staged = *(const u32*)ctl;
         const u32 nst = staged < (u32)a.stage_cap ? staged : (u32)a.stage_cap;
         uint4* ent = (uint4*)(ctl + kCtlBytes);
-        u32* qcnt = (u32*)img;          // the LDS half of the image is dead now
+        u32* qcnt = (u32*)(kImgBytes ? img : smem);   // the LDS half of the image is dead now (no LDS half: a ring is -- every wave has waited vmcnt(0))
         u32* qbase = qcnt + QN;
         if (tid < QN) qcnt[tid] = 0u;
         __syncthreads();
@@ -3505,7 +3637,7 @@ hipError_t launch_scan2(const ScanArgs& a, int qn_tile, int grid, int rows_are_f
 
 // every (query tile, mode, shape) instantiation of k_scan2r, as X(NT, MODE, F8, S, RB, RING)
 #define VF_SCAN2R_PRODUCT(X, NT, MODE) X(NT, MODE, 0, 12, 6, 6, 1) X(NT, MODE, 0, 16, 6, 4, 1) X(NT, MODE, 0, 8, 4, 6, 1) X(NT, MODE, 0, 6, 3, 6, 1) X(NT, MODE, 1, 6, 3, 6, 1) X(NT, MODE, 1, 8, 3, 4, 1) \
-    X(NT, MODE, 2, 6, 3, 6, 1)
+    X(NT, MODE, 2, 6, 3, 6, 1) X(NT, MODE, 3, 6, 6, 6, 1) X(NT, MODE, 4, 6, 3, 6, 1)
 #ifdef VF_EXPERIMENTS
 #define VF_SCAN2R_SHAPES(X, NT, MODE) VF_SCAN2R_PRODUCT(X, NT, MODE) X(NT, MODE, 0, 12, 6, 6, 0) X(NT, MODE, 1, 6, 3, 4, 1)   // (+ the first form: debug bit 10; + a four-segment ring on e4m3 rows of 768: bit 11)
 #else
@@ -3636,7 +3768,8 @@ __global__ __launch_bounds__(1024) void k_sel0(ScanArgs a) {
     __syncthreads();
     if (tid < 64) {
         const int nb = wave_tau_from_lds(lh, a.kprime, tid);
-        if (tid == 0) sbin = nb - a.tau_band > 0 ? nb - a.tau_band : 0;   // (band: ScanArgs::tau_band)
+        const int band = (a.band_q && q < a.nq) ? a.band_q[q] : a.tau_band;   // (ScanArgs::tau_band, or the query's own)
+        if (tid == 0) sbin = nb - band > 0 ? nb - band : 0;
     }
     __syncthreads();
     const int tb = sbin;
@@ -3874,6 +4007,7 @@ __global__ __launch_bounds__(kFinalThreads) void k_final(FinalArgs a) {
     const int mwant = n < a.kprime ? n : a.kprime;   // how many of the best candidates must be re-scored
     const u64* cq = a.cand + (long long)q * a.cap;
     const int tbin = a.tau_bin[q];
+    const int band = a.band_q ? a.band_q[q] : a.band;   // (per query where the query's own quantisation widens it: launch_prep_q8)
     if (n_raw > (u32)a.cap) {   // overflowed list: not every slot need be written -- nothing here can be trusted, exact path
         for (int i = tid; i < a.k; i += kFinalThreads) { a.out_ids[(long long)q * a.k + i] = -1; a.out_scores[(long long)q * a.k + i] = -FLT_MAX; }
         if (tid == 0) { a.flags[q] = 2; a.cand_count_out[q] = n_raw; }
@@ -3901,7 +4035,7 @@ __global__ __launch_bounds__(kFinalThreads) void k_final(FinalArgs a) {
         int nb = wave_tau_from_lds(lh, mwant > 0 ? mwant : 1, tid);
         // band mode (int8 image scan, kprime = k): every candidate within 2 eps of the k-th best approximate score -- `band` fine bins
         // of 1 / 16 384, or band / 16 threshold bins without a threshold -- but none below the scan's threshold (fine bin 0)
-        if (a.band > 0 && nb > 0) nb = max(nb - (tbin > 0 ? a.band : (a.band + 15) / 16), tbin > 0 ? 1 : 0);
+        if (band > 0 && nb > 0) nb = max(nb - (tbin > 0 ? band : (band + 15) / 16), tbin > 0 ? 1 : 0);
         if (tid == 0) s_bin = nb > 0 ? nb : 0;
     }
     __syncthreads();
@@ -3985,7 +4119,7 @@ __global__ __launch_bounds__(kFinalThreads) void k_final(FinalArgs a) {
                 // bin_x(s) < forig + (sbin - 1) / fscale (exact in fp32), so s < that edge mapped back + 2^-20 (bin_x's rounding) -- not by
                 // the smallest survivor, which a sparse band (k = 1) leaves far above the cut
                 float bound = approx_floor;
-                if (a.band > 0 && sbin > 0) bound = (forig + (float)(sbin - 1) / fscale - 0.5f * kHistBins) / (0.5f * kHistBins) + 0x1p-20f;
+                if (band > 0 && sbin > 0) bound = (forig + (float)(sbin - 1) / fscale - 0.5f * kHistBins) / (0.5f * kHistBins) + 0x1p-20f;
                 if (!(ck_k > bound + (a.eps_q ? fmaxf(a.eps_q[q], a.eps) : a.eps))) flag = 1;
             }
         }
