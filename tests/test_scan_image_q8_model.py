@@ -81,8 +81,8 @@ def _queries(kind, nq, seed):
 
 
 def _check_all_pairs(oracle, x, q, planes):
-    code, s_row, inv, rho_row, norm = M.quantise(x)
-    off = M.offsets(rho_row, D)
+    code, s_row, inv, rho_row, norm, res_row = M.quantise(x, full=True)
+    off = M.offsets(res_row, D)
     qn = oracle.normalize(q)
     hi, lo, s, rho_q, real = quantise_query(qn, planes)
     assert np.all(rho_q.astype(np.float64) >= real)              # rho_q as computed bounds the realised residual

@@ -2025,6 +2025,37 @@ extern "C" int vf_debug_prep_q8(const float* qn, int32_t nq, int32_t d, int32_t 
     return VF_OK;
 }
 
+// Test hook (not in the public header): k_prep_rows then k_prep_image on n host rows of d elements (VF_DTYPE_F16 / _F32; any n >= 1, no
+// shard-size rule): the code bytes as stored [n][dp] (dp = d padded to 128), inv_img [n], off_img [n], the canonical norms [n], the
+// largest rho and the sum of the rhos, so that a test can hold the DEVICE's row side of the certificate against the NumPy model
+extern "C" int vf_debug_prep_image(const void* rows, int32_t dtype, int64_t n, int32_t d, unsigned char* codes, float* inv_img, float* off_img,
+                                   float* norm, float* rho_max, float* rho_sum) {
+    DeviceGuard restore_callers_device;
+    if (!rows || !codes || !inv_img || !off_img || !norm || !rho_max || !rho_sum || (dtype != VF_DTYPE_F16 && dtype != VF_DTYPE_F32) || n < 1 ||
+        n > (1 << 24) || d < 1 || d > 8192)
+        return fail(VF_EINVAL, "vf_debug_prep_image: bad argument");
+    const int dp = (d + 127) / 128 * 128;
+    const size_t nn = (size_t)n, in_bytes = nn * d * (dtype == VF_DTYPE_F16 ? 2 : 4), img_bytes = nn * dp;
+    char* d_in = nullptr; unsigned char* d_img = nullptr; float* d_f = nullptr;   // d_f: norm | inv_scan | inv_img | off_img | rho max bits, rho sum
+    VF_HIP(hipMalloc((void**)&d_in, in_bytes));
+    hipError_t e = hipMalloc((void**)&d_img, img_bytes);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_f, (4 * nn + 2) * sizeof(float));
+    if (e == hipSuccess) e = hipMemset(d_f, 0, (4 * nn + 2) * sizeof(float));
+    if (e == hipSuccess) e = hipMemset(d_img, 0xFF, img_bytes);   // (no code is 0xFF: a byte the kernel left alone shows)
+    if (e == hipSuccess) e = hipMemcpy(d_in, rows, in_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = launch_prep_rows(d_in, dtype, n, d, dp, nullptr, d_f, d_f + nn, nullptr);
+    if (e == hipSuccess) e = launch_prep_image(d_in, dtype, n, d, dp, d_f, d_img, d_f + 2 * nn, d_f + 3 * nn, (u32*)(d_f + 4 * nn), d_f + 4 * nn + 1, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(codes, d_img, img_bytes, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(norm, d_f, nn * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(inv_img, d_f + 2 * nn, nn * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(off_img, d_f + 3 * nn, nn * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(rho_max, d_f + 4 * nn, 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(rho_sum, d_f + 4 * nn + 1, 4, hipMemcpyDeviceToHost);
+    (void)hipFree(d_in); (void)hipFree(d_img); (void)hipFree(d_f);
+    if (e != hipSuccess) return fail(VF_EHIP, std::string("vf_debug_prep_image: ") + hipGetErrorString(e));
+    return VF_OK;
+}
+
 // Test hook (not in the public header): C [32][32] = A [32][32] B [32][32]^T through ONE int8 matrix instruction fed the way k_scan2r's
 // int8 body feeds it (host pointers)
 extern "C" int vf_debug_mfma_i8(const signed char* A, const signed char* B, int32_t* C) {
