@@ -56,7 +56,7 @@ typedef struct vf_search_stats {
     int64_t wide_queries;    /* queries those passes served (up to 1024 per pass) */
     int64_t aux_cus;         /* CUs the main scan left to the small kernels of the other slots (0 = no CU split) */
     int64_t scans_overlap;   /* 1 = main scans of consecutive slots were not ordered against each other */
-    int64_t scan_kernel;     /* main-scan kernel of the call: 1 k_scan (register loads), 2 k_scan2 (whole-line LDS-DMA), 3 k_scan_wide, 4 k_scan_wide8 (fp8 matrix instruction), 5 k_scan2r (k_scan2, half the query image in registers), 6 k_scan_ksplit (rows of 2560 to 4096 padded elements: option "wide_rows") */
+    int64_t scan_kernel;     /* main-scan kernel of the call: 1 k_scan (register loads), 2 k_scan2 (whole-line LDS-DMA), 3 k_scan_wide, 4 k_scan_wide8 (fp8 matrix instruction), 5 k_scan2r (k_scan2, half the query image in registers), 6 k_scan_ksplit (rows of 2560 to 4096 padded elements: option "wide_rows"), 7 k_scan_ksplit8 (the same for e4m3 rows) */
     int64_t scan_image;      /* 1 = the main scan read the int8 row image (option "scan_image"), 0 = the rows as stored */
     int64_t reserved[3];
 } vf_search_stats;
@@ -137,7 +137,8 @@ int vf_index_info(vf_index* idx, int64_t* n, int32_t* d, int32_t* dtype, int32_t
 int vf_index_stats(vf_index* idx, vf_search_stats* out);
 /* tuning knobs, by name ("force_path", "sample_rows", "margin", "cap", "waves" ...); tests use
  * force_path to exercise every path on the same data.  Unknown name -> VF_EINVAL.
- * "wide_mfma": matrix instruction of the wide scan (batches of >= 129 queries) over e4m3 rows: -1 auto (= 1), 1 the fp8
+ * "wide_mfma": matrix instruction of the wide scan (batches of >= 129 queries) over e4m3 rows: -1 auto (= 1; = 0 for rows of 2560
+ *   to 4096 padded elements, where the hi + lo query's wider bound costs repairs), 1 the fp8
  *   instruction on the row bytes as stored (k_scan_wide8: the query goes in as a hi + lo pair of e4m3 codes and its exactly
  *   known residual is the query's certificate bound), 0 the fp16 instruction on converted rows (k_scan_wide).  Results are
  *   identical bit for bit; vf_search_stats.scan_kernel says which one ran.
@@ -149,12 +150,15 @@ int vf_index_stats(vf_index* idx, vf_search_stats* out);
  *   row count.  Same results from each.
  * "sample_impl": the sample pass's kernel: -1 auto (k_scan2r's operand path where it exists and the CU split is on), 0 k_scan, 1 k_scan2r
  *   wherever it fits.  Same sample rows and slots either way; results do not change.
- * "wide_rows": the fused path for fp16 / fp32 rows of 2433 to 4096 elements (padded to 2560 .. 4096: Qwen3-Embedding-4B / -8B,
+ * "wide_rows": the fused path for rows of 2433 to 4096 elements (padded to 2560 .. 4096: Qwen3-Embedding-4B / -8B,
  *   gte-Qwen2-7B), whose 32-query image does not fit the LDS: k_scan_ksplit splits the contraction over the workgroup's four waves and
  *   keeps the image in registers + LDS (up to 32 queries per pass; batches of 33 or more go to k_scan_wide).  0 never (such an index
  *   takes the chunked exact path at every size, and "force_path" = 1 is refused), 1 auto (default: from 131 072 rows), 2 wherever it
  *   is possible (more than 16 384 rows).  "force_path" = 1 takes the kernel at any of these sizes unless the option is 0.  e4m3 rows of
- *   these widths stay on the chunked path.  Same results bit for bit; vf_search_stats.scan_kernel = 6 where the kernel ran. */
+ *   these widths (padded to a multiple of 128) have a kernel of their own, k_scan_ksplit8 (a row is dp bytes, converted to fp16 in
+ *   registers at the matrix instruction; vf_search_stats.scan_kernel = 7): auto from 32 768 rows, up to 64 queries in 32-query passes,
+ *   batches of 65 or more on k_scan_wide where the padded width is a multiple of 256.  Same results bit for bit;
+ *   vf_search_stats.scan_kernel = 6 where k_scan_ksplit ran. */
 int vf_index_set_option(vf_index* idx, const char* name, int64_t value);
 /* Live kernel timing with HIP events on the stream the kernels run on (bench.py roofline):
  * after vf_index_set_option(idx, "profile", 1) every fused search records events around its main

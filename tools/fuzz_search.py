@@ -34,6 +34,10 @@ def draw_case(rng, max_work):
         d = pick([768, 768, 1024, 512, 384, 1000]) if dtype != "fp8" else pick([768, 1024])
         opts["scan_impl"] = 5
         opts["sample_impl"] = 1
+    elif os.environ.get("VF_FUZZ_WIDE_ROWS") == "1":   # soak of the four-wave kernels for rows of 2560 to 4096 padded elements: k_scan_ksplit (fp16 / fp32 rows), k_scan_ksplit8 (e4m3 rows), the wide pass behind them
+        dtype = pick(["f16", "f32", "fp8", "fp8", "fp8"])
+        d = pick([2560, 2688, 3000, 3072, 3968, 4096, int(rng.integers(2433, 4097))])
+        opts["wide_rows"] = 2
     elif rng.random() < 0.3:
         opts["scan_impl"] = pick([1, 2, 3, 4, 5])
         opts["sample_impl"] = pick([-1, 0, 1])

@@ -104,7 +104,7 @@ struct Slot {
     hipEvent_t ev_t[4] = {nullptr, nullptr, nullptr, nullptr};  // profile: scan begin/end, pipeline begin/end
     bool timed = false;
     int wide_launches = 0, wide_queries = 0;   // k_scan_wide main passes of the pending search / queries they served
-    int scan_kernel = 0;                       // main-scan kernel of the pending search: 1 k_scan, 2 k_scan2, 3 k_scan_wide
+    int scan_kernel = 0;                       // main-scan kernel of the pending search: 1 k_scan, 2 k_scan2, 3 k_scan_wide, ... 7 k_scan_ksplit8 (veritasfi_hip.h)
     int scan_image = 0;                        // 1: the pending search's scans read the int8 row image
     DevBuf qn, qimg, s0, cnt, tau, hist, hist_coarse, cand, flags, counts;   // fused-path state
     DevBuf dbg, wgbase, tilecnt, sib;
@@ -707,7 +707,7 @@ extern "C" int vf_index_set_option(vf_index* ix, const char* name, int64_t value
         ix->scan_image = value;
     }
     else if (s == "image_mfma") { if (!in_range(-1, 2)) return fail(VF_EINVAL, "image_mfma must be -1 (auto), 0 (the int8 row image on the fp16 matrix instruction, fp16 queries), 1 (on the int8 matrix instruction, the queries as one int8 plane) or 2 (as two planes, hi + lo: the band of 0)"); ix->image_mfma = value; }
-    else if (s == "wide_rows") { if (!in_range(0, 2)) return fail(VF_EINVAL, "wide_rows must be 0 (rows of more than 2432 padded elements never take the fused path), 1 (auto: from 131 072 rows) or 2 (wherever k_scan_ksplit serves them)"); ix->wide_rows = value; }
+    else if (s == "wide_rows") { if (!in_range(0, 2)) return fail(VF_EINVAL, "wide_rows must be 0 (rows of more than 2432 padded elements never take the fused path), 1 (auto: from 131 072 rows, e4m3 rows from 32 768) or 2 (wherever k_scan_ksplit / k_scan_ksplit8 serve them)"); ix->wide_rows = value; }
     else if (s == "debug") ix->debug = value;
     else if (s == "profile") {
         ix->profile = value != 0; ix->prof_scan_ms = ix->prof_pipe_ms = 0.0; ix->prof_launches = 0;
@@ -782,7 +782,7 @@ struct FusedPlan {
 
 static int qn_tile_for(int nq_batch) { return nq_batch <= kQueryTile ? kQueryTile : kMaxBatch; }
 
-// Rows of 2560 to 4096 padded elements (fp16, or the fp16 scan copy of fp32 rows): a 32-query image does not fit the LDS, so k_scan cannot
+// Rows of 2560 to 4096 padded elements (fp16, or the fp16 scan copy of fp32 rows; e4m3 rows: below): a 32-query image does not fit the LDS, so k_scan cannot
 // serve them; k_scan_ksplit does (the contraction split over four waves, the image in registers + LDS).  Option wide_rows: 0 never, 2
 // wherever the kernel serves the rows, 1 (auto) from kWideRowsMinRows rows.
 // The count is measured (tools/bench_wide_rows.py, one box, the settings alternating, three windows of a second each;
@@ -796,9 +796,19 @@ static int qn_tile_for(int nq_batch) { return nq_batch <= kQueryTile ? kQueryTil
 // test_wide_rows_and_path_limits: 17 000 x 2560 on path 2).
 constexpr int64_t kWideRowsMinRows = 131072;
 static bool ksplit_width(const vf_index* ix) { return scan_lds_bytes(ix->dp, kQueryTile) > 160 * 1024; }   // no LDS-resident 32-query image: dp > 2432
+// e4m3 rows of these widths: k_scan_ksplit8 (a row is dp bytes; the same split, image and reduction), under the same option.  Its count is
+// measured the same way (tools/bench_wide_rows.py --dtype fp8, one box, the settings alternating, three windows;
+// profiles/r10_wide_rows_fp8_threshold.log): 32 768 / 65 536 / 131 072 / 262 144 / 1 048 576 rows, 1 / 4 / 32 / 64 / 65 / 96 / 128 queries,
+// k = 100 / 2048, d = 2560 and 4096.  Half the bytes per row halve the scan and the re-score of k' rows, so the fused path wins EVERY cell
+// from the smallest row count of the grid: the closest are k = 2048 with one query at 32 768 rows, 0.339 against 0.364 ms at 2560 and
+// 0.505 against 0.540 at 4096 (four queries: 0.345 / 0.475 and 0.518 / 0.670); at k = 100 it is 0.109 against 0.345 and 0.143 against
+// 0.539 there, and 0.439 against 10.5 and 0.749 against 16.5 ms at 1M rows.  So: 32 768, for every width.
+constexpr int64_t kWideRowsMinRows8 = 32768;
+static bool rows_e4m3(const vf_index* ix) { return ix->dtype == VF_DTYPE_FP8_E4M3; }
+static int ksplit_stage_cap(const vf_index* ix) { return rows_e4m3(ix) ? scan_ksplit8_stage_cap(ix->dp) : scan_ksplit_stage_cap(ix->dp); }
 static bool ksplit_serves(const vf_index* ix, bool forced) {
-    if (ix->wide_rows == 0 || ix->dtype == VF_DTYPE_FP8_E4M3 || scan_ksplit_stage_cap(ix->dp) < 256) return false;
-    return forced || ix->wide_rows == 2 || ix->n >= kWideRowsMinRows;
+    if (ix->wide_rows == 0 || ksplit_stage_cap(ix) < 256) return false;
+    return forced || ix->wide_rows == 2 || ix->n >= (rows_e4m3(ix) ? kWideRowsMinRows8 : kWideRowsMinRows);
 }
 
 static bool fused_possible(const vf_index* ix, int k, bool forced = false) {
@@ -959,12 +969,20 @@ constexpr int kWideMinQueries16 = 65;  // fp16 (and fp32 -> fp16 scan copy) rows
 // every measured row count from 32 768 up and at k = 2048 too (profiles/r08_wide_rows_ab.log, r08_wide_rows_threshold.log).  So the
 // boundary is the second pass: up to 32 queries k_scan_ksplit, from 33 k_scan_wide.
 constexpr int kWideMinQueriesKsplit = 33;
+// The same boundary for e4m3 rows of these widths (profiles/r10_wide_rows_fp8_threshold.log, r10_wide_rows_fp8_ab.log): a pass of
+// k_scan_ksplit8 reads half the bytes of k_scan_ksplit's, k_scan_wide (fp16 instruction on converted rows) runs at the matrix rate as
+// before, so TWO 32-query passes still beat it where the rows are many -- 64 queries, k = 100, ms per batch, k_scan_ksplit8 / k_scan_wide:
+// 262 144 x 2560 0.354 / 0.369, 1M x 2560 0.923 / 1.138, 262 144 x 4096 0.511 / 0.516, 1M x 4096 1.536 / 1.730 (up to 131 072 rows and at
+// k = 2048 the wide pass is ahead at 64 too) -- and three never do: 65 queries 1M x 2560 1.358 / 1.138, 1M x 4096 2.282 / 1.737,
+// 32 768 x 2560 0.327 / 0.195; 96 and 128 queries likewise in every cell.  So the boundary is the third pass: from 65 the wide pass.
+// Paddings it does not take (dp % 256 != 0) stay on 32-query passes of k_scan_ksplit8.
+constexpr int kWideMinQueriesKsplit8 = 65;
 constexpr int kWideMaxQueries = 1024;  // 4 query tiles of 256 per pass: one workgroup per CU
 constexpr int kWideTile = 256;
 
 static bool wide_possible(const vf_index* ix, int nq) {
     const bool ks = ksplit_width(ix);   // rows only k_scan_ksplit holds an image of (32 queries per pass)
-    if (ix->wide_opt == 0 || nq < (ix->wide_opt > 1 ? (int)ix->wide_opt : ks ? kWideMinQueriesKsplit : (ix->dtype == VF_DTYPE_FP8_E4M3 ? kWideMinQueries : kWideMinQueries16))) return false;
+    if (ix->wide_opt == 0 || nq < (ix->wide_opt > 1 ? (int)ix->wide_opt : ks ? (rows_e4m3(ix) ? kWideMinQueriesKsplit8 : kWideMinQueriesKsplit) : (ix->dtype == VF_DTYPE_FP8_E4M3 ? kWideMinQueries : kWideMinQueries16))) return false;
     // a register stage is 2 k-chunks of fp8 rows / 1 of fp16 rows and a tile alternates two stages
     return ix->dp % (ix->dtype == VF_DTYPE_FP8_E4M3 ? 256 : 128) == 0;
 }
@@ -977,7 +995,12 @@ static int wide_pass(vf_index* ix, Slot& s, const FusedPlan& p0, const float* d_
     FusedPlan p = p0;
     if (p.kprime > 256) p.cap = std::max(p.cap, 16384);   // k ~ 1000: ~k' (1 + ln(n / sample)) candidates per query
     // k_scan_wide8 (the fp8 matrix instruction): e4m3 rows, K-tiles of 64, a row group's bytes within a 32-bit lane offset
-    const bool w8 = ix->wide_mfma != 0 && ix->dtype == VF_DTYPE_FP8_E4M3 && ix->dp % 64 == 0 &&
+    // Rows of 2560 to 4096 padded elements take it on request only (wide_mfma = 1), auto keeps k_scan_wide: the query's hi + lo split
+    // leaves a bound eps_q that grows with the width while make_plan's margin is sized for the fp16 bound, so on N(0, 1) rows queries
+    // fail the certificate (2 of 64 at 1M x 2560, 25 of 64 at 1M x 4096) and each pays an exact repair of milliseconds over 1M rows -- 64
+    // queries: 9.49 ms per batch against k_scan_wide's 1.12 at 2560, 57.0 against 1.74 at 4096 (the scans themselves: 0.90 against 0.96 ms,
+    // 1.93 against 1.53; profiles/r10_wide_rows_fp8_ab.log).  Exact either way.
+    const bool w8 = (ix->wide_mfma > 0 || (ix->wide_mfma < 0 && !ksplit_width(ix))) && ix->dtype == VF_DTYPE_FP8_E4M3 && ix->dp % 64 == 0 &&
                     (ix->n / RG + 2 * 256) * (int64_t)ix->dp < (int64_t)0xFFFFFFFFll;
     if (w8) {
         // the query's hi + lo split leaves ||delta|| ~ 6e-4 of the query's norm (eps_q ~ 1.1e-3 at dp = 1024 against the fp16 path's
@@ -1154,7 +1177,7 @@ static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq,
         if (p.image) { a.rows = (const char*)ix->rows_img; a.inv_scan = ix->inv_img; a.off_scan = image_offsets(ix); a.row_bytes = ix->dp; }   // every pass of the batch: sample, seed, main
         a.s0 = s.s0.as<float>(); a.wg_base = s.wgbase.as<long long>(); a.cnt = s.cnt.as<u32>(); a.tau_bin = s.tau.as<int>(); a.hist = s.hist.as<u32>();
         a.cand = s.cand.as<u64>(); a.cap = p.cap; a.kprime = p.kprime; a.tau_band = p.tau_band;
-        a.hist_coarse = s.hist_coarse.as<u32>(); a.stage_cap = ks ? scan_ksplit_stage_cap(ix->dp) : scan_stage_cap(ix->dp, qt);
+        a.hist_coarse = s.hist_coarse.as<u32>(); a.stage_cap = ks ? ksplit_stage_cap(ix) : scan_stage_cap(ix->dp, qt);
         a.tile_cnt = ix->steal_opt ? s.tilecnt.as<u32>() : nullptr; a.scan_grid = p.grid;
         a.dbg = nullptr;
         if (ix->debug & 128) { VF_TRY(s.dbg.ensure((size_t)p.total_waves * ((ix->debug & 512) ? 72 : 4) * sizeof(u64))); a.dbg = s.dbg.as<u64>(); if (ix->debug & 512) VF_HIP(hipMemsetAsync(s.dbg.p, 0, s.dbg.bytes, st)); }
@@ -1182,7 +1205,7 @@ static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq,
         const bool sample_r = p.image || (ix->sample_impl != 0 && ix->scan_impl != 1 && scan2r_stage_cap(ix->dp, qt, f8rows) >= 256 &&
                               (ix->sample_impl == 1 || (!f8rows && s.scan_stream != s.stream && scan2r_auto_width(ix->dp, false)) || r_f8_auto));
         if (ks) {   // one workgroup per range: each loads its share of the image once and scores its range's sample part
-            VF_HIP(launch_scan_ksplit(a, kModeSample, p.grid, st));
+            VF_HIP(rows_e4m3(ix) ? launch_scan_ksplit8(a, kModeSample, p.grid, st) : launch_scan_ksplit(a, kModeSample, p.grid, st));
         } else if (sample_r) {
             const int64_t sg_r = ix->sample_grid > 0 ? ix->sample_grid : (s.scan_stream != s.stream ? resolved_aux(ix) : p.grid);
             ScanArgs as = a;
@@ -1237,7 +1260,10 @@ static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq,
         const bool dbg_r = true;
 #endif
         const int capr = ((ix->scan_impl == 5 || r_auto) && !ix->steal_opt && dbg_r) ? scan2r_stage_cap(ix->dp, qt, f8) : 0;
-        if (ks) {
+        if (ks && f8) {
+            VF_HIP(launch_scan_ksplit8(a, kModeMain, p.grid, sst));
+            s.scan_kernel = 7;
+        } else if (ks) {
             VF_HIP(launch_scan_ksplit(a, kModeMain, p.grid, sst));
             s.scan_kernel = 6;
         } else if (p.image) {   // the int8 row image (image_serves: k_scan2r's e4m3 shapes, stage >= 256)

@@ -187,6 +187,10 @@ hipError_t launch_scan2r_sample(const ScanArgs& a, int qn_tile, int grid, int f8
 hipError_t launch_scan_ksplit(const ScanArgs& a, int mode, int grid, hipStream_t s);
 size_t scan_ksplit_lds_bytes(int dp, int stage_cap);
 int scan_ksplit_stage_cap(int dp);
+// k_scan_ksplit8: the same for e4m3 rows (a.row_bytes = dp; segments of 128 bytes, 5 to 8 per wave); scan_ksplit8_stage_cap = 0: not this kernel
+hipError_t launch_scan_ksplit8(const ScanArgs& a, int mode, int grid, hipStream_t s);
+size_t scan_ksplit8_lds_bytes(int dp, int stage_cap);
+int scan_ksplit8_stage_cap(int dp);
 hipError_t launch_scan_wide(const ScanArgs& a, int mode, int rows_are_fp8, hipStream_t s);
 size_t scan_wide_lds_bytes(int stage_cap);
 // k_scan_wide8: the wide main scan on the fp8 matrix instruction (e4m3 rows; a.qimg = the hi / lo code image of launch_prep_wide8)

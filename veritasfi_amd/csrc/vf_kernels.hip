@@ -1501,6 +1501,164 @@ __global__ __launch_bounds__(kKsThreads) void k_scan_ksplit(ScanArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// k_scan_ksplit8: k_scan_ksplit for the same rows stored as e4m3 bytes (corpus_dtype fp8), 32 queries.
+//
+// A row is dp bytes; a segment is 128 bytes = 128 elements, a row dp / 128 = 20 to 32 segments, wave w's share [S8 w / 4, S8 (w + 1) / 4):
+// 5 to 8 segments.  Lane (r, h) reads the 64 contiguous bytes [64 h, 64 h + 64) of each segment of row r (four 16-byte loads: ks_src with
+// row_bytes = dp, so a lane pair consumes a whole 128-byte line) and converts 8 bytes at a time, right at the matrix instruction, with
+// k_scan's cvt8_e4m3 (exact: every e4m3 value is an fp16 value): a segment is EIGHT v_mfma_f32_32x32x16_f16, and step i of segment sg meets
+// k-group ks8_group(sg, h, i) = 16 sg + 8 h + i of the fp16 query image (launch_prep_queries: the image k_scan_ksplit reads, unchanged).
+// A wave's share of the image is still dp / 4 x 32 x 2 bytes: the first kKs8RegSegs = 5 segments in registers (32 each: 160), the
+// remaining 0 to 3 in LDS (8 KB each: 96 KB at dp = 4096).  A ring slot is 16 registers per segment as in the fp16 kernel, but a wave has
+// at most 8 segments, so the ring holds the wave's WHOLE share of a tile (<= 128 registers): segment j's slot is refilled with segment j
+// of the next tile right behind the instructions that consumed it.  The epilogue's operands (reciprocal norm, threshold) are requested at
+// the head of the tile, AHEAD of those refills -- with the whole next tile queued behind them the reducer's wait for them would otherwise
+// drain the ring.  Reduction across the four waves, reducer rotation, epilogue, candidate stage, flush, ranges and sample slots are
+// k_scan_ksplit's.  The certificate needs no new term: the row side is exact, the query side is the fp16 rounding already in eps, and
+// the sum is one fp32 sum of the same dp products (make_plan).  Geometry: the ks8_* functions of vf_ksplit_geom.h.
+// ------------------------------------------------------------------------------------------------
+static_assert(kKs8CtlBytes == kCtlBytes, "vf_ksplit_geom.h budgets the control block the scans use");
+
+// k_scan's flush for the four-wave kernels: rank the staged entries per query, one returning atomic per non-empty query, write
+__device__ __forceinline__ void ks_flush(const ScanArgs& a, char* ctl, char* red, int tid) {
+    __syncthreads();
+    const u32 staged = *(const u32*)ctl;
+    const u32 nst = staged < (u32)a.stage_cap ? staged : (u32)a.stage_cap;
+    uint4* ent = (uint4*)(ctl + kCtlBytes);
+    u32* qcnt = (u32*)red;          // the reduction area is dead now
+    u32* qbase = qcnt + kQueryTile;
+    if (tid < kQueryTile) qcnt[tid] = 0u;
+    __syncthreads();
+    for (u32 i = tid; i < nst; i += kKsThreads) {
+        const uint4 e = ent[i];
+        const u32 q = e.z & 0xFFu;
+        if (e.w != 1u || q >= (u32)kQueryTile) continue;
+        ent[i].w = 2u + atomicAdd(qcnt + q, 1u);
+    }
+    __syncthreads();
+    if (tid < kQueryTile) {
+        const u32 c = qcnt[tid];
+        qbase[tid] = c ? atomicAdd(a.cnt + tid * kCntStride, c) : 0u;
+    }
+    __syncthreads();
+    for (u32 i = tid; i < nst; i += kKsThreads) {
+        const uint4 e = ent[i];
+        if (e.w < 2u) continue;
+        const u32 q = e.z & 0xFFu;
+        const u32 gs = qbase[q] + (e.w - 2u);
+        if (gs < (u32)a.cap) a.cand[(long long)q * a.cap + gs] = ((u64)e.y << 32) | (u64)e.x;
+    }
+}
+
+template <int MODE, int P>
+__global__ __launch_bounds__(kKsThreads) void k_scan_ksplit8(ScanArgs a) {
+    static_assert(P >= kKs8RegSegs && P <= kKs8MaxSegs, "segments per wave: 5..8");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int XS = P - kKs8RegSegs;   // image segments per wave in LDS
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r31 = lane & 31, h = lane >> 5;
+    const int S = ks8_segs(a.dp);
+    const int sbeg = ks8_seg_begin(S, wid), send = ks8_seg_begin(S, wid + 1);
+    const bool has_last = sbeg + P - 1 < send;   // (wave-uniform) the wave's P-th segment exists
+    const long long swg = (long long)a.samp * kKsSampWaves;
+    const KsPart part = ks_part(a.n, MODE == kModeSample ? a.scan_grid : gridDim.x, blockIdx.x, swg, MODE == kModeSample);
+    const int ntiles = ks_ntiles(part, swg, MODE == kModeSample);
+    char* qx = smem;                                          // [4 waves][XS] image segments
+    char* red = smem + (size_t)kKsWaves * XS * kKs8SegBytes;  // [2][4 waves][4 KB]
+    char* ctl = red + kKsRedBytes;
+
+    typedef unsigned int u4v __attribute__((ext_vector_type(4)));
+    u4v A[P * 4];   // the ring: the wave's share of one tile, 64 bytes per lane and segment
+    auto issue = [&](long long row, int j) {   // segment j of the wave's share of `row` -> its ring slot
+        if (j == P - 1 && !has_last) return;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) A[j * 4 + i] = stream_load((const u4v*)(a.rows + ks_src(row, a.row_bytes, sbeg + j, h, i)));
+    };
+    if (ntiles > 0) {
+        const long long row0 = ks_row(part, a.n, 0, r31);
+#pragma unroll
+        for (int j = 0; j < P; ++j) issue(row0, j);
+    }
+    // the wave's share of the query image: registers, then LDS
+    h8 qr[kKs8RegSegs * 8];
+#pragma unroll
+    for (int j = 0; j < kKs8RegSegs; ++j)
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+            qr[j * 8 + i] = *(const h8*)(a.qimg + ((size_t)ks8_group(sbeg + j, h, i) * kQueryTile + r31) * 8);
+    if constexpr (XS > 0) {
+        for (int j = kKs8RegSegs; j < send - sbeg; ++j) {
+            const uint4* src = (const uint4*)((const char*)a.qimg + (size_t)(sbeg + j) * kKs8SegBytes);
+            uint4* dst = (uint4*)(qx + (size_t)(wid * XS + (j - kKs8RegSegs)) * kKs8SegBytes);
+#pragma unroll
+            for (int i = 0; i < kKs8SegBytes / 16 / 64; ++i) dst[i * 64 + lane] = src[i * 64 + lane];
+        }
+    }
+    {
+        uint4* z = (uint4*)ctl;
+        const int nz = (MODE == kModeMain) ? (kCtlBytes / 16 + a.stage_cap) : 1;
+        for (int i = tid; i < nz; i += kKsThreads) z[i] = make_uint4(0u, 0u, 0u, 0u);
+    }
+    __syncthreads();
+    if (MODE == kModeMain && tid < kQueryTile) ((int*)(ctl + 16))[tid] = a.tau_bin[tid];
+    __syncthreads();
+    const char* qx_lane = qx + (size_t)wid * XS * kKs8SegBytes + ((size_t)ks8_group(0, h, 0) * kQueryTile + r31) * 16;
+
+    EpiRegs<1> epi;
+    for (int t = 0; t < ntiles; ++t) {
+        const long long row_nxt = ks_row(part, a.n, t + 1 < ntiles ? t + 1 : ntiles - 1, r31);
+        const long long t0 = part.lo + (long long)t * kKsRowTile;
+        const bool reducer = (t & 3) == wid;
+        // the epilogue's operands, ahead of this tile's refills
+        epi.inv_lane = a.inv_scan[ks_inv_index(t0, a.n, r31)];
+        epi.sync_tau = MODE == kModeMain && (t & 7) == wid;
+        if (MODE == kModeMain && epi.sync_tau)
+            epi.tau_g[0] = __hip_atomic_load(a.tau_bin + r31, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        f16v acc[1];
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[0][e] = 0.0f;
+#pragma unroll
+        for (int j = 0; j < P; ++j) {
+            if (j < P - 1 || has_last) {
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    const u4v w = A[j * 4 + ks8_step_load(i)];
+                    const h8 af = ks8_step_half(i) ? cvt8_e4m3(w[2], w[3]) : cvt8_e4m3(w[0], w[1]);
+                    h8 b;
+                    if (j < kKs8RegSegs) b = qr[(j < kKs8RegSegs ? j : 0) * 8 + i];
+                    else b = *(const h8*)(qx_lane + (size_t)(j - kKs8RegSegs) * kKs8SegBytes + i * (kQueryTile * 16));
+                    acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, b, acc[0], 0, 0, 0);
+                }
+            }
+            // refill the slot: segment j of the next tile (past the part's end: the last tile again, never consumed)
+            issue(row_nxt, j);
+        }
+        // partial tiles -> LDS, one barrier (LDS wait only: the ring's loads stay in flight), the tile's reducer adds them
+        char* rbuf = red + (size_t)(t & 1) * (kKsWaves * 4096);
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+            *(float4*)(rbuf + wid * 4096 + (g * 64 + lane) * 16) = make_float4(acc[0][4 * g], acc[0][4 * g + 1], acc[0][4 * g + 2], acc[0][4 * g + 3]);
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        if (reducer) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const float4 p0 = *(const float4*)(rbuf + 0 * 4096 + (g * 64 + lane) * 16);
+                const float4 p1 = *(const float4*)(rbuf + 1 * 4096 + (g * 64 + lane) * 16);
+                const float4 p2 = *(const float4*)(rbuf + 2 * 4096 + (g * 64 + lane) * 16);
+                const float4 p3 = *(const float4*)(rbuf + 3 * 4096 + (g * 64 + lane) * 16);
+                acc[0][4 * g] = ((p0.x + p1.x) + p2.x) + p3.x;
+                acc[0][4 * g + 1] = ((p0.y + p1.y) + p2.y) + p3.y;
+                acc[0][4 * g + 2] = ((p0.z + p1.z) + p2.z) + p3.z;
+                acc[0][4 * g + 3] = ((p0.w + p1.w) + p2.w) + p3.w;
+            }
+            tile_epilogue<1, MODE>(a, acc, epi, t0, part.hi, (long long)blockIdx.x * swg + (long long)t * kKsRowTile, lane, ctl);
+        }
+    }
+    if (MODE == kModeMain) ks_flush(a, ctl, red, tid);
+}
+
+// ------------------------------------------------------------------------------------------------
 // k_scan2: the main scan with WHOLE-LINE corpus loads (round 3).  fp16 rows, main mode.
 //
 // What round 3 measured (tools/ubench/stream_read.hip, profiles/r03_stream_read.log): k_scan's A-operand loads -- lane
@@ -3623,6 +3781,26 @@ hipError_t launch_scan_ksplit(const ScanArgs& a, int mode, int grid, hipStream_t
     return hipErrorInvalidValue;
 }
 
+// k_scan_ksplit8 (e4m3 rows of the same widths): segments of 128 bytes, 5 to 8 per wave; the LDS budget is vf_ksplit_geom.h's
+#define VF_KSPLIT8_SHAPES(X) X(5) X(6) X(7) X(8)   // segments per wave P8
+size_t scan_ksplit8_lds_bytes(int dp, int stage_cap) { return (size_t)ks8_lds_bytes(dp, stage_cap); }
+int scan_ksplit8_stage_cap(int dp) { return ks8_stage_cap(dp); }
+// mode kModeSample: `grid` = a.scan_grid workgroups, one per range; kModeMain: a.stage_cap = scan_ksplit8_stage_cap; a.row_bytes = a.dp
+hipError_t launch_scan_ksplit8(const ScanArgs& a, int mode, int grid, hipStream_t s) {
+    if (!ks_serves(a.dp) || a.row_bytes != (long long)a.dp || (mode == kModeSample && grid != a.scan_grid)) return hipErrorInvalidValue;
+    if (mode == kModeMain && (a.stage_cap < 256 || a.stage_cap > ks8_stage_cap(a.dp))) return hipErrorInvalidValue;
+    const int P = ks8_P(ks8_segs(a.dp));
+    const size_t lds = scan_ksplit8_lds_bytes(a.dp, mode == kModeMain ? a.stage_cap : 0);
+#define VF_X(P_) \
+    if (P == P_) { \
+        if (mode == kModeMain) hipLaunchKernelGGL((k_scan_ksplit8<kModeMain, P_>), dim3(grid), dim3(kKsThreads), lds, s, a); \
+        else hipLaunchKernelGGL((k_scan_ksplit8<kModeSample, P_>), dim3(grid), dim3(kKsThreads), lds, s, a); \
+        return hipGetLastError(); }
+    VF_KSPLIT8_SHAPES(VF_X)
+#undef VF_X
+    return hipErrorInvalidValue;
+}
+
 hipError_t launch_scan2(const ScanArgs& a, int qn_tile, int grid, int rows_are_fp8, hipStream_t s) {
     const size_t lds = scan2_lds_bytes(a.dp, qn_tile, a.stage_cap);
     if (qn_tile == kQueryTile) {
@@ -4169,6 +4347,11 @@ hipError_t scan_configure() {
     if ((e = hipFuncSetAttribute((const void*)k_scan_ksplit<kModeMain, P_, D_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e; \
     if ((e = hipFuncSetAttribute((const void*)k_scan_ksplit<kModeSample, P_, D_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
     VF_KSPLIT_SHAPES(VF_X)
+#undef VF_X
+#define VF_X(P_) \
+    if ((e = hipFuncSetAttribute((const void*)k_scan_ksplit8<kModeMain, P_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e; \
+    if ((e = hipFuncSetAttribute((const void*)k_scan_ksplit8<kModeSample, P_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
+    VF_KSPLIT8_SHAPES(VF_X)
 #undef VF_X
     if ((e = hipFuncSetAttribute((const void*)k_scan2<1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
     if ((e = hipFuncSetAttribute((const void*)k_scan2<2, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;

@@ -62,4 +62,36 @@ VF_HD long long ks_inv_index(long long t0, long long n, int r31) {
     return i < n + 63 ? (i < 0 ? 0 : i) : n + 63;
 }
 
+// ---- k_scan_ksplit8: the same rows stored as e4m3 bytes (tests/test_wide_rows_fp8_geometry.py walks these) ------------------------------
+// A row is dp bytes; a segment is 128 BYTES = 128 elements = eight matrix steps, so a row has dp / 128 segments (20 to 32), a wave 5 to 8.
+// Ranges, sample parts, tiles, rows and reciprocal-norm indices are the functions above (ks_part, ks_ntiles, ks_row, ks_inv_index), and
+// the 16 bytes a lane half reads are ks_src with row_bytes = dp.
+constexpr int kKs8RegSegs = 5;      // query segments (128 elements x 32 queries = 32 registers per lane) a wave keeps in registers: 160
+constexpr int kKs8MaxSegs = 8;      // segments per wave at dp = 4096; the ring holds the wave's whole share of a tile (16 registers each)
+constexpr int kKs8SegBytes = 8192;  // one 128-element segment of a 32-query image: 16 k-groups x 32 queries x 16 bytes
+constexpr int kKs8CtlBytes = 272;   // the scans' control block (kCtlBytes; vf_kernels.hip asserts they agree)
+
+VF_HD int ks8_segs(int dp) { return dp >> 7; }
+// wave w owns segments [ks8_seg_begin(S8, w), ks8_seg_begin(S8, w + 1)) of S8: 5 to 8 of them, counts differ by at most one
+VF_HD int ks8_seg_begin(int S8, int w) { return S8 * w / kKsWaves; }
+VF_HD int ks8_P(int S8) { return (S8 + kKsWaves - 1) / kKsWaves; }
+// the k-group (8 elements, 16 bytes per query of the fp16 image) that meets the 8 bytes lane half h converts for step i (0..7) of segment
+// sg: bytes [128 sg + 64 h + 8 i, + 8) of the row are elements of the same numbers
+VF_HD int ks8_group(int sg, int h, int i) { return 16 * sg + 8 * h + i; }
+// which of the four 16-byte loads (ks_src's i) holds step i's 8 bytes, and which half of it
+VF_HD int ks8_step_load(int i) { return i >> 1; }
+VF_HD int ks8_step_half(int i) { return i & 1; }
+// LDS: [4 waves][P8 - 5] image segments + the reduction area + the control block + (main mode) the candidate stage
+VF_HD long long ks8_lds_bytes(int dp, int stage_cap) {
+    const int xs = ks8_P(ks8_segs(dp)) - kKs8RegSegs;
+    return (long long)kKsWaves * (xs > 0 ? xs : 0) * kKs8SegBytes + kKsRedBytes + kKs8CtlBytes + (long long)stage_cap * 16;
+}
+// candidate-stage entries that fit beside them in 160 KB (at most 32 KB of them); < 256 = not this kernel
+VF_HD int ks8_stage_cap(int dp) {
+    if (!ks_serves(dp)) return 0;
+    const long long used = ks8_lds_bytes(dp, 0);
+    const long long freeb = used < 160 * 1024 ? 160 * 1024 - used : 0;
+    return (int)((freeb < 32 * 1024 ? freeb : 32 * 1024) / 16);
+}
+
 }  // namespace vf
