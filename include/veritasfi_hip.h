@@ -39,7 +39,7 @@ enum {
     VF_EINTERNAL = -5
 };
 
-enum { VF_DTYPE_F32 = 0, VF_DTYPE_F16 = 1, VF_DTYPE_FP8_E4M3 = 2 };
+enum { VF_DTYPE_F32 = 0, VF_DTYPE_F16 = 1, VF_DTYPE_FP8_E4M3 = 2, VF_DTYPE_INT8 = 3 };
 
 typedef struct vf_index vf_index;
 
@@ -73,12 +73,20 @@ int vf_device_count(int32_t* out);
  * HBM: the fused scan reads the bytes (half the traffic of fp16) and converts them to fp16 in registers -- exactly,
  * every e4m3 value is an fp16 value -- and the exact re-score decodes the same bytes.  A per-row scale of a
  * scaled-fp8 store cancels in the cosine, so none is taken.
+ * VF_DTYPE_INT8 rows (one byte per element, two's complement, any of the 256 values) stay one byte per element in
+ * HBM as well, and no scale is taken for the same reason: the score of a row is the canonical cosine of its integer
+ * values (as fp32) with the query.  The index holds them with the top bit of every byte flipped (code + 128, the
+ * form of the int8 row image of fp16 rows), so the rows are always COPIED, by every entry point; no fp16 or fp32
+ * copy exists.  Every search path serves them; option scan_image picks the scan: 0 = bytes converted to fp16 in
+ * registers (exact), 2 = the int8 matrix instruction on the bytes as they are wherever a shape exists (rows of 768
+ * elements, k <= 128), 1 = auto.  Rows of 2560 to 4096 padded elements take the chunked exact path.
  * `id_offset` is added to every returned id (row-sharding across ranks). */
 int vf_index_create(vf_index** out, const void* rows, int64_t n, int32_t d, int32_t dtype,
                     int32_t device_id, int64_t id_offset);
 
 /* Same, rows already resident in HBM on `device_id`.  The index BORROWS d_rows (no copy for fp16
- * with d % 128 == 0); the caller keeps it alive until vf_index_destroy. */
+ * with d % 128 == 0); the caller keeps it alive until vf_index_destroy.  VF_DTYPE_INT8 rows are the exception:
+ * they are copied (re-biased on the way), the index keeps no reference to d_rows and the caller may free it at once. */
 int vf_index_create_device(vf_index** out, const void* d_rows, int64_t n, int32_t d, int32_t dtype,
                            int32_t device_id, int64_t id_offset);
 

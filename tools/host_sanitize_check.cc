@@ -50,7 +50,7 @@ static int probe(const std::string& path, long long file_bytes) {
     int64_t n = -7; int32_t d = -7, dt = -7, has = -7;
     const int rc = vf_corpus_file_info(path.c_str(), &n, &d, &dt, &has);
     if (rc == VF_OK) {
-        CHECK(n >= 0 && d > 0 && dt >= 0 && dt <= 2 && (has == 0 || has == 1), "accepted header with n %lld d %d dtype %d", (long long)n, d, dt);
+        CHECK(n >= 0 && d > 0 && dt >= 0 && dt <= 3 && (has == 0 || has == 1), "accepted header with n %lld d %d dtype %d", (long long)n, d, dt);
         const long double need = 64.0L + (long double)n * d * esz((uint32_t)dt) + (has ? (long double)n * 8 : 0);
         CHECK(need <= (long double)file_bytes, "accepted a header needing %.0Lf bytes in a file of %lld", need, file_bytes);
     } else {
@@ -85,7 +85,7 @@ int main(int argc, char** argv) {
     CHECK(probe(write_file("short.vfc", good(0, 1, 4), 0, 63), 63) == VF_EINVAL, "63-byte file");
     { Header h = good(0, 1, 4); h.magic[0] = 'X'; CHECK(probe(write_file("magic.vfc", h, 16), 80) == VF_EINVAL, "bad magic"); }
     { Header h = good(0, 1, 4); h.version = 2; CHECK(probe(write_file("ver.vfc", h, 16), 80) == VF_EUNSUPPORTED, "version 2"); }
-    { Header h = good(3, 1, 4); CHECK(probe(write_file("dtype.vfc", h, 16), 80) == VF_EINVAL, "dtype 3"); }
+    { Header h = good(4, 1, 4); CHECK(probe(write_file("dtype.vfc", h, 16), 80) == VF_EINVAL, "dtype 4"); }
     { Header h = good(0xffffffffu, 1, 4); CHECK(probe(write_file("dtype2.vfc", h, 16), 80) == VF_EINVAL, "dtype 2^32-1"); }
     CHECK(probe(write_file("d0.vfc", good(0, 5, 0), 64), 128) == VF_EINVAL, "d = 0");
     CHECK(probe(write_file("trunc.vfc", good(0, 100, 8), 100 * 8 * 4 - 1), 64 + 3199) == VF_EINVAL, "payload one byte short");
@@ -96,7 +96,7 @@ int main(int argc, char** argv) {
     CHECK(probe(write_file("wrap3.vfc", good(1, (1ull << 63) + 3, 1, 1), 4096), 64 + 4096) == VF_EINVAL, "id table wraps");
     CHECK(probe(write_file("wrap4.vfc", good(0, (1ull << 62) / 3, 12), 4096), 64 + 4096) == VF_EINVAL, "n x d x 4 just past 2^64");
     // ---- files that must be accepted (by the parser; the loader then needs a GPU)
-    for (uint32_t dt = 0; dt <= 2; ++dt)
+    for (uint32_t dt = 0; dt <= 3; ++dt)   // (3 = int8 rows)
         for (uint32_t fl = 0; fl <= 1; ++fl) {
             const uint64_t n = 37; const uint32_t d = 24;
             const size_t pay = n * d * esz(dt) + (fl ? n * 8 : 0);
@@ -110,7 +110,7 @@ int main(int argc, char** argv) {
     std::mt19937_64 rng(12345);
     int accepted = 0;
     for (int it = 0; it < 4000; ++it) {
-        Header h = good((uint32_t)(rng() % 3), rng() % 200, 1 + (uint32_t)(rng() % 64), (uint32_t)(rng() & 1));
+        Header h = good((uint32_t)(rng() % 4), rng() % 200, 1 + (uint32_t)(rng() % 64), (uint32_t)(rng() & 1));
         const size_t pay = (size_t)(h.n * h.d * esz(h.dtype) + ((h.flags & 1) ? h.n * 8 : 0));
         unsigned char* raw = (unsigned char*)&h;
         const int flips = 1 + (int)(rng() % 3);
@@ -136,6 +136,7 @@ int main(int argc, char** argv) {
     CHECK(vf_index_create(&ix, x, -1, 4, 0, 0, 0) == VF_EINVAL, "negative n");
     CHECK(vf_index_create(&ix, x, 2, 0, 0, 0, 0) == VF_EINVAL, "d = 0");
     CHECK(vf_index_create(&ix, x, 2, 4, 9, 0, 0) == VF_EINVAL, "dtype 9");
+    CHECK(vf_index_create(&ix, x, 2, 4, 4, 0, 0) == VF_EINVAL && ix == nullptr, "dtype 4 (3 = int8 is the last)");
     CHECK(vf_index_create(&ix, x, (int64_t)1 << 33, 4, 0, 0, 0) != VF_OK, "2^33 rows from an 8-float buffer is refused before it is read");
     CHECK(vf_index_create_sharded(&ix, x, 2, 4, 0, nullptr, 1) == VF_EINVAL, "null device list");
     CHECK(vf_index_create_sharded(&ix, x, 2, 4, 0, dev, 0) == VF_EINVAL, "zero devices");

@@ -17,7 +17,8 @@ from . import _ffi
 
 MAGIC = b"VFCORPUS"
 _HDR = struct.Struct("<8sIIQII32x")
-_DT = {np.dtype(np.float32): _ffi.VF_DTYPE_F32, np.dtype(np.float16): _ffi.VF_DTYPE_F16, np.dtype(np.uint8): _ffi.VF_DTYPE_FP8_E4M3}
+_DT = {np.dtype(np.float32): _ffi.VF_DTYPE_F32, np.dtype(np.float16): _ffi.VF_DTYPE_F16, np.dtype(np.uint8): _ffi.VF_DTYPE_FP8_E4M3,
+       np.dtype(np.int8): _ffi.VF_DTYPE_INT8}
 _NP = {v: k for k, v in _DT.items()}
 
 
@@ -34,7 +35,8 @@ class CorpusWriter:
         self._f.write(b"\0" * _HDR.size)
 
     def append(self, rows, ids=None) -> None:
-        rows = np.ascontiguousarray(np.asarray(rows), dtype=self.dtype) if self.dtype != np.uint8 else np.ascontiguousarray(rows)
+        # (one-byte codes -- e4m3 bytes, int8 rows -- are taken as they are or refused below, never cast: a cast would wrap them)
+        rows = np.ascontiguousarray(np.asarray(rows), dtype=self.dtype) if self.dtype.itemsize > 1 else np.ascontiguousarray(rows)
         if rows.dtype != self.dtype or rows.ndim != 2 or rows.shape[1] != self.d:
             raise ValueError(f"batch must be [m, {self.d}] of {self.dtype}")
         if (ids is None) != (not self._ids) and self.n:

@@ -156,7 +156,7 @@ struct GroupSlot {
 struct vf_index {
     int device = 0;
     int64_t n = 0;
-    int d = 0, dp = 0, dtype = 0;  // dtype: how rows are HELD in HBM (VF_DTYPE_F32 / _F16 / _FP8_E4M3)
+    int d = 0, dp = 0, dtype = 0;  // dtype: how rows are HELD in HBM (VF_DTYPE_F32 / _F16 / _FP8_E4M3 / _INT8: biased bytes, code + 128)
     int64_t id_offset = 0;
     int n_cu = 256;
     int64_t aux_applied = -1;   // the CU split the first slot's streams were created with (-1: no slot yet); fixed from then on
@@ -168,6 +168,7 @@ struct vf_index {
     float* inv_scan = nullptr;        // [n]
     float* cn_cache = nullptr;        // canonical normalised rows when n <= kSmallN
     unsigned char* rows_img = nullptr;   // int8 row image [n][dp] (fp16 / fp32 rows, option scan_image): biased codes, k_prep_image
+    bool owns_img = false;            // (an int8 index IS its image: rows_img = rows_scan, not owned, residuals and offsets 0)
     float* inv_img = nullptr;         // [n + 64] row scale / canonical norm: the image's approx score = acc x inv_img, then [n + 64] per-row
                                       // score offsets off_img (k_prep_image; the scan adds them: DESIGN.md 4)
     float rho_max = 0.0f;             // largest relative residual ||x - s code|| / ||x|| of a row of the image (rounded up)
@@ -211,13 +212,20 @@ static int ensure_pinned(Slot& s, size_t nq_total) {
 
 static int build_image(vf_index* ix, int64_t mode);
 
+// One byte per element in HBM (e4m3 codes, or the biased bytes of an int8 index): scanned as bytes with the e4m3 geometry, converted in
+// registers (cvt8_e4m3 / cvt8_i8b).  Everything that sizes a row, picks a byte-row kernel shape or counts traffic asks this.
+static bool byte_rows(int dtype) { return dtype == VF_DTYPE_FP8_E4M3 || dtype == VF_DTYPE_INT8; }
+static bool known_dtype(int64_t dtype) { return dtype >= VF_DTYPE_F32 && dtype <= VF_DTYPE_INT8; }
+static size_t dtype_bytes(int dtype) { return dtype == VF_DTYPE_F32 ? 4 : (dtype == VF_DTYPE_F16 ? 2 : 1); }
+static int scan_f8(int dtype) { return dtype == VF_DTYPE_INT8 ? 2 : (dtype == VF_DTYPE_FP8_E4M3 ? 1 : 0); }   // row type of launch_scan / launch_scan_wide
+
 static int build_common(vf_index* ix) {
     hipDeviceProp_t prop;
     VF_HIP(hipGetDeviceProperties(&prop, ix->device));
     ix->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     VF_HIP(scan_configure());
     const int dt = ix->dtype;
-    const size_t scan_esz = dt == VF_DTYPE_FP8_E4M3 ? 1 : 2;  // fp8 rows are scanned as bytes, everything else as fp16
+    const size_t scan_esz = byte_rows(dt) ? 1 : 2;  // fp8 / int8 rows are scanned as bytes, everything else as fp16
     ix->dp = (ix->d + 127) / 128 * 128;  // whole 128-element segment pairs: see pick_G
     const size_t npad = (size_t)ix->n + 64;
     VF_HIP(hipMalloc((void**)&ix->norm, npad * sizeof(float)));
@@ -228,7 +236,7 @@ static int build_common(vf_index* ix) {
     void* scan_out = nullptr;
     if (need_scan) {
         if (dt != VF_DTYPE_F32 && ix->dp == ix->d && ((uintptr_t)ix->rows_orig % 16) == 0) {
-            ix->rows_scan = ix->rows_orig;  // fp16 / fp8 rows of a whole number of segments are scanned in place
+            ix->rows_scan = ix->rows_orig;  // fp16 / fp8 / int8 rows of a whole number of segments are scanned in place
             ix->owns_scan = false;
         } else {
             VF_HIP(hipMalloc((void**)&ix->rows_scan, (size_t)ix->n * ix->dp * scan_esz));
@@ -265,7 +273,7 @@ constexpr int64_t kScan2rMinRows = 1'100'000;   // k_scan2r (where its shapes ex
 // 10M x 384 1.330 -> 1.262, 1.25M x 512 0.266-0.270 -> 0.260-0.265
 static bool scan2r_auto_width(int dp, bool f8) { return f8 ? (dp == 768 || dp == 1024) : (dp == 768 || dp == 1024 || dp == 512 || dp == 384); }
 static int64_t split_limit(const vf_index* ix) {
-    const bool r_rows = ix->dtype != VF_DTYPE_FP8_E4M3 && ix->scan_impl != 4 && ix->scan_impl != 1 && ix->scan_impl != 3 && !ix->steal_opt &&
+    const bool r_rows = !byte_rows(ix->dtype) && ix->scan_impl != 4 && ix->scan_impl != 1 && ix->scan_impl != 3 && !ix->steal_opt &&
                         scan2r_auto_width(ix->dp, false) && scan2r_stage_cap(ix->dp, kMaxBatch, 0) >= 256;
     return r_rows ? INT64_MAX : kSplitMaxRows;
 }
@@ -292,24 +300,43 @@ constexpr int64_t kImageMinRows = 4'000'000;   // measured at 10M rows (DESIGN.m
 constexpr double kImageMaxRho = 1.0 / 64;
 constexpr size_t kImageHeadroom = (size_t)8 << 30;
 constexpr int kImageMfmaAuto = 1;   // option image_mfma = -1
-static bool image_eligible(const vf_index* ix) {
-    return ix->shards.empty() && (ix->dtype == VF_DTYPE_F16 || ix->dtype == VF_DTYPE_F32) && ix->n >= kImageMinRows &&
-           ix->n < (int64_t)0xFFFFFFFFll && ix->dp == 768 && scan2r_stage_cap(ix->dp, kMaxBatch, 2) >= 256;
+// An int8 index is the image itself (build_image): nothing is built or stored twice, so scan_image = 2 takes the int8-MFMA route at any
+// size the fused path serves; auto keeps kImageMinRows, where the route was measured on these very bytes (the conversion route, k_scan's
+// int8 form, below that) -- no threshold of its own has been measured yet.
+static bool image_eligible(const vf_index* ix, int64_t mode) {
+    if (!ix->shards.empty() || ix->n >= (int64_t)0xFFFFFFFFll || ix->dp != 768 || scan2r_stage_cap(ix->dp, kMaxBatch, 2) < 256) return false;
+    if (ix->dtype == VF_DTYPE_INT8) return ix->rows_scan && (mode == 2 ? ix->n > kSmallN : ix->n >= kImageMinRows);
+    return (ix->dtype == VF_DTYPE_F16 || ix->dtype == VF_DTYPE_F32) && ix->n >= kImageMinRows;
 }
 static float* image_offsets(const vf_index* ix) { return ix->inv_img ? ix->inv_img + ix->n + 64 : nullptr; }
 static void free_image(vf_index* ix) {
-    if (ix->rows_img) (void)hipFree(ix->rows_img);
+    if (ix->rows_img && ix->owns_img) (void)hipFree(ix->rows_img);
     if (ix->inv_img) (void)hipFree(ix->inv_img);
-    ix->rows_img = nullptr; ix->inv_img = nullptr; ix->rho_max = ix->rho_mean = 0.0f;
+    ix->rows_img = nullptr; ix->inv_img = nullptr; ix->owns_img = false; ix->rho_max = ix->rho_mean = 0.0f;
 }
 static int build_image(vf_index* ix, int64_t mode) {
-    if (mode == 0 || ix->rows_img || !image_eligible(ix)) return VF_OK;
-    const size_t bytes = (size_t)ix->n * ix->dp, ibytes = 2 * ((size_t)ix->n + 64) * sizeof(float);   // inverses + offsets
+    if (mode == 0 || ix->rows_img || !image_eligible(ix, mode)) return VF_OK;
+    const size_t ibytes = 2 * ((size_t)ix->n + 64) * sizeof(float);   // inverses + offsets
+    if (ix->dtype == VF_DTYPE_INT8) {
+        // the index's own bytes are the codes: row scale 1, so inv_img = 1 / ||c|| = inv_scan; no residual, so offsets, rho_max and rho_mean
+        // are 0 and the band is the certificate's own (image_bound at rho_mean = 0)
+        if (hipMalloc((void**)&ix->inv_img, ibytes) != hipSuccess) {
+            (void)hipGetLastError();
+            ix->inv_img = nullptr;
+            return mode == 2 ? fail(VF_ENOMEM, "scan_image = 2: the row inverses and offsets do not fit in device memory") : VF_OK;
+        }
+        VF_HIP(hipMemset(ix->inv_img, 0, ibytes));
+        VF_HIP(hipMemcpy(ix->inv_img, ix->inv_scan, (size_t)ix->n * sizeof(float), hipMemcpyDeviceToDevice));
+        ix->rows_img = (unsigned char*)ix->rows_scan; ix->owns_img = false;
+        return VF_OK;
+    }
+    const size_t bytes = (size_t)ix->n * ix->dp;
     if (mode == 1) {
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return VF_OK; }
         if (free_b < bytes + ibytes + kImageHeadroom) return VF_OK;   // auto: no room, the rows as stored are scanned
     }
+    ix->owns_img = true;
     if (hipMalloc((void**)&ix->rows_img, bytes) != hipSuccess || hipMalloc((void**)&ix->inv_img, ibytes) != hipSuccess) {
         (void)hipGetLastError();
         free_image(ix);
@@ -411,19 +438,19 @@ static void destroy_index(vf_index* ix) {
     if (ix->norm) (void)hipFree(ix->norm);
     if (ix->inv_scan) (void)hipFree(ix->inv_scan);
     if (ix->cn_cache) (void)hipFree(ix->cn_cache);
-    if (ix->rows_img) (void)hipFree(ix->rows_img);
+    if (ix->rows_img && ix->owns_img) (void)hipFree(ix->rows_img);
     if (ix->inv_img) (void)hipFree(ix->inv_img);
     if (ix->ev_span) (void)hipEventDestroy(ix->ev_span);
     delete ix;
 }
 
+// adopt: the device rows are the caller's own fresh allocation, handed over (the file loader): int8 rows are re-biased in place
 static int create_impl(vf_index** out, const void* rows, bool rows_on_device, int64_t n, int32_t d, int32_t dtype,
-                       int32_t device_id, int64_t id_offset) {
+                       int32_t device_id, int64_t id_offset, bool adopt = false) {
     if (!out) return fail(VF_EINVAL, "vf_index_create: null out");
     *out = nullptr;
     if (n < 0 || d <= 0 || (n > 0 && !rows)) return fail(VF_EINVAL, "vf_index_create: bad rows/n/d");
-    if (dtype != VF_DTYPE_F32 && dtype != VF_DTYPE_F16 && dtype != VF_DTYPE_FP8_E4M3)
-        return fail(VF_EINVAL, "vf_index_create: unknown dtype");
+    if (!known_dtype(dtype)) return fail(VF_EINVAL, "vf_index_create: unknown dtype");
     if (n >= (int64_t)0xFFFFFFFFll) return fail(VF_EUNSUPPORTED, "vf_index_create: more than 2^32-1 rows per shard");
     int ndev = 0;
     VF_HIP(hipGetDeviceCount(&ndev));
@@ -433,11 +460,24 @@ static int create_impl(vf_index** out, const void* rows, bool rows_on_device, in
     if (!ix) return fail(VF_ENOMEM, "vf_index_create: host allocation failed");
     ix->device = device_id; ix->n = n; ix->d = d; ix->id_offset = id_offset;
     ix->dtype = dtype;  // fp8 (OCP e4m3) rows stay fp8 in HBM: scanned as bytes, converted in registers
-    const size_t esz = dtype == VF_DTYPE_F32 ? 4 : (dtype == VF_DTYPE_F16 ? 2 : 1);
+    const size_t esz = dtype_bytes(dtype);
     int rc = VF_OK;
-    if (rows_on_device) {
+    if (rows_on_device && dtype == VF_DTYPE_INT8 && !adopt && n > 0) {
+        // int8 rows are held re-biased (code + 128), so the caller's device rows are copied, not borrowed: one pass, device to device
+        hipError_t e = hipMalloc(&ix->rows_orig, (size_t)n * d);
+        if (e != hipSuccess) rc = fail(VF_ENOMEM, std::string("hipMalloc(corpus): ") + hipGetErrorString(e));
+        else {
+            ix->owns_rows = true;
+            e = launch_rebias_i8(rows, ix->rows_orig, (long long)n * d, nullptr);
+            if (e != hipSuccess) rc = fail(VF_EHIP, std::string("re-biasing the int8 rows: ") + hipGetErrorString(e));
+        }
+    } else if (rows_on_device) {
         ix->rows_orig = const_cast<void*>(rows);
         ix->owns_rows = false;
+        if (dtype == VF_DTYPE_INT8 && n > 0) {   // (adopt: the loader's own buffer, in place)
+            const hipError_t e = launch_rebias_i8(ix->rows_orig, ix->rows_orig, (long long)n * d, nullptr);
+            if (e != hipSuccess) rc = fail(VF_EHIP, std::string("re-biasing the int8 rows: ") + hipGetErrorString(e));
+        }
     } else if (n > 0) {
         hipError_t e = hipMalloc(&ix->rows_orig, (size_t)n * d * esz);
         if (e != hipSuccess) rc = fail(VF_ENOMEM, std::string("hipMalloc(corpus): ") + hipGetErrorString(e));
@@ -445,6 +485,10 @@ static int create_impl(vf_index** out, const void* rows, bool rows_on_device, in
             ix->owns_rows = true;
             e = hipMemcpy(ix->rows_orig, rows, (size_t)n * d * esz, hipMemcpyHostToDevice);
             if (e != hipSuccess) rc = fail(VF_EHIP, std::string("hipMemcpy(corpus): ") + hipGetErrorString(e));
+            else if (dtype == VF_DTYPE_INT8) {
+                e = launch_rebias_i8(ix->rows_orig, ix->rows_orig, (long long)n * d, nullptr);
+                if (e != hipSuccess) rc = fail(VF_EHIP, std::string("re-biasing the int8 rows: ") + hipGetErrorString(e));
+            }
         }
     }
     if (rc == VF_OK) rc = build_common(ix);
@@ -485,8 +529,8 @@ static int read_vfc_header(int fd, const char* path, VfcHeader* h, size_t* esz) 
     if (pread(fd, h, sizeof(*h), 0) != (ssize_t)sizeof(*h)) return fail(VF_EINVAL, std::string("corpus file too short: ") + path);
     if (memcmp(h->magic, "VFCORPUS", 8) != 0) return fail(VF_EINVAL, std::string("not a corpus file (bad magic): ") + path);
     if (h->version != 1) return fail(VF_EUNSUPPORTED, std::string("corpus file version not supported: ") + path);
-    if (h->dtype > VF_DTYPE_FP8_E4M3 || h->d == 0) return fail(VF_EINVAL, std::string("corpus file header is corrupt: ") + path);
-    *esz = h->dtype == VF_DTYPE_F32 ? 4 : (h->dtype == VF_DTYPE_F16 ? 2 : 1);
+    if (!known_dtype(h->dtype) || h->d == 0) return fail(VF_EINVAL, std::string("corpus file header is corrupt: ") + path);
+    *esz = dtype_bytes((int)h->dtype);
     struct stat st;
     if (fstat(fd, &st) != 0) return fail(VF_EINVAL, std::string("cannot stat corpus file: ") + path);
     // n * d * element size (+ the id table) against the file's size, WITHOUT wrapping: a header with n = 2^61 and d = 16 would
@@ -570,7 +614,7 @@ extern "C" int vf_index_create_from_file(vf_index** out, const char* path, int64
         if (ev[i]) (void)hipEventDestroy(ev[i]);
     }
     if (rc == VF_OK) {
-        rc = create_impl(out, d_rows, true, n, (int32_t)h.d, (int32_t)h.dtype, device_id, id_offset);
+        rc = create_impl(out, d_rows, true, n, (int32_t)h.d, (int32_t)h.dtype, device_id, id_offset, true);
         // create_impl borrowed the device rows: hand them over to the index
         if (rc == VF_OK) { (*out)->owns_rows = true; d_rows = nullptr; }
     }
@@ -807,6 +851,9 @@ constexpr int64_t kWideRowsMinRows8 = 32768;
 static bool rows_e4m3(const vf_index* ix) { return ix->dtype == VF_DTYPE_FP8_E4M3; }
 static int ksplit_stage_cap(const vf_index* ix) { return rows_e4m3(ix) ? scan_ksplit8_stage_cap(ix->dp) : scan_ksplit_stage_cap(ix->dp); }
 static bool ksplit_serves(const vf_index* ix, bool forced) {
+    // int8 rows of these widths: no k_scan_ksplit8 form converts them yet, so they take the chunked exact path (path 2) and wide_rows /
+    // force_path = 1 are refused for them as they are at wide_rows = 0
+    if (ix->dtype == VF_DTYPE_INT8) return false;
     if (ix->wide_rows == 0 || ksplit_stage_cap(ix) < 256) return false;
     return forced || ix->wide_rows == 2 || ix->n >= (rows_e4m3(ix) ? kWideRowsMinRows8 : kWideRowsMinRows);
 }
@@ -982,9 +1029,9 @@ constexpr int kWideTile = 256;
 
 static bool wide_possible(const vf_index* ix, int nq) {
     const bool ks = ksplit_width(ix);   // rows only k_scan_ksplit holds an image of (32 queries per pass)
-    if (ix->wide_opt == 0 || nq < (ix->wide_opt > 1 ? (int)ix->wide_opt : ks ? (rows_e4m3(ix) ? kWideMinQueriesKsplit8 : kWideMinQueriesKsplit) : (ix->dtype == VF_DTYPE_FP8_E4M3 ? kWideMinQueries : kWideMinQueries16))) return false;
+    if (ix->wide_opt == 0 || nq < (ix->wide_opt > 1 ? (int)ix->wide_opt : ks ? (rows_e4m3(ix) ? kWideMinQueriesKsplit8 : kWideMinQueriesKsplit) : (byte_rows(ix->dtype) ? kWideMinQueries : kWideMinQueries16))) return false;
     // a register stage is 2 k-chunks of fp8 rows / 1 of fp16 rows and a tile alternates two stages
-    return ix->dp % (ix->dtype == VF_DTYPE_FP8_E4M3 ? 256 : 128) == 0;
+    return ix->dp % (byte_rows(ix->dtype) ? 256 : 128) == 0;
 }
 
 static int wide_pass(vf_index* ix, Slot& s, const FusedPlan& p0, const float* d_queries, int nb, int k, int64_t* d_ids,
@@ -1031,7 +1078,7 @@ static int wide_pass(vf_index* ix, Slot& s, const FusedPlan& p0, const float* d_
         VF_TRY(s.epsq.ensure((size_t)qtot * sizeof(float)));
         VF_HIP(launch_prep_wide8(qn_b, nb, ix->d, ix->dp, qtot, (unsigned char*)s.qimg8.p, s.epsq.as<float>(), st));
     }
-    const bool f8 = ix->dtype == VF_DTYPE_FP8_E4M3;
+    const int f8 = scan_f8(ix->dtype);   // (int8 rows: k_scan_wide converts the biased bytes, exact; the fp8 instruction is for e4m3 codes only)
     ScanArgs a{};
     a.rows = (const char*)ix->rows_scan; a.inv_scan = ix->inv_scan; a.qimg = s.qimg.as<_Float16>();
     a.n = ix->n; a.dp = ix->dp; a.row_bytes = (long long)ix->dp * (f8 ? 1 : 2);
@@ -1173,7 +1220,7 @@ static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq,
                                   p.eps, p.tau_band, p.fine_band, st));
             a.qimg = (const _Float16*)s.qimg8.p; a.q_scale = s.qscale.as<float>(); a.band_q = s.bandq.as<int>();
         }
-        a.n = ix->n; a.dp = ix->dp; a.row_bytes = (long long)ix->dp * (ix->dtype == VF_DTYPE_FP8_E4M3 ? 1 : 2); a.total_waves = p.total_waves; a.samp = p.samp;
+        a.n = ix->n; a.dp = ix->dp; a.row_bytes = (long long)ix->dp * (byte_rows(ix->dtype) ? 1 : 2); a.total_waves = p.total_waves; a.samp = p.samp;
         if (p.image) { a.rows = (const char*)ix->rows_img; a.inv_scan = ix->inv_img; a.off_scan = image_offsets(ix); a.row_bytes = ix->dp; }   // every pass of the batch: sample, seed, main
         a.s0 = s.s0.as<float>(); a.wg_base = s.wgbase.as<long long>(); a.cnt = s.cnt.as<u32>(); a.tau_bin = s.tau.as<int>(); a.hist = s.hist.as<u32>();
         a.cand = s.cand.as<u64>(); a.cap = p.cap; a.kprime = p.kprime; a.tau_band = p.tau_band;
@@ -1200,9 +1247,11 @@ static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq,
         // CU, each walking the sample parts of p.grid / 32 ranges with six-segment rings: the pass is bound by what a CU keeps in flight
         // (k_scan's register-staged loads: 68-71 us for 8 rows per wave in four rounds of 128 workgroups).  sample_impl: -1 auto, 0 k_scan, 1 k_scan2r
         const bool f8rows = ix->dtype == VF_DTYPE_FP8_E4M3 || p.image;   // (image rows: one byte per element, the e4m3 shapes)
+        // an int8 index off the image route: k_scan's int8 form only (k_scan2 / k_scan2r convert e4m3 codes; their int8 forms are the image's)
+        const bool i8conv = ix->dtype == VF_DTYPE_INT8 && !p.image;
         // e4m3 rows (768 / 1024 elements) take it wherever k_scan2r is their main scan (n > 1.1M: below), whole chip or split.
         const bool r_f8_auto = f8rows && ix->scan_impl == 2 && ix->n > kScan2rMinRows && !ix->steal_opt && scan2r_auto_width(ix->dp, true);
-        const bool sample_r = p.image || (ix->sample_impl != 0 && ix->scan_impl != 1 && scan2r_stage_cap(ix->dp, qt, f8rows) >= 256 &&
+        const bool sample_r = p.image || (!i8conv && ix->sample_impl != 0 && ix->scan_impl != 1 && scan2r_stage_cap(ix->dp, qt, f8rows) >= 256 &&
                               (ix->sample_impl == 1 || (!f8rows && s.scan_stream != s.stream && scan2r_auto_width(ix->dp, false)) || r_f8_auto));
         if (ks) {   // one workgroup per range: each loads its share of the image once and scores its range's sample part
             VF_HIP(rows_e4m3(ix) ? launch_scan_ksplit8(a, kModeSample, p.grid, st) : launch_scan_ksplit(a, kModeSample, p.grid, st));
@@ -1214,7 +1263,7 @@ static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq,
         } else {
         const int64_t sg_opt = ix->sample_grid >= 0 ? ix->sample_grid : (s.scan_stream != s.stream ? 4 * resolved_aux(ix) : 0);
         const int sgrid = sg_opt > 0 ? (int)std::min<int64_t>(sg_opt, p.grid) : p.grid;
-        VF_HIP(launch_scan(a, kModeSample, qt, sgrid, (int)ix->scan_g, ix->dtype == VF_DTYPE_FP8_E4M3, st));
+        VF_HIP(launch_scan(a, kModeSample, qt, sgrid, (int)ix->scan_g, scan_f8(ix->dtype), st));
         }
         VF_HIP(launch_sel0(a, qt, st));
         hipStream_t sst = s.scan_stream;
@@ -1242,7 +1291,7 @@ static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq,
         // carry twice the matrix work and the same LDS-DMA issues, and with ONE wave per SIMD nothing hides either -- measured 0.53
         // (k_scan2, round 3) and 0.55-0.60 (k_scan2r, round 6: B fragments in accumulator registers, rings of six) against k_scan's
         // 0.63-0.70 of peak at 10M x 768 / 1024 fp8 (profiles/r03_f8_sweep.log, r06_fp8_scan2r_ab.log)
-        const int cap2 = ((ix->scan_impl == 3 || ((ix->scan_impl == 2 || ix->scan_impl == 4 || ix->scan_impl == 5) && !f8)) && !ix->steal_opt) ? scan2_stage_cap(ix->dp, qt, f8) : 0;
+        const int cap2 = i8conv ? 0 : (((ix->scan_impl == 3 || ((ix->scan_impl == 2 || ix->scan_impl == 4 || ix->scan_impl == 5) && !f8)) && !ix->steal_opt) ? scan2_stage_cap(ix->dp, qt, f8) : 0);
         // k_scan2r (round 6): part of the query image in accumulator registers, deeper rings.  fp16 rows of 768 elements, measured against
         // k_scan2 in separate processes, alternating (profiles/r06_scan2r_ab.log): the 8-GPU rank's shard (1.25M rows) 0.3469-0.3528 ms
         // per batch against 0.3538-0.3602 (2.2 % faster: a wave keeps 24 KB in flight instead of 12), 10M rows level (2.538 vs 2.548 --
@@ -1259,7 +1308,7 @@ static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq,
 #else
         const bool dbg_r = true;
 #endif
-        const int capr = ((ix->scan_impl == 5 || r_auto) && !ix->steal_opt && dbg_r) ? scan2r_stage_cap(ix->dp, qt, f8) : 0;
+        const int capr = ((ix->scan_impl == 5 || r_auto) && !ix->steal_opt && dbg_r && !i8conv) ? scan2r_stage_cap(ix->dp, qt, f8) : 0;
         if (ks && f8) {
             VF_HIP(launch_scan_ksplit8(a, kModeMain, p.grid, sst));
             s.scan_kernel = 7;
@@ -1290,7 +1339,7 @@ static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq,
             VF_HIP(launch_scan2(a2, qt, p.grid, f8, sst));
             s.scan_kernel = 2;
         } else {
-            VF_HIP(launch_scan(a, kModeMain, qt, p.grid, (int)ix->scan_g, ix->dtype == VF_DTYPE_FP8_E4M3, sst));
+            VF_HIP(launch_scan(a, kModeMain, qt, p.grid, (int)ix->scan_g, scan_f8(ix->dtype), sst));
             s.scan_kernel = 1;
         }
         VF_HIP(hipEventRecord(s.ev_scan, sst));
@@ -1298,7 +1347,7 @@ static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq,
             VF_HIP(hipEventRecord(s.ev_t[1], sst));
             const int64_t per_wave = ix->n / p.total_waves;
             const int64_t sampled = std::min<int64_t>(ix->n, (int64_t)p.total_waves * std::min<int64_t>(p.samp, per_wave));
-            ix->prof_bytes = (ix->n - sampled) * (p.image ? (int64_t)ix->dp + 8 : (int64_t)ix->d * (ix->dtype == VF_DTYPE_FP8_E4M3 ? 1 : 2) + 4);
+            ix->prof_bytes = (ix->n - sampled) * (p.image ? (int64_t)ix->dp + 8 : (int64_t)ix->d * (byte_rows(ix->dtype) ? 1 : 2) + 4);
         }
         if (sst != st) VF_HIP(hipStreamWaitEvent(st, s.ev_scan, 0));
         FinalArgs f{};
@@ -1702,9 +1751,8 @@ extern "C" int vf_index_create_sharded(vf_index** out, const void* rows, int64_t
     *out = nullptr;
     VF_TRY(check_devices(device_ids, n_dev, "vf_index_create_sharded"));
     if (n < 0 || d <= 0 || (n > 0 && !rows)) return fail(VF_EINVAL, "vf_index_create_sharded: bad rows/n/d");
-    if (dtype != VF_DTYPE_F32 && dtype != VF_DTYPE_F16 && dtype != VF_DTYPE_FP8_E4M3)
-        return fail(VF_EINVAL, "vf_index_create_sharded: unknown dtype");
-    const size_t esz = dtype == VF_DTYPE_F32 ? 4 : (dtype == VF_DTYPE_F16 ? 2 : 1);
+    if (!known_dtype(dtype)) return fail(VF_EINVAL, "vf_index_create_sharded: unknown dtype");
+    const size_t esz = dtype_bytes(dtype);
     std::vector<vf_index*> shards;
     int rc = VF_OK;
     for (int g = 0; g < n_dev && rc == VF_OK; ++g) {

@@ -151,7 +151,7 @@ struct FinalArgs {
 
 // ---- launchers (defined in vf_kernels.hip) -----------------------------------------------------
 hipError_t launch_prep_rows(const void* rows, int dt /* VF_DTYPE_* */, long long n, int d, int dp,
-                            void* scan /*fp16 [n][dp] (fp8 rows: bytes [n][dp]); null when rows are used in place*/,
+                            void* scan /*fp16 [n][dp] (fp8 / int8 rows: bytes [n][dp]); null when rows are used in place*/,
                             float* norm, float* inv_scan, hipStream_t s);
 // the int8 row image of fp16 / fp32 rows (after launch_prep_rows: it reads `norm`): bytes [n][dp], inv_img [n], max relative residual (float bits)
 hipError_t launch_prep_image(const void* rows, int dt, long long n, int d, int dp, const float* norm, unsigned char* img,
@@ -168,7 +168,9 @@ hipError_t launch_sort_rows(const float* scores, long long score_stride, int nq,
                             long long id_base, long long* out_ids, float* out_scores, int out_stride,
                             hipStream_t s);
 hipError_t launch_scan(const ScanArgs& a, int mode, int qn_tile, int grid, int want_g /*0 = auto*/,
-                       int rows_are_fp8, hipStream_t s);
+                       int f8 /* 0 fp16 rows, 1 e4m3 bytes, 2 the biased bytes of an int8 index */, hipStream_t s);
+// two's-complement int8 rows -> the biased bytes (code + 128) an int8 index holds; in place when in == out
+hipError_t launch_rebias_i8(const void* in, void* out, long long bytes, hipStream_t s);
 // test hook: the scan's hardware e4m3 -> fp16 conversion over `count` codes (device pointers)
 hipError_t launch_debug_cvt_e4m3(const unsigned char* in, float* out, int count, hipStream_t s);
 // test hook: one v_mfma_i32_32x32x32_i8 over A [32][32], B [32][32] int8 -> C [32][32] = A B^T with k_scan2r's operand map (device pointers)
@@ -191,7 +193,7 @@ int scan_ksplit_stage_cap(int dp);
 hipError_t launch_scan_ksplit8(const ScanArgs& a, int mode, int grid, hipStream_t s);
 size_t scan_ksplit8_lds_bytes(int dp, int stage_cap);
 int scan_ksplit8_stage_cap(int dp);
-hipError_t launch_scan_wide(const ScanArgs& a, int mode, int rows_are_fp8, hipStream_t s);
+hipError_t launch_scan_wide(const ScanArgs& a, int mode, int f8 /* as launch_scan's */, hipStream_t s);
 size_t scan_wide_lds_bytes(int stage_cap);
 // k_scan_wide8: the wide main scan on the fp8 matrix instruction (e4m3 rows; a.qimg = the hi / lo code image of launch_prep_wide8)
 hipError_t launch_prep_wide8(const float* qn, int nq, int d, int dp, int qtot, unsigned char* img8, float* eps_q, hipStream_t s);

@@ -65,10 +65,12 @@ __device__ __forceinline__ float e4m3_to_float(u32 b) {
     return (float)__builtin_bit_cast(_Float16, e4m3_to_f16_bits(b));
 }
 
-// element `idx` of a row-major corpus of storage dtype dt (VF_DTYPE_F32 / _F16 / _FP8_E4M3), as fp32 (exact)
+// element `idx` of a row-major corpus of storage dtype dt (VF_DTYPE_F32 / _F16 / _FP8_E4M3 / _INT8), as fp32 (exact)
+// (int8 rows are HELD as biased bytes, code + 128: k_rebias_i8; every kernel that reads them undoes the bias)
 __device__ __forceinline__ float load_elem(const void* rows, int dt, long long idx) {
     if (dt == VF_DTYPE_F16) return (float)((const _Float16*)rows)[idx];
     if (dt == VF_DTYPE_FP8_E4M3) return e4m3_to_float(((const unsigned char*)rows)[idx]);
+    if (dt == VF_DTYPE_INT8) return (float)((int)((const unsigned char*)rows)[idx] - 128);
     return ((const float*)rows)[idx];
 }
 
@@ -91,6 +93,7 @@ __device__ __forceinline__ int next_pow2(int n) {
 //   underflow below 2^-38 of the row max); inv_scan = 1 / (norm * 2^e).
 //   fp16 rows: scan copy only when dp != d (zero padding); scale 1.
 //   fp8 (e4m3) rows: the scan copy stays fp8 BYTES (dp bytes per row, zero padded); scale 1.
+//   int8 rows (biased bytes): likewise dp bytes per row, padded with 128 -- the biased zero; scale 1.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_prep_rows(const void* rows, int dt, long long n, int d, int dp,
                                                     void* scan, float* norm, float* inv_scan) {
@@ -118,10 +121,11 @@ __global__ __launch_bounds__(256) void k_prep_rows(const void* rows, int dt, lon
         norm[r] = nm;
         inv_scan[r] = 1.0f / (nm * scale);
     }
-    if (scan && dt == VF_DTYPE_FP8_E4M3) {
+    if (scan && (dt == VF_DTYPE_FP8_E4M3 || dt == VF_DTYPE_INT8)) {
         unsigned char* out = (unsigned char*)scan + r * (long long)dp;
         const unsigned char* in = (const unsigned char*)rows + base;
-        for (int j = l; j < dp; j += 16) out[j] = j < d ? in[j] : (unsigned char)0;
+        const unsigned char pad = dt == VF_DTYPE_INT8 ? (unsigned char)128 : (unsigned char)0;
+        for (int j = l; j < dp; j += 16) out[j] = j < d ? in[j] : pad;
     } else if (scan) {
         _Float16* out = (_Float16*)scan + r * (long long)dp;
         for (int j = l; j < dp; j += 16) {
@@ -210,6 +214,29 @@ hipError_t launch_prep_rows(const void* rows, int dt, long long n, int d, int dp
     const long long blocks = (n + 15) / 16;
     hipLaunchKernelGGL(k_prep_rows, dim3((unsigned)blocks), dim3(256), 0, s, rows, dt, n, d, dp, scan, norm,
                        inv_scan);
+    return hipGetLastError();
+}
+
+// k_rebias_i8: two's-complement int8 rows -> the biased bytes an int8 index holds (code + 128 = the byte with its top bit flipped), the
+// form of k_prep_image's codes: cvt8_i8b and k_scan2r's int8 bodies read an int8 index as they read that image.  `in` may be `out`.
+__global__ __launch_bounds__(256) void k_rebias_i8(const unsigned char* in, unsigned char* out, long long bytes) {
+    const long long stride = (long long)gridDim.x * 256 * 16;
+    for (long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * 16; i < bytes; i += stride) {
+        if (i + 16 <= bytes && ((((unsigned long long)(in + i)) | ((unsigned long long)(out + i))) & 15ull) == 0) {
+            uint4 v = *(const uint4*)(in + i);
+            v.x ^= 0x80808080u; v.y ^= 0x80808080u; v.z ^= 0x80808080u; v.w ^= 0x80808080u;
+            *(uint4*)(out + i) = v;
+        } else {
+            const long long e = i + 16 < bytes ? i + 16 : bytes;
+            for (long long j = i; j < e; ++j) out[j] = in[j] ^ (unsigned char)0x80;
+        }
+    }
+}
+
+hipError_t launch_rebias_i8(const void* in, void* out, long long bytes, hipStream_t s) {
+    if (bytes <= 0) return hipSuccess;
+    const long long want = (bytes + 256 * 16 - 1) / (256 * 16);
+    hipLaunchKernelGGL(k_rebias_i8, dim3((unsigned)(want < 65536 ? want : 65536)), dim3(256), 0, s, (const unsigned char*)in, (unsigned char*)out, bytes);
     return hipGetLastError();
 }
 
@@ -752,7 +779,8 @@ __device__ __forceinline__ void issue_loads_f8(uint4 (&buf)[2 * G], const char* 
         }
 }
 
-template <int NT, int G>
+// F8 = 1: e4m3 codes (cvt8_e4m3); F8 = 2: the biased bytes of an int8 index (cvt8_i8b) -- both exact, the rest is shared
+template <int NT, int G, int F8 = 1>
 __device__ __forceinline__ void compute_superstep_f8(f16v (&acc)[NT], const uint4 (&buf)[2 * G], const char* lds_lane,
                                                      int ss) {
     constexpr int QN = NT * kQueryTile;
@@ -762,7 +790,9 @@ __device__ __forceinline__ void compute_superstep_f8(f16v (&acc)[NT], const uint
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const uint4 w = buf[g * 2 + (i >> 1)];
-            const h8 afrag = (i & 1) ? cvt8_e4m3(w.z, w.w) : cvt8_e4m3(w.x, w.y);
+            h8 afrag;
+            if constexpr (F8 == 2) afrag = (i & 1) ? cvt8_i8b(w.z, w.w) : cvt8_i8b(w.x, w.y);
+            else afrag = (i & 1) ? cvt8_e4m3(w.z, w.w) : cvt8_e4m3(w.x, w.y);
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
                 const h8 b = *(const h8*)(base + (g * 8 + i) * (QN * 16) + nt * (kQueryTile * 16));
@@ -1109,7 +1139,7 @@ __device__ __forceinline__ void tile_epilogue(const ScanArgs& a, const f16v (&ac
     } while (0)
 #define VF_COMPUTE(ACC, BUF, ...)                                                 \
     do {                                                                          \
-        if constexpr (F8 != 0) compute_superstep_f8<NT, G>(ACC, BUF, __VA_ARGS__); \
+        if constexpr (F8 != 0) compute_superstep_f8<NT, G, F8>(ACC, BUF, __VA_ARGS__); \
         else compute_superstep<NT, G>(ACC, BUF, __VA_ARGS__);                      \
     } while (0)
 
@@ -2609,7 +2639,8 @@ __device__ __forceinline__ void wide_compute(f16v (&acc)[kWideM][kWideNT], const
         for (int m = 0; m < kWideM; ++m) {
             if constexpr (F8 != 0) {
                 const uint4 w = st.w[m][2 * CC + (i >> 1)];
-                afrag[m] = (i & 1) ? cvt8_e4m3(w.z, w.w) : cvt8_e4m3(w.x, w.y);
+                if constexpr (F8 == 2) afrag[m] = (i & 1) ? cvt8_i8b(w.z, w.w) : cvt8_i8b(w.x, w.y);   // the biased bytes of an int8 index
+                else afrag[m] = (i & 1) ? cvt8_e4m3(w.z, w.w) : cvt8_e4m3(w.x, w.y);
             } else {
                 afrag[m] = __builtin_bit_cast(h8, st.w[m][i]);
             }
@@ -3691,12 +3722,12 @@ size_t scan_wide_lds_bytes(int stage_cap) {
     return (size_t)3 * kWideBuf + kWideCtl + (size_t)stage_cap * 16;
 }
 
-hipError_t launch_scan_wide(const ScanArgs& a, int mode, int rows_are_fp8, hipStream_t s) {
+hipError_t launch_scan_wide(const ScanArgs& a, int mode, int f8 /* 0 fp16 rows, 1 e4m3 bytes, 2 int8 bytes (biased) */, hipStream_t s) {
     const int grid = 8 * a.jtiles * ((a.rgroups + 7) / 8);
     const size_t lds = scan_wide_lds_bytes(mode == kModeMain ? a.stage_cap : 0);
 #define VF_WCASE(MODEV, F8V) \
-    if (mode == MODEV && (rows_are_fp8 != 0) == (F8V != 0)) { hipLaunchKernelGGL((k_scan_wide<MODEV, F8V>), dim3(grid), dim3(kWideThreads), lds, s, a); return hipGetLastError(); }
-    VF_WCASE(kModeSample, 0) VF_WCASE(kModeSample, 1) VF_WCASE(kModeMain, 0) VF_WCASE(kModeMain, 1)
+    if (mode == MODEV && f8 == F8V) { hipLaunchKernelGGL((k_scan_wide<MODEV, F8V>), dim3(grid), dim3(kWideThreads), lds, s, a); return hipGetLastError(); }
+    VF_WCASE(kModeSample, 0) VF_WCASE(kModeSample, 1) VF_WCASE(kModeMain, 0) VF_WCASE(kModeMain, 1) VF_WCASE(kModeSample, 2) VF_WCASE(kModeMain, 2)
 #undef VF_WCASE
     return hipErrorInvalidValue;
 }
@@ -3740,12 +3771,13 @@ static int pick_G(int dp, int want, int mode, int f8) {
     return 1;  // segs even => always ok
 }
 
-hipError_t launch_scan(const ScanArgs& a, int mode, int qn_tile, int grid, int want_g, int rows_are_fp8, hipStream_t s) {
-    const int G = pick_G(a.dp, want_g, mode, rows_are_fp8);
+// f8: 0 fp16 rows, 1 e4m3 bytes, 2 the biased bytes of an int8 index (the e4m3 geometry: a row is dp bytes either way)
+hipError_t launch_scan(const ScanArgs& a, int mode, int qn_tile, int grid, int want_g, int f8, hipStream_t s) {
+    const int G = pick_G(a.dp, want_g, mode, f8);
     const int NT = qn_tile / kQueryTile;
 #define VF_CASE(NTV, GV, MODEV)                                                                         \
     if (NT == NTV && G == GV && mode == MODEV)                                                          \
-        return rows_are_fp8 ? launch_scan_inst<NTV, GV, MODEV, 1>(a, grid, s) : launch_scan_inst<NTV, GV, MODEV, 0>(a, grid, s);
+        return f8 == 2 ? launch_scan_inst<NTV, GV, MODEV, 2>(a, grid, s) : f8 ? launch_scan_inst<NTV, GV, MODEV, 1>(a, grid, s) : launch_scan_inst<NTV, GV, MODEV, 0>(a, grid, s);
     VF_CASE(1, 1, kModeMain) VF_CASE(1, 2, kModeMain) VF_CASE(1, 3, kModeMain) VF_CASE(1, 4, kModeMain)
     VF_CASE(2, 1, kModeMain) VF_CASE(2, 2, kModeMain) VF_CASE(2, 3, kModeMain) VF_CASE(2, 4, kModeMain)
     VF_CASE(1, 1, kModeSample) VF_CASE(1, 2, kModeSample) VF_CASE(1, 3, kModeSample) VF_CASE(1, 4, kModeSample)
@@ -3849,6 +3881,8 @@ template <int NT, int G, int MODE>
 static hipError_t configure_one() {
     hipError_t e = hipFuncSetAttribute((const void*)k_scan<NT, G, MODE, 0>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                        160 * 1024);
+    if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute((const void*)k_scan<NT, G, MODE, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return e;
     return hipFuncSetAttribute((const void*)k_scan<NT, G, MODE, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }
@@ -4049,6 +4083,7 @@ __device__ __forceinline__ void rank_select_desc(const u64* keys, int n, u64* ou
 template <int DT> struct RowVec;
 template <> struct RowVec<VF_DTYPE_F16> { typedef uint4 type; };
 template <> struct RowVec<VF_DTYPE_FP8_E4M3> { typedef uint2 type; };
+template <> struct RowVec<VF_DTYPE_INT8> { typedef uint2 type; };
 template <> struct RowVec<VF_DTYPE_F32> { struct type { uint4 a, b; }; };
 
 template <int DT>
@@ -4059,6 +4094,10 @@ __device__ __forceinline__ void decode8(const typename RowVec<DT>::type& v, floa
         for (int e = 0; e < 8; ++e) x[e] = (float)hv[e];
     } else if constexpr (DT == VF_DTYPE_FP8_E4M3) {
         const h8 hv = cvt8_e4m3(v.x, v.y);   // the scan's own conversion (pinned against the oracle's table)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) x[e] = (float)hv[e];
+    } else if constexpr (DT == VF_DTYPE_INT8) {
+        const h8 hv = cvt8_i8b(v.x, v.y);   // biased bytes -> the integers, exactly (the scan's own conversion)
 #pragma unroll
         for (int e = 0; e < 8; ++e) x[e] = (float)hv[e];
     } else {
@@ -4078,9 +4117,9 @@ __device__ __forceinline__ float rescore_pair(const void* rows, long long row, i
     for (int e = 0; e < 8; ++e) acc[e] = 0.0f;
     const char* base = (const char*)rows + row * (long long)d * ESZ;
     const int nblk = d >> 4;
-    if constexpr (DT == VF_DTYPE_FP8_E4M3) {
+    if constexpr (DT == VF_DTYPE_FP8_E4M3 || DT == VF_DTYPE_INT8) {
         if ((d & 15) == 0) {
-            // e4m3 rows: a 16-element block is 16 bytes.  Lane h loads block 2 p + h WHOLE (one 16-byte load instead of two lanes x
+            // e4m3 / int8 rows: a 16-element block is 16 bytes.  Lane h loads block 2 p + h WHOLE (one 16-byte load instead of two lanes x
             // 8 bytes: half the load instructions, twice the bytes in flight per lane -- the gather is latency-bound: round 4,
             // profiles/r04_stamps_final_c5.log: 503 of 863 us of a k = 1000 workgroup at 10M rows) and the pair swaps halves by DPP:
             // lane 0 keeps elements 0..7 of its block and takes elements 0..7 of the partner's, lane 1 the upper halves.  Blocks are
@@ -4250,6 +4289,7 @@ __global__ __launch_bounds__(kFinalThreads) void k_final(FinalArgs a) {
         const float nm = a.norm[row];
         const float acc = a.orig_dtype == VF_DTYPE_F16       ? rescore_pair<VF_DTYPE_F16>(a.rows_orig, row, a.d, qs, nm, h)
                           : a.orig_dtype == VF_DTYPE_FP8_E4M3 ? rescore_pair<VF_DTYPE_FP8_E4M3>(a.rows_orig, row, a.d, qs, nm, h)
+                          : a.orig_dtype == VF_DTYPE_INT8     ? rescore_pair<VF_DTYPE_INT8>(a.rows_orig, row, a.d, qs, nm, h)
                                                               : rescore_pair<VF_DTYPE_F32>(a.rows_orig, row, a.d, qs, nm, h);
         __builtin_amdgcn_wave_barrier();   // every pair of this wave has read its row id before any pair overwrites a slot
         if (h == 0 && i < ns) rk[i] = ((u64)orderkey(acc) << 32) | (u64)(0xFFFFFFFFu - row);
@@ -4361,6 +4401,8 @@ hipError_t scan_configure() {
     if ((e = hipFuncSetAttribute((const void*)k_scan_wide<kModeSample, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
     if ((e = hipFuncSetAttribute((const void*)k_scan_wide<kModeMain, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
     if ((e = hipFuncSetAttribute((const void*)k_scan_wide<kModeMain, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
+    if ((e = hipFuncSetAttribute((const void*)k_scan_wide<kModeSample, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
+    if ((e = hipFuncSetAttribute((const void*)k_scan_wide<kModeMain, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
     if ((e = hipFuncSetAttribute((const void*)k_scan_wide8<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
 #ifdef VF_EXPERIMENTS
     if ((e = hipFuncSetAttribute((const void*)k_scan_wide8<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;

@@ -18,6 +18,21 @@ def _is_torch_tensor(x) -> bool:
     return type(x).__module__.startswith("torch") and hasattr(x, "data_ptr")
 
 
+def quantize_int8(x) -> np.ndarray:
+    """[n, d] floats -> int8 codes, one scale per row (not kept: a cosine does not see a positive per-row scale, so an int8 index
+    stores the codes alone).  The recipe is the device's own (k_prep_image), in fp32: ``sc = absmax / 127`` (zero rows: 1),
+    ``code = clip(rint(x / sc), -127, 127)`` with ties to even.  Non-finite input raises ValueError."""
+    x = np.asarray(x)
+    if x.ndim != 2:
+        raise ValueError("quantize_int8: x must be [n, d]")
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if not np.isfinite(x).all():
+        raise ValueError("quantize_int8: the rows hold non-finite values")
+    mx = np.abs(x).max(axis=1, keepdims=True) if x.shape[1] else np.zeros((x.shape[0], 1), np.float32)
+    sc = np.where(mx > 0, mx / np.float32(127.0), np.float32(1.0)).astype(np.float32)
+    return np.clip(np.rint(x / sc), -127.0, 127.0).astype(np.int8)
+
+
 def _dev_array(device_ids):
     ids = [int(x) for x in device_ids]
     if not ids:
@@ -30,6 +45,8 @@ class DenseIndex:
         """rows: [n, d] float32 / float16 ndarray (copied to HBM) or a CUDA torch tensor (borrowed).
         FP8: a torch.float8_e4m3fn tensor (CPU or CUDA), or a uint8 ndarray / tensor of OCP e4m3 codes passed with
         ``DenseIndex.from_e4m3``; the bytes stay fp8 in HBM (scanned as fp8, converted exactly in registers).
+        INT8: an int8 ndarray or torch.int8 tensor (CPU or CUDA; ``quantize_int8`` makes one from floats) -- one byte per element in
+        HBM, scored as the canonical cosine of the integers; always copied (a CUDA tensor is not borrowed and may be freed at once).
         device_ids=[...]: ONE handle over several GPUs in this process (``vf_index_create_sharded``): host rows are
         split into contiguous blocks, one per listed device; every search method works on it unchanged, device
         buffers live on the home device ``device_ids[0]``."""
@@ -52,6 +69,8 @@ class DenseIndex:
                 if rows.dtype != np.uint8:
                     raise TypeError("e4m3 rows must be uint8 codes")
                 dt = _ffi.VF_DTYPE_FP8_E4M3
+            elif rows.dtype == np.int8:
+                dt = _ffi.VF_DTYPE_INT8
             elif rows.dtype == np.float16:
                 dt = _ffi.VF_DTYPE_F16
             else:
@@ -75,6 +94,8 @@ class DenseIndex:
                     raise ValueError("rows must be a contiguous [n, d] tensor")
                 if e4m3 and rows.dtype == torch.uint8:
                     dt = _ffi.VF_DTYPE_FP8_E4M3
+                elif rows.dtype == torch.int8 and not e4m3:
+                    dt = _ffi.VF_DTYPE_INT8
                 elif rows.dtype == torch.float16:
                     dt = _ffi.VF_DTYPE_F16
                 elif rows.dtype == torch.float32:
@@ -82,7 +103,7 @@ class DenseIndex:
                 else:
                     raise TypeError(f"unsupported corpus dtype {rows.dtype}")
                 self.device_id = rows.device.index if rows.device.index is not None else self.device_id
-                self._keepalive = rows
+                self._keepalive = None if dt == _ffi.VF_DTYPE_INT8 else rows   # (int8 rows are copied: re-biased on the way)
                 self.n, self.d = int(rows.shape[0]), int(rows.shape[1])
                 _ffi.check(L.vf_index_create_device(ctypes.byref(self._h), rows.data_ptr(), self.n, self.d, dt,
                                                     self.device_id, int(id_offset)), "vf_index_create_device")
@@ -95,6 +116,8 @@ class DenseIndex:
             if rows.dtype != np.uint8:
                 raise TypeError("e4m3 rows must be uint8 codes")
             dt = _ffi.VF_DTYPE_FP8_E4M3
+        elif rows.dtype == np.int8:
+            dt = _ffi.VF_DTYPE_INT8
         elif rows.dtype == np.float16:
             dt = _ffi.VF_DTYPE_F16
         else:
@@ -162,6 +185,15 @@ class DenseIndex:
         self._e4m3 = True
         self.__init__(codes, device_id=device_id, id_offset=id_offset, device_ids=device_ids)
         return self
+
+    @classmethod
+    def from_int8(cls, codes, device_id: int = 0, id_offset: int = 0, device_ids=None):
+        """codes: [n, d] int8 (ndarray, CPU or CUDA tensor) -- what ``DenseIndex(codes)`` does for int8 input, but anything else is
+        refused instead of being read as floats (uint8 bytes are e4m3 codes: ``from_e4m3``)."""
+        dt = str(getattr(codes, "dtype", None))
+        if dt not in ("int8", "torch.int8"):
+            raise TypeError(f"int8 rows must be int8, got {dt} (uint8 codes are e4m3: DenseIndex.from_e4m3)")
+        return cls(codes, device_id=device_id, id_offset=id_offset, device_ids=device_ids)
 
     # -- host buffers ------------------------------------------------------------------------------
     def search(self, queries, k: int):

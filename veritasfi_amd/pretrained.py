@@ -15,7 +15,7 @@ from the model's architecture and its tokenizer's id of ``"Yes"``.  The function
 
 ``device_ids`` / ``corpus_dtype`` are the two optional keys SURVEY.md section 5 adds (existing YAMLs keep working without them):
 several devices give one model replica per device (the reference's worker-per-GPU data parallelism, ``step3_mul.py:405-452``) and a
-corpus sharded over them (``FaissRetriever(..., device_ids=[...])``); ``corpus_dtype`` in ``f32 | f16 | fp8`` is how the index holds
+corpus sharded over them (``FaissRetriever(..., device_ids=[...])``); ``corpus_dtype`` in ``f32 | f16 | fp8 | int8`` is how the index holds
 the rows in HBM.  Weights are read with ``transformers`` (fp32 on the host), rounded to fp16 once and handed to the library; nothing
 here runs a forward on the CPU.
 """
@@ -271,8 +271,8 @@ def from_config(cfg, load_models: bool = True):
     if device_ids is not None:
         device_ids = [int(d) for d in (device_ids if isinstance(device_ids, (list, tuple)) else [device_ids])]
     corpus_dtype = str(cfg.get("corpus_dtype", "f32")).lower()
-    if corpus_dtype not in ("f32", "f16", "fp8"):
-        raise ValueError(f"corpus_dtype {corpus_dtype!r}: one of f32, f16, fp8")
+    if corpus_dtype not in ("f32", "f16", "fp8", "int8"):
+        raise ValueError(f"corpus_dtype {corpus_dtype!r}: one of f32, f16, fp8, int8")
     first = device_ids[0] if device_ids else 0
     retriever_cls = functools.partial(FaissRetriever, device_id=first, device_ids=device_ids if device_ids and len(device_ids) > 1 else None,
                                       corpus_dtype=corpus_dtype)
