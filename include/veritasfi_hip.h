@@ -56,7 +56,7 @@ typedef struct vf_search_stats {
     int64_t wide_queries;    /* queries those passes served (up to 1024 per pass) */
     int64_t aux_cus;         /* CUs the main scan left to the small kernels of the other slots (0 = no CU split) */
     int64_t scans_overlap;   /* 1 = main scans of consecutive slots were not ordered against each other */
-    int64_t scan_kernel;     /* main-scan kernel of the call: 1 k_scan (register loads), 2 k_scan2 (whole-line LDS-DMA), 3 k_scan_wide, 4 k_scan_wide8 (fp8 matrix instruction), 5 k_scan2r (k_scan2, half the query image in registers), 6 k_scan_ksplit (rows of 2560 to 4096 padded elements: option "wide_rows"), 7 k_scan_ksplit8 (the same for e4m3 rows) */
+    int64_t scan_kernel;     /* main-scan kernel of the call: 1 k_scan (register loads), 2 k_scan2 (whole-line LDS-DMA), 3 k_scan_wide, 4 k_scan_wide8 (fp8 matrix instruction), 5 k_scan2r (k_scan2, half the query image in registers), 6 k_scan_ksplit (rows of 2560 to 4096 padded elements: option "wide_rows"), 7 k_scan_ksplit8 (the same for e4m3 rows) or its int8 form k_scan_ksplit8i (int8 rows report 7 as the int8 forms of k_scan and k_scan_wide report 1 and 3) */
     int64_t scan_image;      /* 1 = the main scan read the int8 row image (option "scan_image"), 0 = the rows as stored */
     int64_t reserved[3];
 } vf_search_stats;
@@ -165,7 +165,11 @@ int vf_index_stats(vf_index* idx, vf_search_stats* out);
  *   is possible (more than 16 384 rows).  "force_path" = 1 takes the kernel at any of these sizes unless the option is 0.  e4m3 rows of
  *   these widths (padded to a multiple of 128) have a kernel of their own, k_scan_ksplit8 (a row is dp bytes, converted to fp16 in
  *   registers at the matrix instruction; vf_search_stats.scan_kernel = 7): auto from 32 768 rows, up to 64 queries in 32-query passes,
- *   batches of 65 or more on k_scan_wide where the padded width is a multiple of 256.  Same results bit for bit;
+ *   batches of 65 or more on k_scan_wide where the padded width is a multiple of 256.  int8 rows of these widths take the same
+ *   kernel with the int8 conversion (k_scan_ksplit8i, scan_kernel = 7 as well; the same batch rules, the wide pass being k_scan_wide's
+ *   int8 form) from 32 768 rows, and for them that count is a floor at every setting: below it "wide_rows" = 2 and "force_path" = 1
+ *   change nothing (chunked exact path; "force_path" = 1 refused), because 32 768 is the smallest row count at which the byte-row kernel
+ *   has been measured and the behaviour of smaller int8 indexes is pinned by tests/test_gpu_int8_rows.py.  Same results bit for bit;
  *   vf_search_stats.scan_kernel = 6 where k_scan_ksplit ran. */
 int vf_index_set_option(vf_index* idx, const char* name, int64_t value);
 /* Live kernel timing with HIP events on the stream the kernels run on (bench.py roofline):

@@ -104,7 +104,7 @@ struct Slot {
     hipEvent_t ev_t[4] = {nullptr, nullptr, nullptr, nullptr};  // profile: scan begin/end, pipeline begin/end
     bool timed = false;
     int wide_launches = 0, wide_queries = 0;   // k_scan_wide main passes of the pending search / queries they served
-    int scan_kernel = 0;                       // main-scan kernel of the pending search: 1 k_scan, 2 k_scan2, 3 k_scan_wide, ... 7 k_scan_ksplit8 (veritasfi_hip.h)
+    int scan_kernel = 0;                       // main-scan kernel of the pending search: 1 k_scan, 2 k_scan2, 3 k_scan_wide, ... 7 k_scan_ksplit8 / k_scan_ksplit8i (veritasfi_hip.h)
     int scan_image = 0;                        // 1: the pending search's scans read the int8 row image
     DevBuf qn, qimg, s0, cnt, tau, hist, hist_coarse, cand, flags, counts;   // fused-path state
     DevBuf dbg, wgbase, tilecnt, sib;
@@ -751,7 +751,7 @@ extern "C" int vf_index_set_option(vf_index* ix, const char* name, int64_t value
         ix->scan_image = value;
     }
     else if (s == "image_mfma") { if (!in_range(-1, 2)) return fail(VF_EINVAL, "image_mfma must be -1 (auto), 0 (the int8 row image on the fp16 matrix instruction, fp16 queries), 1 (on the int8 matrix instruction, the queries as one int8 plane) or 2 (as two planes, hi + lo: the band of 0)"); ix->image_mfma = value; }
-    else if (s == "wide_rows") { if (!in_range(0, 2)) return fail(VF_EINVAL, "wide_rows must be 0 (rows of more than 2432 padded elements never take the fused path), 1 (auto: from 131 072 rows, e4m3 rows from 32 768) or 2 (wherever k_scan_ksplit / k_scan_ksplit8 serve them)"); ix->wide_rows = value; }
+    else if (s == "wide_rows") { if (!in_range(0, 2)) return fail(VF_EINVAL, "wide_rows must be 0 (rows of more than 2432 padded elements never take the fused path), 1 (auto: from 131 072 rows, e4m3 and int8 rows from 32 768) or 2 (wherever k_scan_ksplit / k_scan_ksplit8 serve them; int8 rows: from 32 768 rows)"); ix->wide_rows = value; }
     else if (s == "debug") ix->debug = value;
     else if (s == "profile") {
         ix->profile = value != 0; ix->prof_scan_ms = ix->prof_pipe_ms = 0.0; ix->prof_launches = 0;
@@ -849,12 +849,19 @@ static bool ksplit_width(const vf_index* ix) { return scan_lds_bytes(ix->dp, kQu
 // 0.539 there, and 0.439 against 10.5 and 0.749 against 16.5 ms at 1M rows.  So: 32 768, for every width.
 constexpr int64_t kWideRowsMinRows8 = 32768;
 static bool rows_e4m3(const vf_index* ix) { return ix->dtype == VF_DTYPE_FP8_E4M3; }
-static int ksplit_stage_cap(const vf_index* ix) { return rows_e4m3(ix) ? scan_ksplit8_stage_cap(ix->dp) : scan_ksplit_stage_cap(ix->dp); }
+// int8 rows of these widths: k_scan_ksplit8i, which is k_scan_ksplit8 with cvt8_i8b at the matrix instruction (the device bytes of an int8
+// index are the biased bytes it converts; geometry, LDS budget and stage cap are the byte-row kernel's).  They are served from 32 768 rows
+// upward and that count is a FLOOR, not only the auto threshold: wide_rows = 2 and force_path = 1 do not go below it either.  32 768 is the
+// smallest row count at which the byte-row kernel has ever been measured (profiles/r10_wide_rows_fp8_threshold.log: it won every cell
+// there), and below it the behaviour of int8 rows is pinned by tests/test_gpu_int8_rows.py::
+// test_int8_chunked_exact_path_and_rows_of_2560_elements (17 000 x 2560: path 2 under wide_rows = 1 and 2, force_path = 1 refused).
+constexpr int64_t kWideRowsMinRowsI8 = 32768;
+static int ksplit_stage_cap(const vf_index* ix) { return byte_rows(ix->dtype) ? scan_ksplit8_stage_cap(ix->dp) : scan_ksplit_stage_cap(ix->dp); }
 static bool ksplit_serves(const vf_index* ix, bool forced) {
-    // int8 rows of these widths: no k_scan_ksplit8 form converts them yet, so they take the chunked exact path (path 2) and wide_rows /
-    // force_path = 1 are refused for them as they are at wide_rows = 0
-    if (ix->dtype == VF_DTYPE_INT8) return false;
     if (ix->wide_rows == 0 || ksplit_stage_cap(ix) < 256) return false;
+    // int8 rows return BEFORE `forced` and wide_rows = 2 are looked at: for them force_path = 1 and wide_rows = 2 do not reach below the
+    // floor as they do for fp16 and e4m3 rows (kWideRowsMinRowsI8, above: a pinned test and no measurement below it)
+    if (ix->dtype == VF_DTYPE_INT8) return ix->n >= kWideRowsMinRowsI8;
     return forced || ix->wide_rows == 2 || ix->n >= (rows_e4m3(ix) ? kWideRowsMinRows8 : kWideRowsMinRows);
 }
 
@@ -1023,13 +1030,15 @@ constexpr int kWideMinQueriesKsplit = 33;
 // k = 2048 the wide pass is ahead at 64 too) -- and three never do: 65 queries 1M x 2560 1.358 / 1.138, 1M x 4096 2.282 / 1.737,
 // 32 768 x 2560 0.327 / 0.195; 96 and 128 queries likewise in every cell.  So the boundary is the third pass: from 65 the wide pass.
 // Paddings it does not take (dp % 256 != 0) stay on 32-query passes of k_scan_ksplit8.
+// int8 rows of these widths (k_scan_ksplit8i) take the same boundary: their wide pass is k_scan_wide<MODE, 2>, the fp16 instruction on
+// converted rows like the kernel the figures above were measured against (k_scan_wide8 is an fp8-instruction kernel and does not apply).
 constexpr int kWideMinQueriesKsplit8 = 65;
 constexpr int kWideMaxQueries = 1024;  // 4 query tiles of 256 per pass: one workgroup per CU
 constexpr int kWideTile = 256;
 
 static bool wide_possible(const vf_index* ix, int nq) {
     const bool ks = ksplit_width(ix);   // rows only k_scan_ksplit holds an image of (32 queries per pass)
-    if (ix->wide_opt == 0 || nq < (ix->wide_opt > 1 ? (int)ix->wide_opt : ks ? (rows_e4m3(ix) ? kWideMinQueriesKsplit8 : kWideMinQueriesKsplit) : (byte_rows(ix->dtype) ? kWideMinQueries : kWideMinQueries16))) return false;
+    if (ix->wide_opt == 0 || nq < (ix->wide_opt > 1 ? (int)ix->wide_opt : ks ? (byte_rows(ix->dtype) ? kWideMinQueriesKsplit8 : kWideMinQueriesKsplit) : (byte_rows(ix->dtype) ? kWideMinQueries : kWideMinQueries16))) return false;
     // a register stage is 2 k-chunks of fp8 rows / 1 of fp16 rows and a tile alternates two stages
     return ix->dp % (byte_rows(ix->dtype) ? 256 : 128) == 0;
 }
@@ -1254,7 +1263,7 @@ static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq,
         const bool sample_r = p.image || (!i8conv && ix->sample_impl != 0 && ix->scan_impl != 1 && scan2r_stage_cap(ix->dp, qt, f8rows) >= 256 &&
                               (ix->sample_impl == 1 || (!f8rows && s.scan_stream != s.stream && scan2r_auto_width(ix->dp, false)) || r_f8_auto));
         if (ks) {   // one workgroup per range: each loads its share of the image once and scores its range's sample part
-            VF_HIP(rows_e4m3(ix) ? launch_scan_ksplit8(a, kModeSample, p.grid, st) : launch_scan_ksplit(a, kModeSample, p.grid, st));
+            VF_HIP(byte_rows(ix->dtype) ? launch_scan_ksplit8(a, kModeSample, p.grid, scan_f8(ix->dtype), st) : launch_scan_ksplit(a, kModeSample, p.grid, st));
         } else if (sample_r) {
             const int64_t sg_r = ix->sample_grid > 0 ? ix->sample_grid : (s.scan_stream != s.stream ? resolved_aux(ix) : p.grid);
             ScanArgs as = a;
@@ -1309,8 +1318,8 @@ static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq,
         const bool dbg_r = true;
 #endif
         const int capr = ((ix->scan_impl == 5 || r_auto) && !ix->steal_opt && dbg_r && !i8conv) ? scan2r_stage_cap(ix->dp, qt, f8) : 0;
-        if (ks && f8) {
-            VF_HIP(launch_scan_ksplit8(a, kModeMain, p.grid, sst));
+        if (ks && byte_rows(ix->dtype)) {   // e4m3 codes: k_scan_ksplit8; int8 rows: k_scan_ksplit8i, reported as 7 too (as k_scan's and k_scan_wide's int8 forms report 1 and 3)
+            VF_HIP(launch_scan_ksplit8(a, kModeMain, p.grid, scan_f8(ix->dtype), sst));
             s.scan_kernel = 7;
         } else if (ks) {
             VF_HIP(launch_scan_ksplit(a, kModeMain, p.grid, sst));

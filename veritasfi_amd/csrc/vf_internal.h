@@ -190,7 +190,8 @@ hipError_t launch_scan_ksplit(const ScanArgs& a, int mode, int grid, hipStream_t
 size_t scan_ksplit_lds_bytes(int dp, int stage_cap);
 int scan_ksplit_stage_cap(int dp);
 // k_scan_ksplit8: the same for e4m3 rows (a.row_bytes = dp; segments of 128 bytes, 5 to 8 per wave); scan_ksplit8_stage_cap = 0: not this kernel
-hipError_t launch_scan_ksplit8(const ScanArgs& a, int mode, int grid, hipStream_t s);
+// rows_f8: 1 e4m3 codes (k_scan_ksplit8), 2 the biased bytes of an int8 index (k_scan_ksplit8i: the same kernel on cvt8_i8b)
+hipError_t launch_scan_ksplit8(const ScanArgs& a, int mode, int grid, int rows_f8, hipStream_t s);
 size_t scan_ksplit8_lds_bytes(int dp, int stage_cap);
 int scan_ksplit8_stage_cap(int dp);
 hipError_t launch_scan_wide(const ScanArgs& a, int mode, int f8 /* as launch_scan's */, hipStream_t s);

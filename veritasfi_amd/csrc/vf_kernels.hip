@@ -1580,10 +1580,12 @@ __device__ __forceinline__ void ks_flush(const ScanArgs& a, char* ctl, char* red
     }
 }
 
-template <int MODE, int P>
-__global__ __launch_bounds__(kKsThreads) void k_scan_ksplit8(ScanArgs a) {
+// The body k_scan_ksplit8 (F8 = 1: e4m3 codes, cvt8_e4m3) and k_scan_ksplit8i (F8 = 2: the biased bytes of an int8 index, cvt8_i8b) share:
+// the conversion at the matrix instruction is the only thing the row type decides
+template <int MODE, int P, int F8>
+__device__ __forceinline__ void ks8_body(const ScanArgs& a, char* smem) {
     static_assert(P >= kKs8RegSegs && P <= kKs8MaxSegs, "segments per wave: 5..8");
-    extern __shared__ __attribute__((aligned(16))) char smem[];
+    static_assert(F8 == 1 || F8 == 2, "row type: 1 e4m3 codes, 2 int8 biased bytes");
     constexpr int XS = P - kKs8RegSegs;   // image segments per wave in LDS
     const int tid = threadIdx.x;
     const int lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1654,7 +1656,9 @@ __global__ __launch_bounds__(kKsThreads) void k_scan_ksplit8(ScanArgs a) {
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
                     const u4v w = A[j * 4 + ks8_step_load(i)];
-                    const h8 af = ks8_step_half(i) ? cvt8_e4m3(w[2], w[3]) : cvt8_e4m3(w[0], w[1]);
+                    h8 af;
+                    if constexpr (F8 == 2) af = ks8_step_half(i) ? cvt8_i8b(w[2], w[3]) : cvt8_i8b(w[0], w[1]);
+                    else af = ks8_step_half(i) ? cvt8_e4m3(w[2], w[3]) : cvt8_e4m3(w[0], w[1]);
                     h8 b;
                     if (j < kKs8RegSegs) b = qr[(j < kKs8RegSegs ? j : 0) * 8 + i];
                     else b = *(const h8*)(qx_lane + (size_t)(j - kKs8RegSegs) * kKs8SegBytes + i * (kQueryTile * 16));
@@ -1686,6 +1690,21 @@ __global__ __launch_bounds__(kKsThreads) void k_scan_ksplit8(ScanArgs a) {
         }
     }
     if (MODE == kModeMain) ks_flush(a, ctl, red, tid);
+}
+
+template <int MODE, int P>
+__global__ __launch_bounds__(kKsThreads) void k_scan_ksplit8(ScanArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    ks8_body<MODE, P, 1>(a, smem);
+}
+
+// k_scan_ksplit8i: the same rows stored as the biased bytes of an int8 index (corpus_dtype int8).  cvt8_i8b turns a byte into the fp16
+// integer it stands for, exactly; the row's scale rides in its inverse norm as in k_scan's int8 form.  Every address, the LDS budget and
+// the stage cap are k_scan_ksplit8's (a row is dp bytes either way); two VALU operations per two codes where cvt8_e4m3 takes one.
+template <int MODE, int P>
+__global__ __launch_bounds__(kKsThreads) void k_scan_ksplit8i(ScanArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    ks8_body<MODE, P, 2>(a, smem);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3818,15 +3837,22 @@ hipError_t launch_scan_ksplit(const ScanArgs& a, int mode, int grid, hipStream_t
 size_t scan_ksplit8_lds_bytes(int dp, int stage_cap) { return (size_t)ks8_lds_bytes(dp, stage_cap); }
 int scan_ksplit8_stage_cap(int dp) { return ks8_stage_cap(dp); }
 // mode kModeSample: `grid` = a.scan_grid workgroups, one per range; kModeMain: a.stage_cap = scan_ksplit8_stage_cap; a.row_bytes = a.dp
-hipError_t launch_scan_ksplit8(const ScanArgs& a, int mode, int grid, hipStream_t s) {
+// rows_f8 as in launch_scan: 1 e4m3 codes (k_scan_ksplit8), 2 the biased bytes of an int8 index (k_scan_ksplit8i)
+hipError_t launch_scan_ksplit8(const ScanArgs& a, int mode, int grid, int rows_f8, hipStream_t s) {
     if (!ks_serves(a.dp) || a.row_bytes != (long long)a.dp || (mode == kModeSample && grid != a.scan_grid)) return hipErrorInvalidValue;
     if (mode == kModeMain && (a.stage_cap < 256 || a.stage_cap > ks8_stage_cap(a.dp))) return hipErrorInvalidValue;
+    if (rows_f8 != 1 && rows_f8 != 2) return hipErrorInvalidValue;
     const int P = ks8_P(ks8_segs(a.dp));
     const size_t lds = scan_ksplit8_lds_bytes(a.dp, mode == kModeMain ? a.stage_cap : 0);
 #define VF_X(P_) \
     if (P == P_) { \
-        if (mode == kModeMain) hipLaunchKernelGGL((k_scan_ksplit8<kModeMain, P_>), dim3(grid), dim3(kKsThreads), lds, s, a); \
-        else hipLaunchKernelGGL((k_scan_ksplit8<kModeSample, P_>), dim3(grid), dim3(kKsThreads), lds, s, a); \
+        if (rows_f8 == 2) { \
+            if (mode == kModeMain) hipLaunchKernelGGL((k_scan_ksplit8i<kModeMain, P_>), dim3(grid), dim3(kKsThreads), lds, s, a); \
+            else hipLaunchKernelGGL((k_scan_ksplit8i<kModeSample, P_>), dim3(grid), dim3(kKsThreads), lds, s, a); \
+        } else { \
+            if (mode == kModeMain) hipLaunchKernelGGL((k_scan_ksplit8<kModeMain, P_>), dim3(grid), dim3(kKsThreads), lds, s, a); \
+            else hipLaunchKernelGGL((k_scan_ksplit8<kModeSample, P_>), dim3(grid), dim3(kKsThreads), lds, s, a); \
+        } \
         return hipGetLastError(); }
     VF_KSPLIT8_SHAPES(VF_X)
 #undef VF_X
@@ -4391,6 +4417,11 @@ hipError_t scan_configure() {
 #define VF_X(P_) \
     if ((e = hipFuncSetAttribute((const void*)k_scan_ksplit8<kModeMain, P_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e; \
     if ((e = hipFuncSetAttribute((const void*)k_scan_ksplit8<kModeSample, P_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
+    VF_KSPLIT8_SHAPES(VF_X)
+#undef VF_X
+#define VF_X(P_) \
+    if ((e = hipFuncSetAttribute((const void*)k_scan_ksplit8i<kModeMain, P_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e; \
+    if ((e = hipFuncSetAttribute((const void*)k_scan_ksplit8i<kModeSample, P_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
     VF_KSPLIT8_SHAPES(VF_X)
 #undef VF_X
     if ((e = hipFuncSetAttribute((const void*)k_scan2<1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
