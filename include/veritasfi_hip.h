@@ -79,7 +79,8 @@ int vf_device_count(int32_t* out);
  * form of the int8 row image of fp16 rows), so the rows are always COPIED, by every entry point; no fp16 or fp32
  * copy exists.  Every search path serves them; option scan_image picks the scan: 0 = bytes converted to fp16 in
  * registers (exact), 2 = the int8 matrix instruction on the bytes as they are wherever a shape exists (rows of 768
- * elements, k <= 128), 1 = auto.  Rows of 2560 to 4096 padded elements take the chunked exact path.
+ * elements, k <= 128), 1 = auto.  Rows of 2560 to 4096 padded elements take the fused path from 32 768 rows (k_scan_ksplit8i: option
+ * "wide_rows" below) and the chunked exact path below that count.
  * `id_offset` is added to every returned id (row-sharding across ranks). */
 int vf_index_create(vf_index** out, const void* rows, int64_t n, int32_t d, int32_t dtype,
                     int32_t device_id, int64_t id_offset);

@@ -22,7 +22,7 @@ import numpy as np
 
 
 def eps_bound(d: int, u16: float, fp32_corpus: bool = False) -> float:
-    """The library's certificate bound (vf_api.hip make_plan) for a given fp16 unit round-off."""
+    """The library's certificate bound (make_plan, vf_route.h) for a given fp16 unit round-off."""
     return u16 * (2.0 if fp32_corpus else 1.0) + np.sqrt(d) * 2.0 ** -24 + 2.0 * d * 2.0 ** -24 + 1e-6
 
 

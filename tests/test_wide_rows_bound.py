@@ -1,4 +1,4 @@
-"""The certificate's summation term covers k_scan_ksplit's order of additions (make_plan in vf_api.hip; tests/adversarial.py's
+"""The certificate's summation term covers k_scan_ksplit's order of additions (make_plan in vf_route.h; tests/adversarial.py's
 eps_bound restates the bound).
 
 The kernel adds a row's dp products in fp32 per wave -- a quarter of the row's 64-element segments each, 16 k-slots per matrix

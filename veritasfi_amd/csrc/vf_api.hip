@@ -7,6 +7,7 @@
 // (src/utils/ensembleRetriever.py:275-279), rank_chunk fusion (src/utils/vllmManager.py:454-457).
 #include "../../include/veritasfi_hip.h"
 #include "vf_internal.h"
+#include "vf_route.h"
 
 #include <fcntl.h>
 #include <float.h>
@@ -178,7 +179,7 @@ struct vf_index {
     // options
     int64_t force_path = -1, sample_rows = -1, margin = -1, cap_opt = 0, waves_opt = 0, scan_g = 0,
             refresh_every = 128, debug = 0, steal_opt = 0, wide_opt = 1, wide_sync = -1, wide_mfma = -1, wide8_waves = 8, wide8_stage = 0,
-            aux_cus = -1, sample_grid = -1, overlap_scans = -1, scan_impl = 2, sample_impl = -1, scan_image = 1, wide_rows = 1, image_mfma = -1;   // aux_cus / overlap_scans: -1 = auto (resolved_split)   // scan_impl: 1 = k_scan (register loads), 2 = k_scan2 (whole-line LDS-DMA) where it fits   // aux_cus: CUs the main scan leaves to the small kernels of the other slots (0 = no split)   // wide_sync: -1 siblings of a wide row group run free (default: fastest), >= 0 = the slack in super-tiles  // steal_opt: cross-workgroup tile pool in the main scan (measured slower: DESIGN.md 5)  // wide_opt: 0 never, 1 auto (nq >= 129), > 1 = from that many queries
+            aux_cus = -1, sample_grid = -1, overlap_scans = -1, scan_impl = 2, sample_impl = -1, scan_image = 1, wide_rows = 1, image_mfma = -1;   // aux_cus / overlap_scans: -1 = auto (route_aux_cus / route_overlap)   // scan_impl: 1 k_scan, 2 auto (k_scan2 for fp16 rows, k_scan2r where it measured faster), 3 k_scan2 wherever it fits, 4 never k_scan2r, 5 k_scan2r wherever a shape exists (veritasfi_hip.h; the rule: vf_route.h)   // aux_cus: CUs the main scan leaves to the small kernels of the other slots (0 = no split)   // wide_sync: -1 siblings of a wide row group run free (default: fastest), >= 0 = the slack in super-tiles  // steal_opt: cross-workgroup tile pool in the main scan (measured slower: DESIGN.md 5)  // wide_opt: 0 never, 1 auto (from kWideMinQueries* queries: vf_route.h), > 1 = from that many queries
     vf_search_stats stats{};
     bool profile = false;
     double prof_scan_ms = 0.0, prof_pipe_ms = 0.0;
@@ -212,12 +213,26 @@ static int ensure_pinned(Slot& s, size_t nq_total) {
 
 static int build_image(vf_index* ix, int64_t mode);
 
-// One byte per element in HBM (e4m3 codes, or the biased bytes of an int8 index): scanned as bytes with the e4m3 geometry, converted in
-// registers (cvt8_e4m3 / cvt8_i8b).  Everything that sizes a row, picks a byte-row kernel shape or counts traffic asks this.
-static bool byte_rows(int dtype) { return dtype == VF_DTYPE_FP8_E4M3 || dtype == VF_DTYPE_INT8; }
 static bool known_dtype(int64_t dtype) { return dtype >= VF_DTYPE_F32 && dtype <= VF_DTYPE_INT8; }
 static size_t dtype_bytes(int dtype) { return dtype == VF_DTYPE_F32 ? 4 : (dtype == VF_DTYPE_F16 ? 2 : 1); }
-static int scan_f8(int dtype) { return dtype == VF_DTYPE_INT8 ? 2 : (dtype == VF_DTYPE_FP8_E4M3 ? 1 : 0); }   // row type of launch_scan / launch_scan_wide
+
+// What the scan route (vf_route.h) decides from: the handle's shape and options and, for the passes of a search, whether the slot's scan
+// stream is CU-masked.  Every routing question below goes through this.
+static RouteIn route_in(const vf_index* ix, const Slot* s = nullptr) {
+    RouteIn in;
+    in.n = ix->n; in.d = ix->d; in.dp = ix->dp; in.dtype = ix->dtype; in.n_cu = ix->n_cu;
+    in.has_scan = ix->rows_scan && ix->inv_scan;
+    in.has_image = ix->rows_img != nullptr; in.rho_mean = ix->rho_mean;
+    in.group = !ix->shards.empty();
+    in.aux_applied = ix->aux_applied;
+    in.masked = s && s->scan_stream && s->scan_stream != s->stream;
+    in.force_path = ix->force_path; in.wide = ix->wide_opt; in.wide_mfma = ix->wide_mfma; in.wide8_waves = ix->wide8_waves;
+    in.wide8_stage = ix->wide8_stage; in.wide_rows = ix->wide_rows; in.scan_impl = ix->scan_impl; in.sample_impl = ix->sample_impl;
+    in.sample_grid = ix->sample_grid; in.steal = ix->steal_opt; in.scan_image = ix->scan_image; in.image_mfma = ix->image_mfma;
+    in.aux_cus = ix->aux_cus; in.overlap_scans = ix->overlap_scans; in.margin = ix->margin; in.cap = ix->cap_opt; in.waves = ix->waves_opt;
+    in.sample_rows = ix->sample_rows; in.debug = ix->debug;
+    return in;
+}
 
 static int build_common(vf_index* ix) {
     hipDeviceProp_t prop;
@@ -254,60 +269,11 @@ static int build_common(vf_index* ix) {
     return VF_OK;
 }
 
-// A slot's stream and events are created on its first use: a one-shot index (the reference builds one per
-// select_top_chunks call, step3_mul.py:233-253) only ever touches slot 0.
-// CU split and scan overlap, resolved.  Auto (-1): shards of up to 6M rows run their main scans on all but 32 CUs (one
-// per shader engine: a mask that takes CUs from only some SEs leaves those SEs with more workgroups than CUs -- the
-// dispatcher hands every SE the same number -- and a scan then takes two rounds; tools/ubench/cu_mask_probe.hip) and let
-// consecutive scans overlap; larger shards keep the whole chip and ordered scans (measured, round 3: 1.25M rows 0.384 ->
-// 0.362 ms per batch, 2.5M 0.717 -> 0.682, 5M 1.280 -> 1.269, 10M no change; profiles/r03_scan2_sweep.log).
-constexpr int64_t kSplitMaxRows = 6'000'000;
-constexpr int64_t kScan2rMinRows = 1'100'000;   // k_scan2r (where its shapes exist) above this many rows: below, the workgroup's longer start costs more than the ring gains
-// Round 6: where k_scan2r serves the rows (fp16 rows of 384 / 512 / 768 / 1024 elements; a wave keeps 16-24 KB in flight there) the split + overlapping scans
-// win at EVERY size -- 7.5M rows 1.878 -> 1.811 ms per batch, 10M rows 2.538 -> 2.466-2.473 (0.7585 -> 0.78 of 8 TB/s), whole chip +
-// ordered scans with k_scan2 being the 2.538; k_scan2r on the whole chip with ordered scans LOSES (2.58-2.59): profiles/r06_scan2r_10m.log
-// the widths on which k_scan2r was MEASURED against the kernel it replaces and is the default (its other shapes: scan_impl = 5)
-// fp16 rows of 1024 / 512 / 384 elements (round 6, profiles/r06_scan2r_fp16_other_widths_ab.log; k_scan2r + its sample pass on the CU split
-// with overlapping scans against the default before): 8M x 1024 2.725 -> 2.63-2.65 ms per batch (0.754 -> 0.774-0.781 of 8 TB/s; k_scan served
-// that width: k_scan2's image does not fit), 1.25M x 1024 0.465-0.467 -> 0.430-0.444, 10M x 512 1.711 -> 1.620-1.643 (0.765 -> 0.785-0.796),
-// 10M x 384 1.330 -> 1.262, 1.25M x 512 0.266-0.270 -> 0.260-0.265
-static bool scan2r_auto_width(int dp, bool f8) { return f8 ? (dp == 768 || dp == 1024) : (dp == 768 || dp == 1024 || dp == 512 || dp == 384); }
-static int64_t split_limit(const vf_index* ix) {
-    const bool r_rows = !byte_rows(ix->dtype) && ix->scan_impl != 4 && ix->scan_impl != 1 && ix->scan_impl != 3 && !ix->steal_opt &&
-                        scan2r_auto_width(ix->dp, false) && scan2r_stage_cap(ix->dp, kMaxBatch, 0) >= 256;
-    return r_rows ? INT64_MAX : kSplitMaxRows;
-}
-static int64_t resolved_aux(const vf_index* ix) {
-    if (ix->aux_applied >= 0) return ix->aux_applied;   // what the existing scan streams are masked with (0 if masking failed)
-    int64_t a = ix->aux_cus >= 0 ? ix->aux_cus : (ix->n <= split_limit(ix) ? 32 : 0);
-    if (a <= 0 || ix->n_cu < 64 || a * 2 > ix->n_cu) return 0;
-    return a;
-}
-static bool resolved_overlap(const vf_index* ix) {
-    return ix->overlap_scans >= 0 ? ix->overlap_scans != 0 : resolved_aux(ix) > 0;
-}
-
-// ---- the int8 row image ---------------------------------------------------------------------------------
-// fp16 / fp32 rows of 768 elements in a shard of at least kImageMinRows rows get a second copy at one byte per element (plus a float per
-// row): the main scan of a batch with k <= kImageMaxK reads 772 instead of 1 540 bytes per row (768 wide) and k_final's band re-score
-// keeps the results those of the canonical arithmetic.  Option scan_image: 0 off, 1 auto (default: only with kImageHeadroom of device
-// memory left over after it), 2 force.  A shard whose worst row leaves more than kImageMaxRho of residual keeps no image: its eps band
-// would hold a large part of the corpus (a row with one huge element and the rest near zero: tests/adversarial.py).
-// k and width limits: the band must fit k_final's 4 096-entry survivor area.  Measured with the first band (2 rho_max wide,
-// tests/test_gpu_scan_image.py): 4M x 768, k = 256 and 4M x 1024, k = 100 overflowed it for most queries; 768, k <= 128 did not
-constexpr int kImageMaxK = 128;
-constexpr int64_t kImageMinRows = 4'000'000;   // measured at 10M rows; the shards of a 4- or 8-GPU split (2.5M / 1.25M rows) keep the fp16 scan
+// ---- the int8 row image (when one is built and when a search reads it: vf_route.h) ----------------------------------
+// A shard whose worst row leaves more than kImageMaxRho of residual keeps no image; auto (scan_image = 1) builds one only with
+// kImageHeadroom of device memory left over after it.
 constexpr double kImageMaxRho = 1.0 / 64;
 constexpr size_t kImageHeadroom = (size_t)8 << 30;
-constexpr int kImageMfmaAuto = 1;   // option image_mfma = -1
-// An int8 index is the image itself (build_image): nothing is built or stored twice, so scan_image = 2 takes the int8-MFMA route at any
-// size the fused path serves; auto keeps kImageMinRows, where the route was measured on these very bytes (the conversion route, k_scan's
-// int8 form, below that) -- no threshold of its own has been measured yet.
-static bool image_eligible(const vf_index* ix, int64_t mode) {
-    if (!ix->shards.empty() || ix->n >= (int64_t)0xFFFFFFFFll || ix->dp != 768 || scan2r_stage_cap(ix->dp, kMaxBatch, 2) < 256) return false;
-    if (ix->dtype == VF_DTYPE_INT8) return ix->rows_scan && (mode == 2 ? ix->n > kSmallN : ix->n >= kImageMinRows);
-    return (ix->dtype == VF_DTYPE_F16 || ix->dtype == VF_DTYPE_F32) && ix->n >= kImageMinRows;
-}
 static float* image_offsets(const vf_index* ix) { return ix->inv_img ? ix->inv_img + ix->n + 64 : nullptr; }
 static void free_image(vf_index* ix) {
     if (ix->rows_img && ix->owns_img) (void)hipFree(ix->rows_img);
@@ -315,7 +281,7 @@ static void free_image(vf_index* ix) {
     ix->rows_img = nullptr; ix->inv_img = nullptr; ix->owns_img = false; ix->rho_max = ix->rho_mean = 0.0f;
 }
 static int build_image(vf_index* ix, int64_t mode) {
-    if (mode == 0 || ix->rows_img || !image_eligible(ix, mode)) return VF_OK;
+    if (mode == 0 || ix->rows_img || !image_eligible(route_in(ix), mode)) return VF_OK;
     const size_t ibytes = 2 * ((size_t)ix->n + 64) * sizeof(float);   // inverses + offsets
     if (ix->dtype == VF_DTYPE_INT8) {
         // the index's own bytes are the codes: row scale 1, so inv_img = 1 / ||c|| = inv_scan; no residual, so offsets, rho_max and rho_mean
@@ -360,6 +326,8 @@ static int build_image(vf_index* ix, int64_t mode) {
     return VF_OK;
 }
 
+// A slot's stream and events are created on its first use: a one-shot index (the reference builds one per
+// select_top_chunks call, step3_mul.py:233-253) only ever touches slot 0.
 static int ensure_slot(vf_index* ix, Slot& s) {
     if (s.stream) return VF_OK;
     VF_HIP(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
@@ -368,7 +336,7 @@ static int ensure_slot(vf_index* ix, Slot& s) {
     // leaves `aux_cus` CUs alone (mask bits interleave over the 8 XCDs: bits [0, n_cu - aux) = all but the last aux / 8 CUs
     // of every XCD; tools/ubench/cu_mask_probe.hip); everything else runs on an unmasked stream and finds those CUs free.
     s.scan_stream = s.stream;
-    int64_t aux = resolved_aux(ix);
+    int64_t aux = route_aux_cus(route_in(ix));
     if (aux) {
         const int words = (ix->n_cu + 31) / 32;
         std::vector<uint32_t> mask(words, 0u);
@@ -751,7 +719,7 @@ extern "C" int vf_index_set_option(vf_index* ix, const char* name, int64_t value
         ix->scan_image = value;
     }
     else if (s == "image_mfma") { if (!in_range(-1, 2)) return fail(VF_EINVAL, "image_mfma must be -1 (auto), 0 (the int8 row image on the fp16 matrix instruction, fp16 queries), 1 (on the int8 matrix instruction, the queries as one int8 plane) or 2 (as two planes, hi + lo: the band of 0)"); ix->image_mfma = value; }
-    else if (s == "wide_rows") { if (!in_range(0, 2)) return fail(VF_EINVAL, "wide_rows must be 0 (rows of more than 2432 padded elements never take the fused path), 1 (auto: from 131 072 rows, e4m3 and int8 rows from 32 768) or 2 (wherever k_scan_ksplit / k_scan_ksplit8 serve them; int8 rows: from 32 768 rows)"); ix->wide_rows = value; }
+    else if (s == "wide_rows") { if (!in_range(0, 2)) return fail(VF_EINVAL, std::string("wide_rows must be 0 (rows of more than 2432 padded elements never take the fused path), 1 (auto: from ") + std::to_string(kWideRowsMinRows) + " rows, e4m3 rows from " + std::to_string(kWideRowsMinRows8) + ", int8 rows from " + std::to_string(kWideRowsMinRowsI8) + ") or 2 (wherever k_scan_ksplit / k_scan_ksplit8 serve them; int8 rows: from " + std::to_string(kWideRowsMinRowsI8) + " rows)"); ix->wide_rows = value; }
     else if (s == "debug") ix->debug = value;
     else if (s == "profile") {
         ix->profile = value != 0; ix->prof_scan_ms = ix->prof_pipe_ms = 0.0; ix->prof_launches = 0;
@@ -815,88 +783,8 @@ static int exact_search(vf_index* ix, Slot& s, const float* qn_dev, int nq, int 
 }
 
 // ------------------------------------------------------------------------------------------------
-// path selection + fused pipeline
+// the fused pipeline (which path and which kernels serve a search: vf_route.h)
 // ------------------------------------------------------------------------------------------------
-struct FusedPlan {
-    int kprime, cap, total_waves, grid, samp;
-    float eps;
-    bool image;              // the scans read the int8 row image: kprime = k, thresholds and the re-score follow the eps band
-    int tau_band, fine_band; // that band (2 eps, rounded up, + one bin) in threshold bins (1 / 1024) and in k_final's fine bins (1 / 16 384)
-};
-
-static int qn_tile_for(int nq_batch) { return nq_batch <= kQueryTile ? kQueryTile : kMaxBatch; }
-
-// Rows of 2560 to 4096 padded elements (fp16, or the fp16 scan copy of fp32 rows; e4m3 rows: below): a 32-query image does not fit the LDS, so k_scan cannot
-// serve them; k_scan_ksplit does (the contraction split over four waves, the image in registers + LDS).  Option wide_rows: 0 never, 2
-// wherever the kernel serves the rows, 1 (auto) from kWideRowsMinRows rows.
-// The count is measured (tools/bench_wide_rows.py, one box, the settings alternating, three windows of a second each;
-// profiles/r08_wide_rows_threshold.log): the chunked exact path against this one at 32 768 / 65 536 / 131 072 / 262 144 / 1 048 576 rows,
-// 1 / 4 / 64 queries, k = 100 / 2048.  At k = 100 the fused path wins everywhere (32 768 x 2560, one query: 0.139 against 0.329 ms).  At
-// k = 2048 with one or four queries k_final's re-score of k' = 2 560+ rows per query is the step, and the fused path LOSES at 32 768 rows
-// (2560: 0.579 / 0.619 against 0.357 / 0.479 ms; 4096: 0.912 / 0.975 against 0.520 / 0.571) and, for 4096-wide rows, at 65 536
-// (1.231 / 1.287 against 1.025 / 1.104; 2560-wide rows are 1 to 4 % ahead there: a tie); from 131 072 rows it wins every cell at both widths
-// (k = 2048, one query: 0.845 against 1.375 ms at 2560, 1.406 against 2.036 at 4096) and the margin grows with n (1M x 2560: 0.86
-// against 10.1 ms).  So: 131 072 for every width.  Below it the existing behaviour stays (tests/test_gpu_retrieval.py::
-// test_wide_rows_and_path_limits: 17 000 x 2560 on path 2).
-constexpr int64_t kWideRowsMinRows = 131072;
-static bool ksplit_width(const vf_index* ix) { return scan_lds_bytes(ix->dp, kQueryTile) > 160 * 1024; }   // no LDS-resident 32-query image: dp > 2432
-// e4m3 rows of these widths: k_scan_ksplit8 (a row is dp bytes; the same split, image and reduction), under the same option.  Its count is
-// measured the same way (tools/bench_wide_rows.py --dtype fp8, one box, the settings alternating, three windows;
-// profiles/r10_wide_rows_fp8_threshold.log): 32 768 / 65 536 / 131 072 / 262 144 / 1 048 576 rows, 1 / 4 / 32 / 64 / 65 / 96 / 128 queries,
-// k = 100 / 2048, d = 2560 and 4096.  Half the bytes per row halve the scan and the re-score of k' rows, so the fused path wins EVERY cell
-// from the smallest row count of the grid: the closest are k = 2048 with one query at 32 768 rows, 0.339 against 0.364 ms at 2560 and
-// 0.505 against 0.540 at 4096 (four queries: 0.345 / 0.475 and 0.518 / 0.670); at k = 100 it is 0.109 against 0.345 and 0.143 against
-// 0.539 there, and 0.439 against 10.5 and 0.749 against 16.5 ms at 1M rows.  So: 32 768, for every width.
-constexpr int64_t kWideRowsMinRows8 = 32768;
-static bool rows_e4m3(const vf_index* ix) { return ix->dtype == VF_DTYPE_FP8_E4M3; }
-// int8 rows of these widths: k_scan_ksplit8i, which is k_scan_ksplit8 with cvt8_i8b at the matrix instruction (the device bytes of an int8
-// index are the biased bytes it converts; geometry, LDS budget and stage cap are the byte-row kernel's).  They are served from 32 768 rows
-// upward and that count is a FLOOR, not only the auto threshold: wide_rows = 2 and force_path = 1 do not go below it either.  32 768 is the
-// smallest row count at which the byte-row kernel has ever been measured (profiles/r10_wide_rows_fp8_threshold.log: it won every cell
-// there), and below it the behaviour of int8 rows is pinned by tests/test_gpu_int8_rows.py::
-// test_int8_chunked_exact_path_and_rows_of_2560_elements (17 000 x 2560: path 2 under wide_rows = 1 and 2, force_path = 1 refused).
-constexpr int64_t kWideRowsMinRowsI8 = 32768;
-static int ksplit_stage_cap(const vf_index* ix) { return byte_rows(ix->dtype) ? scan_ksplit8_stage_cap(ix->dp) : scan_ksplit_stage_cap(ix->dp); }
-static bool ksplit_serves(const vf_index* ix, bool forced) {
-    if (ix->wide_rows == 0 || ksplit_stage_cap(ix) < 256) return false;
-    // int8 rows return BEFORE `forced` and wide_rows = 2 are looked at: for them force_path = 1 and wide_rows = 2 do not reach below the
-    // floor as they do for fp16 and e4m3 rows (kWideRowsMinRowsI8, above: a pinned test and no measurement below it)
-    if (ix->dtype == VF_DTYPE_INT8) return ix->n >= kWideRowsMinRowsI8;
-    return forced || ix->wide_rows == 2 || ix->n >= (rows_e4m3(ix) ? kWideRowsMinRows8 : kWideRowsMinRows);
-}
-
-static bool fused_possible(const vf_index* ix, int k, bool forced = false) {
-    if (ix->n <= 1024 || k > kMaxKFused || k <= 0) return false;
-    // corpora of up to kSmallN rows are built WITHOUT the scan copy and its inverse norms (they never take the fused path on their
-    // own): forcing path 1 on one must be refused, not run on null operands (round 4: found by the option fuzz -- a memory fault)
-    if (!ix->rows_scan || !ix->inv_scan) return false;
-    if (ksplit_width(ix)) return ix->n > kSmallN && ksplit_serves(ix, forced);
-    return true;
-}
-
-static int batch_limit(const vf_index* ix) {
-    // 64 queries need dp * 64 * 2 bytes of LDS; fall back to 32-query passes for wide rows
-    // (k_scan_ksplit's rows: 32 as well)
-    return scan_lds_bytes(ix->dp, kMaxBatch) <= 160 * 1024 ? kMaxBatch : kQueryTile;
-}
-
-// The int8 image's certificate.  The row the scan sees is s code / ||c|| = c / ||c|| + r with ||r|| = rho_row, so its
-// approximate score moves by |q16 . r| <= ||q16|| rho_row <= (1 + 2^-11)(1 + 2^-20) rho_row more than on the fp16 path, and the scan's
-// fp32 sum, whose terms now add up to at most 1 + rho_row, by d 2^-24 rho_row more: off_row (k_prep_image, rounded up).  The scan adds
-// off_row to every score it forms, so canonical <= key + eps holds for every row with the fp16 path's eps (+ 10^-7 for that addition's
-// rounding) -- the certificate k_final tests is the fp16 path's.  What the band must hold: the k-th canonical is ~ the k-th key minus
-// that row's off, so every row whose key is within eps + off of the k-th best key must be re-scored.  The band is eps + 1.5 rho_mean c
-// + 2^-9 (a top-k row up to ~1.75 x the average residual); a query whose rows lie further out fails the certificate and takes the exact
-// path.  Widths in threshold bins (1 / 1024) and fine bins (1 / 16 384), rounded up + one bin.
-static void image_bound(int d, int dtype, float rho_mean, float* eps, int* tau_band, int* fine_band) {
-    const double u16 = 1.0 / 2048.0;
-    const double base = u16 * (dtype == VF_DTYPE_F32 ? 2.0 : 1.0) + sqrt((double)d) * ldexp(1.0, -24) + 2.0 * d * ldexp(1.0, -24) + 1e-6;
-    const float e = (float)(base + 1e-7);
-    const double band = (double)e + 1.5 * rho_mean * (1.0 + u16) * (1.0 + ldexp(1.0, -20)) + ldexp(1.0, -9);
-    *eps = e;
-    *tau_band = (int)ceil(band * (kHistBins / 2)) + 1;
-    *fine_band = (int)ceil(band * (kHistBins / 2) * 16) + 1;
-}
 
 // Test hook (not in the public header; exported by the test build only): the bound and bands above, for tests/test_scan_image_model.py
 extern "C" int vf_debug_image_bound(int32_t d, int32_t dtype, float rho_mean, float* eps, int32_t* tau_band, int32_t* fine_band) {
@@ -918,153 +806,14 @@ extern "C" int vf_debug_image_q8_bound(float rho_q, float eps_img, int32_t tau_b
     return VF_OK;
 }
 
-// Which matrix instruction scans the image (option image_mfma): 1 = v_mfma_i32_32x32x32_i8 on the codes as they are, the
-// queries quantised to one int8 plane whose residual widens each query's certificate bound and band; 0 = the codes converted to fp16
-// 2 = the same on hi + lo planes (the residual quantised again at step / 254: rho_q < 10^-4, the band of 0, twice the instructions of 1)
-static int image_planes(const vf_index* ix, int qt) {   // 0: the fp16 instruction
-    const int m = ix->image_mfma < 0 ? kImageMfmaAuto : (int)ix->image_mfma;
-    return (m >= 1 && scan2r_stage_cap(ix->dp, qt, 2 + m) >= 256) ? m : 0;
-}
-
-// the int8 image serves a fused batch when it exists, k is within kImageMaxK and the scans are k_scan2r's (the options that pick another
-// kernel, the tile pool or k_scan's sample pass keep the rows as stored); wide passes never reach it (wide_pass returns before)
-static bool image_serves(const vf_index* ix, int k, int qt) {
-    return ix->rows_img && k <= kImageMaxK && (ix->scan_impl == 2 || ix->scan_impl == 5) && !ix->steal_opt && ix->sample_impl != 0 &&
-           scan2r_stage_cap(ix->dp, qt, 2) >= 256;
-}
-
-static FusedPlan make_plan(const vf_index* ix, int k, bool image = false) {
-    FusedPlan p;
-    p.image = image; p.tau_band = 0; p.fine_band = 0;
-    // k' = k + margin, rounded up to a multiple of 32 (whole re-score rounds of 32 row groups)
-    int margin = ix->margin >= 0 ? (int)ix->margin : std::max(24, k / 4);
-    // Rows only k_scan_ksplit serves (2560 to 4096 padded elements): the certificate needs the k-th canonical score to clear the k'-th
-    // approximate score by eps, and eps grows with d (2 d 2^-24: 4.9e-4 at d = 4096, beside 2^-11 per fp16 rounding) while the scores of
-    // isotropic rows crowd together like 1 / sqrt(d).  Around rank k such rows lie k z sqrt(d) to the unit of score (z = the normal
-    // quantile of k / n, <= sqrt(2 ln(n / k))), so k + k / 4 leaves a gap of 1.2 to 1.8 eps at d = 3072 .. 4096 and a fifth to a third of
-    // the queries of an N(0, 1) corpus failed the certificate (40 000 rows, k = 100; exact through the repair, at its price).  The margin
-    // is set for an expected gap of 2.5 eps on such rows -- the sum of `margin` spacings scatters by 1 / sqrt(margin) of itself, so 2.5 is
-    // four to five deviations at margin >= 40; real embeddings spread wider and need less.  A speed setting: results do not depend on it.
-    const double u16 = 1.0 / 2048.0;
-    const float eps_plan = (float)(u16 * (ix->dtype == VF_DTYPE_F32 ? 2.0 : 1.0) + sqrt((double)ix->d) * ldexp(1.0, -24) +
-                                   2.0 * ix->d * ldexp(1.0, -24) + 1e-6);
-    if (ix->margin < 0 && ksplit_width(ix)) {
-        const double z = sqrt(2.0 * log(std::max(3.0, (double)ix->n / k)));
-        margin = std::max(margin, (int)ceil(2.5 * eps_plan * k * z * sqrt((double)ix->d)));
-    }
-    p.kprime = ix->margin >= 0 ? k + margin : (k + margin + 31) / 32 * 32;
-    p.kprime = std::min(p.kprime, 4096);  // k_final ranks into a fixed 4096-entry LDS array (k <= kMaxKFused = 2048)
-    int cap = kMaxCap;
-    while (cap < 4 * p.kprime && cap < 16384) cap <<= 1;
-    if (ix->cap_opt > 0) { cap = 1; while (cap < ix->cap_opt) cap <<= 1; cap = std::min(cap, 16384); }
-    while (cap < 2 * p.kprime) cap <<= 1;
-    p.cap = cap;
-    const int64_t scan_cus = ix->n_cu - resolved_aux(ix);
-    int64_t wgs = std::min<int64_t>(scan_cus, std::max<int64_t>(1, ix->n / 512));
-    if (ix->waves_opt > 0) wgs = std::max<int64_t>(1, ix->waves_opt / (kScanThreads / 64));
-    p.grid = (int)wgs;
-    p.total_waves = p.grid * (kScanThreads / 64);
-    // sample rows per wave of the sample pass.  Auto: 16, but 4 for shards of up to 1.1M rows -- there a batch's own chain (k_final of
-    // the slot's previous batch -> host turn-around -> prep -> sample pass -> seed -> main scan; two slots in flight) is longer than
-    // two scans, so a shorter sample pass shortens the step although the looser seed admits 1.7 x the candidates: configs[1]
-    // (1M x 768) 0.304 -> 0.290 ms per batch; from 1.25M rows on the step is the scan's and nothing changes, at 10M the larger
-    // candidate lists cost 1.7 % (profiles/r04_sample_rows_sweep.log)
-    // (only while the sample still holds 16 k' rows: a top-2048 search seeds its threshold from the k'-th best sample score)
-    // Round 6, one box, fresh index per setting (profiles/r06_small_sweep_*.log): 1M rows 4 / 8 / 16 per wave = 0.2965 / 0.2915-0.2951 /
-    // 0.3111 ms per batch, 1.25M rows 0.3559 / 0.3515-0.3534 / 0.3539-0.3550, 1.25M x 1024 0.4447 / 0.4479 / 0.4470: 8 is level with the best
-    // of the other two at every small-shard size, so it is the rule up to 1.5M rows (16 beyond: the scan hides the pass there).
-    p.samp = ix->sample_rows > 0 ? (int)ix->sample_rows : ((ix->n <= 1500000 && 8ll * p.total_waves >= 16ll * p.kprime) ? 8 : 16);
-    // A query's candidate list holds about k' (1 + ln(n / sample rows)) entries -- the k'-th best of a growing prefix moves up like that --
-    // times the lag of the threshold refresh (measured 1.2-1.3 at k = 100 .. 2048).  The 4 k' rule above is short of that for deep
-    // searches over large shards: round 6 found the reference's own call shape, k = 2048 with one to four queries
-    // (src/utils/ensembleRetriever.py:64-66), overflowing its 16384-entry lists from 1M rows up and k = 1000 its 8192 -- correct results
-    // through the exact re-run, at 56-72 ms instead of 2 (5M rows).  The list is sized for 1.6 x the expectation, up to 32768 entries
-    // (what the wide passes use; k_final reads the list from global memory, so its length costs HBM, not LDS).
-    if (ix->cap_opt <= 0) {
-        const double sample_rows = (double)p.total_waves * p.samp;
-        const double expect = p.kprime * (1.0 + log(std::max(1.0, (double)ix->n / std::max(1.0, sample_rows))));
-        while (p.cap < (int)(1.6 * expect) && p.cap < 32768) p.cap <<= 1;
-    }
-    // |approx - canonical| bound (DESIGN.md "Exactness certificate").  fp16 has an 11-bit significand, so
-    // round-to-nearest moves an element by at most 2^-11 of its magnitude: rounding the normalised query moves the
-    // dot product by <= 2^-11 * sum|q_j c_j| <= 2^-11 (Cauchy-Schwarz, both vectors of unit norm); rounding an fp32
-    // corpus row to fp16 adds the same again.  Then the fp16 subnormal floor (2^-25 per element against a unit
-    // vector: sqrt(d) * 2^-24 covers it twice) and the two fp32 dot products (d * 2^-24 each).
-    // (k_scan_ksplit adds a row's dp products per quarter, then across quarters: still one sum of the same terms with dp - 1 additions, and
-    // d 2^-24 times the sum of their magnitudes (<= 1 + 2^-11) bounds the error of ANY order -- tests/test_wide_rows_bound.py)
-    p.eps = eps_plan;
-    if (image) {
-        image_bound(ix->d, ix->dtype, ix->rho_mean, &p.eps, &p.tau_band, &p.fine_band);
-        p.kprime = k;
-        // a list holds ~ (rows in the band) x (1 + ln(n / sample rows)) x the refresh lag -- several thousand per query on ordinary data
-        // (DESIGN.md 4): the largest list the fused path has, 256 KB per query, whatever the `cap` option says (that option sizes the
-        // count-based lists only); its length costs memory, not time (k_final reads what was written)
-        p.cap = 32768;
-    }
-    return p;
-}
-
-static int select_path(const vf_index* ix, int k) {
-    if (ix->force_path >= 0) {
-        if (ix->force_path == 1 && !fused_possible(ix, k, true)) return -1;
-        return (int)ix->force_path;
-    }
-    if (ix->n <= kSmallN) return 0;
-    return fused_possible(ix, k) ? 1 : 2;
-}
-
 // ---- wide passes (k_scan_wide): up to 1024 queries share ONE read of the shard --------------------------------------
-constexpr int kWideMinQueries = 129;   // e4m3 rows: below this the 64-query HBM-bound passes are faster (2 of them at most)
-constexpr int kWideMinQueries16 = 65;  // fp16 (and fp32 -> fp16 scan copy) rows: TWO 64-query passes cost two reads of the shard (5.2 ms at 10M x 768), one wide pass 4.2-4.3 ms (round 4, profiles/r04_wide_threshold.log)
-// rows of 2560 to 4096 padded elements: k_scan_ksplit reads the shard once per 32 queries, k_scan_wide (its query operand streams through
-// LDS in 32-KB chunks, so its LDS does not grow with dp; exact at these widths, checked against the oracle) once per 256 at the matrix
-// rate.  1M x 2560, k = 100, ms per batch, k_scan_ksplit / k_scan_wide: 4 queries 0.974 / 1.559, 32: 0.989 / 1.576, 64 (two passes): 1.739 /
-// 1.483, 128: 3.475 / 1.583; 1M x 4096: 32: 1.545 / 2.452, 64: 2.738 / 2.308, 128: 5.475 / 2.413; at 64 queries k_scan_wide is ahead at
-// every measured row count from 32 768 up and at k = 2048 too (profiles/r08_wide_rows_ab.log, r08_wide_rows_threshold.log).  So the
-// boundary is the second pass: up to 32 queries k_scan_ksplit, from 33 k_scan_wide.
-constexpr int kWideMinQueriesKsplit = 33;
-// The same boundary for e4m3 rows of these widths (profiles/r10_wide_rows_fp8_threshold.log, r10_wide_rows_fp8_ab.log): a pass of
-// k_scan_ksplit8 reads half the bytes of k_scan_ksplit's, k_scan_wide (fp16 instruction on converted rows) runs at the matrix rate as
-// before, so TWO 32-query passes still beat it where the rows are many -- 64 queries, k = 100, ms per batch, k_scan_ksplit8 / k_scan_wide:
-// 262 144 x 2560 0.354 / 0.369, 1M x 2560 0.923 / 1.138, 262 144 x 4096 0.511 / 0.516, 1M x 4096 1.536 / 1.730 (up to 131 072 rows and at
-// k = 2048 the wide pass is ahead at 64 too) -- and three never do: 65 queries 1M x 2560 1.358 / 1.138, 1M x 4096 2.282 / 1.737,
-// 32 768 x 2560 0.327 / 0.195; 96 and 128 queries likewise in every cell.  So the boundary is the third pass: from 65 the wide pass.
-// Paddings it does not take (dp % 256 != 0) stay on 32-query passes of k_scan_ksplit8.
-// int8 rows of these widths (k_scan_ksplit8i) take the same boundary: their wide pass is k_scan_wide<MODE, 2>, the fp16 instruction on
-// converted rows like the kernel the figures above were measured against (k_scan_wide8 is an fp8-instruction kernel and does not apply).
-constexpr int kWideMinQueriesKsplit8 = 65;
-constexpr int kWideMaxQueries = 1024;  // 4 query tiles of 256 per pass: one workgroup per CU
-constexpr int kWideTile = 256;
-
-static bool wide_possible(const vf_index* ix, int nq) {
-    const bool ks = ksplit_width(ix);   // rows only k_scan_ksplit holds an image of (32 queries per pass)
-    if (ix->wide_opt == 0 || nq < (ix->wide_opt > 1 ? (int)ix->wide_opt : ks ? (byte_rows(ix->dtype) ? kWideMinQueriesKsplit8 : kWideMinQueriesKsplit) : (byte_rows(ix->dtype) ? kWideMinQueries : kWideMinQueries16))) return false;
-    // a register stage is 2 k-chunks of fp8 rows / 1 of fp16 rows and a tile alternates two stages
-    return ix->dp % (byte_rows(ix->dtype) ? 256 : 128) == 0;
-}
-
-static int wide_pass(vf_index* ix, Slot& s, const FusedPlan& p0, const float* d_queries, int nb, int k, int64_t* d_ids,
+static int wide_pass(vf_index* ix, Slot& s, const RouteIn& in, const FusedPlan& p0, const float* d_queries, int nb, int k, int64_t* d_ids,
                      float* d_scores, int flag_off, float* qn_b, bool timed, hipStream_t st, int slot_id) {
-    const int qtot = (nb + kWideTile - 1) / kWideTile * kWideTile;
-    const int J = qtot / kWideTile;
-    const int RG = std::max(1, ix->n_cu / J);
+    const WidePass w = route_wide_pass(in, p0, nb);
+    const int qtot = w.qtot, J = w.jtiles, RG = w.rgroups, samp = w.samp;
+    const bool w8 = w.main == kKernelWide8;
     FusedPlan p = p0;
-    if (p.kprime > 256) p.cap = std::max(p.cap, 16384);   // k ~ 1000: ~k' (1 + ln(n / sample)) candidates per query
-    // k_scan_wide8 (the fp8 matrix instruction): e4m3 rows, K-tiles of 64, a row group's bytes within a 32-bit lane offset
-    // Rows of 2560 to 4096 padded elements take it on request only (wide_mfma = 1), auto keeps k_scan_wide: the query's hi + lo split
-    // leaves a bound eps_q that grows with the width while make_plan's margin is sized for the fp16 bound, so on N(0, 1) rows queries
-    // fail the certificate (2 of 64 at 1M x 2560, 25 of 64 at 1M x 4096) and each pays an exact repair of milliseconds over 1M rows -- 64
-    // queries: 9.49 ms per batch against k_scan_wide's 1.12 at 2560, 57.0 against 1.74 at 4096 (the scans themselves: 0.90 against 0.96 ms,
-    // 1.93 against 1.53; profiles/r10_wide_rows_fp8_ab.log).  Exact either way.
-    const bool w8 = (ix->wide_mfma > 0 || (ix->wide_mfma < 0 && !ksplit_width(ix))) && ix->dtype == VF_DTYPE_FP8_E4M3 && ix->dp % 64 == 0 &&
-                    (ix->n / RG + 2 * 256) * (int64_t)ix->dp < (int64_t)0xFFFFFFFFll;
-    if (w8) {
-        // the query's hi + lo split leaves ||delta|| ~ 6e-4 of the query's norm (eps_q ~ 1.1e-3 at dp = 1024 against the fp16 path's
-        // 6.1e-4): the plan's k' = k + k / 4 still clears it on ordinary data (the k -> k' gap is ~2.4e-3); a deeper k' (k + k / 2) was the
-        // first setting and cost 14 % more candidates for nothing (profiles/r04_wide8_kprime.log)
-        if (p.kprime > 256) p.cap = std::max(p.cap, 32768);
-    }
-    const int samp = J >= 2 ? 64 : 32;   // sample rows per row group = samp * 8: 32768 / 65536 rows in all
+    p.cap = w.cap;
     const size_t slen = (size_t)RG * samp * 8;
     VF_TRY(s.qimg.ensure((size_t)ix->dp * qtot * 2));
     VF_TRY(s.s0.ensure((size_t)qtot * slen * sizeof(float)));
@@ -1087,14 +836,14 @@ static int wide_pass(vf_index* ix, Slot& s, const FusedPlan& p0, const float* d_
         VF_TRY(s.epsq.ensure((size_t)qtot * sizeof(float)));
         VF_HIP(launch_prep_wide8(qn_b, nb, ix->d, ix->dp, qtot, (unsigned char*)s.qimg8.p, s.epsq.as<float>(), st));
     }
-    const int f8 = scan_f8(ix->dtype);   // (int8 rows: k_scan_wide converts the biased bytes, exact; the fp8 instruction is for e4m3 codes only)
+    const RowForm f8 = w.rows;
     ScanArgs a{};
     a.rows = (const char*)ix->rows_scan; a.inv_scan = ix->inv_scan; a.qimg = s.qimg.as<_Float16>();
     a.n = ix->n; a.dp = ix->dp; a.row_bytes = (long long)ix->dp * (f8 ? 1 : 2);
     a.total_waves = RG * 8; a.samp = samp;
     a.s0 = s.s0.as<float>(); a.wg_base = s.wgbase.as<long long>(); a.cnt = s.cnt.as<u32>(); a.tau_bin = s.tau.as<int>();
     a.hist = s.hist.as<u32>(); a.hist_coarse = s.hist_coarse.as<u32>(); a.cand = s.cand.as<u64>(); a.cap = p.cap; a.kprime = p.kprime;
-    a.stage_cap = 3584; a.dbg = nullptr; a.debug = (int)ix->debug;   // 56 KB of candidate stage: the LDS the 96 KB of operand buffers and the control block leave
+    a.stage_cap = kWideStageCap; a.dbg = nullptr; a.debug = (int)ix->debug;
     a.refresh_every = 1;   // a power of two on this path (block completion is tested with a mask)
     while (a.refresh_every * 2 <= (int)std::min<int64_t>(256, std::max<int64_t>(1, ix->refresh_every))) a.refresh_every *= 2;
     a.nq = nb; a.qn_total = qtot; a.jtiles = J; a.rgroups = RG;
@@ -1104,8 +853,7 @@ static int wide_pass(vf_index* ix, Slot& s, const FusedPlan& p0, const float* d_
     VF_HIP(launch_sel0(a, qtot, st));
     for (int o = 0; o < kSlots; ++o)
         if (o != slot_id && ix->slots[o].ev_scan) VF_HIP(hipStreamWaitEvent(st, ix->slots[o].ev_scan, 0));
-    const int w8_waves = ix->wide8_waves == 4 ? 4 : 8;
-    const int J8 = w8 && w8_waves == 4 ? (nb + 127) / 128 : J;   // query tiles of the main pass: 128 wide for the two-workgroups-per-CU form
+    const int w8_waves = w.waves, J8 = w.main_jtiles;
     if (J8 > 1 && ix->wide_sync >= 0) {   // sibling progress words of the main pass (see k_scan_wide; eight per row group)
         VF_TRY(s.sib.ensure((size_t)RG * 8 * sizeof(u32)));
         VF_HIP(hipMemsetAsync(s.sib.p, 0, (size_t)RG * 8 * sizeof(u32), st));
@@ -1116,7 +864,7 @@ static int wide_pass(vf_index* ix, Slot& s, const FusedPlan& p0, const float* d_
         ScanArgs a8 = a;
         a8.qimg = (const _Float16*)s.qimg8.p;
         a8.jtiles = J8;
-        a8.stage_cap = ix->wide8_stage > 0 ? (int)std::min<int64_t>(ix->wide8_stage, scan_wide8_stage_cap(w8_waves)) : scan_wide8_stage_cap(w8_waves);
+        a8.stage_cap = w.stage_cap;
         if (ix->debug & 128) {   // per-wave phase times of k_scan_wide8 (vf_index_debug_read)
             VF_TRY(s.dbg.ensure((size_t)8 * J8 * ((RG + 7) / 8) * w8_waves * 16 * sizeof(u64)));
             VF_HIP(hipMemsetAsync(s.dbg.p, 0, s.dbg.bytes, st));
@@ -1141,7 +889,7 @@ static int wide_pass(vf_index* ix, Slot& s, const FusedPlan& p0, const float* d_
     f.dbg = nullptr;
     if (ix->debug & 256) { VF_TRY(s.dbg.ensure((size_t)qtot * 8 * sizeof(u64))); f.dbg = s.dbg.as<u64>(); }
     VF_HIP(launch_final(f, nb, st));
-    s.scan_kernel = w8 ? 4 : 3;
+    s.scan_kernel = w.main;
     return VF_OK;
 }
 
@@ -1149,7 +897,7 @@ static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq,
                       float* d_scores, hipStream_t user) {
     Slot& s = ix->slots[slot_id];
     if (s.pending) return fail(VF_EINVAL, "vf_index_search_begin: slot already has a pending search");
-    const int path = select_path(ix, k);
+    const int path = route_path(route_in(ix), k);
     if (path < 0) return fail(VF_EUNSUPPORTED, "forced fused path is not possible for this n / k / d");
     if (path != 1 && ix->n > kSmallN && k > 8192)  // checked before anything is enqueued (k_merge_topk's LDS sort)
         return fail(VF_EUNSUPPORTED, "exact chunked search supports k <= 8192 when n > 16384");
@@ -1157,7 +905,10 @@ static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq,
     VF_HIP(hipEventRecord(s.ev_in, user));
     VF_HIP(hipStreamWaitEvent(s.stream, s.ev_in, 0));
     hipStream_t st = s.stream;
-    const int bl = batch_limit(ix);
+    // (after ensure_slot: the plan's grid and the sample pass follow the CU split as it was applied to this slot's streams)
+    const RouteIn in = route_in(ix, &s);
+    const SearchRoute r = route_search(in, nq, k);
+    const int bl = r.per_pass;
     VF_TRY(s.qn.ensure((size_t)std::max(nq, 1) * ix->d * sizeof(float)));
     VF_TRY(s.qimg.ensure(scan_lds_bytes(ix->dp, kMaxBatch)));
     VF_TRY(ensure_pinned(s, (size_t)nq));
@@ -1177,18 +928,15 @@ static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq,
         return VF_OK;
     }
 
-    const bool ks = ksplit_width(ix);   // (path 1 on such rows: select_path found that k_scan_ksplit serves them)
-    const bool img = !ks && !wide_possible(ix, nq) && image_serves(ix, k, qn_tile_for(std::min(bl, nq)));
-    FusedPlan p = make_plan(ix, k, img);
-    s.scan_image = img ? 1 : 0;
-    s.image_i8 = img ? image_planes(ix, qn_tile_for(std::min(bl, nq))) : 0;
-    const int img_f8 = 2 + s.image_i8;   // k_scan2r's row type of the image scans
-    if (wide_possible(ix, nq)) {
+    const FusedPlan& p = r.plan;
+    s.scan_image = r.image ? 1 : 0;
+    s.image_i8 = r.planes;
+    if (r.wide) {
         s.timed = ix->profile;
         if (s.timed) VF_HIP(hipEventRecord(s.ev_t[2], st));
-        for (int b0 = 0; b0 < nq; b0 += kWideMaxQueries) {
-            const int nb = std::min(kWideMaxQueries, nq - b0);
-            VF_TRY(wide_pass(ix, s, p, d_queries + (size_t)b0 * ix->d, nb, k, d_ids + (size_t)b0 * k, d_scores + (size_t)b0 * k,
+        for (int b0 = 0; b0 < nq; b0 += bl) {
+            const int nb = std::min(bl, nq - b0);
+            VF_TRY(wide_pass(ix, s, in, p, d_queries + (size_t)b0 * ix->d, nb, k, d_ids + (size_t)b0 * k, d_scores + (size_t)b0 * k,
                              b0, s.qn.as<float>() + (size_t)b0 * ix->d, s.timed && b0 == 0, st, slot_id));
             ++s.wide_launches; s.wide_queries += nb;
         }
@@ -1214,7 +962,8 @@ static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq,
     }
     for (int b0 = 0; b0 < nq; b0 += bl) {
         const int nb = std::min(bl, nq - b0);
-        const int qt = qn_tile_for(nb);
+        const BatchRoute b = route_batch(in, r, nb);
+        const int qt = b.tile;
         float* qn_b = s.qn.as<float>() + (size_t)b0 * ix->d;
         // (the int8 plane replaces the fp16 image: that one is not built)
         VF_HIP(launch_prep_queries(d_queries + (size_t)b0 * ix->d, nb, ix->d, ix->dp, qt, qn_b, s.image_i8 ? nullptr : s.qimg.as<_Float16>(), st));
@@ -1233,7 +982,7 @@ static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq,
         if (p.image) { a.rows = (const char*)ix->rows_img; a.inv_scan = ix->inv_img; a.off_scan = image_offsets(ix); a.row_bytes = ix->dp; }   // every pass of the batch: sample, seed, main
         a.s0 = s.s0.as<float>(); a.wg_base = s.wgbase.as<long long>(); a.cnt = s.cnt.as<u32>(); a.tau_bin = s.tau.as<int>(); a.hist = s.hist.as<u32>();
         a.cand = s.cand.as<u64>(); a.cap = p.cap; a.kprime = p.kprime; a.tau_band = p.tau_band;
-        a.hist_coarse = s.hist_coarse.as<u32>(); a.stage_cap = ks ? ksplit_stage_cap(ix) : scan_stage_cap(ix->dp, qt);
+        a.hist_coarse = s.hist_coarse.as<u32>(); a.stage_cap = b.stage_cap;
         a.tile_cnt = ix->steal_opt ? s.tilecnt.as<u32>() : nullptr; a.scan_grid = p.grid;
         a.dbg = nullptr;
         if (ix->debug & 128) { VF_TRY(s.dbg.ensure((size_t)p.total_waves * ((ix->debug & 512) ? 72 : 4) * sizeof(u64))); a.dbg = s.dbg.as<u64>(); if (ix->debug & 512) VF_HIP(hipMemsetAsync(s.dbg.p, 0, s.dbg.bytes, st)); }
@@ -1250,29 +999,16 @@ static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq,
         // are a NaN, which k_sel0's "v > -inf" test skips.  Never needed once n >= TW * samp.
         if (ix->n / p.total_waves < p.samp)
             VF_HIP(hipMemsetAsync(a.s0, 0xFF, (size_t)qt * p.total_waves * p.samp * sizeof(float), st));
-        // sample pass: a FEW workgroups walk the sample parts of all ranges (each stages the query image once)
-        // (auto: 4 workgroups per spare CU when the CU split is on, one per range otherwise)
-        // Round 6: where k_scan2r's operand path is the default (scan2r_auto_width) the sample pass takes it too -- ONE workgroup per spare
-        // CU, each walking the sample parts of p.grid / 32 ranges with six-segment rings: the pass is bound by what a CU keeps in flight
-        // (k_scan's register-staged loads: 68-71 us for 8 rows per wave in four rounds of 128 workgroups).  sample_impl: -1 auto, 0 k_scan, 1 k_scan2r
-        const bool f8rows = ix->dtype == VF_DTYPE_FP8_E4M3 || p.image;   // (image rows: one byte per element, the e4m3 shapes)
-        // an int8 index off the image route: k_scan's int8 form only (k_scan2 / k_scan2r convert e4m3 codes; their int8 forms are the image's)
-        const bool i8conv = ix->dtype == VF_DTYPE_INT8 && !p.image;
-        // e4m3 rows (768 / 1024 elements) take it wherever k_scan2r is their main scan (n > 1.1M: below), whole chip or split.
-        const bool r_f8_auto = f8rows && ix->scan_impl == 2 && ix->n > kScan2rMinRows && !ix->steal_opt && scan2r_auto_width(ix->dp, true);
-        const bool sample_r = p.image || (!i8conv && ix->sample_impl != 0 && ix->scan_impl != 1 && scan2r_stage_cap(ix->dp, qt, f8rows) >= 256 &&
-                              (ix->sample_impl == 1 || (!f8rows && s.scan_stream != s.stream && scan2r_auto_width(ix->dp, false)) || r_f8_auto));
-        if (ks) {   // one workgroup per range: each loads its share of the image once and scores its range's sample part
-            VF_HIP(byte_rows(ix->dtype) ? launch_scan_ksplit8(a, kModeSample, p.grid, scan_f8(ix->dtype), st) : launch_scan_ksplit(a, kModeSample, p.grid, st));
-        } else if (sample_r) {
-            const int64_t sg_r = ix->sample_grid > 0 ? ix->sample_grid : (s.scan_stream != s.stream ? resolved_aux(ix) : p.grid);
+        switch (b.sample) {
+        case kKernelKsplit: VF_HIP(launch_scan_ksplit(a, kModeSample, b.sample_grid, st)); break;
+        case kKernelKsplit8: VF_HIP(launch_scan_ksplit8(a, kModeSample, b.sample_grid, b.sample_rows, st)); break;
+        case kKernelScan2r: {
             ScanArgs as = a;
             as.stage_cap = 0;
-            VF_HIP(launch_scan2r_sample(as, qt, (int)std::min<int64_t>(std::max<int64_t>(sg_r, 1), p.grid), p.image ? img_f8 : (int)f8rows, st));
-        } else {
-        const int64_t sg_opt = ix->sample_grid >= 0 ? ix->sample_grid : (s.scan_stream != s.stream ? 4 * resolved_aux(ix) : 0);
-        const int sgrid = sg_opt > 0 ? (int)std::min<int64_t>(sg_opt, p.grid) : p.grid;
-        VF_HIP(launch_scan(a, kModeSample, qt, sgrid, (int)ix->scan_g, scan_f8(ix->dtype), st));
+            VF_HIP(launch_scan2r_sample(as, qt, b.sample_grid, b.sample_rows, st));
+            break;
+        }
+        default: VF_HIP(launch_scan(a, kModeSample, qt, b.sample_grid, (int)ix->scan_g, b.sample_rows, st));
         }
         VF_HIP(launch_sel0(a, qt, st));
         hipStream_t sst = s.scan_stream;
@@ -1283,7 +1019,7 @@ static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq,
         // Main scans of different slots run one after the other (a scan workgroup owns its CU); ordering them explicitly
         // keeps queueing time out of the timed bracket.  With overlap_scans they are left to the dispatcher: the next
         // scan's workgroups start on the CUs the previous one has finished with (no idle tail), at the price of that bracket.
-        if (!resolved_overlap(ix))
+        if (!route_overlap(in))
             for (int o = 0; o < kSlots; ++o)
                 if (o != slot_id && ix->slots[o].ev_scan) VF_HIP(hipStreamWaitEvent(sst, ix->slots[o].ev_scan, 0));
         if (s.timed && b0 == 0) {
@@ -1295,48 +1031,12 @@ static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq,
             ix->span_slot[slot_id] = true;
             VF_HIP(hipEventRecord(s.ev_t[0], sst));
         }
-        const int f8 = ix->dtype == VF_DTYPE_FP8_E4M3 ? 1 : 0;
-        // k_scan2 serves fp16 rows by default; e4m3 rows only on request (scan_impl = 3, or 5 for k_scan2r's e4m3 shapes): per byte they
-        // carry twice the matrix work and the same LDS-DMA issues, and with ONE wave per SIMD nothing hides either -- measured 0.53
-        // (k_scan2, round 3) and 0.55-0.60 (k_scan2r, round 6: B fragments in accumulator registers, rings of six) against k_scan's
-        // 0.63-0.70 of peak at 10M x 768 / 1024 fp8 (profiles/r03_f8_sweep.log, r06_fp8_scan2r_ab.log)
-        const int cap2 = i8conv ? 0 : (((ix->scan_impl == 3 || ((ix->scan_impl == 2 || ix->scan_impl == 4 || ix->scan_impl == 5) && !f8)) && !ix->steal_opt) ? scan2_stage_cap(ix->dp, qt, f8) : 0);
-        // k_scan2r (round 6): part of the query image in accumulator registers, deeper rings.  fp16 rows of 768 elements, measured against
-        // k_scan2 in separate processes, alternating (profiles/r06_scan2r_ab.log): the 8-GPU rank's shard (1.25M rows) 0.3469-0.3528 ms
-        // per batch against 0.3538-0.3602 (2.2 % faster: a wave keeps 24 KB in flight instead of 12), 10M rows level (2.538 vs 2.548 --
-        // the scan sits on the copy ceiling there), configs[1] (1M rows) 3 % SLOWER (0.303-0.315 vs 0.293-0.303: that step is the
-        // prologue chain's, and the workgroup's start is 2.3 us longer).  So: auto (scan_impl = 2) takes it above 1.1M rows wherever the
-        // scans run on the CU split and overlap (which, for these rows, is every size: split_limit); 5 forces it, 4 forbids it.
-        // e4m3 rows (round 6, after the filter rewrite): k_scan2r was 0.55-0.60 against k_scan's 0.63-0.70 while a tile's threshold filter
-        // cost a lone wave 4 500 cycles; with the filter at ~1 000 it is 0.694-0.698 against 0.627-0.656 at 10M x 768 and 0.717-0.719
-        // against 0.693-0.700 at 10M x 1024 (whole chip, ordered scans; split + overlap loses 3-5 % there), +2-3 % at 1.25M rows with its
-        // own sample pass, level at 1M: the same row threshold as fp16 rows, no CU-split condition (profiles/r06_after_filter_kernel_choice.log)
-        const bool r_auto = ix->scan_impl == 2 && ix->n > kScan2rMinRows && scan2r_auto_width(ix->dp, f8 != 0) && (f8 || (s.scan_stream != s.stream && resolved_overlap(ix)));   // (fp16 rows: with the CU split and overlapping scans only: above)
-#ifdef VF_EXPERIMENTS
-        const bool dbg_r = f8 || !(ix->debug & (32 | 64));   // (bits 5 / 6 are k_scan2's experiments on fp16 rows, k_scan2r's on e4m3 rows)
-#else
-        const bool dbg_r = true;
-#endif
-        const int capr = ((ix->scan_impl == 5 || r_auto) && !ix->steal_opt && dbg_r && !i8conv) ? scan2r_stage_cap(ix->dp, qt, f8) : 0;
-        if (ks && byte_rows(ix->dtype)) {   // e4m3 codes: k_scan_ksplit8; int8 rows: k_scan_ksplit8i, reported as 7 too (as k_scan's and k_scan_wide's int8 forms report 1 and 3)
-            VF_HIP(launch_scan_ksplit8(a, kModeMain, p.grid, scan_f8(ix->dtype), sst));
-            s.scan_kernel = 7;
-        } else if (ks) {
-            VF_HIP(launch_scan_ksplit(a, kModeMain, p.grid, sst));
-            s.scan_kernel = 6;
-        } else if (p.image) {   // the int8 row image (image_serves: k_scan2r's e4m3 shapes, stage >= 256)
+        switch (b.main) {
+        case kKernelKsplit8: VF_HIP(launch_scan_ksplit8(a, kModeMain, p.grid, b.main_rows, sst)); break;
+        case kKernelKsplit: VF_HIP(launch_scan_ksplit(a, kModeMain, p.grid, sst)); break;
+        case kKernelScan2r: VF_HIP(launch_scan2r(a, qt, p.grid, b.main_rows, sst)); break;
+        case kKernelScan2: {
             ScanArgs a2 = a;
-            a2.stage_cap = scan2r_stage_cap(ix->dp, qt, img_f8);
-            VF_HIP(launch_scan2r(a2, qt, p.grid, img_f8, sst));
-            s.scan_kernel = 5;
-        } else if (capr >= 256) {
-            ScanArgs a2 = a;
-            a2.stage_cap = capr;
-            VF_HIP(launch_scan2r(a2, qt, p.grid, f8, sst));
-            s.scan_kernel = 5;
-        } else if (cap2 >= 256) {   // whole-line LDS-DMA loads: image + four rings + a stage of >= 256 entries fit the 160 KB
-            ScanArgs a2 = a;
-            a2.stage_cap = cap2;
 #ifdef VF_EXPERIMENTS
             if (ix->debug & 32) {   // timing experiment: compute unit -> range table (k_scan2, debug bit 5)
                 const bool fresh = s.sib.bytes < 4096;
@@ -1345,12 +1045,12 @@ static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq,
                 a2.sib = s.sib.as<u32>();
             }
 #endif
-            VF_HIP(launch_scan2(a2, qt, p.grid, f8, sst));
-            s.scan_kernel = 2;
-        } else {
-            VF_HIP(launch_scan(a, kModeMain, qt, p.grid, (int)ix->scan_g, scan_f8(ix->dtype), sst));
-            s.scan_kernel = 1;
+            VF_HIP(launch_scan2(a2, qt, p.grid, b.main_rows, sst));
+            break;
         }
+        default: VF_HIP(launch_scan(a, kModeMain, qt, p.grid, (int)ix->scan_g, b.main_rows, sst));
+        }
+        s.scan_kernel = b.main;
         VF_HIP(hipEventRecord(s.ev_scan, sst));
         if (s.timed && b0 == 0) {
             VF_HIP(hipEventRecord(s.ev_t[1], sst));
@@ -1386,8 +1086,9 @@ static int end_impl(vf_index* ix, int slot_id) {
     VF_HIP(hipEventSynchronize(s.ev_done));
     vf_search_stats stt{};
     stt.path = s.path; stt.n_queries = s.nq; stt.wide_launches = s.wide_launches; stt.wide_queries = s.wide_queries;
-    stt.aux_cus = (s.path == 1 && s.scan_stream && s.scan_stream != s.stream) ? resolved_aux(ix) : 0;
-    stt.scans_overlap = (s.path == 1 && resolved_overlap(ix)) ? 1 : 0;
+    const SplitReport split = route_split_report(route_in(ix, &s), s.path);
+    stt.aux_cus = split.aux_cus;
+    stt.scans_overlap = split.scans_overlap;
     stt.scan_kernel = s.scan_kernel;
     stt.scan_image = (s.path == 1) ? s.scan_image : 0;
     if (s.path == 1 && s.nq > 0 && s.k > 0) {

@@ -9,7 +9,7 @@
 
 #include <string>
 
-#include "vf_ksplit_geom.h"
+#include "vf_ksplit_geom.h"   // + vf_scan_lds.h: the design constants, RowForm and every scan kernel's LDS budget
 
 namespace vf {
 
@@ -55,17 +55,6 @@ __device__ __forceinline__ void bitonic_sort_desc(u64* s, int n, int tid, int nt
         }
     }
 }
-
-// ---- fixed design constants ------------------------------------------------------
-constexpr int kQueryTile = 32;        // queries per MFMA N-tile (v_mfma_f32_32x32x16_f16)
-constexpr int kMaxBatch = 64;         // queries per scan pass (2 N-tiles); larger nq loops
-constexpr int kRowTile = 32;          // corpus rows per MFMA M-tile
-constexpr int kScanThreads = 512;     // 8 waves per workgroup, one workgroup per CU
-constexpr int kHistBins = 2048;       // threshold histogram over cosine in [-1, 1]
-constexpr int kSmallN = 16384;        // <= this many rows: exact dense path (LDS sort)
-constexpr int kMaxCap = 8192;         // candidate slots per query in the fused path (u64 each)
-constexpr int kCntStride = 32;        // u32 elements between per-query counters: one 128-B line each
-constexpr int kMaxKFused = 2048;      // largest k the fused path serves (k' <= 4096 <= cap/2)
 
 enum ScanMode { kModeSample = 0, kModeMain = 1 };
 
@@ -167,8 +156,9 @@ hipError_t launch_dense_dot16(const float* qn, int nq, const float* cn, long lon
 hipError_t launch_sort_rows(const float* scores, long long score_stride, int nq, int n, int k,
                             long long id_base, long long* out_ids, float* out_scores, int out_stride,
                             hipStream_t s);
+// The RowForm a launcher takes says how its kernel reads a row (vf_scan_lds.h); each names the forms it is built for.
 hipError_t launch_scan(const ScanArgs& a, int mode, int qn_tile, int grid, int want_g /*0 = auto*/,
-                       int f8 /* 0 fp16 rows, 1 e4m3 bytes, 2 the biased bytes of an int8 index */, hipStream_t s);
+                       RowForm rows /* kRowsF16, kRowsE4m3, kRowsI8 */, hipStream_t s);
 // two's-complement int8 rows -> the biased bytes (code + 128) an int8 index holds; in place when in == out
 hipError_t launch_rebias_i8(const void* in, void* out, long long bytes, hipStream_t s);
 // test hook: the scan's hardware e4m3 -> fp16 conversion over `count` codes (device pointers)
@@ -176,30 +166,21 @@ hipError_t launch_debug_cvt_e4m3(const unsigned char* in, float* out, int count,
 // test hook: one v_mfma_i32_32x32x32_i8 over A [32][32], B [32][32] int8 -> C [32][32] = A B^T with k_scan2r's operand map (device pointers)
 hipError_t launch_debug_mfma_i8(const signed char* A, const signed char* B, int* C, hipStream_t s);
 // k_scan2: the main scan with whole-line LDS-DMA corpus loads (fp16 or e4m3 rows); a.stage_cap = scan2_stage_cap(...) >= 256
-hipError_t launch_scan2(const ScanArgs& a, int qn_tile, int grid, int rows_are_fp8, hipStream_t s);
-size_t scan2_lds_bytes(int dp, int qn_tile, int stage_cap);
-int scan2_stage_cap(int dp, int qn_tile, int rows_are_fp8);
+hipError_t launch_scan2(const ScanArgs& a, int qn_tile, int grid, RowForm rows /* kRowsF16, kRowsE4m3 */, hipStream_t s);
 // k_scan2r: k_scan2 with part of the query image in registers and deeper rings (fp16 rows of 768 elements, e4m3 rows of 768 / 1024); scan2r_stage_cap < 256 = not this kernel
-size_t scan2r_lds_bytes(int dp, int qn_tile, int stage_cap, int f8);
-int scan2r_stage_cap(int dp, int qn_tile, int f8);
-hipError_t launch_scan2r(const ScanArgs& a, int qn_tile, int grid, int f8, hipStream_t s);
-hipError_t launch_scan2r_sample(const ScanArgs& a, int qn_tile, int grid, int f8, hipStream_t s);
+// (+ the int8 row image in its three forms: kRowsI8, kRowsI8Mfma1, kRowsI8Mfma2)
+hipError_t launch_scan2r(const ScanArgs& a, int qn_tile, int grid, RowForm rows, hipStream_t s);
+hipError_t launch_scan2r_sample(const ScanArgs& a, int qn_tile, int grid, RowForm rows, hipStream_t s);
 // k_scan_ksplit: the fused scan of fp16 rows with 2560 <= dp <= 4096 (32 queries; the contraction split over the workgroup's four waves,
 // the query image in registers + LDS); scan_ksplit_stage_cap = 0: not this kernel
 hipError_t launch_scan_ksplit(const ScanArgs& a, int mode, int grid, hipStream_t s);
-size_t scan_ksplit_lds_bytes(int dp, int stage_cap);
-int scan_ksplit_stage_cap(int dp);
-// k_scan_ksplit8: the same for e4m3 rows (a.row_bytes = dp; segments of 128 bytes, 5 to 8 per wave); scan_ksplit8_stage_cap = 0: not this kernel
-// rows_f8: 1 e4m3 codes (k_scan_ksplit8), 2 the biased bytes of an int8 index (k_scan_ksplit8i: the same kernel on cvt8_i8b)
-hipError_t launch_scan_ksplit8(const ScanArgs& a, int mode, int grid, int rows_f8, hipStream_t s);
-size_t scan_ksplit8_lds_bytes(int dp, int stage_cap);
-int scan_ksplit8_stage_cap(int dp);
-hipError_t launch_scan_wide(const ScanArgs& a, int mode, int f8 /* as launch_scan's */, hipStream_t s);
-size_t scan_wide_lds_bytes(int stage_cap);
+// k_scan_ksplit8: the same for e4m3 rows (a.row_bytes = dp; segments of 128 bytes, 5 to 8 per wave); ks8_stage_cap = 0: not this kernel
+// rows: kRowsE4m3 (k_scan_ksplit8) or kRowsI8, the biased bytes of an int8 index (k_scan_ksplit8i: the same kernel on cvt8_i8b)
+hipError_t launch_scan_ksplit8(const ScanArgs& a, int mode, int grid, RowForm rows, hipStream_t s);
+hipError_t launch_scan_wide(const ScanArgs& a, int mode, RowForm rows /* as launch_scan's */, hipStream_t s);
 // k_scan_wide8: the wide main scan on the fp8 matrix instruction (e4m3 rows; a.qimg = the hi / lo code image of launch_prep_wide8)
 hipError_t launch_prep_wide8(const float* qn, int nq, int d, int dp, int qtot, unsigned char* img8, float* eps_q, hipStream_t s);
 hipError_t launch_scan_wide8(const ScanArgs& a, int waves /* 8: 256-query tiles, one workgroup per CU; 4: 128-query tiles, two per CU */, hipStream_t s);
-int scan_wide8_stage_cap(int waves);
 int scan_wide8_occupancy(int waves, int stage_cap);
 // The int8 query plane of the image scan on the int8 matrix instruction (k_scan2r, F8 = 3): codes in the B-operand order
 // [dp / 16][qn_tile][16], the code step s_q, and per query what its own quantisation residual rho_q = ||qn - s_q code|| (fp64, rounded
@@ -207,7 +188,6 @@ int scan_wide8_occupancy(int waves, int stage_cap);
 // band_q: [2][qn_tile] ints -- threshold bins, then k_final's fine bins.
 hipError_t launch_prep_q8(const float* qn, int nq, int d, int dp, int qn_tile, int planes /* 1, or 2: hi + lo, [dp / 16][2][qn_tile][16] */, signed char* img8, float* q_scale, float* eps_q, int* band_q,
                           float eps_img, int tau_band, int fine_band, hipStream_t s);
-// k_scan2<NT, 2>: the narrow main scan on the fp8 matrix instruction (launch_scan2 with rows_are_fp8 = 2; a.qimg = this image)
 hipError_t launch_sel0(const ScanArgs& a, int qn_tile, hipStream_t s);
 hipError_t launch_final(FinalArgs a, int nq, hipStream_t s);
 hipError_t launch_merge_topk(const long long* ids_parts, const float* score_parts, int nparts, int nq,
@@ -219,8 +199,6 @@ hipError_t launch_fuse_rank(const float* a, const float* b, int n, float* out, l
 // bytes of one packed per-shard result [ids nq*k int64][scores nq*k fp32], padded to 16 so that every part of an
 // all-gathered buffer keeps its int64 ids 8-byte aligned (nq*k odd would otherwise put part 1 on a 4-byte boundary)
 inline long long packed_part_bytes(int nq, int k) { return ((long long)nq * k * 12 + 15) / 16 * 16; }
-size_t scan_lds_bytes(int dp, int qn_tile);
-int scan_stage_cap(int dp, int qn_tile);
 hipError_t scan_configure();   // sets max dynamic LDS on the scan kernels (once per process/device)
 
 }  // namespace vf

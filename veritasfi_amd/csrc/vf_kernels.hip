@@ -872,13 +872,7 @@ __device__ __forceinline__ int wave_tau_two_level(const u32* coarse_q, const u32
     return L * 32 + (63 - __clzll((long long)ok));
 }
 
-// ---- LDS control block of k_scan (right after the query image) ---------------------------------
-//   +0   u32 stage_cnt     candidates staged by this workgroup (main mode)
-//   +4   u32 next_tile     next unclaimed tile of the workgroup's row range
-//   +16  int tau_lds[64]   the workgroup's copy of the per-query threshold bins
-//   +272 uint4 entries[stage_cap]
-constexpr int kCtlBytes = 272;
-
+// (the LDS control block of k_scan, right after the query image: kCtlBytes, vf_scan_lds.h)
 template <int NT>
 __device__ __forceinline__ constexpr int QN_of() { return NT * kQueryTile; }
 
@@ -1547,7 +1541,6 @@ __global__ __launch_bounds__(kKsThreads) void k_scan_ksplit(ScanArgs a) {
 // k_scan_ksplit's.  The certificate needs no new term: the row side is exact, the query side is the fp16 rounding already in eps, and
 // the sum is one fp32 sum of the same dp products (make_plan).  Geometry: the ks8_* functions of vf_ksplit_geom.h.
 // ------------------------------------------------------------------------------------------------
-static_assert(kKs8CtlBytes == kCtlBytes, "vf_ksplit_geom.h budgets the control block the scans use");
 
 // k_scan's flush for the four-wave kernels: rank the staged entries per query, one returning atomic per non-empty query, write
 __device__ __forceinline__ void ks_flush(const ScanArgs& a, char* ctl, char* red, int tid) {
@@ -1736,7 +1729,7 @@ __global__ __launch_bounds__(kKsThreads) void k_scan_ksplit8i(ScanArgs a) {
 #define VF_SCAN2_SERVICE 0   // 1: a fifth wave publishes the staged blocks (measured 8 % SLOWER, round 3: DESIGN.md, k_scan2) -- A/B builds only
 #endif
 constexpr bool kScan2Service = VF_SCAN2_SERVICE != 0;
-constexpr int kScan2Waves = 4, kScan2Threads = (kScan2Waves + (kScan2Service ? 1 : 0)) * 64, kRing = 3, kSegBytes = 4096, kScratchBytes = 1024;   // four streaming waves + the service wave; scratch: two 512-B halves (tile parity)
+constexpr int kScan2Threads = (kScan2Waves + (kScan2Service ? 1 : 0)) * 64;   // four streaming waves + the service wave (rings, scratch and their LDS budget: vf_scan_lds.h)
 
 __device__ __forceinline__ void dma16(const void* g, unsigned lds_base) {
     unsigned keep;
@@ -1771,18 +1764,6 @@ __device__ __forceinline__ void dma16x4(unsigned long long ua, unsigned v0, unsi
 }
 __device__ __forceinline__ unsigned lds_addr(const void* p) {
     return (unsigned)(size_t)(__attribute__((address_space(3))) const char*)p;
-}
-
-size_t scan2_lds_bytes(int dp, int qn_tile, int stage_cap) {
-    const size_t img = (size_t)dp * qn_tile * 2;
-    return img + (size_t)kScan2Waves * (kRing * kSegBytes + kScratchBytes) + kCtlBytes + (size_t)stage_cap * 16;
-}
-int scan2_stage_cap(int dp, int qn_tile, int rows_are_fp8) {   // candidate-stage entries that fit beside image + rings; < 256 = "does not fit"
-    const size_t fixed = scan2_lds_bytes(dp, qn_tile, 0);
-    if ((dp >> (rows_are_fp8 ? 7 : 6)) < kRing) return 0;  // the ring holds three 128-byte segments of ONE row set at start-up
-    if (fixed + 256 * 16 > 160 * 1024) return 0;
-    const size_t area = std::min<size_t>(160 * 1024 - fixed, 32 * 1024);
-    return (int)(area / 16);
 }
 
 // The SERVICE wave of k_scan2 (wave 4; it shares SIMD 0 with streaming wave 0).  Round 3 measured where a small shard's launch
@@ -2133,42 +2114,7 @@ __global__ __launch_bounds__(kScan2Threads) void k_scan2(ScanArgs a) {
 // The register half is fetched with ordinary loads BEFORE anything else and settled with the s_waitcnt BUILTIN (which the compiler's
 // own wait insertion accounts for): no vector-memory load with a register destination is pending while tiles run (k_attention2's rule).
 // ------------------------------------------------------------------------------------------------
-// The shapes it is built for -- (row bytes per 128-byte segment count S, register segments RB, ring depth RING):
-//   fp16 rows, dp =  768: S = 12, RB = 6 (192 registers of B fragments at 64 queries), RING = 6
-//   fp16 rows, dp = 1024: S = 16, RB = 6, RING = 4 (80 KB of image in LDS: k_scan2 has no room for this width at all)
-//   fp16 rows, dp =  512: S =  8, RB = 4, RING = 6;   dp = 384: S = 6, RB = 3, RING = 6
-//   e4m3 rows, dp =  768: S =  6, RB = 3 (a segment is 128 elements: 16 KB of image, 64 registers), RING = 6
-//   e4m3 rows, dp = 1024: S =  8, RB = 3 (with the 32 accumulators the 256 accumulator registers hold no fourth), RING = 4
-// (e4m3 rows are converted in registers like k_scan2's F8 variant: every e4m3 value is an fp16 value, the image is shared.)
-// F8 = 2: the int8 row image of fp16 / fp32 rows of 768 elements (k_prep_image) -- one byte per element like e4m3 rows, so the e4m3
-// shape; the bytes are converted by cvt8_i8b (exact), the row's scale rides in its inverse norm and its quantisation bound is added to
-// every score (ScanArgs::off_scan).
-struct Scan2rShape { int S, RB, RING; };
-static Scan2rShape scan2r_shape(int dp, int f8) {
-    if (!f8 && dp == 768) return {12, 6, 6};
-    if (!f8 && dp == 1024) return {16, 6, 4};   // (bge-m3 / bge-large rows: the reference's own width, config/example.yaml:3)
-    if (!f8 && dp == 512) return {8, 4, 6};
-    if (!f8 && dp == 384) return {6, 3, 6};
-    if (f8 == 3) return dp == 768 ? Scan2rShape{6, 6, 6} : Scan2rShape{0, 0, 0};   // one int8 query plane: every B fragment in registers
-    if (f8 == 4) return dp == 768 ? Scan2rShape{6, 3, 6} : Scan2rShape{0, 0, 0};   // hi + lo planes: half in registers, half in LDS, as the fp16 image
-    if (f8 && dp == 768) return {6, 3, 6};
-    if (f8 && dp == 1024) return {8, 3, 4};
-    return {0, 0, 0};
-}
-
-size_t scan2r_lds_bytes(int dp, int qn_tile, int stage_cap, int f8) {
-    const Scan2rShape sh = scan2r_shape(dp, f8);
-    const size_t seg_img = (size_t)(f8 ? 128 : 64) * qn_tile * 2;
-    return (size_t)(sh.S - sh.RB) * seg_img + (size_t)kScan2Waves * (sh.RING * kSegBytes + kScratchBytes) + kCtlBytes + (size_t)stage_cap * 16;
-}
-int scan2r_stage_cap(int dp, int qn_tile, int f8) {   // < 256 = "not this kernel"
-    if (scan2r_shape(dp, f8).S == 0) return 0;
-    const size_t fixed = scan2r_lds_bytes(dp, qn_tile, 0, f8);
-    if (fixed + 256 * 16 > 160 * 1024) return 0;
-    const size_t area = std::min<size_t>(160 * 1024 - fixed, 32 * 1024);
-    return (int)(area / 16);
-}
-
+// The shapes it is built for and what they take of the LDS: scan2r_shape, scan2r_lds_bytes, scan2r_stage_cap (vf_scan_lds.h).
 // AR = 1 (the shipped form): the register part of the image is PINNED to the accumulator half of the register file -- an empty asm with a
 // "+a" operand per fragment, after which the fragment IS an accumulator-register value and the matrix instruction names it as its B
 // operand directly (v_mfma ... v[6:9], a[32:35], ...) -- and every LDS read of a segment is issued before its first matrix instruction.
@@ -2603,13 +2549,11 @@ __global__ __launch_bounds__(kScan2Waves * 64) void k_scan2r(ScanArgs a) {
 // different query tiles have equal b % 8 (one XCD under round-robin placement: their row reads share that L2;
 // speed only) and are adjacent in dispatch order.
 // ------------------------------------------------------------------------------------------------
-constexpr int kWideQ = 256, kWideNT = kWideQ / kQueryTile, kWideKC = 64, kWideRows = 256;
+constexpr int kWideNT = kWideQ / kQueryTile, kWideRows = 256;   // (kWideQ, kWideKC, the query chunk buffers and the control block: vf_scan_lds.h)
 #ifndef VF_WIDE_THREADS
 #define VF_WIDE_THREADS 512
 #endif
 constexpr int kWideThreads = VF_WIDE_THREADS, kWideWaves = kWideThreads / 64, kWideM = kWideRows / kWideWaves / kRowTile;   // row tiles per wave: 1 (8 waves) or 2 (4 waves)
-constexpr int kWideBuf = (kWideKC / 8) * kWideQ * 16;   // 32 KB per query chunk
-constexpr int kWideCtl = 16 + 3 * kWideQ * 4;            // stage_cnt | tau_lds[256] | qcnt[256] | qbase[256]
 constexpr int kSampWaves = kScanThreads / 64;            // sample rows per row group = samp * 8 (k_sel0's slot map)
 
 // One register stage of corpus data = DC consecutive 64-element chunks of this lane's two rows: fp8 rows 2 chunks
@@ -3110,7 +3054,6 @@ __global__ __launch_bounds__(kWideThreads) void k_scan_wide(ScanArgs a) {
 #undef VF_ISSUE_B
 }
 
-size_t scan_wide_lds_bytes(int stage_cap);
 // ------------------------------------------------------------------------------------------------
 // k_scan_wide8: the wide scan on the instruction BASELINE configs[4] names -- v_mfma_scale_f32_32x32x64_f8f6f4 -- for e4m3 rows.
 //
@@ -3704,12 +3647,6 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? 2 : 1) void k_scan_wide8(S
 #undef VF8_STEP
 #undef VF8_ACC_OPS
 
-// waves = 8: a.jtiles 256-query tiles, one 512-thread workgroup per CU; waves = 4: a.jtiles 128-query tiles, two 256-thread workgroups per CU
-size_t scan_wide8_lds_bytes(int waves, int stage_cap) {
-    return waves == 8 ? scan_wide_lds_bytes(stage_cap) : (size_t)65536 + (16 + 3 * 128 * 4) + (size_t)stage_cap * 16;
-}
-int scan_wide8_stage_cap(int waves) { return waves == 8 ? 3584 : 896; }   // what the operand stages and the control block leave of 160 / 80 KB
-
 // resident workgroups per CU of the wide8 kernel with that many candidate-stage entries (hipOccupancyMaxActiveBlocksPerMultiprocessor)
 int scan_wide8_occupancy(int waves, int stage_cap) {
     int n = -1;
@@ -3737,11 +3674,7 @@ hipError_t launch_scan_wide8(const ScanArgs& a, int waves, hipStream_t s) {
     return hipGetLastError();
 }
 
-size_t scan_wide_lds_bytes(int stage_cap) {
-    return (size_t)3 * kWideBuf + kWideCtl + (size_t)stage_cap * 16;
-}
-
-hipError_t launch_scan_wide(const ScanArgs& a, int mode, int f8 /* 0 fp16 rows, 1 e4m3 bytes, 2 int8 bytes (biased) */, hipStream_t s) {
+hipError_t launch_scan_wide(const ScanArgs& a, int mode, RowForm f8 /* kRowsF16, kRowsE4m3 or kRowsI8 */, hipStream_t s) {
     const int grid = 8 * a.jtiles * ((a.rgroups + 7) / 8);
     const size_t lds = scan_wide_lds_bytes(mode == kModeMain ? a.stage_cap : 0);
 #define VF_WCASE(MODEV, F8V) \
@@ -3749,15 +3682,6 @@ hipError_t launch_scan_wide(const ScanArgs& a, int mode, int f8 /* 0 fp16 rows, 
     VF_WCASE(kModeSample, 0) VF_WCASE(kModeSample, 1) VF_WCASE(kModeMain, 0) VF_WCASE(kModeMain, 1) VF_WCASE(kModeSample, 2) VF_WCASE(kModeMain, 2)
 #undef VF_WCASE
     return hipErrorInvalidValue;
-}
-
-// dynamic LDS of k_scan: query image + (main mode) candidate stage
-size_t scan_lds_bytes(int dp, int qn_tile) { return (size_t)dp * qn_tile * 2 + kCtlBytes; }
-int scan_stage_cap(int dp, int qn_tile) {
-    const size_t used = scan_lds_bytes(dp, qn_tile);
-    const size_t freeb = used < 160 * 1024 ? 160 * 1024 - used : 0;
-    const size_t area = freeb < 32 * 1024 ? freeb : 32 * 1024;
-    return (int)(area / 16);
 }
 
 template <int NT, int G, int MODE, int F8>
@@ -3790,8 +3714,8 @@ static int pick_G(int dp, int want, int mode, int f8) {
     return 1;  // segs even => always ok
 }
 
-// f8: 0 fp16 rows, 1 e4m3 bytes, 2 the biased bytes of an int8 index (the e4m3 geometry: a row is dp bytes either way)
-hipError_t launch_scan(const ScanArgs& a, int mode, int qn_tile, int grid, int want_g, int f8, hipStream_t s) {
+// f8: kRowsF16, kRowsE4m3 or kRowsI8, the biased bytes of an int8 index (the e4m3 geometry: a row is dp bytes either way)
+hipError_t launch_scan(const ScanArgs& a, int mode, int qn_tile, int grid, int want_g, RowForm f8, hipStream_t s) {
     const int G = pick_G(a.dp, want_g, mode, f8);
     const int NT = qn_tile / kQueryTile;
 #define VF_CASE(NTV, GV, MODEV)                                                                         \
@@ -3805,18 +3729,8 @@ hipError_t launch_scan(const ScanArgs& a, int mode, int qn_tile, int grid, int w
     return hipErrorInvalidValue;
 }
 
-// k_scan_ksplit: LDS = the image segments the registers do not hold + the reduction area + control block + (main mode) candidate stage
+// k_scan_ksplit (its LDS budget: scan_ksplit_lds_bytes, vf_ksplit_geom.h)
 #define VF_KSPLIT_SHAPES(X) X(10, 10) X(11, 11) X(12, 6) X(13, 13) X(14, 7) X(15, 5) X(16, 8)   // (segments per wave P, ring depth ks_D(P))
-size_t scan_ksplit_lds_bytes(int dp, int stage_cap) {
-    const int xs = ks_P(ks_segs(dp)) - kKsRegSegs;
-    return (size_t)kKsWaves * (xs > 0 ? xs : 0) * kKsSegBytes + kKsRedBytes + kCtlBytes + (size_t)stage_cap * 16;
-}
-int scan_ksplit_stage_cap(int dp) {
-    if (!ks_serves(dp)) return 0;
-    const size_t used = scan_ksplit_lds_bytes(dp, 0);
-    const size_t freeb = used < 160 * 1024 ? 160 * 1024 - used : 0;
-    return (int)((freeb < 32 * 1024 ? freeb : 32 * 1024) / 16);
-}
 // mode kModeSample: `grid` = a.scan_grid workgroups, one per range (each scores its range's sample part); kModeMain: a.stage_cap = scan_ksplit_stage_cap
 hipError_t launch_scan_ksplit(const ScanArgs& a, int mode, int grid, hipStream_t s) {
     if (!ks_serves(a.dp) || a.row_bytes != (long long)a.dp * 2 || (mode == kModeSample && grid != a.scan_grid)) return hipErrorInvalidValue;
@@ -3834,19 +3748,17 @@ hipError_t launch_scan_ksplit(const ScanArgs& a, int mode, int grid, hipStream_t
 
 // k_scan_ksplit8 (e4m3 rows of the same widths): segments of 128 bytes, 5 to 8 per wave; the LDS budget is vf_ksplit_geom.h's
 #define VF_KSPLIT8_SHAPES(X) X(5) X(6) X(7) X(8)   // segments per wave P8
-size_t scan_ksplit8_lds_bytes(int dp, int stage_cap) { return (size_t)ks8_lds_bytes(dp, stage_cap); }
-int scan_ksplit8_stage_cap(int dp) { return ks8_stage_cap(dp); }
-// mode kModeSample: `grid` = a.scan_grid workgroups, one per range; kModeMain: a.stage_cap = scan_ksplit8_stage_cap; a.row_bytes = a.dp
-// rows_f8 as in launch_scan: 1 e4m3 codes (k_scan_ksplit8), 2 the biased bytes of an int8 index (k_scan_ksplit8i)
-hipError_t launch_scan_ksplit8(const ScanArgs& a, int mode, int grid, int rows_f8, hipStream_t s) {
+// mode kModeSample: `grid` = a.scan_grid workgroups, one per range; kModeMain: a.stage_cap = ks8_stage_cap; a.row_bytes = a.dp
+// rows: kRowsE4m3 (k_scan_ksplit8) or kRowsI8, the biased bytes of an int8 index (k_scan_ksplit8i)
+hipError_t launch_scan_ksplit8(const ScanArgs& a, int mode, int grid, RowForm rows, hipStream_t s) {
     if (!ks_serves(a.dp) || a.row_bytes != (long long)a.dp || (mode == kModeSample && grid != a.scan_grid)) return hipErrorInvalidValue;
     if (mode == kModeMain && (a.stage_cap < 256 || a.stage_cap > ks8_stage_cap(a.dp))) return hipErrorInvalidValue;
-    if (rows_f8 != 1 && rows_f8 != 2) return hipErrorInvalidValue;
+    if (rows != kRowsE4m3 && rows != kRowsI8) return hipErrorInvalidValue;
     const int P = ks8_P(ks8_segs(a.dp));
-    const size_t lds = scan_ksplit8_lds_bytes(a.dp, mode == kModeMain ? a.stage_cap : 0);
+    const size_t lds = (size_t)ks8_lds_bytes(a.dp, mode == kModeMain ? a.stage_cap : 0);
 #define VF_X(P_) \
     if (P == P_) { \
-        if (rows_f8 == 2) { \
+        if (rows == kRowsI8) { \
             if (mode == kModeMain) hipLaunchKernelGGL((k_scan_ksplit8i<kModeMain, P_>), dim3(grid), dim3(kKsThreads), lds, s, a); \
             else hipLaunchKernelGGL((k_scan_ksplit8i<kModeSample, P_>), dim3(grid), dim3(kKsThreads), lds, s, a); \
         } else { \
@@ -3859,7 +3771,8 @@ hipError_t launch_scan_ksplit8(const ScanArgs& a, int mode, int grid, int rows_f
     return hipErrorInvalidValue;
 }
 
-hipError_t launch_scan2(const ScanArgs& a, int qn_tile, int grid, int rows_are_fp8, hipStream_t s) {
+hipError_t launch_scan2(const ScanArgs& a, int qn_tile, int grid, RowForm rows /* kRowsF16 or kRowsE4m3 */, hipStream_t s) {
+    const bool rows_are_fp8 = rows != kRowsF16;
     const size_t lds = scan2_lds_bytes(a.dp, qn_tile, a.stage_cap);
     if (qn_tile == kQueryTile) {
         if (rows_are_fp8) hipLaunchKernelGGL((k_scan2<1, 1>), dim3(grid), dim3(kScan2Threads), lds, s, a);
@@ -3880,7 +3793,7 @@ hipError_t launch_scan2(const ScanArgs& a, int qn_tile, int grid, int rows_are_f
 #define VF_SCAN2R_SHAPES(X, NT, MODE) VF_SCAN2R_PRODUCT(X, NT, MODE)
 #endif
 #define VF_SCAN2R_ALL(X) VF_SCAN2R_SHAPES(X, 1, kModeMain) VF_SCAN2R_SHAPES(X, 2, kModeMain) VF_SCAN2R_SHAPES(X, 1, kModeSample) VF_SCAN2R_SHAPES(X, 2, kModeSample)
-static hipError_t launch_scan2r_any(const ScanArgs& a, int qn_tile, int mode, int grid, int f8, size_t lds, hipStream_t s) {
+static hipError_t launch_scan2r_any(const ScanArgs& a, int qn_tile, int mode, int grid, RowForm f8, size_t lds, hipStream_t s) {
     Scan2rShape sh = scan2r_shape(a.dp, f8);
 #ifdef VF_EXPERIMENTS
     if (f8 == 1 && a.dp == 768 && (a.debug & 2048)) sh.RING = 4;   // timing experiment: is the scan bound by what a wave keeps in flight?  (LDS sized for six: harmless)
@@ -3895,11 +3808,11 @@ static hipError_t launch_scan2r_any(const ScanArgs& a, int qn_tile, int mode, in
 #undef VF_X
     return done ? hipGetLastError() : hipErrorInvalidValue;
 }
-hipError_t launch_scan2r(const ScanArgs& a, int qn_tile, int grid, int f8, hipStream_t s) {
+hipError_t launch_scan2r(const ScanArgs& a, int qn_tile, int grid, RowForm f8, hipStream_t s) {
     return launch_scan2r_any(a, qn_tile, kModeMain, grid, f8, scan2r_lds_bytes(a.dp, qn_tile, a.stage_cap, f8), s);
 }
 // the sample pass on k_scan2r's operand path: `grid` workgroups walk the sample parts of a.scan_grid ranges (a.samp rows per wave of k_scan's geometry)
-hipError_t launch_scan2r_sample(const ScanArgs& a, int qn_tile, int grid, int f8, hipStream_t s) {
+hipError_t launch_scan2r_sample(const ScanArgs& a, int qn_tile, int grid, RowForm f8, hipStream_t s) {
     return launch_scan2r_any(a, qn_tile, kModeSample, grid, f8, scan2r_lds_bytes(a.dp, qn_tile, 0, f8), s);
 }
 

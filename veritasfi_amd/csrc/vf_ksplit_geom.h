@@ -1,13 +1,10 @@
 // vf_ksplit_geom.h -- the address geometry of k_scan_ksplit (rows of 2560 to 4096 padded elements), as plain functions the kernel, its
 // launcher and a host-compiled test (tests/test_wide_rows_geometry.py: UBSan, every (n, grid, sample rows, wave, tile, lane)) share.
+// The LDS budgets of the two kernels follow their geometry (the constants they share with the other scans: vf_scan_lds.h).
 // No HIP header: the host compiler reads it as it stands.
 #pragma once
 
-#if defined(__HIPCC__)
-#define VF_HD __host__ __device__ __forceinline__
-#else
-#define VF_HD inline
-#endif
+#include "vf_scan_lds.h"   // VF_HD, kCtlBytes, stage_entries
 
 namespace vf {
 
@@ -61,6 +58,13 @@ VF_HD long long ks_inv_index(long long t0, long long n, int r31) {
     const long long i = t0 + r31;
     return i < n + 63 ? (i < 0 ? 0 : i) : n + 63;
 }
+// LDS of k_scan_ksplit: the image segments the registers do not hold + the reduction area + control block + (main mode) candidate stage
+VF_HD size_t scan_ksplit_lds_bytes(int dp, int stage_cap) {
+    const int xs = ks_P(ks_segs(dp)) - kKsRegSegs;
+    return (size_t)kKsWaves * (xs > 0 ? xs : 0) * kKsSegBytes + kKsRedBytes + kCtlBytes + (size_t)stage_cap * 16;
+}
+// candidate-stage entries that fit beside them; 0 = not this kernel
+VF_HD int scan_ksplit_stage_cap(int dp) { return ks_serves(dp) ? stage_entries(scan_ksplit_lds_bytes(dp, 0)) : 0; }
 
 // ---- k_scan_ksplit8: the same rows stored as e4m3 bytes (tests/test_wide_rows_fp8_geometry.py walks these) ------------------------------
 // A row is dp bytes; a segment is 128 BYTES = 128 elements = eight matrix steps, so a row has dp / 128 segments (20 to 32), a wave 5 to 8.
@@ -69,7 +73,7 @@ VF_HD long long ks_inv_index(long long t0, long long n, int r31) {
 constexpr int kKs8RegSegs = 5;      // query segments (128 elements x 32 queries = 32 registers per lane) a wave keeps in registers: 160
 constexpr int kKs8MaxSegs = 8;      // segments per wave at dp = 4096; the ring holds the wave's whole share of a tile (16 registers each)
 constexpr int kKs8SegBytes = 8192;  // one 128-element segment of a 32-query image: 16 k-groups x 32 queries x 16 bytes
-constexpr int kKs8CtlBytes = 272;   // the scans' control block (kCtlBytes; vf_kernels.hip asserts they agree)
+constexpr int kKs8CtlBytes = kCtlBytes;   // the scans' control block, under the name tests/test_wide_rows_fp8_geometry.py knows it by
 
 VF_HD int ks8_segs(int dp) { return dp >> 7; }
 // wave w owns segments [ks8_seg_begin(S8, w), ks8_seg_begin(S8, w + 1)) of S8: 5 to 8 of them, counts differ by at most one
@@ -84,14 +88,11 @@ VF_HD int ks8_step_half(int i) { return i & 1; }
 // LDS: [4 waves][P8 - 5] image segments + the reduction area + the control block + (main mode) the candidate stage
 VF_HD long long ks8_lds_bytes(int dp, int stage_cap) {
     const int xs = ks8_P(ks8_segs(dp)) - kKs8RegSegs;
-    return (long long)kKsWaves * (xs > 0 ? xs : 0) * kKs8SegBytes + kKsRedBytes + kKs8CtlBytes + (long long)stage_cap * 16;
+    return (long long)kKsWaves * (xs > 0 ? xs : 0) * kKs8SegBytes + kKsRedBytes + kCtlBytes + (long long)stage_cap * 16;
 }
 // candidate-stage entries that fit beside them in 160 KB (at most 32 KB of them); < 256 = not this kernel
 VF_HD int ks8_stage_cap(int dp) {
-    if (!ks_serves(dp)) return 0;
-    const long long used = ks8_lds_bytes(dp, 0);
-    const long long freeb = used < 160 * 1024 ? 160 * 1024 - used : 0;
-    return (int)((freeb < 32 * 1024 ? freeb : 32 * 1024) / 16);
+    return ks_serves(dp) ? stage_entries((size_t)ks8_lds_bytes(dp, 0)) : 0;
 }
 
 }  // namespace vf
