@@ -87,12 +87,12 @@ static int eval_lines() {
         const Routed o = route(c);
         const bool fused = o.r.path == 1, narrow = fused && !o.r.wide && o.passes > 0;
         std::printf("path=%d wide=%d per_pass=%d passes=%d scan_image=%d planes=%d aux_cus=%d scans_overlap=%d scan_kernel=%d wide_launches=%d "
-                    "wide_queries=%d tile=%d sample=%d sample_grid=%d sample_rows=%d main_rows=%d stage_cap=%d kprime=%d cap=%d grid=%d samp=%d\n",
+                    "wide_queries=%d tile=%d sample=%d sample_grid=%d sample_rows=%d main_rows=%d stage_cap=%d kprime=%d cap=%d grid=%d samp=%d total_waves=%d\n",
                     o.r.path, (int)o.r.wide, o.r.per_pass, o.passes, fused && o.r.image ? 1 : 0, o.r.planes, o.split.aux_cus, o.split.scans_overlap,
                     o.scan_kernel, o.wide_launches, o.wide_queries, narrow ? o.first.tile : 0, narrow ? (int)o.first.sample : 0,
                     narrow ? o.first.sample_grid : 0, narrow ? (int)o.first.sample_rows : -1,
                     narrow ? (int)o.last.main_rows : (fused && o.passes ? (int)o.wlast.rows : -1), narrow ? o.last.stage_cap : (fused && o.passes ? o.wlast.stage_cap : 0),
-                    fused ? o.r.plan.kprime : 0, fused ? (o.r.wide && o.passes ? o.wlast.cap : o.r.plan.cap) : 0, fused ? o.r.plan.grid : 0, fused ? o.r.plan.samp : 0);
+                    fused ? o.r.plan.kprime : 0, fused ? (o.r.wide && o.passes ? o.wlast.cap : o.r.plan.cap) : 0, fused ? o.r.plan.grid : 0, fused ? o.r.plan.samp : 0, fused ? o.r.plan.total_waves : 0);
     }
     return 0;
 }

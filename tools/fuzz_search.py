@@ -5,39 +5,76 @@ of dim for the fp8 instruction, k around the row count, sample rows 4 / 16), one
 (all on device 0: the merge and the id offsets), every result compared bit for bit (ids and score bits) with
 oracle.canonical.  Test infrastructure: the oracle is the checker, never the thing measured.
 
-    python tools/fuzz_search.py --seconds 240 --seed 1 [--max-work 2e10]
+    python tools/fuzz_search.py --seconds 240 --seed 1 [--max-work 2e10] [--profile scan2r|wide_rows|int8]
 
-Prints one line per case that FAILS (with the arguments to reproduce it) and a summary; exit code 1 on any failure."""
+Profiles narrow the draw to one family of kernels (draw_case); without one the draw is the general one, and its random stream is
+pinned by tests/test_fuzz_profiles.py.  Prints one line per case that FAILS (with the arguments to reproduce it) and a summary; exit code 1 on any failure."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np
 
 
-def draw_case(rng, max_work):
+PROFILES = ("scan2r", "wide_rows", "int8")
+
+
+def env_profile():
+    """The profile the environment asks for (VF_FUZZ_SCAN2R=1, VF_FUZZ_WIDE_ROWS=1), or None."""
+    if os.environ.get("VF_FUZZ_SCAN2R") == "1":
+        return "scan2r"
+    if os.environ.get("VF_FUZZ_WIDE_ROWS") == "1":
+        return "wide_rows"
+    return None
+
+
+def draw_case(rng, max_work, profile=None):
+    """One random case.  profile: None (the environment's, else the general draw), or one of PROFILES.  The general draw consumes the
+    random stream exactly as it always has (tests/test_fuzz_profiles.py holds it to a recorded fixture): the suite's fixed-seed fuzz
+    keeps its cases.  A profile overrides what it is about AFTER the common draws."""
+    if profile is None:
+        profile = env_profile()
+    assert profile is None or profile in PROFILES, profile
     pick = lambda xs: xs[int(rng.integers(len(xs)))]
     dtype = pick(["f32", "f16", "f16", "fp8", "fp8"])
     d = pick([1, 7, 16, 33, 64, 100, 128, 200, 256, 384, 512, 768, 768, 1000, 1024, 1024, 1536, 2048, int(rng.integers(1, 2049))])
     nq = pick([1, 1, 2, 3, 8, 31, 63, 64, 65, 66, 100, 127, 128, 129, 130, 200, 256, 257, 300, int(rng.integers(1, 400))])
     n_edges = [1, 2, 15, 255, 256, 257, 1000, 16383, 16384, 16385, 16640, 20000, 32768, 40000, 65536, 70001, 131072, 200000, 300000]
     n = pick(n_edges + [int(np.exp(rng.uniform(0, np.log(400000))))] * 6)
-    while float(n) * nq * d > max_work and n > 17000:
-        n = max(17000, n // 2)
-    while float(n) * nq * d > max_work and nq > 1:
-        nq = max(1, nq // 2)
+
+    def fit(n, nq, d, keep_n=False):   # the oracle's cost under max_work: rows first (down to a fused-path size), then queries
+        while not keep_n and float(n) * nq * d > max_work and n > 17000:
+            n = max(17000, n // 2)
+        while float(n) * nq * d > max_work and nq > 1:
+            nq = max(1, nq // 2)
+        return n, nq
+    n, nq = fit(n, nq, d)
     k = pick([1, 2, 10, 100, 100, 128, 500, 1000, 1000, 2048, n, n + 3, max(1, n - 1), int(rng.integers(1, 2049))])
     k = max(1, min(k, 2048))
     data = pick(["normal", "normal", "dupes", "clusters", "scaled", "zeros", "sorted", "lowrank"])
     opts = {}
-    if os.environ.get("VF_FUZZ_SCAN2R") == "1":   # soak of round 6's kernels: k_scan2r for the scan and for the sample pass -- fp16 rows of 384 / 512 / 768 / 1024 (1000 pads to it), e4m3 rows of 768 / 1024
+    if profile == "scan2r":   # soak of round 6's kernels: k_scan2r for the scan and for the sample pass -- fp16 rows of 384 / 512 / 768 / 1024 (1000 pads to it), e4m3 rows of 768 / 1024
         dtype = pick(["f16", "f16", "f32", "fp8", "fp8"])
         d = pick([768, 768, 1024, 512, 384, 1000]) if dtype != "fp8" else pick([768, 1024])
         opts["scan_impl"] = 5
         opts["sample_impl"] = 1
-    elif os.environ.get("VF_FUZZ_WIDE_ROWS") == "1":   # soak of the four-wave kernels for rows of 2560 to 4096 padded elements: k_scan_ksplit (fp16 / fp32 rows), k_scan_ksplit8 (e4m3 rows), the wide pass behind them
-        dtype = pick(["f16", "f32", "fp8", "fp8", "fp8"])
+    elif profile == "wide_rows":   # soak of the four-wave kernels for rows of 2560 to 4096 padded elements: k_scan_ksplit (fp16 / fp32 rows), k_scan_ksplit8 (e4m3 rows), k_scan_ksplit8i (int8 rows), the wide pass behind them
+        dtype = pick(["f16", "f32", "fp8", "fp8", "fp8", "int8", "int8"])
         d = pick([2560, 2688, 3000, 3072, 3968, 4096, int(rng.integers(2433, 4097))])
         opts["wide_rows"] = 2
+        if dtype == "int8":   # int8 rows of these widths are served from 32 768 rows up, whatever the option says: both sides of that floor
+            n = pick([20000, 32767, 32768, 32769, 33000, 40000])
+        n, nq = fit(n, nq, d, keep_n=dtype == "int8")
+    elif profile == "int8":   # an int8 index on every route: small, the conversion route (k_scan's int8 form), the int8 matrix instruction on the index's own bytes (k_scan2r, d = 768, k <= 128), the wide pass, chunked exact
+        dtype = "int8"
+        d = pick([1, 7, 100, 128, 768, 768, 768, 1000, 1024, 1536, 2048, 2432])
+        n, nq = fit(n, nq, d)
+        k = max(1, min(pick([1, 2, 10, 64, 100, 100, 127, 128, 128, 129, 500, 2048, n, int(rng.integers(1, 2049))]), 2048))   # mostly <= 128: the image route's limit
+        data = pick(["normal", "normal", "dupes", "clusters", "scaled", "zeros", "sorted", "lowrank", "raw", "raw"])
+        opts["scan_image"] = pick([0, 1, 2, 2])
+        opts["image_mfma"] = pick([-1, 0, 1, 2])
+        if rng.random() < 0.3:
+            opts["scan_impl"] = pick([1, 2, 3, 4, 5])
+            opts["sample_impl"] = pick([-1, 0, 1])
     elif rng.random() < 0.3:
         opts["scan_impl"] = pick([1, 2, 3, 4, 5])
         opts["sample_impl"] = pick([-1, 0, 1])
@@ -78,6 +115,13 @@ def make_data(case):
         r = min(3, d)
         basis = rng.standard_normal((r, d)).astype(np.float32)
         c = (rng.standard_normal((n, r)).astype(np.float32) @ basis).astype(np.float32)
+    if case["dtype"] == "int8":               # the codes ARE the corpus: the oracle scores their integer values as fp32
+        if data == "raw":                     # every one of the 256 values, -128 included (quantize_int8 never writes it)
+            codes = rng.integers(-128, 128, size=(n, d), dtype=np.int8)
+        else:
+            import veritasfi_amd as vf
+            codes = vf.quantize_int8(c)
+        return codes, codes.astype(np.float32), q
     if case["dtype"] == "fp8":
         import torch
         from oracle import ref_numpy as R
@@ -91,6 +135,12 @@ def make_data(case):
     return None, c, q
 
 
+def make_index(vf, case, codes, rows, dev_ids=None):
+    if case["dtype"] == "int8":
+        return vf.DenseIndex.from_int8(codes, device_ids=dev_ids)
+    return vf.DenseIndex.from_e4m3(codes, device_ids=dev_ids) if codes is not None else vf.DenseIndex(rows, device_ids=dev_ids)
+
+
 def run_case(vf, oracle, case, repeat=1):
     codes, rows, q = make_data(case)
     if case["data"] == "sorted":            # score-sorted corpus (ascending for query 0): thresholds rise all the way through
@@ -100,7 +150,7 @@ def run_case(vf, oracle, case, repeat=1):
         if codes is not None:
             codes = np.ascontiguousarray(codes[order])
     dev_ids = [0] * case.get("shards", 1) if case.get("shards", 1) > 1 else None
-    ix = vf.DenseIndex.from_e4m3(codes, device_ids=dev_ids) if codes is not None else vf.DenseIndex(rows, device_ids=dev_ids)
+    ix = make_index(vf, case, codes, rows, dev_ids)
     try:
         for key, val in case["opts"].items():
             try:
@@ -138,6 +188,7 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--max-work", type=float, default=2e10, help="cap on rows x queries x dim per case (the oracle's cost)")
     ap.add_argument("--case", default=None, help="JSON of one case to re-run")
+    ap.add_argument("--profile", default=None, choices=PROFILES, help="narrow the draw to one family of kernels (default: VF_FUZZ_SCAN2R / VF_FUZZ_WIDE_ROWS, else the general draw)")
     ap.add_argument("--repeat", type=int, default=1, help="searches per case on the same index (all compared with the oracle)")
     a = ap.parse_args()
     import veritasfi_amd as vf
@@ -155,13 +206,13 @@ def main():
     n_cases = n_fail = 0
     paths = {}
     while time.time() - t0 < a.seconds:
-        case = draw_case(rng, a.max_work)
+        case = draw_case(rng, a.max_work, a.profile)
         try:
             ok, st, why = run_case(vf, canonical, case, a.repeat)
         except Exception as e:   # noqa: BLE001 -- a fuzz driver reports everything
             ok, st, why = False, {}, {"exception": repr(e)}
         n_cases += 1
-        key = (st.get("path"), st.get("scan_kernel"), case["dtype"])
+        key = (st.get("path"), st.get("scan_kernel"), st.get("scan_image"), case["dtype"])
         if case.get("shards", 1) > 1:
             paths[("sharded handle",)] = paths.get(("sharded handle",), 0) + 1
         paths[key] = paths.get(key, 0) + 1
@@ -173,7 +224,7 @@ def main():
         if n_cases % 25 == 0:
             print(f"... {n_cases} cases, {n_fail} failures, {time.time() - t0:.0f} s", flush=True)
     print(json.dumps({"cases": n_cases, "failures": n_fail, "seconds": round(time.time() - t0, 1), "seed": a.seed,
-                      "by_path_kernel_dtype": {str(k): v for k, v in sorted(paths.items(), key=str)}}))
+                      "by_path_kernel_image_dtype": {str(k): v for k, v in sorted(paths.items(), key=str)}}))
     return 1 if n_fail else 0
 
 

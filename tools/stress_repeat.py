@@ -23,6 +23,12 @@ CASES = [
     ("narrow fp16 rows, 64 queries: k_scan2r for the scan and the sample pass (round 6)", dict(dtype="f16", d=768, nq=64, n=200000, k=100, data="normal", seed=18), {"scan_impl": 5, "sample_impl": 1}),
     ("narrow fp16 rows, 20 queries, clustered data: k_scan2r<1>", dict(dtype="f16", d=768, nq=20, n=150000, k=1000, data="clusters", seed=19), {"scan_impl": 5, "sample_impl": 1}),
     ("narrow fp32 rows (fp16 scan copy), 64 queries, duplicates: k_scan2r", dict(dtype="f32", d=768, nq=64, n=100000, k=100, data="dupes", seed=20), {"scan_impl": 5, "sample_impl": 1}),
+    # rounds 7 to 12: the int8 image route on an int8 index's own bytes (k_scan2r on the int8 matrix instruction), the conversion route, k_scan_ksplit
+    ("int8 rows, 64 queries: the int8 matrix instruction, one query plane (k_scan2r, image route)", dict(dtype="int8", d=768, nq=64, n=120000, k=100, data="normal", seed=21), {"scan_image": 2, "image_mfma": 1}),
+    ("int8 rows, same, hi + lo query planes", dict(dtype="int8", d=768, nq=64, n=120000, k=100, data="normal", seed=21), {"scan_image": 2, "image_mfma": 2}),
+    ("int8 rows, same, converted in registers (k_scan's int8 form)", dict(dtype="int8", d=768, nq=64, n=120000, k=100, data="normal", seed=21), {"scan_image": 0}),
+    ("int8 rows, 64 queries, duplicates: the image route", dict(dtype="int8", d=768, nq=64, n=120000, k=100, data="dupes", seed=22), {"scan_image": 2, "image_mfma": 1}),
+    ("fp16 rows of 2560 elements, 32 queries (k_scan_ksplit)", dict(dtype="f16", d=2560, nq=32, n=40000, k=100, data="normal", seed=23), {"wide_rows": 2}),
 ]
 
 
@@ -41,7 +47,7 @@ def main():
         codes, rows, q = fz.make_data(case)
         oi, os_ = canonical.search(rows, q, case["k"])
         dev_ids = [0] * case.get("shards", 1) if case.get("shards", 1) > 1 else None
-        ix = vf.DenseIndex.from_e4m3(codes, device_ids=dev_ids) if codes is not None else vf.DenseIndex(rows, device_ids=dev_ids)
+        ix = fz.make_index(vf, case, codes, rows, dev_ids)
         for key, val in opts.items():
             ix.set_option(key, val)
         bad = 0
@@ -52,7 +58,7 @@ def main():
         st = ix.stats()
         ix.close()
         total_bad += bad
-        print(json.dumps({"what": what, "runs": a.runs, "failures": bad, "scan_kernel": st.get("scan_kernel"), "path": st.get("path"),
+        print(json.dumps({"what": what, "runs": a.runs, "failures": bad, "scan_kernel": st.get("scan_kernel"), "scan_image": st.get("scan_image"), "path": st.get("path"),
                           "exact_reruns": st.get("exact_reruns")}), flush=True)
     return 1 if total_bad else 0
 
