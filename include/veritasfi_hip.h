@@ -40,6 +40,7 @@ enum {
 };
 
 enum { VF_DTYPE_F32 = 0, VF_DTYPE_F16 = 1, VF_DTYPE_FP8_E4M3 = 2, VF_DTYPE_INT8 = 3 };
+#define VF_INDEX_APPEND 0x100   /* or'ed into `dtype` of vf_index_create / vf_index_create_device: append to the handle in *out (below) */
 
 typedef struct vf_index vf_index;
 
@@ -90,6 +91,26 @@ int vf_index_create(vf_index** out, const void* rows, int64_t n, int32_t d, int3
  * they are copied (re-biased on the way), the index keeps no reference to d_rows and the caller may free it at once. */
 int vf_index_create_device(vf_index** out, const void* d_rows, int64_t n, int32_t d, int32_t dtype,
                            int32_t device_id, int64_t id_offset);
+
+/* ---- appending rows to a live index (IndexFlatIP.add, src/utils/faissRetriever.py:18-24; the ingest loop of src/load_data.py:98-128) ----
+ * Both entry points above append when `dtype` carries VF_INDEX_APPEND: *out must hold a live handle on entry and holds the same handle
+ * on return, whatever the result.  `rows` (host for vf_index_create, device memory of `device_id` for vf_index_create_device) are
+ * [n, d] of dtype & 0xFF; d and that dtype must be the handle's, device_id the handle's device (a group's home device); id_offset
+ * is ignored.  Row i of the call gets id = the handle's id_offset + its row count before the call + i; n == 0 succeeds and does
+ * nothing.  Without the flag nothing changes (dtype 4 and above, 0x100 | 4 too, stay "unknown dtype").
+ * Only the new rows are prepared (one kernel over them), so a call costs what its rows cost, whatever the index holds -- except when
+ * the row arrays are full (they grow by half, device to device, the old ones freed after the new are complete: option "reserve_rows"
+ * avoids it) and when the row count crosses a point at which a fresh build differs (16 384 rows: the scan copy replaces the cache of
+ * normalised rows; the int8 row image's threshold).  Afterwards the handle is what vf_index_create over all the rows would have built:
+ * same search paths, same kernels, same results.  An index that borrows the caller's device rows takes its own copy on the first
+ * append (the caller's memory is never written and may be freed from then on).
+ * VF_EINVAL "search pending" while any slot is between _begin and _end; VF_EUNSUPPORTED beyond 2^32-2 rows in a shard; on every
+ * failure (VF_ENOMEM, VF_EHIP included) the handle is unchanged and still searchable.  Argument errors are reported before any HIP call.
+ * A group handle (vf_index_create_sharded, vf_index_group) puts the rows into its LAST shard, so ids stay one contiguous range and
+ * vf_index_shards is unchanged; that shard grows while the others do not, and nothing re-balances them: a group that is mostly
+ * appended rows searches at the speed of its last shard.
+ * vf_index_set_option(idx, "reserve_rows", total) makes room for `total` rows now (a borrowed index takes its copy now), so that
+ * appends up to that count move nothing; a value at or below the row count does nothing, 2^32-1 and above per shard is VF_EUNSUPPORTED. */
 
 /* ---- ONE handle over several devices (single-process serving) -------------------------------------------------
  * The reference serves from one process (RAGManager singleton, src/utils/ragManager.py:17-30; it builds

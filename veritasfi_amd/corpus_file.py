@@ -23,36 +23,85 @@ _NP = {v: k for k, v in _DT.items()}
 
 
 class CorpusWriter:
-    """Append row batches, then close (writes the header last so that a partial file never validates)."""
+    """Append row batches, then close (writes the header last so that a partial file never validates).
 
-    def __init__(self, path: str, d: int, dtype=np.float16, e4m3: bool = False):
-        self.path, self.d, self.n = path, int(d), 0
-        self.dtype = np.dtype(np.uint8) if e4m3 else np.dtype(dtype)
+    ``mode="a"`` extends a file that exists (``d`` and ``dtype`` default to the header's and must equal it when given; every batch
+    carries ids exactly when the file has an id table): what a live index was given through ``DenseIndex.add`` is written here, so
+    a restart that loads the file sees the same rows.  The new rows are written first, then the id table, then the header: a
+    file WITHOUT an id table is valid at every instant (the header names the old row count until ``close``, and the old rows
+    are never touched).  A file WITH one keeps its table behind the rows, so the new rows overwrite it: between the first ``append``
+    and ``close`` the header still validates but the table it points to is gone -- ``abort`` (and leaving the ``with`` block on an
+    error) puts the old table back; an append cut short by a crash does not, so keep the ids elsewhere until ``close`` returns."""
+
+    def __init__(self, path: str, d: int = None, dtype=None, e4m3: bool = False, mode: str = "w"):
+        if mode not in ("w", "a"):
+            raise ValueError("mode must be 'w' or 'a'")
+        self.path, self.mode = path, mode
+        self._ids = []
+        self._want_ids = None   # None: the first batch decides ("w"); True / False: what the file holds ("a")
+        if mode == "a":
+            h = read_header(path)
+            held = _NP[h["dtype"]]
+            want = None if (dtype is None and not e4m3) else (np.dtype(np.uint8) if e4m3 else np.dtype(dtype))
+            if d is not None and int(d) != h["d"]:
+                raise ValueError(f"{path} holds rows of {h['d']} elements, not {int(d)}")
+            if want is not None and want != held:
+                raise ValueError(f"{path} holds {held} rows, not {want}")
+            self.d, self.n, self.dtype = int(h["d"]), int(h["n"]), held
+            self._n0, self._want_ids = self.n, bool(h["has_ids"])
+            self._size0 = _HDR.size + self.n * self.d * held.itemsize + (8 * self.n if h["has_ids"] else 0)
+            if os.path.getsize(path) < self._size0:
+                raise ValueError(f"{path} is truncated")
+            self._old_ids = np.array(external_ids(path)) if h["has_ids"] else None
+            if self._old_ids is not None:
+                self._ids.append(self._old_ids)
+            self._f = open(path, "r+b")
+            self._f.seek(_HDR.size + self.n * self.d * held.itemsize)   # behind the last row: onto the id table, if there is one
+            return
+        if d is None:
+            raise ValueError("d is required for a new corpus file")
+        self.d, self.n = int(d), 0
+        self.dtype = np.dtype(np.uint8) if e4m3 else np.dtype(np.float16 if dtype is None else dtype)
         if self.dtype not in _DT:
             raise TypeError(f"unsupported corpus dtype {self.dtype}")
-        self._ids = []
         self._f = open(path, "wb")
         self._f.write(b"\0" * _HDR.size)
 
     def append(self, rows, ids=None) -> None:
         # (one-byte codes -- e4m3 bytes, int8 rows -- are taken as they are or refused below, never cast: a cast would wrap them)
+        # (an extended file takes rows of its own type only: its older rows were written from that type, and so is a live index's copy)
+        if self.mode == "a" and np.asarray(rows).dtype != self.dtype:
+            raise ValueError(f"batch must be [m, {self.d}] of {self.dtype}")
         rows = np.ascontiguousarray(np.asarray(rows), dtype=self.dtype) if self.dtype.itemsize > 1 else np.ascontiguousarray(rows)
         if rows.dtype != self.dtype or rows.ndim != 2 or rows.shape[1] != self.d:
             raise ValueError(f"batch must be [m, {self.d}] of {self.dtype}")
+        if self._want_ids is not None and (ids is not None) != self._want_ids:
+            raise ValueError("the file has an id table: every batch must carry ids" if self._want_ids else
+                             "the file has no id table: no batch may carry ids")
         if (ids is None) != (not self._ids) and self.n:
             raise ValueError("either every batch carries ids or none does")
-        self._f.write(rows.tobytes())
         if ids is not None:
             ids = np.asarray(ids, dtype=np.int64)
             if ids.shape != (rows.shape[0],):
                 raise ValueError("ids must be one int64 per row")
+        self._f.write(rows.tobytes())
+        if ids is not None:
             self._ids.append(ids)
         self.n += rows.shape[0]
 
     def abort(self) -> None:
-        """Leave on an error: the header is NOT written (the file keeps its zeroed first 64 bytes, which no reader
-        accepts) and the partial file is removed."""
+        """Leave on an error.  A new file: the header is NOT written (the file keeps its zeroed first 64 bytes, which no reader
+        accepts) and the partial file is removed.  An extended file: it is put back as it was -- the old id table rewritten behind
+        the old rows, the new rows cut off; its header was never touched."""
         if self._f is None:
+            return
+        if self.mode == "a":
+            self._f.seek(_HDR.size + self._n0 * self.d * self.dtype.itemsize)
+            if self._old_ids is not None:
+                self._f.write(self._old_ids.tobytes())
+            self._f.truncate(self._size0)
+            self._f.close()
+            self._f = None
             return
         self._f.close()
         self._f = None
@@ -66,6 +115,7 @@ class CorpusWriter:
             return
         if self._ids:
             self._f.write(np.concatenate(self._ids).tobytes())
+        self._f.flush()   # rows and id table are in the file before the header names them
         self._f.seek(0)
         self._f.write(_HDR.pack(MAGIC, 1, _DT[self.dtype], self.n, self.d, 1 if self._ids else 0))
         self._f.close()
@@ -85,6 +135,15 @@ def write(path: str, rows, ids=None, e4m3: bool = False) -> None:
     rows = np.asarray(rows)
     with CorpusWriter(path, rows.shape[1], rows.dtype, e4m3=e4m3) as w:
         w.append(rows, ids)
+
+
+def append(path: str, rows, ids=None) -> int:
+    """Extend the corpus file at ``path`` by ``rows`` (and their ``ids``, when the file has an id table); returns the row number of
+    the first one.  See ``CorpusWriter`` (mode "a") for what an interrupted call leaves behind."""
+    with CorpusWriter(path, mode="a") as w:
+        first = w.n
+        w.append(rows, ids)
+    return first
 
 
 def info(path: str) -> dict:

@@ -157,6 +157,8 @@ struct GroupSlot {
 struct vf_index {
     int device = 0;
     int64_t n = 0;
+    int64_t cap = 0;            // rows every row-side array below has room for (>= n; == n until "reserve_rows" or an append grows them).  Arrays the
+                                // handle does not own (borrowed rows, rows scanned in place) have room for n only: an append takes an owned copy first
     int d = 0, dp = 0, dtype = 0;  // dtype: how rows are HELD in HBM (VF_DTYPE_F32 / _F16 / _FP8_E4M3 / _INT8: biased bytes, code + 128)
     int64_t id_offset = 0;
     int n_cu = 256;
@@ -165,15 +167,17 @@ struct vf_index {
     void* rows_orig = nullptr;        // as given (fp32 or fp16), [n][d]
     void* rows_scan = nullptr;    // fp16 [n][dp]; may alias rows_orig
     bool owns_scan = false;
-    float* norm = nullptr;            // canonical norms [n]
-    float* inv_scan = nullptr;        // [n]
-    float* cn_cache = nullptr;        // canonical normalised rows when n <= kSmallN
-    unsigned char* rows_img = nullptr;   // int8 row image [n][dp] (fp16 / fp32 rows, option scan_image): biased codes, k_prep_image
+    float* norm = nullptr;            // canonical norms [cap + 64]
+    float* inv_scan = nullptr;        // [cap + 64]
+    float* cn_cache = nullptr;        // canonical normalised rows when n <= kSmallN ([min(cap, kSmallN)][d])
+    unsigned char* rows_img = nullptr;   // int8 row image [cap][dp] (fp16 / fp32 rows, option scan_image): biased codes, k_prep_image
     bool owns_img = false;            // (an int8 index IS its image: rows_img = rows_scan, not owned, residuals and offsets 0)
-    float* inv_img = nullptr;         // [n + 64] row scale / canonical norm: the image's approx score = acc x inv_img, then [n + 64] per-row
+    float* inv_img = nullptr;         // [cap + 64] row scale / canonical norm: the image's approx score = acc x inv_img, then [cap + 64] per-row
                                       // score offsets off_img (k_prep_image; the scan adds them: DESIGN.md 4)
     float rho_max = 0.0f;             // largest relative residual ||x - s code|| / ||x|| of a row of the image (rounded up)
     float rho_mean = 0.0f;            // their average: sets the re-score band
+    bool image_refused = false;       // a row left more residual than an image may hold (kImageMaxRho): appends do not try again (setting scan_image does)
+    float rho_sum = 0.0f;             // ... and their sum, which appended rows add to (rho_mean = rho_sum / n, as a fresh build forms it)
     std::mutex mu;
     Slot slots[kSlots];
     // options
@@ -189,6 +193,7 @@ struct vf_index {
     bool span_slot[4] = {false, false, false, false};   // slots whose ev_t[1] (end of their latest timed scan) belongs to this span
     // host-buffer entry (vf_index_search): per-handle device staging, grown on demand, reused across calls
     DevBuf st_q, st_ids, st_sc;
+    DevBuf st_add, st_rho;            // appends: the new rows on their way in (host rows, rows of another device), the image's two residual words
     // ---- group handle (vf_index_create_sharded / vf_index_group): the corpus is row-sharded over `shards`, one per
     // device; this handle owns them.  device = the HOME device: queries arrive there and the merged result lands there.
     std::vector<vf_index*> shards;
@@ -242,7 +247,8 @@ static int build_common(vf_index* ix) {
     const int dt = ix->dtype;
     const size_t scan_esz = byte_rows(dt) ? 1 : 2;  // fp8 / int8 rows are scanned as bytes, everything else as fp16
     ix->dp = (ix->d + 127) / 128 * 128;  // whole 128-element segment pairs: see pick_G
-    const size_t npad = (size_t)ix->n + 64;
+    ix->cap = ix->n;
+    const size_t npad = (size_t)ix->cap + 64;
     VF_HIP(hipMalloc((void**)&ix->norm, npad * sizeof(float)));
     VF_HIP(hipMalloc((void**)&ix->inv_scan, npad * sizeof(float)));
     VF_HIP(hipMemset(ix->norm, 0, npad * sizeof(float)));
@@ -254,7 +260,7 @@ static int build_common(vf_index* ix) {
             ix->rows_scan = ix->rows_orig;  // fp16 / fp8 / int8 rows of a whole number of segments are scanned in place
             ix->owns_scan = false;
         } else {
-            VF_HIP(hipMalloc((void**)&ix->rows_scan, (size_t)ix->n * ix->dp * scan_esz));
+            VF_HIP(hipMalloc((void**)&ix->rows_scan, (size_t)ix->cap * ix->dp * scan_esz));
             ix->owns_scan = true;
             scan_out = ix->rows_scan;
         }
@@ -262,7 +268,7 @@ static int build_common(vf_index* ix) {
     VF_HIP(launch_prep_rows(ix->rows_orig, dt, ix->n, ix->d, ix->dp, scan_out, ix->norm, ix->inv_scan, nullptr));
     VF_TRY(build_image(ix, ix->scan_image));
     if (ix->n > 0 && ix->n <= kSmallN) {
-        VF_HIP(hipMalloc((void**)&ix->cn_cache, (size_t)ix->n * ix->d * sizeof(float)));
+        VF_HIP(hipMalloc((void**)&ix->cn_cache, (size_t)std::min<int64_t>(ix->cap, kSmallN) * ix->d * sizeof(float)));
         VF_HIP(launch_normalize_rows(ix->rows_orig, dt, 0, ix->n, ix->d, ix->norm, ix->cn_cache, nullptr));
     }
     VF_HIP(hipDeviceSynchronize());
@@ -274,15 +280,15 @@ static int build_common(vf_index* ix) {
 // kImageHeadroom of device memory left over after it.
 constexpr double kImageMaxRho = 1.0 / 64;
 constexpr size_t kImageHeadroom = (size_t)8 << 30;
-static float* image_offsets(const vf_index* ix) { return ix->inv_img ? ix->inv_img + ix->n + 64 : nullptr; }
+static float* image_offsets(const vf_index* ix) { return ix->inv_img ? ix->inv_img + ix->cap + 64 : nullptr; }   // (sized by capacity: appends fill both halves in place)
 static void free_image(vf_index* ix) {
     if (ix->rows_img && ix->owns_img) (void)hipFree(ix->rows_img);
     if (ix->inv_img) (void)hipFree(ix->inv_img);
-    ix->rows_img = nullptr; ix->inv_img = nullptr; ix->owns_img = false; ix->rho_max = ix->rho_mean = 0.0f;
+    ix->rows_img = nullptr; ix->inv_img = nullptr; ix->owns_img = false; ix->rho_max = ix->rho_mean = ix->rho_sum = 0.0f;
 }
 static int build_image(vf_index* ix, int64_t mode) {
     if (mode == 0 || ix->rows_img || !image_eligible(route_in(ix), mode)) return VF_OK;
-    const size_t ibytes = 2 * ((size_t)ix->n + 64) * sizeof(float);   // inverses + offsets
+    const size_t ibytes = 2 * ((size_t)ix->cap + 64) * sizeof(float);   // inverses + offsets
     if (ix->dtype == VF_DTYPE_INT8) {
         // the index's own bytes are the codes: row scale 1, so inv_img = 1 / ||c|| = inv_scan; no residual, so offsets, rho_max and rho_mean
         // are 0 and the band is the certificate's own (image_bound at rho_mean = 0)
@@ -296,7 +302,7 @@ static int build_image(vf_index* ix, int64_t mode) {
         ix->rows_img = (unsigned char*)ix->rows_scan; ix->owns_img = false;
         return VF_OK;
     }
-    const size_t bytes = (size_t)ix->n * ix->dp;
+    const size_t bytes = (size_t)ix->cap * ix->dp;
     if (mode == 1) {
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return VF_OK; }
@@ -320,8 +326,9 @@ static int build_image(vf_index* ix, int64_t mode) {
     float rho, sum;
     memcpy(&rho, &bits[0], sizeof(rho));
     memcpy(&sum, &bits[1], sizeof(sum));
-    if (!(rho <= kImageMaxRho)) { free_image(ix); return VF_OK; }   // (a NaN fails the test too)
+    if (!(rho <= kImageMaxRho)) { free_image(ix); ix->image_refused = true; return VF_OK; }   // (a NaN fails the test too)
     ix->rho_max = rho;
+    ix->rho_sum = sum;
     ix->rho_mean = sum / (float)ix->n;
     return VF_OK;
 }
@@ -385,7 +392,7 @@ static void destroy_index(vf_index* ix) {
     }
     (void)hipSetDevice(ix->device);
     (void)hipDeviceSynchronize();
-    ix->st_q.release(); ix->st_ids.release(); ix->st_sc.release();
+    ix->st_q.release(); ix->st_ids.release(); ix->st_sc.release(); ix->st_add.release(); ix->st_rho.release();
     for (int i = 0; i < kSlots; ++i) {
         Slot& s = ix->slots[i];
         DevBuf* bufs[] = {&s.qn, &s.qimg, &s.s0, &s.cnt, &s.tau, &s.hist, &s.hist_coarse, &s.cand, &s.flags, &s.counts, &s.dense_s,
@@ -465,14 +472,214 @@ static int create_impl(vf_index** out, const void* rows, bool rows_on_device, in
     return VF_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Appends (VF_INDEX_APPEND; DESIGN.md "Appending rows").  IndexFlatIP.add on an index that exists (src/utils/faissRetriever.py:18-24,
+// fed in batches of 100 by src/load_data.py:98-128): the new rows are prepared by ONE kernel over them alone (k_append_rows) into the
+// room behind row n of every array the handle holds, and the row count is raised last -- a search reads rows below n only, so a failure
+// on the way leaves the handle as it was.  After it the handle is what vf_index_create over all the rows would have built: the
+// transitions a fresh build makes at a row count (the scan copy instead of the small-corpus cache above kSmallN, the int8 row image at
+// its threshold) are made when an append crosses it, and an image is dropped when a new row leaves more residual than it may hold.
+// ------------------------------------------------------------------------------------------------
+constexpr int64_t kMaxShardRows = 0xFFFFFFFFll;   // a shard holds fewer rows than this (candidate keys carry 32-bit row numbers)
+
+static bool search_pending(const vf_index* ix) {
+    for (const Slot& s : ix->slots) if (s.pending) return true;
+    for (const GroupSlot& g : ix->gslots) if (g.pending) return true;
+    for (const vf_index* sh : ix->shards) if (search_pending(sh)) return true;
+    return false;
+}
+
+// Every row-side array of the handle re-allocated for new_cap rows, its n rows copied device to device; borrowed rows (and rows scanned
+// in place) become the handle's own copy.  The new arrays are complete before an old one is freed: on a failure they are freed and the
+// handle is as it was.  The handle's device is current.
+static int regrow(vf_index* ix, int64_t new_cap) {
+    const size_t esz = dtype_bytes(ix->dtype), scan_esz = byte_rows(ix->dtype) ? 1 : 2;
+    const size_t n = (size_t)ix->n, npad = (size_t)new_cap + 64, d = (size_t)ix->d, dp = (size_t)ix->dp;
+    const bool scan_owned = ix->rows_scan && ix->owns_scan, scan_alias = ix->rows_scan && !ix->owns_scan;
+    const bool img_owned = ix->rows_img && ix->owns_img, img_alias = ix->rows_img && !ix->owns_img;
+    void *rows = nullptr, *scan = nullptr, *norm = nullptr, *inv = nullptr, *cn = nullptr, *img = nullptr, *iimg = nullptr;
+    struct Want { void** p; size_t bytes; bool on; const void* from; size_t copy; bool zero; };
+    const Want want[] = {
+        {&rows, (size_t)new_cap * d * esz, true, ix->rows_orig, n * d * esz, false},
+        {&scan, (size_t)new_cap * dp * scan_esz, scan_owned, ix->rows_scan, n * dp * scan_esz, false},
+        {&norm, npad * sizeof(float), true, ix->norm, n * sizeof(float), true},            // (the zeroed tail of 64 and the room between)
+        {&inv, npad * sizeof(float), true, ix->inv_scan, n * sizeof(float), true},
+        {&cn, (size_t)std::min<int64_t>(new_cap, kSmallN) * d * sizeof(float), ix->cn_cache != nullptr, ix->cn_cache, n * d * sizeof(float), false},
+        {&img, (size_t)new_cap * dp, img_owned, ix->rows_img, n * dp, false},
+        {&iimg, 2 * npad * sizeof(float), ix->inv_img != nullptr, ix->inv_img, n * sizeof(float), true},
+    };
+    hipError_t e = hipSuccess;
+    bool no_mem = false;
+    for (const Want& w : want) {
+        if (!w.on || e != hipSuccess) continue;
+        e = hipMalloc(w.p, w.bytes);
+        if (e != hipSuccess) { no_mem = true; *w.p = nullptr; break; }
+        if (w.zero) e = hipMemsetAsync(*w.p, 0, w.bytes, nullptr);
+        if (e == hipSuccess && w.copy && w.from) e = hipMemcpyAsync(*w.p, w.from, w.copy, hipMemcpyDeviceToDevice, nullptr);
+    }
+    if (e == hipSuccess && iimg && n)   // the offsets half starts behind the inverses' capacity, old and new
+        e = hipMemcpyAsync((float*)iimg + npad, image_offsets(ix), n * sizeof(float), hipMemcpyDeviceToDevice, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();   // the copies are done, and so is every reader of the old arrays
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        for (const Want& w : want) if (*w.p) (void)hipFree(*w.p);
+        return no_mem ? fail(VF_ENOMEM, std::string("growing the index to ") + std::to_string(new_cap) + " rows: " + hipGetErrorString(e))
+                      : fail(VF_EHIP, std::string("growing the index: ") + hipGetErrorString(e));
+    }
+    if (ix->owns_rows && ix->rows_orig) (void)hipFree(ix->rows_orig);
+    ix->rows_orig = rows; ix->owns_rows = true;
+    if (scan_owned) { (void)hipFree(ix->rows_scan); ix->rows_scan = scan; }
+    else if (scan_alias) ix->rows_scan = rows;   // still scanned in place: hipMalloc's alignment serves the scan
+    (void)hipFree(ix->norm); ix->norm = (float*)norm;
+    (void)hipFree(ix->inv_scan); ix->inv_scan = (float*)inv;
+    if (ix->cn_cache) { (void)hipFree(ix->cn_cache); ix->cn_cache = (float*)cn; }
+    if (img_owned) { (void)hipFree(ix->rows_img); ix->rows_img = (unsigned char*)img; }
+    else if (img_alias) ix->rows_img = (unsigned char*)ix->rows_scan;
+    if (ix->inv_img) { (void)hipFree(ix->inv_img); ix->inv_img = (float*)iimg; }
+    ix->cap = new_cap;
+    return VF_OK;
+}
+
+// m > 0 rows onto a plain handle: its mutex is held, no search is pending, n + m is in range.  src_device < 0: host rows.
+static int append_rows(vf_index* ix, const void* rows, int src_device, int64_t m) {
+    const int dt = ix->dtype;
+    const int64_t n0 = ix->n, n1 = n0 + m;
+    const size_t esz = dtype_bytes(dt), scan_esz = byte_rows(dt) ? 1 : 2;
+    VF_HIP(hipSetDevice(ix->device));
+    // room: 1.5 x the capacity at least, so that a run of appends without "reserve_rows" copies each row a bounded number of times
+    if (!ix->owns_rows || n1 > ix->cap) VF_TRY(regrow(ix, std::max<int64_t>(n1, std::min<int64_t>(ix->cap + ix->cap / 2, kMaxShardRows - 1))));
+    const void* src = rows;
+    if (src_device != ix->device) {
+        const size_t bytes = (size_t)m * ix->d * esz;
+        VF_TRY(ix->st_add.ensure(bytes));
+        if (src_device < 0) VF_HIP(hipMemcpy(ix->st_add.p, rows, bytes, hipMemcpyHostToDevice));
+        else VF_HIP(hipMemcpyPeer(ix->st_add.p, ix->device, rows, src_device, bytes));
+        src = ix->st_add.p;
+    }
+    // crossing kSmallN upward: the handle was built without the operands of the fused scan; a fresh build has them
+    const bool cross = n0 <= kSmallN && n1 > kSmallN && !ix->rows_scan;
+    const bool scan_in_place = dt != VF_DTYPE_F32 && ix->dp == ix->d;   // (the rows are the handle's own allocation by now: aligned)
+    void* new_scan = nullptr;
+    if (cross && !scan_in_place && hipMalloc(&new_scan, (size_t)ix->cap * ix->dp * scan_esz) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(VF_ENOMEM, "append: the scan copy does not fit in device memory");
+    }
+    // (a handle created empty holds no small-corpus cache yet; a fresh build of these rows would)
+    float* new_cn = nullptr;
+    if (n0 == 0 && n1 <= kSmallN && !ix->cn_cache &&
+        hipMalloc((void**)&new_cn, (size_t)std::min<int64_t>(ix->cap, kSmallN) * ix->d * sizeof(float)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(VF_ENOMEM, "append: the cache of normalised rows does not fit in device memory");
+    }
+    auto drop_new = [&]() { if (new_scan) (void)hipFree(new_scan); if (new_cn) (void)hipFree(new_cn); };
+    AppendArgs a{};
+    a.src = src; a.dt = dt; a.d = ix->d; a.dp = ix->dp; a.n0 = n0; a.m = m;
+    a.rows = ix->rows_orig; a.scan = (ix->rows_scan && ix->owns_scan) ? ix->rows_scan : nullptr;
+    a.norm = ix->norm; a.inv_scan = ix->inv_scan;
+    a.cn = new_cn ? new_cn : ((ix->cn_cache && n1 <= kSmallN) ? ix->cn_cache : nullptr);
+    hipError_t e = hipSuccess;
+    if (ix->rows_img) {
+        a.inv_img = ix->inv_img; a.off_img = image_offsets(ix);
+        if (ix->owns_img) {
+            int rc = ix->st_rho.ensure(2 * sizeof(u32));
+            if (rc != VF_OK) { drop_new(); return rc; }
+            a.img = ix->rows_img; a.rho_max_bits = ix->st_rho.as<u32>(); a.rho_sum = (float*)(a.rho_max_bits + 1);
+            e = hipMemsetAsync(ix->st_rho.p, 0, 2 * sizeof(u32), nullptr);
+        }
+    }
+    if (e == hipSuccess) e = launch_append_rows(a, nullptr);
+    // (the scan copy of ALL rows: one pass of the create-time kernel, which writes the norms it wrote before)
+    if (e == hipSuccess && new_scan) e = launch_prep_rows(ix->rows_orig, dt, n1, ix->d, ix->dp, new_scan, ix->norm, ix->inv_scan, nullptr);
+    u32 bits[2] = {0u, 0u};
+    if (e == hipSuccess) e = a.img ? hipMemcpy(bits, ix->st_rho.p, sizeof(bits), hipMemcpyDeviceToHost) : hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) {
+        drop_new();
+        return fail(VF_EHIP, std::string("append: ") + hipGetErrorString(e));
+    }
+    // commit: the rows exist from here on
+    float* old_cn = ix->cn_cache;
+    ix->n = n1;
+    if (new_cn) ix->cn_cache = new_cn;
+    if (cross) {
+        ix->rows_scan = new_scan ? new_scan : ix->rows_orig; ix->owns_scan = new_scan != nullptr;
+        ix->cn_cache = nullptr;
+    }
+    if (a.img) {
+        float rho, sum;
+        memcpy(&rho, &bits[0], sizeof(rho));
+        memcpy(&sum, &bits[1], sizeof(sum));
+        if (!(rho <= kImageMaxRho)) { free_image(ix); ix->image_refused = true; }   // a fresh build would have refused the image (a NaN fails the test too)
+        else { ix->rho_max = std::max(ix->rho_max, rho); ix->rho_sum += sum; ix->rho_mean = ix->rho_sum / (float)ix->n; }
+    }
+    // the image a fresh build of this many rows would hold (it appears at a row count: image_eligible)
+    if (!ix->rows_img && !ix->image_refused) {
+        const int rc = build_image(ix, ix->scan_image);
+        if (rc != VF_OK) {   // back to the handle as it was
+            const std::string keep = g_err;
+            free_image(ix);
+            ix->n = n0;
+            if (new_cn) { (void)hipFree(new_cn); ix->cn_cache = nullptr; }
+            if (cross) { ix->rows_scan = nullptr; ix->owns_scan = false; ix->cn_cache = old_cn; if (new_scan) (void)hipFree(new_scan); }
+            g_err = keep;
+            return rc;
+        }
+    }
+    if (cross && old_cn) (void)hipFree(old_cn);
+    if (ix->st_add.bytes > ((size_t)64 << 20)) ix->st_add.release();
+    return VF_OK;
+}
+
+// vf_index_create / vf_index_create_device with VF_INDEX_APPEND in `dtype`.  Every argument error is reported before the first HIP call.
+static int append_entry(vf_index** out, const void* rows, bool rows_on_device, int64_t n, int32_t d, int32_t dtype, int32_t device_id) {
+    if (!out) return fail(VF_EINVAL, "vf_index_create: null out");
+    const int32_t base = dtype & ~VF_INDEX_APPEND;
+    if (!known_dtype(base)) return fail(VF_EINVAL, "vf_index_create: unknown dtype");
+    if (n < 0 || d <= 0 || (n > 0 && !rows)) return fail(VF_EINVAL, "vf_index_create: bad rows/n/d");
+    vf_index* ix = *out;
+    if (!ix) return fail(VF_EINVAL, "vf_index_create: VF_INDEX_APPEND needs a live handle in *out");
+    if (d != ix->d || base != ix->dtype)
+        return fail(VF_EINVAL, "vf_index_create: VF_INDEX_APPEND: d and dtype must be the handle's (" + std::to_string(ix->d) + ", " + std::to_string(ix->dtype) + ")");
+    if (device_id != ix->device) return fail(VF_EINVAL, "vf_index_create: VF_INDEX_APPEND: device_id must be the handle's device " + std::to_string(ix->device));
+    std::lock_guard<std::mutex> g(ix->mu);
+    if (search_pending(ix)) return fail(VF_EINVAL, "vf_index_create: VF_INDEX_APPEND: search pending (a slot is between _begin and _end)");
+    if (n == 0) return VF_OK;
+    vf_index* target = ix->shards.empty() ? ix : ix->shards.back();   // a group: the rows go to its last shard, ids stay one range
+    if (target->n + n >= kMaxShardRows) return fail(VF_EUNSUPPORTED, "vf_index_create: VF_INDEX_APPEND: more than 2^32-1 rows per shard");
+    DeviceGuard restore_callers_device;
+    const int src_device = rows_on_device ? device_id : -1;
+    if (target == ix) return append_rows(ix, rows, src_device, n);
+    std::lock_guard<std::mutex> lk(target->mu);
+    VF_TRY(append_rows(target, rows, src_device, n));
+    ix->n += n;
+    return VF_OK;
+}
+
+// option "reserve_rows": room for `total` rows now, so that appends up to it move nothing (a group: in its last shard, where they go)
+static int reserve_rows(vf_index* ix, int64_t total) {
+    std::lock_guard<std::mutex> g(ix->mu);
+    vf_index* target = ix->shards.empty() ? ix : ix->shards.back();
+    if (target != ix) total -= ix->n - target->n;
+    if (total >= kMaxShardRows) return fail(VF_EUNSUPPORTED, "reserve_rows: more than 2^32-1 rows per shard");
+    if (total <= target->n) return VF_OK;
+    if (search_pending(ix)) return fail(VF_EINVAL, "reserve_rows cannot change while a search is pending");
+    std::unique_lock<std::mutex> lk;
+    if (target != ix) lk = std::unique_lock<std::mutex>(target->mu);
+    if (target->owns_rows && total <= target->cap) return VF_OK;
+    DeviceGuard restore_callers_device;
+    VF_HIP(hipSetDevice(target->device));
+    return regrow(target, std::max(total, target->cap));
+}
+
 extern "C" int vf_index_create(vf_index** out, const void* rows, int64_t n, int32_t d, int32_t dtype,
                                int32_t device_id, int64_t id_offset) {
+    if (dtype >= 0 && (dtype & VF_INDEX_APPEND)) return append_entry(out, rows, false, n, d, dtype, device_id);
     DeviceGuard restore_callers_device;
     return create_impl(out, rows, false, n, d, dtype, device_id, id_offset);
 }
 
 extern "C" int vf_index_create_device(vf_index** out, const void* d_rows, int64_t n, int32_t d, int32_t dtype,
                                       int32_t device_id, int64_t id_offset) {
+    if (dtype >= 0 && (dtype & VF_INDEX_APPEND)) return append_entry(out, d_rows, true, n, d, dtype, device_id);
     DeviceGuard restore_callers_device;
     return create_impl(out, d_rows, true, n, d, dtype, device_id, id_offset);
 }
@@ -673,6 +880,7 @@ extern "C" int vf_index_slots(vf_index* ix, int32_t* out) {
 
 extern "C" int vf_index_set_option(vf_index* ix, const char* name, int64_t value) {
     if (!ix || !name) return fail(VF_EINVAL, "vf_index_set_option: null argument");
+    if (strcmp(name, "reserve_rows") == 0) return reserve_rows(ix, value);
     for (vf_index* sh : ix->shards) VF_TRY(vf_index_set_option(sh, name, value));  // a group forwards to every shard
     std::lock_guard<std::mutex> g(ix->mu);
     const std::string s(name);
@@ -714,6 +922,7 @@ extern "C" int vf_index_set_option(vf_index* ix, const char* name, int64_t value
         DeviceGuard restore_callers_device;
         VF_HIP(hipSetDevice(ix->device));
         VF_HIP(hipDeviceSynchronize());
+        ix->image_refused = false;
         if (value == 0) free_image(ix);
         else VF_TRY(build_image(ix, value));
         ix->scan_image = value;

@@ -145,6 +145,21 @@ hipError_t launch_prep_rows(const void* rows, int dt /* VF_DTYPE_* */, long long
 // the int8 row image of fp16 / fp32 rows (after launch_prep_rows: it reads `norm`): bytes [n][dp], inv_img [n], max relative residual (float bits)
 hipError_t launch_prep_image(const void* rows, int dt, long long n, int d, int dp, const float* norm, unsigned char* img,
                              float* inv_img, float* off_img, u32* rho_max_bits, float* rho_sum, hipStream_t s);
+// k_append_rows: the index build for the m rows of one append, in one launch (VF_INDEX_APPEND).  Source row i becomes row n0 + i of the
+// handle's arrays, which the caller has sized for n0 + m rows at least; optional outputs are null where the handle does not hold them.
+struct AppendArgs {
+    const void* src;         // [m][d] of dt as the caller gave them (int8: two's complement), on the handle's device
+    int dt, d, dp;
+    long long n0, m;
+    void* rows;              // the handle's stored rows (int8: biased bytes)
+    void* scan;              // its owned scan copy [.][dp], or null (none, or the rows are scanned in place)
+    float* norm; float* inv_scan;
+    float* cn;               // the small-corpus cache of normalised rows, or null
+    unsigned char* img;      // an OWNED int8 row image's codes, or null
+    float* inv_img; float* off_img;       // the image's inverses and offsets (an int8 index: the inverses alone, img = null); null without an image
+    u32* rho_max_bits; float* rho_sum;    // with `img`: largest residual of the new rows (float bits) and their sum, zeroed by the caller
+};
+hipError_t launch_append_rows(const AppendArgs& a, hipStream_t s);
 hipError_t launch_prep_queries(const float* q, int nq, int d, int dp, int qn_tile /*32 or 64*/,
                                float* qn, _Float16* qimg, hipStream_t s);
 hipError_t launch_normalize_rows(const void* rows, int dt /* VF_DTYPE_* */, long long row0, long long nrows, int d,

@@ -5,6 +5,7 @@
 //
 // Kernels
 //   k_prep_rows        index build: canonical row norms, fp16 scan copy (+ per-row pow2 scale); fp8 rows stay bytes
+//   k_append_rows      an append to a live index: everything the build does for a row, for the new rows alone, in one launch
 //   k_prep_queries     per batch: canonical query normalisation, fp16 LDS image for the MFMA scan
 //   k_scan<NT,G,MODE,F8>  THE hot kernel: streams the corpus once (fp16 rows, or fp8-e4m3 bytes converted in
 //                      registers), 32x32x16 f16 MFMA against the LDS-resident query tile, threshold-filter
@@ -65,12 +66,16 @@ __device__ __forceinline__ float e4m3_to_float(u32 b) {
     return (float)__builtin_bit_cast(_Float16, e4m3_to_f16_bits(b));
 }
 
+// an int8 index holds biased bytes (code + 128 = the two's-complement byte with its top bit flipped: k_rebias_i8, k_append_rows)
+__device__ __forceinline__ unsigned char rebias_byte(unsigned char b) { return b ^ (unsigned char)0x80; }
+__device__ __forceinline__ float i8b_to_float(unsigned char biased) { return (float)((int)biased - 128); }
+
 // element `idx` of a row-major corpus of storage dtype dt (VF_DTYPE_F32 / _F16 / _FP8_E4M3 / _INT8), as fp32 (exact)
 // (int8 rows are HELD as biased bytes, code + 128: k_rebias_i8; every kernel that reads them undoes the bias)
 __device__ __forceinline__ float load_elem(const void* rows, int dt, long long idx) {
     if (dt == VF_DTYPE_F16) return (float)((const _Float16*)rows)[idx];
     if (dt == VF_DTYPE_FP8_E4M3) return e4m3_to_float(((const unsigned char*)rows)[idx]);
-    if (dt == VF_DTYPE_INT8) return (float)((int)((const unsigned char*)rows)[idx] - 128);
+    if (dt == VF_DTYPE_INT8) return i8b_to_float(((const unsigned char*)rows)[idx]);
     return ((const float*)rows)[idx];
 }
 
@@ -95,12 +100,11 @@ __device__ __forceinline__ int next_pow2(int n) {
 //   fp8 (e4m3) rows: the scan copy stays fp8 BYTES (dp bytes per row, zero padded); scale 1.
 //   int8 rows (biased bytes): likewise dp bytes per row, padded with 128 -- the biased zero; scale 1.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_prep_rows(const void* rows, int dt, long long n, int d, int dp,
-                                                    void* scan, float* norm, float* inv_scan) {
-    const int l = threadIdx.x & 15;
-    const long long r = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);
-    if (r >= n) return;  // whole 16-lane group leaves together
-    const long long base = r * (long long)d;
+// The per-row steps of the index build, shared by the create-time kernels (k_prep_rows, k_prep_image, k_normalize_rows) and by
+// k_append_rows, which runs them for appended rows only: one definition each, so a row gets the same bits whichever kernel prepared it.
+// All of them run in a 16-lane group, lane l taking the elements j = l (mod 16).
+// sum of squares (canonical order) and largest magnitude of a row, reduced over the group (every lane returns both)
+__device__ __forceinline__ void row_sumsq_max(const void* rows, int dt, long long base, int d, int l, float* sumsq, float* absmax) {
     float acc = 0.0f, mx = 0.0f;
     for (int j = l; j < d; j += 16) {
         const float x = load_elem(rows, dt, base + j);
@@ -110,29 +114,50 @@ __global__ __launch_bounds__(256) void k_prep_rows(const void* rows, int dt, lon
     acc = group16_tree(acc);
     acc = __shfl(acc, 0, 16);
     for (int o = 8; o; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 16));
-    const float nm = canon_norm_from_sumsq(acc);
+    *sumsq = acc; *absmax = mx;
+}
+// the power of two an fp32 row is scaled by on its way to the fp16 scan copy (every other dtype: 1)
+__device__ __forceinline__ float row_scan_scale(int dt, float mx) {
     float scale = 1.0f;
     if (dt == VF_DTYPE_F32 && mx > 0.0f && mx <= FLT_MAX) {
         int e;
         frexpf(mx, &e);  // mx = f * 2^e, f in [0.5, 1)
         scale = ldexpf(1.0f, 14 - e);
     }
-    if (l == 0) {
-        norm[r] = nm;
-        inv_scan[r] = 1.0f / (nm * scale);
-    }
-    if (scan && (dt == VF_DTYPE_FP8_E4M3 || dt == VF_DTYPE_INT8)) {
-        unsigned char* out = (unsigned char*)scan + r * (long long)dp;
+    return scale;
+}
+__device__ __forceinline__ float row_inv_scan(float nm, float scale) { return 1.0f / (nm * scale); }
+// the padded scan row: one-byte rows as they are (padding: 0, int8 rows the biased zero 128), everything else as fp16(x * scale)
+__device__ __forceinline__ void write_scan_row(const void* rows, int dt, long long base, int d, int dp, void* scan_row, float scale, int l) {
+    if (dt == VF_DTYPE_FP8_E4M3 || dt == VF_DTYPE_INT8) {
+        unsigned char* out = (unsigned char*)scan_row;
         const unsigned char* in = (const unsigned char*)rows + base;
         const unsigned char pad = dt == VF_DTYPE_INT8 ? (unsigned char)128 : (unsigned char)0;
         for (int j = l; j < dp; j += 16) out[j] = j < d ? in[j] : pad;
-    } else if (scan) {
-        _Float16* out = (_Float16*)scan + r * (long long)dp;
+    } else {
+        _Float16* out = (_Float16*)scan_row;
         for (int j = l; j < dp; j += 16) {
             const float x = j < d ? load_elem(rows, dt, base + j) * scale : 0.0f;
             out[j] = (_Float16)x;
         }
     }
+}
+
+__global__ __launch_bounds__(256) void k_prep_rows(const void* rows, int dt, long long n, int d, int dp,
+                                                    void* scan, float* norm, float* inv_scan) {
+    const int l = threadIdx.x & 15;
+    const long long r = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);
+    if (r >= n) return;  // whole 16-lane group leaves together
+    const long long base = r * (long long)d;
+    float acc, mx;
+    row_sumsq_max(rows, dt, base, d, l, &acc, &mx);
+    const float nm = canon_norm_from_sumsq(acc);
+    const float scale = row_scan_scale(dt, mx);
+    if (l == 0) {
+        norm[r] = nm;
+        inv_scan[r] = row_inv_scan(nm, scale);
+    }
+    if (scan) write_scan_row(rows, dt, base, d, dp, (char*)scan + r * (long long)dp * ((dt == VF_DTYPE_FP8_E4M3 || dt == VF_DTYPE_INT8) ? 1 : 2), scale, l);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -144,6 +169,53 @@ __global__ __launch_bounds__(256) void k_prep_rows(const void* rows, int dt, lon
 // the sum (the band's width).  off_img = rho (1 + 2^-11)(1 + 2^-20) + d 2^-24 rho, rounded up: what the row's
 // quantisation can move its score by, added to its approximate score by the scan (k_scan2r, F8 = 2) so that canonical <= key + eps.
 // ------------------------------------------------------------------------------------------------
+// the row's largest magnitude (group-reduced), whether it is finite, and the code step it gives
+__device__ __forceinline__ float image_row_step(const void* rows, int dt, long long base, int d, int l, bool* finite) {
+    float mx = 0.0f;
+    for (int j = l; j < d; j += 16) mx = fmaxf(mx, fabsf(load_elem(rows, dt, base + j)));
+    for (int o = 8; o; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 16));
+    *finite = mx <= FLT_MAX;
+    return (*finite && mx > 0.0f) ? mx / 127.0f : 1.0f;
+}
+// the quantiser: the row's dp biased codes to `img_row`; returns the squared residual ||x - sc code||^2 in fp64, group-reduced
+__device__ __forceinline__ double image_row_codes(const void* rows, int dt, long long base, int d, int dp, float sc, unsigned char* img_row, int l) {
+    double res = 0.0;
+    unsigned* out = (unsigned*)img_row;
+    for (int j0 = 4 * l; j0 < dp; j0 += 64) {   // four codes per lane per step: one 32-bit vector store
+        u32 w = 0u;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int j = j0 + e;
+            float code = 0.0f;
+            if (j < d) {
+                const float x = load_elem(rows, dt, base + j);
+                code = fminf(fmaxf(rintf(x / sc), -127.0f), 127.0f);
+                const double dx = (double)x - (double)sc * (double)code;
+                res += dx * dx;
+            }
+            w |= (u32)((int)code + 128) << (8 * e);
+        }
+        out[j0 >> 2] = w;
+    }
+    for (int o = 8; o; o >>= 1) res += __shfl_xor(res, o, 16);
+    return res;
+}
+// the round-up steps: the row's inverse, its relative residual and its score offset, each rounded up from fp64
+__device__ __forceinline__ void image_row_bounds(double res, float sc, float nm, int d, bool finite, float* inv, float* rho_out, float* off_out) {
+    *inv = (float)((double)sc / (double)nm);
+    float rho, off;
+    if (!finite) rho = off = INFINITY;
+    else {
+        const double rd = sqrt(res) / (double)nm;
+        rho = (float)rd;
+        if ((double)rho < rd) rho = nextafterf(rho, INFINITY);
+        const double od = rd * (1.0 + 0x1p-11) * (1.0 + 0x1p-20) + (double)d * 0x1p-24 * rd;
+        off = (float)od;
+        if ((double)off < od) off = nextafterf(off, INFINITY);
+    }
+    *rho_out = rho; *off_out = off;
+}
+
 __global__ __launch_bounds__(256) void k_prep_image(const void* rows, int dt, long long n, int d, int dp, const float* norm,
                                                      unsigned char* img, float* inv_img, float* off_img, u32* rho_max_bits, float* rho_sum) {
     __shared__ u32 wg_max;
@@ -154,43 +226,13 @@ __global__ __launch_bounds__(256) void k_prep_image(const void* rows, int dt, lo
     const long long r = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);
     if (r < n) {   // (no early return: the whole block meets at the barrier below)
         const long long base = r * (long long)d;
-        float mx = 0.0f;
-        for (int j = l; j < d; j += 16) mx = fmaxf(mx, fabsf(load_elem(rows, dt, base + j)));
-        for (int o = 8; o; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 16));
-        const bool finite = mx <= FLT_MAX;
-        const float sc = (finite && mx > 0.0f) ? mx / 127.0f : 1.0f;
-        double res = 0.0;
-        unsigned* out = (unsigned*)(img + r * (long long)dp);
-        for (int j0 = 4 * l; j0 < dp; j0 += 64) {   // four codes per lane per step: one 32-bit vector store
-            u32 w = 0u;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int j = j0 + e;
-                float code = 0.0f;
-                if (j < d) {
-                    const float x = load_elem(rows, dt, base + j);
-                    code = fminf(fmaxf(rintf(x / sc), -127.0f), 127.0f);
-                    const double dx = (double)x - (double)sc * (double)code;
-                    res += dx * dx;
-                }
-                w |= (u32)((int)code + 128) << (8 * e);
-            }
-            out[j0 >> 2] = w;
-        }
-        for (int o = 8; o; o >>= 1) res += __shfl_xor(res, o, 16);
+        bool finite;
+        const float sc = image_row_step(rows, dt, base, d, l, &finite);
+        const double res = image_row_codes(rows, dt, base, d, dp, sc, img + r * (long long)dp, l);
         if (l == 0) {
-            const float nm = norm[r];
-            inv_img[r] = (float)((double)sc / (double)nm);
-            float rho, off;
-            if (!finite) rho = off = INFINITY;
-            else {
-                const double rd = sqrt(res) / (double)nm;
-                rho = (float)rd;
-                if ((double)rho < rd) rho = nextafterf(rho, INFINITY);
-                const double od = rd * (1.0 + 0x1p-11) * (1.0 + 0x1p-20) + (double)d * 0x1p-24 * rd;
-                off = (float)od;
-                if ((double)off < od) off = nextafterf(off, INFINITY);
-            }
+            float inv, rho, off;
+            image_row_bounds(res, sc, norm[r], d, finite, &inv, &rho, &off);
+            inv_img[r] = inv;
             off_img[r] = off;
             atomicMax(&wg_max, __float_as_uint(rho));
             atomicAdd(&wg_sum, finite ? rho : 0.0f);
@@ -228,7 +270,7 @@ __global__ __launch_bounds__(256) void k_rebias_i8(const unsigned char* in, unsi
             *(uint4*)(out + i) = v;
         } else {
             const long long e = i + 16 < bytes ? i + 16 : bytes;
-            for (long long j = i; j < e; ++j) out[j] = in[j] ^ (unsigned char)0x80;
+            for (long long j = i; j < e; ++j) out[j] = rebias_byte(in[j]);
         }
     }
 }
@@ -347,12 +389,15 @@ hipError_t launch_prep_q8(const float* qn, int nq, int d, int dp, int qn_tile, i
 // ------------------------------------------------------------------------------------------------
 // exact dense path
 // ------------------------------------------------------------------------------------------------
+// one element of a canonically normalised row (the small-corpus cache, the chunked exact path)
+__device__ __forceinline__ float normalised_elem(float x, float nm) { return x * canon_inv(nm); }
+
 __global__ __launch_bounds__(256) void k_normalize_rows(const void* rows, int dt, long long row0,
                                                          long long nrows, int d, const float* norm, float* out) {
     const long long total = nrows * (long long)d;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
         const long long r = i / d;
-        out[i] = load_elem(rows, dt, (row0 + r) * (long long)d + (i - r * d)) * canon_inv(norm[row0 + r]);
+        out[i] = normalised_elem(load_elem(rows, dt, (row0 + r) * (long long)d + (i - r * d)), norm[row0 + r]);
     }
 }
 
@@ -363,6 +408,74 @@ hipError_t launch_normalize_rows(const void* rows, int dt, long long row0, long 
     if (blocks > 65536) blocks = 65536;
     hipLaunchKernelGGL(k_normalize_rows, dim3((unsigned)blocks), dim3(256), 0, s, rows, dt, row0, nrows, d, norm,
                        out);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_append_rows: everything the index build does for a row, for the m rows of ONE append (vf_index_create* with VF_INDEX_APPEND), in one
+// launch -- one 16-lane group per row, as k_prep_rows.  Source row i becomes row g = n0 + i of the handle: the stored row (int8 rows
+// re-biased), norm and inv_scan, the padded scan row when the handle owns a scan copy, the normalised row when it keeps the small-corpus
+// cache, and codes, inverse, offset and the two residual statistics when it holds an int8 row image (an int8 index, whose image is its
+// scan rows: the inverse only).  Every value comes from the device functions the create-time kernels call, so it is what they would
+// have written for that row.  Everything lands in rows >= n0, which no search reads before the host commits the new row count.
+// The passes re-read the row (as k_prep_rows and k_prep_image do): from `src`, except that two's-complement int8 input is read back
+// from the stored row, where the same lane has just written the biased bytes it reads.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_append_rows(AppendArgs a) {
+    __shared__ u32 wg_max;
+    __shared__ float wg_sum;
+    const bool stats = a.img != nullptr;   // (uniform: the barriers below are met by the whole block or by nobody)
+    if (stats) {
+        if (threadIdx.x == 0) { wg_max = 0u; wg_sum = 0.0f; }
+        __syncthreads();
+    }
+    const int l = threadIdx.x & 15, dt = a.dt, d = a.d;
+    const long long r = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);
+    if (r < a.m) {
+        const long long g = a.n0 + r, sbase = r * (long long)d, gbase = g * (long long)d;
+        // the stored row: the source's own bits (int8: biased)
+        if (dt == VF_DTYPE_F32) for (int j = l; j < d; j += 16) ((float*)a.rows)[gbase + j] = ((const float*)a.src)[sbase + j];
+        else if (dt == VF_DTYPE_F16) for (int j = l; j < d; j += 16) ((unsigned short*)a.rows)[gbase + j] = ((const unsigned short*)a.src)[sbase + j];
+        else if (dt == VF_DTYPE_INT8) for (int j = l; j < d; j += 16) ((unsigned char*)a.rows)[gbase + j] = rebias_byte(((const unsigned char*)a.src)[sbase + j]);
+        else for (int j = l; j < d; j += 16) ((unsigned char*)a.rows)[gbase + j] = ((const unsigned char*)a.src)[sbase + j];
+        const void* rd = dt == VF_DTYPE_INT8 ? (const void*)a.rows : a.src;   // what the lane-per-element passes read
+        const long long rbase = dt == VF_DTYPE_INT8 ? gbase : sbase;
+        float acc, mx;
+        row_sumsq_max(rd, dt, rbase, d, l, &acc, &mx);
+        const float nm = canon_norm_from_sumsq(acc);
+        const float scale = row_scan_scale(dt, mx);
+        const float inv = row_inv_scan(nm, scale);
+        if (l == 0) {
+            a.norm[g] = nm;
+            a.inv_scan[g] = inv;
+            if (a.inv_img && !a.img) a.inv_img[g] = inv;   // an int8 index is its own image: row scale 1, no residual, offset 0
+        }
+        if (a.scan) write_scan_row(rd, dt, rbase, d, a.dp, (char*)a.scan + g * (long long)a.dp * ((dt == VF_DTYPE_FP8_E4M3 || dt == VF_DTYPE_INT8) ? 1 : 2), scale, l);
+        if (a.cn) for (int j = l; j < d; j += 16) a.cn[gbase + j] = normalised_elem(load_elem(rd, dt, rbase + j), nm);
+        if (stats) {   // fp16 / fp32 rows only (its four-codes-per-lane pass reads elements other lanes stored: from `src`)
+            bool finite;
+            const float sc = image_row_step(a.src, dt, sbase, d, l, &finite);
+            const double res = image_row_codes(a.src, dt, sbase, d, a.dp, sc, a.img + g * (long long)a.dp, l);
+            if (l == 0) {
+                float iinv, rho, off;
+                image_row_bounds(res, sc, nm, d, finite, &iinv, &rho, &off);
+                a.inv_img[g] = iinv;
+                a.off_img[g] = off;
+                atomicMax(&wg_max, __float_as_uint(rho));
+                atomicAdd(&wg_sum, finite ? rho : 0.0f);
+            }
+        }
+    }
+    if (stats) {
+        __syncthreads();
+        if (threadIdx.x == 0 && wg_max) { atomicMax(a.rho_max_bits, wg_max); atomicAdd(a.rho_sum, wg_sum); }
+    }
+}
+
+hipError_t launch_append_rows(const AppendArgs& a, hipStream_t s) {
+    if (a.m <= 0) return hipSuccess;
+    const long long blocks = (a.m + 15) / 16;
+    hipLaunchKernelGGL(k_append_rows, dim3((unsigned)blocks), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

@@ -15,6 +15,37 @@ from .index import DenseIndex, quantize_int8
 logger = logging.getLogger(__name__)
 
 
+def encode_rows(embeddings: np.ndarray, corpus_dtype: str):
+    """[n, d] embeddings -> (the rows as an index of ``corpus_dtype`` holds them, whether they are e4m3 codes): the one recipe of the
+    constructor and of ``add_embeddings``, so appended rows are stored exactly as rows given at construction are."""
+    if corpus_dtype == "f32":
+        return (embeddings if embeddings.dtype == np.float16 else embeddings.astype("float32")), False
+    if corpus_dtype == "f16":
+        return embeddings.astype(np.float16), False
+    if corpus_dtype == "fp8":
+        import torch
+        # torch's cast to e4m3 does not saturate (|x| > 448 becomes a NaN code) and flushes small magnitudes (the components of a
+        # unit vector of 768+ dimensions sit around the subnormal edge 2^-6).  A cosine does not change under a positive per-row
+        # scale, so every row is scaled by the POWER OF TWO that puts its largest magnitude into [224, 448]: exact in fp32 (the
+        # rounding of in-range values is what it was), nothing can overflow, and the small components keep their three bits
+        x = np.ascontiguousarray(embeddings.astype(np.float32))
+        if not np.isfinite(x).all():
+            raise ValueError("corpus_dtype='fp8': the embeddings hold non-finite values")
+        peak = np.abs(x).max(axis=1, keepdims=True).astype(np.float64)
+        x = x * np.exp2(np.floor(np.log2(448.0 / np.where(peak > 0, peak, 448.0)))).astype(np.float32)
+        np.clip(x, -448.0, 448.0, out=x)
+        codes = torch.from_numpy(x).to(torch.float8_e4m3fn).view(torch.uint8).numpy()
+        if ((codes & 0x7F) == 0x7F).any():
+            raise ValueError("corpus_dtype='fp8': the cast produced NaN codes")
+        return codes, True
+    if corpus_dtype == "int8":
+        try:
+            return quantize_int8(embeddings), False
+        except ValueError as e:
+            raise ValueError(f"corpus_dtype='int8': {e}") from None
+    raise ValueError(f"corpus_dtype {corpus_dtype!r}: one of f32, f16, fp8, int8")
+
+
 class FaissRetriever:
     """Exact cosine retriever; the corpus lives in HBM, search runs as hand-written gfx950 kernels."""
 
@@ -33,46 +64,49 @@ class FaissRetriever:
         # rows_as_given: the index holds the embeddings' own values (nothing was rounded to a narrower type), so a cosine taken from
         # the rows is the cosine of the embeddings (EnsembleRetriever.compute_similarity_mtx serves known texts from them)
         self.rows_as_given = corpus_dtype == "f32" or (corpus_dtype == "f16" and embeddings.dtype == np.float16)
-        if corpus_dtype == "f32":
-            x = embeddings if embeddings.dtype == np.float16 else embeddings.astype("float32")
-            self.index = DenseIndex(x, device_id=device_id, device_ids=device_ids)
-        elif corpus_dtype == "f16":
-            self.index = DenseIndex(embeddings.astype(np.float16), device_id=device_id, device_ids=device_ids)
-        elif corpus_dtype == "fp8":
-            import torch
-            # torch's cast to e4m3 does not saturate (|x| > 448 becomes a NaN code) and flushes small magnitudes (the components of a
-            # unit vector of 768+ dimensions sit around the subnormal edge 2^-6).  A cosine does not change under a positive per-row
-            # scale, so every row is scaled by the POWER OF TWO that puts its largest magnitude into [224, 448]: exact in fp32 (the
-            # rounding of in-range values is what it was), nothing can overflow, and the small components keep their three bits
-            x = np.ascontiguousarray(embeddings.astype(np.float32))
-            if not np.isfinite(x).all():
-                raise ValueError("corpus_dtype='fp8': the embeddings hold non-finite values")
-            peak = np.abs(x).max(axis=1, keepdims=True).astype(np.float64)
-            x = x * np.exp2(np.floor(np.log2(448.0 / np.where(peak > 0, peak, 448.0)))).astype(np.float32)
-            np.clip(x, -448.0, 448.0, out=x)
-            codes = torch.from_numpy(x).to(torch.float8_e4m3fn).view(torch.uint8).numpy()
-            if ((codes & 0x7F) == 0x7F).any():
-                raise ValueError("corpus_dtype='fp8': the cast produced NaN codes")
-            self.index = DenseIndex.from_e4m3(codes, device_id=device_id, device_ids=device_ids)
-        elif corpus_dtype == "int8":
-            try:
-                codes = quantize_int8(embeddings)
-            except ValueError as e:
-                raise ValueError(f"corpus_dtype='int8': {e}") from None
-            self.index = DenseIndex(codes, device_id=device_id, device_ids=device_ids)
-        else:
-            raise ValueError(f"corpus_dtype {corpus_dtype!r}: one of f32, f16, fp8, int8")
+        self.corpus_dtype = corpus_dtype
+        rows, e4m3 = encode_rows(embeddings, corpus_dtype)
+        make = DenseIndex.from_e4m3 if e4m3 else DenseIndex
+        self.index = make(rows, device_id=device_id, device_ids=device_ids)
         logger.info(f"Building HIP dense index with {len(embeddings)} vectors of dimension {dimension}")
 
     @classmethod
-    def from_index(cls, index: DenseIndex, embedding_fn, rows_as_given: bool = True):
+    def from_index(cls, index: DenseIndex, embedding_fn, rows_as_given: bool = True, corpus_dtype: str = None):
         """The same retriever over an index that already exists -- ``DenseIndex.from_file`` (the corpus file the embed loop wrote,
         corpus_file.py: no Chroma round trip at start-up, ensembleRetriever.py:39-43), a device tensor, a sharded group.  Use it as
         ``EnsembleRetriever(..., retriever_cls=lambda _embeddings, fn: FaissRetriever.from_index(ix, fn))``.
-        rows_as_given: the index holds the embedder's own values (see __init__)."""
+        rows_as_given: the index holds the embedder's own values (see __init__).
+        corpus_dtype: how that index holds its rows (``f32 | f16 | fp8 | int8``), for ``add_embeddings`` / ``add_texts``: the retriever did
+        not build the index, so it appends only when told the recipe the rows were stored with."""
+        if corpus_dtype is not None and corpus_dtype not in ("f32", "f16", "fp8", "int8"):
+            raise ValueError(f"corpus_dtype {corpus_dtype!r}: one of f32, f16, fp8, int8")
         self = cls.__new__(cls)
-        self.embeddings, self.index, self.rows_as_given = embedding_fn, index, bool(rows_as_given)
+        self.embeddings, self.index, self.rows_as_given, self.corpus_dtype = embedding_fn, index, bool(rows_as_given), corpus_dtype
         return self
+
+    def add_embeddings(self, embeddings) -> np.ndarray:
+        """Append [m, d] embeddings to the live index (reference: ``index.add(x)`` at :24, which upstream runs once); returns their ids,
+        int64 [m].  They are stored by the constructor's recipe for this retriever's ``corpus_dtype``."""
+        if getattr(self, "corpus_dtype", None) is None:
+            raise ValueError("this retriever wraps an index it did not build: pass corpus_dtype to from_index to append to it")
+        embeddings = np.array(embeddings)
+        if embeddings.ndim != 2:
+            raise ValueError("embeddings must be a 2-D array-like [m, d]")
+        rows, _ = encode_rows(embeddings, self.corpus_dtype)
+        first = self.index.add(rows)
+        return np.arange(first, first + len(rows), dtype=np.int64)
+
+    def add_texts(self, texts) -> np.ndarray:
+        """Embed ``texts`` as documents (``embed_documents``; ``embed_query`` per text where that is all the embedder has) and append
+        them; returns their ids."""
+        texts = list(texts)
+        if getattr(self, "corpus_dtype", None) is None:
+            raise ValueError("this retriever wraps an index it did not build: pass corpus_dtype to from_index to append to it")
+        if not texts:
+            return np.empty(0, dtype=np.int64)
+        embed_docs = getattr(self.embeddings, "embed_documents", None)
+        vectors = embed_docs(texts) if embed_docs is not None else [self.embeddings.embed_query(t) for t in texts]
+        return self.add_embeddings(np.asarray(vectors, dtype=np.float32).reshape(len(texts), -1))
 
     def invoke(self, querys: list, k: int):
         """(I, D) = ids and cosine scores, best first, shape [len(querys), k]; -1 / -FLT_MAX pad a corpus with fewer than k rows

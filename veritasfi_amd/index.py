@@ -195,6 +195,83 @@ class DenseIndex:
             raise TypeError(f"int8 rows must be int8, got {dt} (uint8 codes are e4m3: DenseIndex.from_e4m3)")
         return cls(codes, device_id=device_id, id_offset=id_offset, device_ids=device_ids)
 
+    # -- appending -----------------------------------------------------------------------------------
+    def _held_dtype(self) -> int:
+        """VF_DTYPE_* of the rows as the index holds them (``vf_index_info``)."""
+        dt = _ffi.c_i32(0)
+        _ffi.check(_ffi.lib().vf_index_info(self._h, None, None, ctypes.byref(dt), None), "vf_index_info")
+        return int(dt.value)
+
+    def add(self, rows) -> int:
+        """Append rows to the live index (``faiss.IndexFlatIP.add``, faissRetriever.py:24, on an index that exists) and return the id
+        of the first one; the rest follow it (``id_offset + n`` before the call, upward), and ``self.n`` grows by their count.
+        Inputs are the constructor's: an ndarray or CPU tensor (copied), or a CUDA tensor on the index's device (read in place, free
+        afterwards); e4m3 rows as uint8 codes or ``float8_e4m3fn``; int8 rows as int8.  The rows must be of the type the index holds --
+        the one the constructor would have picked for them -- or TypeError is raised: nothing is cast across widths.  An index that
+        borrowed a CUDA tensor at construction takes its own copy on the first call and lets the tensor go.  Only the new rows are
+        prepared (``reserve`` keeps the arrays from growing); a group handle puts them into its last shard."""
+        L = _ffi.lib()
+        held = self._held_dtype()
+        names = {_ffi.VF_DTYPE_F32: "float32", _ffi.VF_DTYPE_F16: "float16", _ffi.VF_DTYPE_FP8_E4M3: "e4m3 codes (uint8)", _ffi.VF_DTYPE_INT8: "int8"}
+
+        def refuse(got):
+            raise TypeError(f"add: the index holds {names[held]} rows, got {got}")
+
+        first = self.id_offset + self.n
+        if _is_torch_tensor(rows):
+            import torch
+            if rows.dtype == getattr(torch, "float8_e4m3fn", None):
+                if held != _ffi.VF_DTYPE_FP8_E4M3:
+                    refuse(rows.dtype)
+                rows = rows.view(torch.uint8)
+            if rows.is_cuda:
+                if rows.dim() != 2 or not rows.is_contiguous():
+                    raise ValueError("rows must be a contiguous [m, d] tensor")
+                dt = {torch.uint8: _ffi.VF_DTYPE_FP8_E4M3, torch.int8: _ffi.VF_DTYPE_INT8, torch.float16: _ffi.VF_DTYPE_F16,
+                      torch.float32: _ffi.VF_DTYPE_F32}.get(rows.dtype)
+                if dt != held:
+                    refuse(rows.dtype)
+                if int(rows.shape[1]) != self.d:
+                    raise ValueError(f"rows must be [m, {self.d}], got {tuple(rows.shape)}")
+                m = int(rows.shape[0])
+                dev = rows.device.index if rows.device.index is not None else self.device_id
+                _ffi.check(L.vf_index_create_device(ctypes.byref(self._h), rows.data_ptr(), m, self.d, dt | _ffi.VF_INDEX_APPEND, dev, 0),
+                           "vf_index_create_device (append)")
+                return self._added(first, m)
+            rows = rows.numpy()
+        rows = np.asarray(rows)
+        if rows.ndim != 2 or rows.shape[1] != self.d:
+            raise ValueError(f"rows must be [m, {self.d}], got {rows.shape}")
+        if rows.dtype == np.uint8 and held == _ffi.VF_DTYPE_FP8_E4M3:
+            dt = held
+        elif rows.dtype == np.int8:
+            dt = _ffi.VF_DTYPE_INT8
+        elif rows.dtype == np.float16:
+            dt = _ffi.VF_DTYPE_F16
+        else:
+            dt = _ffi.VF_DTYPE_F32
+        if dt != held:
+            refuse(rows.dtype)
+        if dt == _ffi.VF_DTYPE_F32:
+            rows = rows.astype(np.float32, copy=False)
+        rows = np.ascontiguousarray(rows)
+        m = int(rows.shape[0])
+        _ffi.check(L.vf_index_create(ctypes.byref(self._h), rows.ctypes.data, m, self.d, dt | _ffi.VF_INDEX_APPEND, self.device_id, 0),
+                   "vf_index_create (append)")
+        return self._added(first, m)
+
+    def _added(self, first: int, m: int) -> int:
+        self.n += m
+        if m and self.device_ids is None:
+            self._keepalive = None   # the index holds its own copy of the rows now
+        return first
+
+    def reserve(self, total: int) -> None:
+        """Room for ``total`` rows now (option ``reserve_rows``), so that ``add`` up to that count moves nothing."""
+        self.set_option("reserve_rows", int(total))
+        if int(total) > self.n and self.device_ids is None:
+            self._keepalive = None
+
     # -- host buffers ------------------------------------------------------------------------------
     def search(self, queries, k: int):
         """queries [nq, d] -> (ids int64 [nq, k], scores float32 [nq, k]); ids first, as
