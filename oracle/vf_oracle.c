@@ -35,7 +35,8 @@
  *                 (fvec_renorm_L2: inv_nr = 1.0 / sqrtf(nr); x[i] *= inv_nr); sklearn divides
  *                 instead, which differs in the last bit only (goldens are compared at 2e-6)
  *   cos(q,c)    : dot16(qn, cn, d)
- *   ranking     : descending score, ties broken by LOWER id first.
+ *   ranking     : descending score, ties broken by LOWER id first; -0.0 ties with +0.0, and a search
+ *                 reports either as +0.0 (vf_oracle_merge_topk copies the bits it is given).
  *
  * Build: see oracle/Makefile (gcc -O3 -mavx2 -mfma -mf16c -ffp-contract=off -fopenmp).
  */
@@ -209,7 +210,8 @@ static int search_impl(const void* corpus, int is_half, int64_t n, int d, const 
             else src = (const float*)corpus + r * (int64_t)d;
             canon_normalize(src, d, cn);
             for (int q = 0; q < nq; ++q) {
-                vf_hit x = { dot16(qn + (size_t)q * d, cn, d), r };
+                /* + 0.0f: a search reports a zero score as +0.0; -0.0 arises when every product underflows negative */
+                vf_hit x = { dot16(qn + (size_t)q * d, cn, d) + 0.0f, r };
                 if (kk > 0) heap_offer(myh + (size_t)q * kk, &myc[q], kk, x);
             }
         }

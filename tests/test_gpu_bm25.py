@@ -162,10 +162,27 @@ def test_zipf_1m_documents_64_queries(tmp_path):
 def test_10m_documents_few_queries(tmp_path):
     ix = zipf_index(tmp_path, 10_000_000, 100_000, 3, seed=9)
     queries = [np.array([0, 5, 40], np.int32), np.array([1, 1, 700, 3], np.int32), np.array([99_999], np.int32)]
+    n = ix.num_docs
     with vf.BM25Retriever(str(tmp_path), stemmer=None) as r:
         ids, sc = r.search_columns(queries, 2048)
-    for i, cols in enumerate(queries):
-        check(ix, cols, 2048, ids[i], sc[i])
+        for i, cols in enumerate(queries):
+            check(ix, cols, 2048, ids[i], sc[i])
+        # deep k (k > 4096: the global bitonic sort) at the sizes where its grid-stride loops take a second turn and the
+        # zero tail's block prefix carries: one full ranking of query 0 on the CPU, two searches held to its prefixes
+        want = ref_scores(ix, queries[0])
+        assert np.count_nonzero(want) > 4_194_304 + 1000   # more selected keys than 8192 workgroups of pairs / 4096 of padding cover
+        full_ids, full_sc = ref_topk(want, n)
+        # k = 5M < touched: the select runs, 2^23 keys are sorted (16384 workgroups of pairs against a cap of 8192).
+        # k = n: every touched key is taken, then the zero tail over all 306 bitmap blocks (> 256: k_bm25_tail_scan carries)
+        assert (n + 32767) // 32768 > 256
+        for k in (5_000_000, n):
+            ids, sc = r.search_columns([queries[0]], k)
+            assert np.array_equal(np.asarray(ids[0], np.int64), full_ids[:k]), k
+            assert np.array_equal(np.asarray(sc[0], np.float32).view(np.uint32), full_sc[:k].view(np.uint32)), k
+        del full_ids, full_sc, ids, sc
+        # deep k with almost everything in the tail (17 touched documents), starting in bitmap block 0
+        ids, sc = r.search_columns([queries[2]], 4097)
+        check(ix, queries[2], 4097, ids[0], sc[0])
 
 
 class _Store:
