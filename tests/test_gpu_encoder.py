@@ -643,6 +643,9 @@ def test_encoder_handle_is_thread_safe(vf):
 
 
 # ---- decoder-only family: Qwen3-style embedder with last_token_pool, token-logit scorer -----------
+# (These are whole forwards against HF fp32 at model-level tolerances.  The decoder's kernels are checked ONE BY ONE -- causal
+#  attention at every position, RoPE table, q/k-norm + RoPE, RMSNorm, SwiGLU, gather, last-token pooling / logit -- against float64
+#  references in tests/test_gpu_decoder_kernels.py.)
 def _hf_qwen3(hidden, layers, heads, kv_heads, head_dim, ffn, vocab=800, seed=3, causal_lm=False):
     import torch
     from transformers import Qwen3Config, Qwen3ForCausalLM, Qwen3Model

@@ -4175,6 +4175,57 @@ extern "C" int vf_decoder_create(vf_decoder** out, const vf_decoder_config* cfg,
     return VF_OK;
 }
 
+// ---- the launches of the decoder's kernels: grid and block arithmetic in ONE place each, shared by the forward below and by the
+//      vf_debug_dec_* test hooks (tests/test_gpu_decoder_kernels.py), so that a test of one kernel runs production's launch ----
+static void dec_launch_rope_table(float theta, int T, int dh, float2* tab, hipStream_t st) {
+    const int cells = T * (dh / 2);
+    hipLaunchKernelGGL(k_rope_table, dim3((cells + 255) / 256), dim3(256), 0, st, theta, T, dh, tab);
+}
+static void dec_launch_gather_rows(const int* ids, const half_t* table, int M, int H, float scale, float* out, hipStream_t st) {
+    hipLaunchKernelGGL(k_gather_rows, dim3((M + 7) / 8), dim3(256), 0, st, ids, table, M, H, scale, out);
+}
+template <typename TOUT>
+static void dec_launch_rmsnorm(const float* x, const float* w, float woff, float eps, int M, int H, TOUT* y, hipStream_t st) {
+    hipLaunchKernelGGL(k_rmsnorm<TOUT>, dim3((M + 7) / 8), dim3(256), 0, st, x, w, woff, eps, M, H, y);
+}
+static void dec_launch_qknorm_rope(half_t* qkv, int M, int T, int ld, int heads, int kv_heads, int DH, const float* qw, const float* kw,
+                                   float eps, int qk_norm, const float2* tab, const int* pos, hipStream_t st) {
+    const int tpw = 256 / (DH / 16);   // tokens per workgroup: 64, 32 or 16
+    hipLaunchKernelGGL(k_qknorm_rope, dim3((M + tpw - 1) / tpw, 3), dim3(256), 0, st, qkv, M, T, ld, heads, kv_heads, DH, qw, kw, eps,
+                       qk_norm, tab, pos);
+}
+// causal grouped-query attention over qkv rows of ld elements; false: no kernel for this head dim (nothing launched)
+static bool dec_launch_attention(const half_t* qkv, const int* mask, const int* seq_off, int b, int t, int ld, int heads, int kv_heads,
+                                 int DH, float scale, half_t* ctx, int ctx_ld, hipStream_t st) {
+    const dim3 agrid((t + 127) / 128, heads, b);
+    if (DH == 64) {
+        hipLaunchKernelGGL((k_attention_stream2<64, true>), agrid, dim3(256), sizeof(AttnStream2Lds<64>), st, qkv, mask, t, ld, heads,
+                           kv_heads, scale, ctx, ctx_ld, seq_off);
+    } else if (DH == 128) {
+        hipLaunchKernelGGL((k_attention_stream2<128, true>), agrid, dim3(256), sizeof(AttnStream2Lds<128>), st, qkv, mask, t, ld, heads,
+                           kv_heads, scale, ctx, ctx_ld, seq_off);
+    } else if (DH == 256) {
+        hipLaunchKernelGGL((k_attention_stream2<256, true>), agrid, dim3(256), sizeof(AttnStream2Lds<256>), st, qkv, mask, t, ld, heads,
+                           kv_heads, scale, ctx, ctx_ld, seq_off);
+    } else {
+        return false;
+    }
+    return true;
+}
+static void dec_launch_swiglu(const half_t* gu, int M, int F, int act_kind, half_t* act, hipStream_t st) {
+    hipLaunchKernelGGL(k_swiglu, dim3(((F >> 3) + 255) / 256, M < 32768 ? M : 32768), dim3(256), 0, st, gu, (long long)M, F, act_kind, act);
+}
+static void dec_launch_token_logit(const half_t* x, const int* mask, int b, int T, int Tv, int H, int all_last, const half_t* row,
+                                   float* out, const int* seq_off, hipStream_t st) {
+    hipLaunchKernelGGL(k_token_logit, dim3(b), dim3(64), 0, st, x, mask, T, Tv, H, all_last, row, out, seq_off);
+}
+static void dec_launch_pool(const half_t* x, const int* mask, int b, int T, int Tv, int H, int pooling, int normalize, int all_last,
+                            float* out, const int* seq_off, hipStream_t st) {
+    const size_t pool_lds = ((size_t)H * 2 + 256) * sizeof(float);
+    hipLaunchKernelGGL(k_pool, dim3(b), dim3(256), pool_lds, st, x, mask, T, Tv, H, pooling, normalize, all_last, 0, nullptr, nullptr,
+                       nullptr, nullptr, out, seq_off);
+}
+
 static int dec_ensure_ws(vf_decoder* d, int B, int T) {
     VFT_HIP(handle_stream(&d->stream));   // (the zero fills below run on the handle's stream, in front of its forward)
     int tokens = (B * T + 255) / 256 * 256;
@@ -4205,10 +4256,9 @@ static int dec_ensure_ws(vf_decoder* d, int B, int T) {
     VFT_HIP(hipMemsetAsync(d->ctx, 0, Mp * QD * 2, d->stream));
     VFT_HIP(hipMemsetAsync(d->gu, 0, Mp * 2 * F * 2, d->stream));
     VFT_HIP(hipMemsetAsync(d->act, 0, Mp * F * 2, d->stream));
-    const int cells = kDecMaxT * (c.head_dim / 2);
     // on the handle's own stream, like the memsets above: the forwards run there, and a non-blocking stream does not order itself behind
     // the NULL stream (round-5 advisor: the first forward after a (re)allocation could read a table not written yet)
-    hipLaunchKernelGGL(k_rope_table, dim3((cells + 255) / 256), dim3(256), 0, d->stream, c.rope_theta, kDecMaxT, c.head_dim, d->rope);
+    dec_launch_rope_table(c.rope_theta, kDecMaxT, c.head_dim, d->rope, d->stream);
     VFT_HIP(hipGetLastError());
     d->cap_tokens = tokens; d->cap_b = B; d->rope_T = kDecMaxT;
     VFT_HIP(gws_ensure(d->gws, d->stream));
@@ -4223,39 +4273,26 @@ static int dec_layers_device(vf_decoder* d, int b, int t, hipStream_t st, float*
     const vf_decoder_config& c = d->cfg;
     const int H = c.hidden, F = c.ffn, DH = c.head_dim, QD = (int)dec_qd(c), KD = (int)dec_kd(c), QKV = QD + 2 * KD;
     const int M = seq_off ? Mpk : b * t, Mp = (M + 255) / 256 * 256;
-    hipLaunchKernelGGL(k_gather_rows, dim3((M + 7) / 8), dim3(256), 0, st, d->d_ids, d->w16 + d->o_embed, M, H,
-                       c.embed_scale > 0.f ? c.embed_scale : 1.0f, d->x);
+    dec_launch_gather_rows(d->d_ids, d->w16 + d->o_embed, M, H, c.embed_scale > 0.f ? c.embed_scale : 1.0f, d->x, st);
     float *px = d->x, *py = d->y;   // residual stream in fp32; GEMM operands (d->n, d->ctx, d->act) in fp16
     const float scale = 1.0f / sqrtf((float)DH);
     const float woff = c.norm_plus_one ? 1.0f : 0.0f;
-    const dim3 agrid((t + 127) / 128, c.heads, b);
     for (int l = 0; l < c.layers; ++l) {
         const half_t* W = d->w16 + d->o_layers + (size_t)l * d->layer16;
         const half_t *Wqkv = W, *Wo = Wqkv + (size_t)QKV * H, *Wgu = Wo + (size_t)H * QD, *Wdn = Wgu + (size_t)2 * F * H;
         const float* P = d->w32 + d->f_layers + (size_t)l * d->layer32;
         const float *ln1 = P, *ln2 = P + H, *qn = P + 2 * H, *kn = qn + DH;
-        hipLaunchKernelGGL(k_rmsnorm<half_t>, dim3((M + 7) / 8), dim3(256), 0, st, px, ln1, woff, c.rms_eps, M, H, d->n);
+        dec_launch_rmsnorm<half_t>(px, ln1, woff, c.rms_eps, M, H, d->n, st);
         VFT_HIP(gemm<EPI_BIAS>(d->n, Wqkv, nullptr, nullptr, d->qkv, Mp, QKV, H, st, 0, &d->gws));
-        hipLaunchKernelGGL(k_qknorm_rope, dim3((M + 256 / (DH / 16) - 1) / (256 / (DH / 16)), 3), dim3(256), 0, st, d->qkv, M, t, QKV, c.heads, c.kv_heads, DH,
-                           qn, kn, c.rms_eps, c.qk_norm, d->rope, pos);
-        if (DH == 64) {
-                hipLaunchKernelGGL((k_attention_stream2<64, true>), agrid, dim3(256), sizeof(AttnStream2Lds<64>), st, d->qkv, d->d_mask,
-                                   t, QKV, c.heads, c.kv_heads, scale, d->ctx, QD, seq_off);
-        } else if (DH == 128) {
-                hipLaunchKernelGGL((k_attention_stream2<128, true>), agrid, dim3(256), sizeof(AttnStream2Lds<128>), st, d->qkv, d->d_mask,
-                                   t, QKV, c.heads, c.kv_heads, scale, d->ctx, QD, seq_off);
-        } else {
-                hipLaunchKernelGGL((k_attention_stream2<256, true>), agrid, dim3(256), sizeof(AttnStream2Lds<256>), st, d->qkv, d->d_mask,
-                                   t, QKV, c.heads, c.kv_heads, scale, d->ctx, QD, seq_off);
-        }
+        dec_launch_qknorm_rope(d->qkv, M, t, QKV, c.heads, c.kv_heads, DH, qn, kn, c.rms_eps, c.qk_norm, d->rope, pos, st);
+        dec_launch_attention(d->qkv, d->d_mask, seq_off, b, t, QKV, c.heads, c.kv_heads, DH, scale, d->ctx, QD, st);   // (head dim checked at create)
         VFT_HIP(gemm<EPI_RESIDUAL_F32>(d->ctx, Wo, nullptr, (const half_t*)px, (half_t*)py, Mp, H, QD, st));
         std::swap(px, py);
-        hipLaunchKernelGGL(k_rmsnorm<half_t>, dim3((M + 7) / 8), dim3(256), 0, st, px, ln2, woff, c.rms_eps, M, H, d->n);
+        dec_launch_rmsnorm<half_t>(px, ln2, woff, c.rms_eps, M, H, d->n, st);
         hipError_t ger = hipSuccess;
         if (!gemm_gated(d->n, Wgu, d->act, Mp, F, H, c.act, st, &ger)) {   // gate / up products and the activation in one launch
             VFT_HIP(gemm<EPI_BIAS>(d->n, Wgu, nullptr, nullptr, d->gu, Mp, 2 * F, H, st, 0, &d->gws));
-            hipLaunchKernelGGL(k_swiglu, dim3(((F >> 3) + 255) / 256, M < 32768 ? M : 32768), dim3(256), 0, st, d->gu, (long long)M, F, c.act,
-                               d->act);
+            dec_launch_swiglu(d->gu, M, F, c.act, d->act, st);
         }
         VFT_HIP(ger);
         VFT_HIP(gemm<EPI_RESIDUAL_F32>(d->act, Wdn, nullptr, (const half_t*)px, (half_t*)py, Mp, H, F, st));
@@ -4371,16 +4408,9 @@ static int dec_forward_impl(vf_decoder* d, const int32_t* ids, const int32_t* ma
             float* pxp = nullptr;
             VFT_TRY(dec_layers_device(d, b, tmax, st, &pxp, d->d_seq, (int)rows, d->d_pos));
             const float woffp = c.norm_plus_one ? 1.0f : 0.0f;
-            hipLaunchKernelGGL(k_rmsnorm<half_t>, dim3(((int)rows + 7) / 8), dim3(256), 0, st, pxp, d->w32 + d->f_final, woffp, c.rms_eps,
-                               (int)rows, H, d->n);
-            if (c.head == 2) {
-                hipLaunchKernelGGL(k_token_logit, dim3(b), dim3(64), 0, st, d->n, d->d_mask, tmax, tmax, H, 0, d->w16 + d->o_head_row,
-                                   d->d_out, d->d_seq);
-            } else {
-                const size_t pool_lds = ((size_t)H * 2 + 256) * sizeof(float);
-                hipLaunchKernelGGL(k_pool, dim3(b), dim3(256), pool_lds, st, d->n, d->d_mask, tmax, tmax, H, c.pooling, c.normalize, 0,
-                                   0, nullptr, nullptr, nullptr, nullptr, d->d_out, d->d_seq);
-            }
+            dec_launch_rmsnorm<half_t>(pxp, d->w32 + d->f_final, woffp, c.rms_eps, (int)rows, H, d->n, st);
+            if (c.head == 2) dec_launch_token_logit(d->n, d->d_mask, b, tmax, tmax, H, 0, d->w16 + d->o_head_row, d->d_out, d->d_seq, st);
+            else dec_launch_pool(d->n, d->d_mask, b, tmax, tmax, H, c.pooling, c.normalize, 0, d->d_out, d->d_seq, st);
             VFT_HIP(hipGetLastError());
             VFT_HIP(hipMemcpyAsync(out, d->d_out, (size_t)b * (c.head == 2 ? 1 : H) * 4, hipMemcpyDeviceToHost, st));
             VFT_HIP(hipStreamSynchronize(st));
@@ -4393,21 +4423,15 @@ static int dec_forward_impl(vf_decoder* d, const int32_t* ids, const int32_t* ma
     float* px = nullptr;
     VFT_TRY(dec_layers_device(d, b, t, st, &px));
     const float woff = c.norm_plus_one ? 1.0f : 0.0f;
-    hipLaunchKernelGGL(k_rmsnorm<half_t>, dim3((M + 7) / 8), dim3(256), 0, st, px, d->w32 + d->f_final, woff, c.rms_eps, M, H, d->n);
+    dec_launch_rmsnorm<half_t>(px, d->w32 + d->f_final, woff, c.rms_eps, M, H, d->n, st);
     int all_last = 0;
     if (c.pooling == 2 || c.head == 2) {
         hipLaunchKernelGGL(k_all_last_set, dim3(1), dim3(64), 0, st, d->d_mask, b, t, t_valid, d->d_flag);
         VFT_HIP(hipMemcpyAsync(&all_last, d->d_flag, 4, hipMemcpyDeviceToHost, st));
         VFT_HIP(hipStreamSynchronize(st));
     }
-    if (c.head == 2) {
-        hipLaunchKernelGGL(k_token_logit, dim3(b), dim3(64), 0, st, d->n, d->d_mask, t, t_valid, H, all_last, d->w16 + d->o_head_row,
-                           d->d_out);
-    } else {
-        const size_t pool_lds = ((size_t)H * 2 + 256) * sizeof(float);
-        hipLaunchKernelGGL(k_pool, dim3(b), dim3(256), pool_lds, st, d->n, d->d_mask, t, t_valid, H, c.pooling, c.normalize, all_last,
-                           0, nullptr, nullptr, nullptr, nullptr, d->d_out);
-    }
+    if (c.head == 2) dec_launch_token_logit(d->n, d->d_mask, b, t, t_valid, H, all_last, d->w16 + d->o_head_row, d->d_out, nullptr, st);
+    else dec_launch_pool(d->n, d->d_mask, b, t, t_valid, H, c.pooling, c.normalize, all_last, d->d_out, nullptr, st);
     VFT_HIP(hipGetLastError());
     VFT_HIP(hipMemcpyAsync(out, d->d_out, (size_t)b * (c.head == 2 ? 1 : H) * 4, hipMemcpyDeviceToHost, st));
     VFT_HIP(hipStreamSynchronize(st));
@@ -4434,8 +4458,7 @@ extern "C" int vf_decoder_forward_hidden(vf_decoder* d, const int32_t* ids, cons
     VFT_HIP(hipMemcpyAsync(d->d_mask, mask, ntok * 4, hipMemcpyHostToDevice, st));
     float* px = nullptr;
     VFT_TRY(dec_layers_device(d, b, t, st, &px));
-    hipLaunchKernelGGL(k_rmsnorm<float>, dim3((M + 7) / 8), dim3(256), 0, st, px, d->w32 + d->f_final, c.norm_plus_one ? 1.0f : 0.0f,
-                       c.rms_eps, M, H, d->d_hidden);
+    dec_launch_rmsnorm<float>(px, d->w32 + d->f_final, c.norm_plus_one ? 1.0f : 0.0f, c.rms_eps, M, H, d->d_hidden, st);
     VFT_HIP(hipGetLastError());
     VFT_HIP(hipMemcpyAsync(out_hidden, d->d_hidden, ntok * H * 4, hipMemcpyDeviceToHost, st));
     VFT_HIP(hipStreamSynchronize(st));
@@ -5071,5 +5094,65 @@ extern "C" int vf_debug_attention_packed(const void* qkv, const int* mask, const
     if (er != hipSuccess) return -1;
     if (B <= 0 || heads <= 0 || Tmax <= 0 || Tmax % 32 || Tmax > kEncResidentT || !seq_off) return -2;
     launch_attention2<0>((const half_t*)qkv, mask, B, Tmax, heads, (half_t*)ctx, (hipStream_t)stream, seq_off);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// Test hooks (tests/test_gpu_decoder_kernels.py): ONE decoder kernel each, on the caller's device buffers and stream, through the launch
+// helper the forward uses (dec_launch_*).  Every refusal (-2) returns before anything is launched.
+// The causal grouped-query attention of dec_layers_device: qkv rows [q (heads*dh) | k (kv_heads*dh) | v (kv_heads*dh)], mask per row,
+// seq_off (device, B + 1 ints) or null, ctx rows of ctx_ld elements.  Packed: T is the longest sequence, every length a multiple of 32.
+extern "C" int vf_debug_dec_attention(const void* qkv, const int* mask, const int* seq_off, int B, int T, int heads, int kv_heads,
+                                      int head_dim, float scale, void* ctx, int ctx_ld, void* stream) {
+    if (configure_once() != hipSuccess) return -1;
+    if (!qkv || !mask || !ctx || B <= 0 || heads <= 0 || kv_heads <= 0 || heads % kv_heads != 0) return -2;
+    if (T <= 0 || T % 32 != 0 || T > kDecMaxT) return -2;
+    if (head_dim != 64 && head_dim != 128 && head_dim != 256) return -2;
+    if (ctx_ld < heads * head_dim || ctx_ld % 4 != 0) return -2;
+    if (!dec_launch_attention((const half_t*)qkv, mask, seq_off, B, T, (heads + 2 * kv_heads) * head_dim, heads, kv_heads, head_dim, scale,
+                              (half_t*)ctx, ctx_ld, (hipStream_t)stream))
+        return -2;
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+extern "C" int vf_debug_dec_rope_table(float theta, int T, int dh, void* tab, void* stream) {
+    if (!tab || !(theta > 0.f) || T <= 0 || T > kDecMaxT || (dh != 64 && dh != 128 && dh != 256)) return -2;
+    dec_launch_rope_table(theta, T, dh, (float2*)tab, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// qkv [M][(heads + 2 kv_heads) * dh] in place; tab: kDecMaxT rows of k_rope_table; pos_ids (device, M ints in [0, 4096)) or null: tok % T
+extern "C" int vf_debug_dec_qknorm_rope(void* qkv, int M, int T, int heads, int kv_heads, int dh, const float* qw, const float* kw, float eps,
+                                        int qk_norm, const void* tab, const int* pos_ids, void* stream) {
+    if (!qkv || !tab || M <= 0 || T <= 0 || T > kDecMaxT || heads <= 0 || kv_heads <= 0 || (dh != 64 && dh != 128 && dh != 256)) return -2;
+    if (qk_norm && (!qw || !kw)) return -2;
+    dec_launch_qknorm_rope((half_t*)qkv, M, T, (heads + 2 * kv_heads) * dh, heads, kv_heads, dh, qw, kw, eps, qk_norm, (const float2*)tab,
+                           pos_ids, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+extern "C" int vf_debug_dec_rmsnorm(const float* x, const float* w, float woff, float eps, int M, int H, void* y, int out_fp32, void* stream) {
+    if (!x || !w || !y || M <= 0 || H <= 0 || H % 4 != 0) return -2;
+    if (out_fp32) dec_launch_rmsnorm<float>(x, w, woff, eps, M, H, (float*)y, (hipStream_t)stream);
+    else dec_launch_rmsnorm<half_t>(x, w, woff, eps, M, H, (half_t*)y, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+extern "C" int vf_debug_dec_swiglu(const void* gu, int M, int F, int act_kind, void* act, void* stream) {
+    if (!gu || !act || M <= 0 || F <= 0 || F % 8 != 0 || (act_kind != 0 && act_kind != 1)) return -2;
+    dec_launch_swiglu((const half_t*)gu, M, F, act_kind, (half_t*)act, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+extern "C" int vf_debug_dec_gather_rows(const int* ids, const void* table, int M, int H, float scale, float* out, void* stream) {
+    if (!ids || !table || !out || M <= 0 || H <= 0 || H % 8 != 0) return -2;
+    dec_launch_gather_rows(ids, (const half_t*)table, M, H, scale, out, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// the pooled position's "Yes" logit / the last-token row (k_pool, pooling 2): x [rows][H] fp16, out [B] / [B][H] fp32
+extern "C" int vf_debug_dec_token_logit(const void* x, const int* mask, const int* seq_off, int B, int T, int Tv, int H, int all_last,
+                                        const void* row, float* out, void* stream) {
+    if (!x || !mask || !row || !out || B <= 0 || T <= 0 || Tv <= 0 || Tv > T || H <= 0) return -2;
+    dec_launch_token_logit((const half_t*)x, mask, B, T, Tv, H, all_last, (const half_t*)row, out, seq_off, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+extern "C" int vf_debug_dec_pool_last(const void* x, const int* mask, const int* seq_off, int B, int T, int Tv, int H, int all_last,
+                                      int normalize, float* out, void* stream) {
+    if (!x || !mask || !out || B <= 0 || T <= 0 || Tv <= 0 || Tv > T || H <= 0 || H > 4096) return -2;
+    dec_launch_pool((const half_t*)x, mask, B, T, Tv, H, 2, normalize, all_last, out, seq_off, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
