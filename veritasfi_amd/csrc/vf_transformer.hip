@@ -25,6 +25,7 @@
 //   k_pool            CLS / mean / last-token pooling (+ L2 normalise)  or  RoBERTa classification head
 #include "../../include/veritasfi_hip.h"
 #include "vf_internal.h"
+#include "vf_gemm_route.h"   // tile geometry, the EPI_* codes the route reads, route_gemm and the small decisions beside it
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -191,15 +192,15 @@ __global__ __launch_bounds__(256) void k_layernorm(const half_t* y, const float*
 // EPI_RESIDUAL_F32: C and R are FP32 buffers, C = R + acc (+ bias): the decoder family's residual stream is kept in fp32 (the
 // reference runs those models in the checkpoint's wider dtype: experiments/retriever/step3_mul.py:62-64), only the
 // GEMM operands are fp16.
-enum { EPI_BIAS = 0, EPI_BIAS_GELU = 1, EPI_BIAS_RESIDUAL = 2, EPI_RESIDUAL_F32 = 3,
-       EPI_GATED_SILU = 4, EPI_GATED_GELU = 5,
+// EPI_BIAS = 0, EPI_BIAS_GELU = 1, EPI_BIAS_RESIDUAL = 2, EPI_RESIDUAL_F32 = 3 and EPI_BIAS_QGELU = 11 (C = quick_gelu(A.W^T + b): x sigmoid(1.702 x), the
+// vision tower's activation (CLIP)) are the codes gemm()'s route reads: vf_gemm_route.h.  The codes of the kernels' other epilogues:
+enum { EPI_GATED_SILU = 4, EPI_GATED_GELU = 5,   // k_gemm8p_tn only: C[M][N/2] = act(A.Wgate^T) * (A.Wup^T), W = [gate rows | up rows]
        /* 6: was the LayerNorm-in-the-tail experiment (deleted in round 4) */
        // LayerNorm folded into the products around it (k_gemm8p_tn only; LnFold, DESIGN.md 7 "LayerNorm without a launch"):
        EPI_LNA = 7,            // C = rstd_m (A.W'^T - mean_m colsum(W')_n) + c_n : A is the RAW pre-LayerNorm sum, W' = W diag(gamma)
        EPI_LNA_GELU = 8,       // ... + GELU
        EPI_RES_STATS = 9,      // C = A.W^T + b + R (R already normalised), and the row sums (sum, sum of squares) of C
-       EPI_LNRES_STATS = 10,
-       EPI_BIAS_QGELU = 11 };  // C = quick_gelu(A.W^T + b): x sigmoid(1.702 x), the vision tower's activation (CLIP) // C = A.W^T + b + LayerNorm(R) from the raw R and its row sums, and the row sums of C   // k_gemm8p_tn only: C[M][N/2] = act(A.Wgate^T) * (A.Wup^T), W = [gate rows | up rows]
+       EPI_LNRES_STATS = 10 }; // C = A.W^T + b + LayerNorm(R) from the raw R and its row sums, and the row sums of C
 
 // exact-GELU x Phi(x) = max(x, 0) - (|x| / 2) erfc(|x| / sqrt 2), with the complementary error function as
 // exp2 of a polynomial:  -log2 erfc(a / sqrt 2) = a (c1 + a (c2 + a (c3 + a (c4 + a c5)))), fitted on [0, 6] with the
@@ -256,7 +257,7 @@ __device__ __forceinline__ float quick_gelu(float x) {
     return __builtin_fmaf(-a, s, fmaxf(x, 0.0f));
 }
 __device__ __forceinline__ f2v quick_gelu2(f2v x) { return f2v{quick_gelu(x[0]), quick_gelu(x[1])}; }
-constexpr int GBM = 128, GBN = 128, GBK = 64, GLD = GBK + 8;
+constexpr int GBK = 64, GLD = GBK + 8;
 
 template <int EPI>
 __global__ __launch_bounds__(256) void k_gemm_tn(const half_t* __restrict__ A, const half_t* __restrict__ W,
@@ -384,7 +385,7 @@ __global__ __launch_bounds__(256) void k_gemm_tn(const half_t* __restrict__ A, c
 // 256 threads = 4 waves, one 32 x 32 MFMA tile each; BK = 64, two register-staged LDS buffers.
 // Requires M % 64 == 0, N % 64 == 0, (K / S) % 64 == 0.
 // ------------------------------------------------------------------------------------------------
-constexpr int SBM = 64, SBN = 64, SBK = 64, SLD = SBK + 8;
+constexpr int SLD = SBK + 8;
 
 template <int EPI>
 __global__ __launch_bounds__(256) void k_gemm_splitk(const half_t* __restrict__ A, const half_t* __restrict__ W,
@@ -496,8 +497,6 @@ __global__ __launch_bounds__(256) void k_gemm_splitk(const half_t* __restrict__ 
     if (tid == 0) __hip_atomic_store(counters + t, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next launch
 }
 
-constexpr int LBM = 256, LBN = 256;   // the 256 x 256 tile of the 8-phase / persistent kernels
-
 // ------------------------------------------------------------------------------------------------
 // k_gemm_dma16_tn: 128 (M) x 256 (N) tile, 4 waves (2 x 2, wave tile 64 x 128 = 2 x 4 MFMA tiles), BK = 32,
 // THREE 24 KB LDS slots filled by LDS-DMA (72 KB per workgroup), so that TWO workgroups share a CU.
@@ -509,7 +508,7 @@ constexpr int LBM = 256, LBN = 256;   // the 256 x 256 tile of the 8-phase / per
 // LDS rows are 64 B (4 chunks of 16 B); chunk c of row r sits at physical chunk c ^ ((r >> 2) & 3): the DMA
 // lanes fetch the matching logical chunk, and a ds_read_b128 lane group (16 rows) touches 16 distinct slots.
 // ------------------------------------------------------------------------------------------------
-constexpr int DBM = 128, DBN = 256, DBK = 32, DTHREADS = 256, DSLOT = 24576, DLDS = 3 * DSLOT;
+constexpr int DTHREADS = 256, DSLOT = 24576, DLDS = 3 * DSLOT;
 
 // The kernel described above, with 16x16x32 MFMAs (the guide measures that MFMA shape at 1.12-1.15x the FLOP/s of 32x32x16 with
 // operands from LDS; the 32x32x16 form of round 1 measured 4-6 % slower and is gone).  Lane (r = lane & 15, kb = lane >> 4) reads rows r of a 16-row tile at k-block kb, so the chunk
@@ -820,10 +819,9 @@ struct GemmWs {
     unsigned* cnt = nullptr;     // [kSkMaxTiles][2] arrivals + XCD mask, then 4 statistics words
     size_t bytes = 0;
 };
-constexpr int kSkMaxTiles = 256;
 
 // geometry of the 256 x 256 x 64 kernels (k_gemm8p_tn, k_gemm9_tn): 512 threads, eight 16-KB half-tile slots + a dump slot
-constexpr int PBM = 256, PBN = 256, PBK = 64, PTHREADS = 512, PSLOT = 16384, PLDS = 2 * 4 * PSLOT + PSLOT;
+constexpr int PTHREADS = 512, PSLOT = 16384, PLDS = 2 * 4 * PSLOT + PSLOT;
 // ------------------------------------------------------------------------------------------------
 // The co-operative split-K finish, shared by the 8-phase kernel's tail tiles and the persistent kernel's whole-product cut (round 5):
 // `acc` holds this slice's partial sums of the tile in the kernel's own register layout (both kernels: acc[mi][ni], 16-row block mi of
@@ -3109,7 +3107,6 @@ static void launch_attention2(const half_t* qkv, const int* mask, int B, int T, 
     hipLaunchKernelGGL(k_attention2<MODE>, dim3(grid), dim3(64 * waves), lds, st, qkv, mask, B, T, heads * ADH, ct, seq_off, ctx, nsplit);
 }
 
-constexpr int kSplitMax = 8, kSplitMaxRows = 64;  // split-K only for single short sequences (measured: slower from 256 tokens)
 constexpr int kEncResidentT = 512;   // longest sequence whose K / V^T fit the resident-attention kernel's LDS
 constexpr int kEncMaxT = 8192;       // longest sequence the encoder takes (streaming attention beyond kEncResidentT)
 
@@ -3325,15 +3322,6 @@ static int device_cus() {
     return n;
 }
 
-// split count for the small-M kernel: enough workgroups to cover the chip, at least two K-steps per split
-static int pick_splits(int tiles, int K) {
-    const int steps = K / SBK;
-    int best = 1;
-    for (int sp = 1; sp <= kSplitMax; ++sp)
-        if (steps % sp == 0 && steps / sp >= 2 && tiles * sp <= 512) best = sp;
-    return best;
-}
-
 template <int EPI>
 static hipError_t gemm_splitk(const half_t* A, const half_t* W, const float* bias, const half_t* R, half_t* C, int Mrows,
                               int N, int K, float* part, unsigned* cnt, hipStream_t st) {
@@ -3343,8 +3331,6 @@ static hipError_t gemm_splitk(const half_t* A, const half_t* W, const float* bia
     return hipGetLastError();
 }
 
-static long long p8_min_wgs();   // tiles from which the 8-phase kernel is the default (defined with the LnFold helpers)
-static bool p8_min_forced();     // the test hook vf_debug_gemm_8p_min_wgs has set that number: the same gate then applies to k_gemm9_tn
 static std::atomic<int> g_loop2{getenv("VF_GEMM_8P_LOOP2") ? atoi(getenv("VF_GEMM_8P_LOOP2")) : 1};   // default: the two-phase loop (round 3: 2-7 % on the products, 0.7-2 % on the forward)
 extern "C" int vf_debug_gemm_8p_loop2(int on) { return on >= 0 ? g_loop2.exchange(on ? 1 : 0) : g_loop2.load(); }   // A/B: two-phase main loop of k_gemm8p_tn
 static std::atomic<unsigned long long*> g_gemm9_dbg{nullptr};
@@ -3360,8 +3346,11 @@ static std::atomic<int> g_gemm9_split{-1};   // -1: VF_GEMM_9_SPLIT decides; 0 /
 extern "C" int vf_debug_gemm9_split(int on) { return g_gemm9_split.exchange(on < 0 ? -1 : (on ? 1 : 0)); }   // A/B: the whole-product K cut inside the persistent kernel
 static std::atomic<int> g_gemm9{-1};   // -1: VF_GEMM_9 decides; 0 / 1: forced by the test hook
 extern "C" int vf_debug_gemm9(int on) { return g_gemm9.exchange(on < 0 ? -1 : (on ? 1 : 0)); }   // A/B: the persistent register-epilogue kernel as the default large product
+static std::atomic<long long> g_p8_min_override{-1};
+// Test hook: lower the tile count from which the 8-phase kernel (and with it the folded LayerNorm) is used, so that a small model
+// exercises that path.
+extern "C" long long vf_debug_gemm_8p_min_wgs(long long v) { return g_p8_min_override.exchange(v); }
 static LnFold lf_plain() { LnFold l{}; l.loop2 = g_loop2.load(std::memory_order_relaxed); return l; }
-static int device_cus();
 
 // Split-K tail of the 8-phase products: fp32 partials + arrival counters.  The workspace belongs to a HANDLE (round 4: it
 // used to be process-global, which raced between handles on different threads / devices): each encoder / decoder / vision
@@ -3371,12 +3360,11 @@ static int device_cus();
 static std::atomic<int> g_splitk_tail{getenv("VF_NO_SPLITK_TAIL") ? 0 : getenv("VF_SPLITK_TAIL") ? std::min(2, std::max(0, atoi(getenv("VF_SPLITK_TAIL")))) : 1};
 extern "C" int vf_debug_splitk_tail(int on) { return on >= 0 ? g_splitk_tail.exchange(on > 2 ? 2 : on) : g_splitk_tail.load(); }   // 0 off, 1 long-K products only (default), 2 every product with a partial last round
 static std::atomic<int> g_sk_dbg{getenv("VF_SK_DBG") ? atoi(getenv("VF_SK_DBG")) : 0};   // sk_coop_finish's experiment / test bits
-static bool splitk_tail_on() { return g_splitk_tail.load(std::memory_order_relaxed) != 0; }
 static std::mutex g_gws_mu;
 static std::vector<GemmWs*> g_gws_all;    // every live workspace (statistics hook only)
 static hipError_t gws_ensure(GemmWs& g, hipStream_t zero_on) {   // current device = the handle's; zero_on: the handle's stream (the counters are zeroed in front of its first product)
     if (g.ws) return hipSuccess;
-    const size_t nb = (size_t)std::max(device_cus(), kSkMaxTiles) * PBM * PBN * sizeof(float);
+    const size_t nb = gemm_ws_bytes(device_cus());
     hipError_t e = hipMalloc((void**)&g.ws, nb);
     if (e == hipSuccess) e = hipMalloc((void**)&g.cnt, ((size_t)kSkMaxTiles * 2 + 4) * sizeof(unsigned));
     if (e == hipSuccess) e = zero_on ? hipMemsetAsync(g.cnt, 0, ((size_t)kSkMaxTiles * 2 + 4) * sizeof(unsigned), zero_on) : hipMemset(g.cnt, 0, ((size_t)kSkMaxTiles * 2 + 4) * sizeof(unsigned));
@@ -3422,186 +3410,110 @@ extern "C" int vf_debug_splitk_stats(unsigned* out2, int dbg) {
     return seen ? 1 : 0;
 }
 
+// The knobs of a product's route (vf_gemm_route.h): the environment, read once per process, under the test hooks, read on each call.
+static GemmKnobs gemm_knobs(int force_kind = 0) {
+    static const GemmKnobs env = [] {
+        const auto i = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
+        const auto ll = [](const char* name, long long dflt) { const char* e = getenv(name); return e ? atoll(e) : dflt; };
+        GemmKnobs k;
+        k.kind = i("VF_GEMM_KIND", k.kind);
+        k.dma_min_wgs = ll("VF_GEMM_DMA_MIN_WGS", k.dma_min_wgs);
+        k.p8_min_wgs = ll("VF_GEMM_8P_MIN_WGS", k.p8_min_wgs);
+        k.p8_f32_min_wgs = ll("VF_GEMM_8P_F32_MIN_WGS", k.p8_f32_min_wgs);
+        k.gemm9 = i("VF_GEMM_9", k.gemm9);
+        k.gemm9_min_wgs = ll("VF_GEMM_9_MIN_WGS", k.gemm9_min_wgs);
+        k.gemm9_split = i("VF_GEMM_9_SPLIT", k.gemm9_split);
+        k.split_min_k = i("VF_GEMM_9_SPLIT_MINK", k.split_min_k);
+        k.split_min_kt = i("VF_GEMM_9_SPLIT_MINKT", k.split_min_kt);
+        k.gemm9_streamk = i("VF_GEMM_9_STREAMK", k.gemm9_streamk);
+        k.streamk_min_saved = i("VF_GEMM_9_STREAMK_MIN_SAVED", k.streamk_min_saved);
+        k.stagger_pct = i("VF_GEMM_9_STAGGER", k.stagger_pct);
+#ifdef VF_EXPERIMENTS
+        k.experiments = true;
+#endif
+        return k;
+    }();
+    GemmKnobs k = env;
+    if (force_kind) k.kind = force_kind;
+    const long long p8 = g_p8_min_override.load(std::memory_order_relaxed);
+    if (p8 >= 0) { k.p8_min_wgs = p8; k.p8_forced = true; }
+    const int h9 = g_gemm9.load(std::memory_order_relaxed), hsplit = g_gemm9_split.load(std::memory_order_relaxed),
+              hsk = g_gemm9_streamk.load(std::memory_order_relaxed);
+    if (h9 >= 0) k.gemm9 = h9;
+    if (hsplit >= 0) k.gemm9_split = hsplit;
+    if (hsk >= 0) k.gemm9_streamk = hsk;
+    k.splitk_tail = g_splitk_tail.load(std::memory_order_relaxed);   // (VF_SPLITK_TAIL / VF_NO_SPLITK_TAIL are its initial value)
+    return k;
+}
+
+static GemmIn gemm_in(int epi, int M, int N, int K, int force_kind, bool has_ws, size_t ws_bytes) {
+    GemmIn in;
+    in.epi = epi; in.M = M; in.N = N; in.K = K; in.n_cu = device_cus();
+    in.has_ws = has_ws; in.ws_bytes = has_ws ? ws_bytes : 0;
+    in.knobs = gemm_knobs(force_kind);
+    return in;
+}
+
+// One product C = epi(A W^T): route_gemm (vf_gemm_route.h) picks the kernel, its grid and its cut; this launches it.
 template <int EPI>
 static hipError_t gemm(const half_t* A, const half_t* W, const float* bias, const half_t* R, half_t* C, int M, int N,
                        int K, hipStream_t st, int force_kind = 0, GemmWs* gws = nullptr) {
-    // Tile choice (VF_GEMM_KIND overrides for A/B runs: 5 = DMA 128x256 with 16x16x32 MFMAs (the default large-problem
-    // kernel), 6 = its 128-wide instance, 1 = 128x256 with 32x32x16 MFMAs, 2 = 256x256, 3 = 128x128):
-    //  * 128 x 256 DMA tiles, two workgroups per CU, when they give at least VF_GEMM_DMA_MIN_WGS workgroups
-    //    (16x16x32 MFMAs: 4 % faster in isolation, 6 % on the 100-pair forward than the 32x32x16 form);
-    //  * 128 x 128 register-staged tiles for everything smaller (micro-batches of 8 pairs, single queries).
-    // The 256 x 256 single-workgroup-per-CU kernel measured equal in isolation and 6 % slower inside the forward
-    // (its GELU epilogue has nothing to hide under); it stays selectable for experiments.
-    static const int env_kind = getenv("VF_GEMM_KIND") ? atoi(getenv("VF_GEMM_KIND")) : 0;
-    const int kind = force_kind ? force_kind : env_kind;
-    static const long long dma_min = getenv("VF_GEMM_DMA_MIN_WGS") ? atoll(getenv("VF_GEMM_DMA_MIN_WGS")) : 384;
-    const bool dma_ok = M % DBM == 0 && N % DBN == 0 && K % DBK == 0;
-    const bool big_ok = M % LBM == 0 && N % LBN == 0;
-    if constexpr (EPI == EPI_RESIDUAL_F32) {   // fp32 residual epilogue: 8-phase, the 128 x 256 DMA kernel or the 128 x 128 one
-        static const long long p8f_min = getenv("VF_GEMM_8P_F32_MIN_WGS") ? atoll(getenv("VF_GEMM_8P_F32_MIN_WGS")) : 256;   // (Qwen3-4B shape, 320 tiles: 66.4 vs 68.9 ms per forward)
-        if (big_ok && K % PBK == 0 && K >= 2 * PBK && (kind == 7 || (kind == 0 && (long long)(M / PBM) * (N / PBN) >= p8f_min))) {
-            hipLaunchKernelGGL(k_gemm8p_tn<EPI>, dim3((N / PBN) * (M / PBM)), dim3(PTHREADS), PLDS, st, A, W, bias, R, C, M, N, K, lf_plain());
-            return hipGetLastError();
+    const bool has_ws = gws && gws->ws;
+    const GemmRoute r = route_gemm(gemm_in(EPI, M, N, K, force_kind, has_ws, has_ws ? gws->bytes : 0));
+    constexpr bool epi9 = EPI == EPI_BIAS || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_QGELU || EPI == EPI_BIAS_RESIDUAL;   // the epilogues k_gemm9_tn is built for ...
+    constexpr bool epi9_cut = epi9 && EPI != EPI_BIAS_QGELU;                                                               // ... and its cut forms
+    const dim3 grid(r.grid);
+    switch (r.kernel) {
+    case kGemmTn128:
+        hipLaunchKernelGGL(k_gemm_tn<EPI>, grid, dim3(256), (size_t)2 * (GBM + GBN) * GLD * sizeof(half_t), st, A, W, bias, R, C, M, N, K);
+        return hipGetLastError();
+    case kGemmDma16:
+        hipLaunchKernelGGL((k_gemm_dma16_tn<EPI, 256>), grid, dim3(DTHREADS), DLDS, st, A, W, bias, R, C, M, N, K);
+        return hipGetLastError();
+    case kGemm8p: {
+        LnFold lf = lf_plain();
+        if (r.slices) {   // the split-K tail (LnFold::sk_*): `tail_tiles` tiles behind `full_tiles` whole ones, each in `slices` slices
+            lf.sk_ws = gws->ws; lf.sk_cnt = gws->cnt; lf.sk_nfull = r.full_tiles; lf.sk_S = r.slices; lf.sk_ntail = r.tail_tiles;
+            lf.sk_stat = gws->cnt + 2 * (size_t)kSkMaxTiles; lf.sk_dbg = g_sk_dbg.load(std::memory_order_relaxed);
         }
-        if (dma_ok && (long long)(M / DBM) * (N / DBN) >= dma_min && kind != 3) {
-            hipLaunchKernelGGL((k_gemm_dma16_tn<EPI, 256>), dim3((N / DBN) * (M / DBM)), dim3(DTHREADS), DLDS, st, A, W, bias, R, C, M, N, K);
-            return hipGetLastError();
-        }
-        const dim3 grid32((N / GBN) * (M / GBM));
-        hipLaunchKernelGGL(k_gemm_tn<EPI>, grid32, dim3(256), (size_t)2 * (GBM + GBN) * GLD * sizeof(half_t), st, A, W, bias, R, C, M, N, K);
+        hipLaunchKernelGGL(k_gemm8p_tn<EPI>, grid, dim3(PTHREADS), PLDS, st, A, W, bias, R, C, M, N, K, lf);
         return hipGetLastError();
     }
-    else {
-    // 256 x 256 8-phase tiles (one workgroup per CU) once they fill the chip 1.5 times over; measured against the
-    // 128 x 256 DMA kernel at M = 51200: 225 / 79 / 265 / 246 us vs 278 / 79 / 296 / 295 us (QKV / out / FFN-up / FFN-down
-    // shapes of a 768-wide encoder; the vendor library: 210 / 66 / 234 / 217)
-    const long long p8_min = p8_min_wgs();
-    if constexpr (EPI == EPI_BIAS || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_QGELU || EPI == EPI_BIAS_RESIDUAL) {
-        // round 4: the persistent two-phase kernel with the register-direct epilogue (k_gemm9_tn)
-        // Default (VF_GEMM_9=0 switches it off) wherever the partial last round does not matter: K < 2048, or whole rounds.  In the 100-pair
-        // forward, per layer (profiles/r04_rerank_layer_8p_vs_gemm9.txt): 768 wide: QKV 167 vs 188 us, out projection 82 vs 87, FFN-up + GELU
-        // 235 vs 271; 1024 wide: 277 vs 281, 129 vs 127, 408 vs 408.  Long-K products with a remainder (FFN-down: K = 3072 / 4096, 600 / 800
-        // tiles) keep the 8-phase kernel, whose split-K tail is worth more there than the persistent pipeline (391 vs 360 us at K = 4096).
-        static const int p9 = getenv("VF_GEMM_9") ? atoi(getenv("VF_GEMM_9")) : 1;
-        const int p9_now = g_gemm9.load(std::memory_order_relaxed) >= 0 ? g_gemm9.load(std::memory_order_relaxed) : p9;
-        // Mid-size products (the per-rank batches of a data-parallel re-rank: 13 / 25 / 50 pairs x 512 tokens = 78 ... 1200 tiles): every
-        // kernel forced on every shape of the layer (tools/gpu_r04_midsize.sh, profiles/r04_midsize_kernels.log) -- the 256 x 256
-        // persistent kernel wins from ~128 tiles on, partial round or not: 12 800 x 768 x 3072 59.6 us against 89.8 (128 x 256 DMA kernel)
-        // and 94.4 (128 x 128), 0.91 x the vendor library; 6 656 x 2304 x 768 27.6 against 34.8 / 41.4.  Below that (78 tiles: out
-        // projection and FFN-down of a 13-pair batch) the small-tile kernels are level or ahead (62.8 vs 56.1 us inside the forward).
-        // The old gate (1.5 rounds of tiles, shared with the 8-phase kernel) left 10-50 % on mid-size batches.
-        static const long long p9_min = getenv("VF_GEMM_9_MIN_WGS") ? atoll(getenv("VF_GEMM_9_MIN_WGS")) : 128;
-        const long long tiles_ll = (long long)(M / PBM) * (N / PBN);
-        // Round 5: LESS than a round of tiles with a long K -- FFN-down of the 13 pairs one rank of an 8-GPU data-parallel re-rank scores
-        // (6 656 x 768 x 3072: 78 tiles = a third of the CUs busy for 62.8 us where the vendor library takes 36.5) -- is cut whole
-        // along K inside the persistent kernel: S slices per tile (8 x ceil(tiles / 8) x S workgroups <= the CUs, each slice >= 8
-        // K-tiles), finished co-operatively through the handle's workspace (sk_coop_finish).  VF_GEMM_9_SPLIT=0 switches it off (A/B).
-        if constexpr (EPI != EPI_BIAS_QGELU) {
-            static const int p9_split = getenv("VF_GEMM_9_SPLIT") ? atoi(getenv("VF_GEMM_9_SPLIT")) : 1;
-            const int split_now = g_gemm9_split.load(std::memory_order_relaxed) >= 0 ? g_gemm9_split.load(std::memory_order_relaxed) : p9_split;
-            static const int split_min_k = getenv("VF_GEMM_9_SPLIT_MINK") ? atoi(getenv("VF_GEMM_9_SPLIT_MINK")) : 2048;      // experiments
-            static const int split_min_kt = getenv("VF_GEMM_9_SPLIT_MINKT") ? atoi(getenv("VF_GEMM_9_SPLIT_MINKT")) : 8;
-            if (big_ok && K % PBK == 0 && K >= split_min_k && (kind == 0 || kind == 11) && p9_now && split_now && !p8_min_forced() && splitk_tail_on() && gws && gws->ws &&
-                tiles_ll <= kSkMaxTiles) {
-                const int tiles = (int)tiles_ll, ncu = device_cus() & ~7, nkt = K / PBK, pad = (tiles + 7) & ~7;
-                int S = 0;
-                for (int c = 4; c >= 2; --c)
-                    if (pad * c <= ncu && nkt / c >= split_min_kt && (size_t)tiles * c * PBM * PBN * sizeof(float) <= gws->bytes) { S = c; break; }
-                if (S >= 2) {
-                    const SkCtx sk{gws->ws, gws->cnt, gws->cnt + 2 * (size_t)kSkMaxTiles, S, g_sk_dbg.load(std::memory_order_relaxed)};
-                    g_gemm9_split_launches.fetch_add(1, std::memory_order_relaxed);
-                    hipLaunchKernelGGL((k_gemm9_tn<EPI, true>), dim3(pad * S), dim3(PTHREADS), RLDS, st, A, W, bias, R, C, M, N, K, 0, g_gemm9_dbg.load(std::memory_order_relaxed), sk);
-                    return hipGetLastError();
-                }
-            }
+    case kGemm9:
+        if constexpr (epi9) {
+            hipLaunchKernelGGL(k_gemm9_tn<EPI>, grid, dim3(PTHREADS), RLDS, st, A, W, bias, R, C, M, N, K, r.stagger_ticks, g_gemm9_dbg.load(std::memory_order_relaxed), SkCtx{nullptr, nullptr, nullptr, 0, 0});
+            return hipGetLastError();
         }
-        // Round 5, stream-K (k_gemm9_tn<EPI, 2>): a product whose LAST round is mostly empty -- 1.2 rounds of FFN-up at 13 pairs, 2.3 of
-        // FFN-up / 0.6 of FFN-down at 25, 2.3 of FFN-down at 100 -- deals the K-tiles out evenly instead of the tiles, when that saves at
-        // least VF_GEMM_9_STREAMK_MIN_SAVED K-tiles of a workgroup's time over whole tiles.  Built, exact, deterministic -- and SLOWER on
-        // every shape of the forward, so OFF unless asked for (VF_GEMM_9_STREAMK=1, vf_debug_gemm9_streamk(1), kind 12): nearly every
-        // workgroup dumps one 256-KB fp32 partial and reads one back -- 64 MB written through and 64 MB read per launch, ~27 us at what the
-        // chip sustains for that -- against the 10-20 us the even deal saves: 6 656 x 3072 x 768 64.7 us against 49.7 with whole tiles,
-        // 12 800 x 768 x 3072 90.8 against 79.0, the 13- / 25- / 100-pair forwards 2.62 / 4.38 / 13.0 ms against 2.39 / 3.77 / 11.3, same
-        // box, same call (profiles/r05_streamk.log).  The whole-product cut above pays the same toll per slice but only where two thirds of
-        // the chip would otherwise idle.
-#ifdef VF_EXPERIMENTS   // (off even there unless asked for; the default build does not carry the kernel)
-        if constexpr (EPI != EPI_BIAS_QGELU) {
-            static const int p9_sk = getenv("VF_GEMM_9_STREAMK") ? atoi(getenv("VF_GEMM_9_STREAMK")) : 0;
-            static const int sk_min_saved = getenv("VF_GEMM_9_STREAMK_MIN_SAVED") ? atoi(getenv("VF_GEMM_9_STREAMK_MIN_SAVED")) : 5;
-            const int sk_now = g_gemm9_streamk.load(std::memory_order_relaxed) >= 0 ? g_gemm9_streamk.load(std::memory_order_relaxed) : p9_sk;
-            if (big_ok && K % PBK == 0 && K >= 4 * PBK && (kind == 12 || (kind == 0 && p9_now && sk_now && !p8_min_forced())) && gws && gws->ws) {
-                const int ncu = device_cus() & ~7, nkt = K / PBK;
-                const long long dp_len = (tiles_ll + ncu - 1) / ncu * nkt, sk_len = (tiles_ll * nkt + ncu - 1) / ncu;
-                if ((kind == 12 || dp_len - sk_len >= sk_min_saved) && ncu >= 8 && ncu <= kSkMaxTiles && tiles_ll >= 8 && tiles_ll <= 12ll * ncu /* <= 16 segments per workgroup */ &&
-                    (tiles_ll / 8) * nkt / (ncu / 8) >= 6 && (size_t)ncu * PBM * PBN * sizeof(float) <= gws->bytes) {
-                    const SkCtx sk{gws->ws, gws->cnt, gws->cnt + 2 * (size_t)kSkMaxTiles, 0, g_sk_dbg.load(std::memory_order_relaxed)};
-                    g_gemm9_streamk_launches.fetch_add(1, std::memory_order_relaxed);
-                    hipLaunchKernelGGL((k_gemm9_tn<EPI, 2>), dim3(ncu), dim3(PTHREADS), RLDS, st, A, W, bias, R, C, M, N, K, 0, g_gemm9_dbg.load(std::memory_order_relaxed), sk);
-                    return hipGetLastError();
-                }
-            }
+        break;
+    case kGemm9Split:
+        if constexpr (epi9_cut) {
+            const SkCtx sk{gws->ws, gws->cnt, gws->cnt + 2 * (size_t)kSkMaxTiles, r.slices, g_sk_dbg.load(std::memory_order_relaxed)};
+            g_gemm9_split_launches.fetch_add(1, std::memory_order_relaxed);
+            hipLaunchKernelGGL((k_gemm9_tn<EPI, true>), grid, dim3(PTHREADS), RLDS, st, A, W, bias, R, C, M, N, K, 0, g_gemm9_dbg.load(std::memory_order_relaxed), sk);
+            return hipGetLastError();
+        }
+        break;
+    case kGemm9StreamK:
+#ifdef VF_EXPERIMENTS   // (the default build does not carry the kernel, and says so to the route: GemmKnobs::experiments)
+        if constexpr (epi9_cut) {
+            const SkCtx sk{gws->ws, gws->cnt, gws->cnt + 2 * (size_t)kSkMaxTiles, 0, g_sk_dbg.load(std::memory_order_relaxed)};
+            g_gemm9_streamk_launches.fetch_add(1, std::memory_order_relaxed);
+            hipLaunchKernelGGL((k_gemm9_tn<EPI, 2>), grid, dim3(PTHREADS), RLDS, st, A, W, bias, R, C, M, N, K, 0, g_gemm9_dbg.load(std::memory_order_relaxed), sk);
+            return hipGetLastError();
         }
 #endif
-        const bool p9_size = p8_min_forced() ? tiles_ll >= p8_min : tiles_ll >= p9_min;
-        if (big_ok && K % PBK == 0 && K >= 4 * PBK && (kind == 10 || (kind == 0 && p9_now && p9_size))) {
-            const int tiles = (M / PBM) * (N / PBN), ncu = device_cus() & ~7, nkt = K / PBK;
-            const int G = tiles < ncu ? tiles : ncu;
-            // long-K products of MORE than two rounds with a remainder keep the 8-phase kernel (split-K tail): 800 tiles at K = 4096 360 vs
-            // 391 us, 600 at K = 3072 231 vs 235; up to two rounds the persistent kernel is level or ahead (400 tiles at K = 4096: 178 vs
-            // 188 us; 300 at K = 3072: 131 vs 126; profiles/r04_midsize_kernels.log, r04_midsize_large.log)
-            // Round 5, after the relaxed arrival made the finish cheaper: between one and two rounds, when the remainder can be cut at least
-            // in two (<= half the CUs), the 8-phase kernel's tail wins as well -- 300 tiles at K = 3072 (FFN-down of 50 pairs) 136 vs
-            // 145-147 us; a remainder too large to cut stays here (450 tiles: 180-183 vs 186-187; profiles/r05_tail8p_vs_gemm9.log)
-            const int rem_pad = ((tiles % ncu) + 7) & ~7;
-            const bool tail_cuttable = K >= 2048 && tiles > ncu && tiles % ncu != 0 && 2 * rem_pad <= ncu && splitk_tail_on() && gws && gws->ws;
-            if (kind == 10 || K < 2048 || tiles % G == 0 || (tiles <= 2 * ncu && !tail_cuttable)) {
-                // a tile's time in ticks of the 100 MHz real-time counter: ~1.5 us per K-tile + 2 (the stagger spreads the workgroups over it)
-                static const int stg = getenv("VF_GEMM_9_STAGGER") ? atoi(getenv("VF_GEMM_9_STAGGER")) : 100;   // per cent of a tile's time; 0 = off
-                const int ticks = tiles > ncu ? (int)((150ll * nkt + 200) * stg / 100) : 0;
-                hipLaunchKernelGGL(k_gemm9_tn<EPI>, dim3(G), dim3(PTHREADS), RLDS, st, A, W, bias, R, C, M, N, K, ticks, g_gemm9_dbg.load(std::memory_order_relaxed), SkCtx{nullptr, nullptr, nullptr, 0, 0});
-                return hipGetLastError();
-            }
-        }
+        break;
     }
-    // Less than HALF a round of 256 x 256 tiles with a very long K (FFN-down of a 13-pair batch at 1024 wide: 104 tiles, K = 4096): the
-    // 8-phase kernel with EVERY tile cut along K (2-4 slices, co-operative finish) -- 6656 x 1024 x 4096 67-68 us against 78-80 (128 x 128
-    // tiles) and 80 (persistent kernel, 104 workgroups); the 13-pair forward 6.36 -> 6.17 ms.  At K = 3072 (78 tiles, 768 wide) the cut wins
-    // 3 % in isolation (55-56 us against 56-58) and LOSES 4 % inside the forward (2.52 against 2.42 ms: 40 MB of partials through a cold
-    // L2), so the gate is K >= 4096 (profiles/r04_skcoop.log, r04_skcoop_forward.log)
-    bool sub_split = false;
-    if constexpr (EPI == EPI_BIAS || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_RESIDUAL) {
-        const long long t_ll = big_ok ? (long long)(M / PBM) * (N / PBN) : 0;
-        const int cus = device_cus();
-        const long long pad_ll = (t_ll + 7) & ~7ll;
-        const long long s_ll = pad_ll > 0 ? std::min<long long>(std::min<long long>(cus / pad_ll, K / PBK / 2), 4) : 0;   // the slice count chosen below
-        sub_split = kind == 0 && !p8_min_forced() && big_ok && K % PBK == 0 && K >= 4096 && t_ll > 0 && s_ll >= 2 &&
-                    splitk_tail_on() && gws && gws->ws && t_ll <= kSkMaxTiles && (size_t)t_ll * s_ll * PBM * PBN * sizeof(float) <= gws->bytes;
-    }
-    bool tail8 = false;   // one to two rounds, long K, a remainder that can be cut at least in two: this kernel's split-K tail (see the persistent kernel's gate above)
-    if constexpr (EPI == EPI_BIAS || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_RESIDUAL) {
-        const long long t_ll = big_ok ? (long long)(M / PBM) * (N / PBN) : 0;
-        const int ncu8 = device_cus() & ~7;
-        tail8 = kind == 0 && ncu8 > 0 && K >= 2048 && K % PBK == 0 && t_ll > ncu8 && t_ll <= 2ll * ncu8 && t_ll % ncu8 != 0 && 2 * (((int)(t_ll % ncu8) + 7) & ~7) <= ncu8 &&
-                splitk_tail_on() && gws && gws->ws && !p8_min_forced();
-    }
-    if (big_ok && K % PBK == 0 && K >= 2 * PBK && (kind == 7 || sub_split || tail8 || (kind == 0 && ((long long)(M / PBM) * (N / PBN) >= p8_min ||
-                                                                               (K >= 2048 && (long long)(M / PBM) * (N / PBN) > 2 * (device_cus() & ~7) && !p8_min_forced()))))) {
-        // (Peeling the rows of a partial last round -- 600 tiles on 256 CUs are 2.34 rounds of work in 3 -- into the 128 x 256
-        // kernel was measured: no gain, the half-size workgroups alone on their CUs run at a quarter of the MFMA rate.)
-        // Round 3: the tiles of the partial last round are cut along K instead (LnFold::sk_*): S slices per tail tile so that
-        // the slices still fit one round, each at least two K-tiles long.
-        const int tiles = (N / PBN) * (M / PBM);
-        LnFold lf = lf_plain();
-        int grid = tiles;
-        if constexpr (EPI == EPI_BIAS || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_RESIDUAL) {
-            // a product of less than one round (tiles <= CUs: the per-rank batches of a data-parallel re-rank) is cut whole
-            const int cus = device_cus(), nk = K / PBK;
-            const int ntail = cus <= 0 ? 0 : (tiles > cus ? tiles % cus : tiles), pad = (ntail + 7) & ~7;
-            // Measured (tools/gpu_r03_splitk.sh): a slice pays ~5 us to leave its 256 KB of partials and the last arrival ~9 us per
-            // 256 KB it reads back from memory (one CU pulls 50-60 GB/s), so the cut only pays where half a tile's main loop is
-            // worth more: long-K products (K >= 2048: FFN-down), two slices.  Cutting the K = 768 products (S = 2..4) made the
-            // forward SLOWER (12.53 vs 12.26 ms); the general form stays reachable through vf_debug_splitk_tail(2).
-            const int mode = g_splitk_tail.load(std::memory_order_relaxed);
-            int S = ntail > 0 ? std::min(std::min(cus / pad, nk / 2), 4) : 0;
-            if (mode == 1 && !sub_split) S = (nk >= 32 && S >= 2 && tiles > cus) ? 2 : 0;
-            if (S >= 2 && splitk_tail_on() && gws && gws->ws && ntail <= kSkMaxTiles && (size_t)ntail * S * PBM * PBN * sizeof(float) <= gws->bytes) {
-                lf.sk_ws = gws->ws; lf.sk_cnt = gws->cnt; lf.sk_nfull = tiles - ntail; lf.sk_S = S; lf.sk_ntail = ntail;
-                lf.sk_stat = gws->cnt + 2 * (size_t)kSkMaxTiles; lf.sk_dbg = g_sk_dbg.load(std::memory_order_relaxed);
-                grid = tiles - ntail + pad * S;
-            }
-        }
-        hipLaunchKernelGGL(k_gemm8p_tn<EPI>, dim3(grid), dim3(PTHREADS), PLDS, st, A, W, bias, R, C, M, N, K, lf);
-        return hipGetLastError();
-    }
-    if (dma_ok && (kind == 5 || (kind == 0 && (long long)(M / DBM) * (N / DBN) >= dma_min))) {
-        hipLaunchKernelGGL((k_gemm_dma16_tn<EPI, 256>), dim3((N / DBN) * (M / DBM)), dim3(DTHREADS), DLDS, st, A, W, bias, R, C, M, N, K);
-        return hipGetLastError();
-    }
-    const dim3 grid((N / GBN) * (M / GBM));
-    const size_t lds = (size_t)2 * (GBM + GBN) * GLD * sizeof(half_t);
-    hipLaunchKernelGGL(k_gemm_tn<EPI>, grid, dim3(256), lds, st, A, W, bias, R, C, M, N, K);
-    return hipGetLastError();
-    }
+    return hipErrorInvalidValue;   // a route to a kernel this epilogue (or this build) does not have: never a quiet substitute
+}
+
+// Test hook: what gemm() would decide right now for one product -- the live knobs, the device's CU count and a workspace sized as
+// gws_ensure sizes it -- as {kernel, grid, slices, tail tiles, full tiles, stagger ticks} (GemmRoute).  Launches nothing.
+extern "C" int vf_debug_gemm_route(int M, int N, int K, int epi, int kind, int* out6) {
+    if (!out6 || M <= 0 || N <= 0 || K <= 0 || M % 128 || N % 128 || K % 32) return -2;
+    const GemmRoute r = route_gemm(gemm_in(epi, M, N, K, kind, true, gemm_ws_bytes(device_cus())));
+    out6[0] = (int)r.kernel; out6[1] = r.grid; out6[2] = r.slices; out6[3] = r.tail_tiles; out6[4] = r.full_tiles; out6[5] = r.stagger_ticks;
+    return 0;
 }
 
 // Gated MLP front half in one launch: C[M][F] = act(A . Wgate^T) * (A . Wup^T), Wgu = [gate rows (F) | up rows (F)] x K.  Returns
@@ -3610,7 +3522,7 @@ static bool gemm_gated(const half_t* A, const half_t* Wgu, half_t* C, int M, int
     static const bool off = getenv("VF_NO_GATED_GEMM") != nullptr;   // A/B switch
     const int N = 2 * F;
     *er = hipSuccess;
-    if (off || M % PBM || N % PBN || F % 128 || K % PBK || K < 2 * PBK || (long long)(M / PBM) * (N / PBN) < 384) return false;
+    if (off || !gated_ok(M, F, K)) return false;
     if (act_kind == 1)
         hipLaunchKernelGGL(k_gemm8p_tn<EPI_GATED_GELU>, dim3((N / PBN) * (M / PBM)), dim3(PTHREADS), PLDS, st, A, Wgu, nullptr, nullptr, C, M, N, K, lf_plain());
     else
@@ -3624,10 +3536,7 @@ static hipError_t gemm_skinny(const half_t* A, const half_t* W, const float* bia
                               int K, hipStream_t st, float* part = nullptr, unsigned* counters = nullptr) {
     // K split over workgroups when K is long and the column tiles alone leave most of the chip idle (see the kernel)
     static const bool no_split = getenv("VF_NO_SKINNY_SPLIT") != nullptr;
-    int S = 1;
-    if (part && counters && !no_split && K >= 2048 && N / 16 <= 64 && N / 16 <= 4096)
-        for (int c = 2; c <= kSplitMax; ++c)
-            if (K % (c * 256) == 0 && (N / 16) * c <= 256) S = c;
+    const int S = skinny_slices(N, K, part && counters && !no_split);
     const dim3 grid((N / 16) * S), block(kSkinnyWaves * 64);
     switch ((Mvalid + 15) >> 4) {   // 16-row tiles that hold real rows
     case 1: hipLaunchKernelGGL((k_gemm_skinny<EPI, 1>), grid, block, 0, st, A, W, bias, R, C, Mvalid, N, K, S, part, counters); break;
@@ -3662,7 +3571,6 @@ __global__ __launch_bounds__(256) void k_fold_ln(const half_t* __restrict__ W, c
     if (lane == 0) { colsum[n] = cs; cvec[n] = cv + b[n]; }
 }
 
-static std::atomic<long long> g_p8_min_override{-1};
 static std::atomic<long long> g_ln_fold_forwards{0};
 // MEASURED SLOWER, so off unless asked for (VF_LN_FOLD=1 / vf_debug_ln_fold(1)): the two k_layernorm launches of a layer cost
 // 2 x 29.5 us; the folded form removes them and adds their arithmetic to four epilogues that run on the MFMA waves with
@@ -3670,16 +3578,8 @@ static std::atomic<long long> g_ln_fold_forwards{0};
 // (tools/gpu_r03_fold.sh).  It is exact to the same tolerances (errors vs HF fp32 slightly smaller: x is never rounded to fp16).
 static std::atomic<int> g_ln_fold{getenv("VF_LN_FOLD") ? 1 : 0};
 extern "C" int vf_debug_ln_fold(int on) { return on >= 0 ? g_ln_fold.exchange(on ? 1 : 0) : g_ln_fold.load(); }
-// Test hooks: lower the tile count from which the 8-phase kernel (and with it the folded LayerNorm) is used, so that a small
-// model exercises that path; forwards that took the folded path so far.
-extern "C" long long vf_debug_gemm_8p_min_wgs(long long v) { return g_p8_min_override.exchange(v); }
+// Test hook: forwards that took the folded path so far (vf_debug_gemm_8p_min_wgs lowers the tile count from which a small model takes it).
 extern "C" long long vf_debug_ln_fold_forwards() { return g_ln_fold_forwards.load(std::memory_order_relaxed); }
-static bool p8_min_forced() { return g_p8_min_override.load(std::memory_order_relaxed) >= 0; }
-static long long p8_min_wgs() {
-    static const long long env = getenv("VF_GEMM_8P_MIN_WGS") ? atoll(getenv("VF_GEMM_8P_MIN_WGS")) : 384;
-    const long long o = g_p8_min_override.load(std::memory_order_relaxed);
-    return o >= 0 ? o : env;
-}
 
 static size_t fold16_layer(const vf_encoder_config& c) { return (size_t)3 * c.hidden * c.hidden + (size_t)c.ffn * c.hidden; }
 static size_t fold32_layer(const vf_encoder_config& c) { return (size_t)6 * c.hidden + 2 * (size_t)c.ffn; }
@@ -3687,11 +3587,11 @@ static size_t fold32_layer(const vf_encoder_config& c) { return (size_t)6 * c.hi
 // the folded path serves a forward whose four products per layer all take the 8-phase kernel
 static bool enc_fold_ok(const vf_encoder* e, int Mp) {
     const bool off = g_ln_fold.load(std::memory_order_relaxed) == 0;
-    static const int env_kind = getenv("VF_GEMM_KIND") ? atoi(getenv("VF_GEMM_KIND")) : 0;
+    const GemmKnobs kn = gemm_knobs();
     const vf_encoder_config& c = e->cfg;
-    if (off || env_kind != 0) return false;
+    if (off || kn.kind != 0) return false;
     if (Mp % PBM || c.hidden % PBN || c.ffn % PBN || c.hidden < 2 * PBK || !e->stats_a) return false;
-    return (long long)(Mp / PBM) * (c.hidden / PBN) >= p8_min_wgs();
+    return (long long)(Mp / PBM) * (c.hidden / PBN) >= kn.p8_min_wgs;
 }
 
 static int enc_ensure_fold(vf_encoder* e, hipStream_t st) {
@@ -3735,9 +3635,11 @@ static int enc_forward_device(vf_encoder* e, int B, int T, int Tv, bool has_tt, 
     const int H = c.hidden, F = c.ffn, M = seq_off ? Mpk : B * T, Mp = (M + 255) / 256 * 256;
     const int Ms = (M + 63) / 64 * 64;
     static const bool no_splitk = getenv("VF_NO_SPLITK") != nullptr;  // A/B switch
-    const bool small = !no_splitk && Ms <= kSplitMaxRows && H % 64 == 0 && F % 64 == 0;
     static const bool no_skinny = getenv("VF_NO_SKINNY") != nullptr;  // A/B switch
-    const bool skinny = !no_skinny && M <= 64 && H % 256 == 0 && F % 256 == 0;   // one short sequence: weight-streaming GEMMs
+    // the product class (vf_gemm_route.h): skinny = one short sequence, weight-streaming GEMMs; split-K for the long-K product of a
+    // single short sequence; everything else through gemm()
+    const bool skinny = enc_product_class(M, H, F, false, !no_skinny, !no_splitk) == kEncSkinny;
+    const bool ffn_down_splitk = enc_product_class(M, H, F, true, !no_skinny, !no_splitk) == kEncSplitK;
     if (!seq_off) hipLaunchKernelGGL(k_position_ids, dim3(B), dim3(64), 0, st, e->d_mask, B, T, c.roberta_pad_idx, e->d_pos);
     hipLaunchKernelGGL(k_embed_ln, dim3((M + 7) / 8), dim3(256), 0, st, e->d_ids, e->d_pos, has_tt ? e->d_tt : nullptr,
                        e->w16 + e->o_word, e->w16 + e->o_pos, e->w16 + e->o_type, e->w32 + e->f_emb_g, e->w32 + e->f_emb_b,
@@ -3755,7 +3657,7 @@ static int enc_forward_device(vf_encoder* e, int B, int T, int Tv, bool has_tt, 
     // weights, the next residual product normalises its residual element by element.  e->y holds y1 (attention sum),
     // e->x holds y2 (FFN sum) of the previous layer; the last layer writes y2 over y1 and one k_layernorm produces e->x.
 #ifdef VF_EXPERIMENTS
-    const bool fold = !skinny && !small && enc_fold_ok(e, Mp);
+    const bool fold = !skinny && !(!no_splitk && enc_short(M, H, F)) && enc_fold_ok(e, Mp);
     if (fold) { VFT_TRY(enc_ensure_fold(e, st)); g_ln_fold_forwards.fetch_add(1, std::memory_order_relaxed); }
 #else
     constexpr bool fold = false;   // measured slower at every batch size: the folded epilogues are built with -DVF_EXPERIMENTS only
@@ -3822,10 +3724,7 @@ static int enc_forward_device(vf_encoder* e, int B, int T, int Tv, bool has_tt, 
         else VFT_HIP(gemm<EPI_BIAS_GELU>(e->x, W1, b1, nullptr, e->hbuf, Mp, F, H, st, 0, &e->gws));
         if (skinny) {
             VFT_HIP(gemm_skinny<EPI_BIAS_RESIDUAL>(e->hbuf, W2, b2, e->x, e->y, M, H, F, st, e->sk_part, e->sk_cnt));
-        } else if (small && F >= 2048) {
-            // a single short sequence: the long-K product (K = ffn) is split over K across the chip (1.17 -> 1.00 ms per
-            // forward); the K = hidden products are not (the split's extra dependent memory round trips cost more than
-            // 12 short K-steps), nor anything from 256 tokens up (measured slower)
+        } else if (ffn_down_splitk) {   // a single short sequence: the long-K product (K = ffn) is split over K across the chip
             VFT_HIP(gemm_splitk<EPI_BIAS_RESIDUAL>(e->hbuf, W2, b2, e->x, e->y, Ms, H, F, e->sk_part, e->sk_cnt, st));
         } else {
             VFT_HIP(gemm<EPI_BIAS_RESIDUAL>(e->hbuf, W2, b2, e->x, e->y, Mp, H, F, st, 0, &e->gws));
