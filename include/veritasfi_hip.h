@@ -41,6 +41,7 @@ enum {
 
 enum { VF_DTYPE_F32 = 0, VF_DTYPE_F16 = 1, VF_DTYPE_FP8_E4M3 = 2, VF_DTYPE_INT8 = 3 };
 #define VF_INDEX_APPEND 0x100   /* or'ed into `dtype` of vf_index_create / vf_index_create_device: append to the handle in *out (below) */
+#define VF_INDEX_REMOVE 0x200   /* as the whole `dtype` of vf_index_create: remove rows from the handle in *out (below) */
 
 typedef struct vf_index vf_index;
 
@@ -111,6 +112,36 @@ int vf_index_create_device(vf_index** out, const void* d_rows, int64_t n, int32_
  * appended rows searches at the speed of its last shard.
  * vf_index_set_option(idx, "reserve_rows", total) makes room for `total` rows now (a borrowed index takes its copy now), so that
  * appends up to that count move nothing; a value at or below the row count does nothing, 2^32-1 and above per shard is VF_EUNSUPPORTED. */
+
+/* ---- removing rows from a live index (faiss IndexFlat.remove_ids: later rows shift down, ids stay the positions) ----
+ * vf_index_create(&h, ids, n_ids, d, VF_INDEX_REMOVE, device_id, 0): *out holds a live handle on entry and the same handle on return,
+ * whatever the result; `rows` is const int64_t ids[n_ids] in HOST memory, global ids (id_offset .. id_offset + n - 1 of the handle);
+ * d and device_id must be the handle's (a group's home device); id_offset is ignored.  The flag is honoured only when dtype is
+ * VF_INDEX_REMOVE exactly: with any other bit (VF_INDEX_APPEND | VF_INDEX_REMOVE | x included) the value stays "unknown dtype", and
+ * vf_index_create_device has no removal form (0x200 is "unknown dtype" there).
+ * The listed rows leave and every later row moves down by the number removed before it, so the ids of the handle stay one range and a
+ * host list indexed by id stays aligned after the same deletions.  Duplicates in the list count once; n_ids == 0 succeeds and does
+ * nothing.  An id outside the handle's range is VF_EINVAL, names the offending position and removes nothing -- strict on purpose: a
+ * stale row number after an earlier shift is the classic mistake.  VF_EINVAL "search pending" while any slot is between _begin and
+ * _end.  Argument errors (null out, null handle, d or device mismatch, null ids with n_ids > 0, negative n_ids) are reported before
+ * any HIP call.
+ * Afterwards the handle is what vf_index_create over the remaining rows, in their order, would have built: same search paths, same
+ * kernels, same image use, same result bits -- including the transitions a fresh build makes at a row count (at or below 16 384 rows
+ * the cache of normalised rows replaces the scan copy; below the int8 row image's threshold the image goes; above it the image is
+ * rebuilt, and an index that had refused its image over a row that is gone gets one).  The capacity does not shrink: a later append
+ * uses the room.  Nothing below the first removed row is read or written, so a call costs what the rows behind it cost; removing the
+ * last rows moves nothing.  The rows move in chunks through a staging buffer of up to 64 MB (option "compact_chunk_rows": destination
+ * rows per chunk, 0 = auto).  An index that borrows the caller's device rows takes its own copy first (the caller's memory is never
+ * written and may be freed from then on).  A plain handle may lose all its rows; it then behaves like a handle created empty.
+ * A group handle removes each id in the shard that holds it, every shard on its own device, and lowers the id_offset of every later
+ * shard, so ids stay one contiguous range.  A removal that would leave a shard of a group without rows is VF_EUNSUPPORTED and removes
+ * nothing (nothing re-balances a group); all shards are checked before any is changed.
+ * Failures: every allocation the call needs (the staging buffer, the owned copy of borrowed rows, a new cache of normalised rows, a
+ * new image) is made before the first byte moves, so VF_ENOMEM leaves the handle exactly as it was.  A HIP runtime error AFTER the
+ * first move cannot be undone in place: the call returns VF_EHIP and the handle is marked damaged -- every later search, append and
+ * removal on it returns VF_EHIP with a message that says so, and so do vf_cosine_matrix_rows / _mixed and the options "reserve_rows"
+ * and "scan_image", which read or rebuild the row arrays; vf_index_destroy still works.  The remaining calls (info, stats, the other
+ * options) touch no row and answer as before. */
 
 /* ---- ONE handle over several devices (single-process serving) -------------------------------------------------
  * The reference serves from one process (RAGManager singleton, src/utils/ragManager.py:17-30; it builds

@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("VF_LIB_PATH") or os.path.join(_HERE, "lib", "libverit
 VF_OK = 0
 VF_DTYPE_F32, VF_DTYPE_F16, VF_DTYPE_FP8_E4M3, VF_DTYPE_INT8 = 0, 1, 2, 3
 VF_INDEX_APPEND = 0x100   # or'ed into the dtype of vf_index_create / vf_index_create_device: append to the handle in *out
+VF_INDEX_REMOVE = 0x200   # the whole dtype of vf_index_create: `rows` are int64 ids to remove from the handle in *out
 
 c_i32, c_i64, c_f32 = ctypes.c_int32, ctypes.c_int64, ctypes.c_float
 p_i32, p_i64, p_f32 = ctypes.POINTER(c_i32), ctypes.POINTER(c_i64), ctypes.POINTER(c_f32)

@@ -146,6 +146,57 @@ def append(path: str, rows, ids=None) -> int:
     return first
 
 
+def remove(path: str, ids, block_rows: int = 65536) -> int:
+    """Remove the rows ``ids`` (file row numbers; duplicates count once) from the corpus file at ``path``, later rows moving down as
+    they do in a live index (``DenseIndex.remove``): a restart that loads the file sees what the index saw.  Returns the number
+    removed.  The compacted file -- with its id table, if it has one -- is written beside the old one, synced, and takes its place in one
+    ``os.replace``: a crash leaves the old file intact or the new one complete, never a mixture.  The directory is synced afterwards
+    where the platform allows it, so that the replacement itself survives a power loss; where it does not (the sync is refused), the
+    old file may come back after one.  A row number outside the file raises ValueError and changes nothing."""
+    ids = np.asarray(ids, dtype=np.int64).ravel()
+    h = read_header(path)
+    n, d, dt = int(h["n"]), int(h["d"]), _NP[h["dtype"]]
+    bad = np.flatnonzero((ids < 0) | (ids >= n))
+    if bad.size:
+        raise ValueError(f"remove: ids[{int(bad[0])}] = {int(ids[bad[0]])} is outside the file's rows [0, {n})")
+    gone = np.unique(ids)
+    if gone.size == 0:
+        return 0
+    if os.path.getsize(path) < _HDR.size + n * d * dt.itemsize + (8 * n if h["has_ids"] else 0):
+        raise ValueError(f"{path} is truncated")
+    keep = np.ones(n, dtype=bool)
+    keep[gone] = False
+    rows = rows_memmap(path)
+    old_ids = external_ids(path)
+    tmp = f"{path}.remove-{os.getpid()}.tmp"
+    try:
+        with open(tmp, "wb") as f:
+            f.write(_HDR.pack(MAGIC, 1, h["dtype"], n - int(gone.size), d, 1 if h["has_ids"] else 0))
+            for r0 in range(0, n, block_rows):
+                f.write(np.ascontiguousarray(rows[r0:r0 + block_rows][keep[r0:r0 + block_rows]]).tobytes())
+            if old_ids is not None:
+                f.write(np.ascontiguousarray(np.asarray(old_ids)[keep]).tobytes())
+            f.flush()
+            os.fsync(f.fileno())
+        del rows, old_ids
+        os.replace(tmp, path)
+        try:                                                           # the rename is durable once its directory is
+            dfd = os.open(os.path.dirname(os.path.abspath(path)), os.O_RDONLY)
+            try:
+                os.fsync(dfd)
+            finally:
+                os.close(dfd)
+        except OSError:
+            pass
+    except BaseException:
+        try:
+            os.remove(tmp)
+        except OSError:
+            pass
+        raise
+    return int(gone.size)
+
+
 def info(path: str) -> dict:
     """Header fields through the library's own validator (vf_corpus_file_info)."""
     n, d, dt, has = _ffi.c_i64(0), _ffi.c_i32(0), _ffi.c_i32(0), _ffi.c_i32(0)

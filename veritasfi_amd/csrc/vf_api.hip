@@ -194,6 +194,9 @@ struct vf_index {
     // host-buffer entry (vf_index_search): per-handle device staging, grown on demand, reused across calls
     DevBuf st_q, st_ids, st_sc;
     DevBuf st_add, st_rho;            // appends: the new rows on their way in (host rows, rows of another device), the image's two residual words
+    DevBuf st_cmp, st_rem;            // removals: the staging buffer of the row compaction, the sorted removed rows
+    int64_t compact_chunk_rows = 0;   // option: destination rows per chunk of a removal's compaction (0 = auto: kCompactStageBytes of the widest array)
+    bool damaged = false;             // a HIP error struck a removal after its first row had moved: searches, appends and removals are refused from then on
     // ---- group handle (vf_index_create_sharded / vf_index_group): the corpus is row-sharded over `shards`, one per
     // device; this handle owns them.  device = the HOME device: queries arrive there and the merged result lands there.
     std::vector<vf_index*> shards;
@@ -217,6 +220,8 @@ static int ensure_pinned(Slot& s, size_t nq_total) {
 }
 
 static int build_image(vf_index* ix, int64_t mode);
+static int image_alloc(vf_index* ix, int64_t mode);
+static int image_fill(vf_index* ix);
 
 static bool known_dtype(int64_t dtype) { return dtype >= VF_DTYPE_F32 && dtype <= VF_DTYPE_INT8; }
 static size_t dtype_bytes(int dtype) { return dtype == VF_DTYPE_F32 ? 4 : (dtype == VF_DTYPE_F16 ? 2 : 1); }
@@ -302,7 +307,13 @@ static int build_image(vf_index* ix, int64_t mode) {
         ix->rows_img = (unsigned char*)ix->rows_scan; ix->owns_img = false;
         return VF_OK;
     }
-    const size_t bytes = (size_t)ix->cap * ix->dp;
+    VF_TRY(image_alloc(ix, mode));
+    return ix->rows_img ? image_fill(ix) : VF_OK;
+}
+// the two arrays of an owned image, sized by the handle's capacity (a removal makes this call before it moves a row, image_fill
+// after).  Auto (mode 1) without the room leaves the handle without an image and succeeds.
+static int image_alloc(vf_index* ix, int64_t mode) {
+    const size_t ibytes = 2 * ((size_t)ix->cap + 64) * sizeof(float), bytes = (size_t)ix->cap * ix->dp;
     if (mode == 1) {
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return VF_OK; }
@@ -314,15 +325,20 @@ static int build_image(vf_index* ix, int64_t mode) {
         free_image(ix);
         return mode == 2 ? fail(VF_ENOMEM, "scan_image = 2: the int8 row image does not fit in device memory") : VF_OK;
     }
-    u32* d_rho = nullptr;   // [0] largest rho (float bits), [1] sum of rho (float)
-    VF_HIP(hipMalloc((void**)&d_rho, 2 * sizeof(u32)));
+    return VF_OK;
+}
+// codes, inverses, offsets and residual statistics of the handle's n rows into the owned image's arrays; an image whose worst row
+// leaves too much residual is freed again and refused
+static int image_fill(vf_index* ix) {
+    const size_t ibytes = 2 * ((size_t)ix->cap + 64) * sizeof(float);
+    VF_TRY(ix->st_rho.ensure(2 * sizeof(u32)));
+    u32* d_rho = ix->st_rho.as<u32>();   // [0] largest rho (float bits), [1] sum of rho (float)
     VF_HIP(hipMemset(d_rho, 0, 2 * sizeof(u32)));
     VF_HIP(hipMemset(ix->inv_img, 0, ibytes));
     VF_HIP(launch_prep_image(ix->rows_orig, ix->dtype, ix->n, ix->d, ix->dp, ix->norm, ix->rows_img, ix->inv_img, image_offsets(ix), d_rho,
                              (float*)(d_rho + 1), nullptr));
     u32 bits[2] = {0u, 0u};
     VF_HIP(hipMemcpy(bits, d_rho, sizeof(bits), hipMemcpyDeviceToHost));
-    (void)hipFree(d_rho);
     float rho, sum;
     memcpy(&rho, &bits[0], sizeof(rho));
     memcpy(&sum, &bits[1], sizeof(sum));
@@ -392,7 +408,7 @@ static void destroy_index(vf_index* ix) {
     }
     (void)hipSetDevice(ix->device);
     (void)hipDeviceSynchronize();
-    ix->st_q.release(); ix->st_ids.release(); ix->st_sc.release(); ix->st_add.release(); ix->st_rho.release();
+    ix->st_q.release(); ix->st_ids.release(); ix->st_sc.release(); ix->st_add.release(); ix->st_rho.release(); ix->st_cmp.release(); ix->st_rem.release();
     for (int i = 0; i < kSlots; ++i) {
         Slot& s = ix->slots[i];
         DevBuf* bufs[] = {&s.qn, &s.qimg, &s.s0, &s.cnt, &s.tau, &s.hist, &s.hist_coarse, &s.cand, &s.flags, &s.counts, &s.dense_s,
@@ -481,6 +497,8 @@ static int create_impl(vf_index** out, const void* rows, bool rows_on_device, in
 // its threshold) are made when an append crosses it, and an image is dropped when a new row leaves more residual than it may hold.
 // ------------------------------------------------------------------------------------------------
 constexpr int64_t kMaxShardRows = 0xFFFFFFFFll;   // a shard holds fewer rows than this (candidate keys carry 32-bit row numbers)
+// what every search, append and removal answers once a removal has failed half-way (remove_run)
+static const char* kDamagedMsg = "the index was damaged by a HIP error in the middle of a removal (VF_INDEX_REMOVE): only vf_index_destroy works on it";
 
 static bool search_pending(const vf_index* ix) {
     for (const Slot& s : ix->slots) if (s.pending) return true;
@@ -641,6 +659,7 @@ static int append_entry(vf_index** out, const void* rows, bool rows_on_device, i
         return fail(VF_EINVAL, "vf_index_create: VF_INDEX_APPEND: d and dtype must be the handle's (" + std::to_string(ix->d) + ", " + std::to_string(ix->dtype) + ")");
     if (device_id != ix->device) return fail(VF_EINVAL, "vf_index_create: VF_INDEX_APPEND: device_id must be the handle's device " + std::to_string(ix->device));
     std::lock_guard<std::mutex> g(ix->mu);
+    if (ix->damaged) return fail(VF_EHIP, std::string("vf_index_create: VF_INDEX_APPEND: ") + kDamagedMsg);
     if (search_pending(ix)) return fail(VF_EINVAL, "vf_index_create: VF_INDEX_APPEND: search pending (a slot is between _begin and _end)");
     if (n == 0) return VF_OK;
     vf_index* target = ix->shards.empty() ? ix : ix->shards.back();   // a group: the rows go to its last shard, ids stay one range
@@ -657,6 +676,7 @@ static int append_entry(vf_index** out, const void* rows, bool rows_on_device, i
 // option "reserve_rows": room for `total` rows now, so that appends up to it move nothing (a group: in its last shard, where they go)
 static int reserve_rows(vf_index* ix, int64_t total) {
     std::lock_guard<std::mutex> g(ix->mu);
+    if (ix->damaged) return fail(VF_EHIP, std::string("reserve_rows: ") + kDamagedMsg);
     vf_index* target = ix->shards.empty() ? ix : ix->shards.back();
     if (target != ix) total -= ix->n - target->n;
     if (total >= kMaxShardRows) return fail(VF_EUNSUPPORTED, "reserve_rows: more than 2^32-1 rows per shard");
@@ -670,8 +690,227 @@ static int reserve_rows(vf_index* ix, int64_t total) {
     return regrow(target, std::max(total, target->cap));
 }
 
+// ------------------------------------------------------------------------------------------------
+// Removals (VF_INDEX_REMOVE; DESIGN.md 3.2 "Removing rows").  IndexFlat.remove_ids on a live index: the rows leave and every later
+// row moves down, so ids stay the positions 0 .. n - 1 (what src/utils/ensembleRetriever.py:76 indexes its metadata with).  After it
+// the handle is what vf_index_create over the remaining rows would have built.  A removal has two parts.  remove_prepare makes every
+// allocation the call needs and changes nothing a search could see (a handle that borrows its rows takes its own copy, as an append
+// does); a failure there leaves the handle as it was.  remove_run moves the rows (k_compact_rows, chunk by chunk through a staging
+// buffer: vf_compact.h), brings every derived array to the bits of a fresh build, makes the transitions a fresh build makes at the
+// new row count and lowers the row count; a HIP error there cannot be undone and marks the handle damaged.
+//   rows_orig, an owned scan copy, norm, inv_scan: compacted by the mover -- each entry depends on its own row alone, so the moved
+//   bits are the bits a fresh build computes.  The cache of normalised rows (n <= kSmallN) is small by definition: the create-time
+//   kernel rewrites it from the first removed row on.  An owned int8 image is rebuilt by the create-time kernel on the rows that remain
+//   (its residual statistics are sums and maxima over all rows); an int8 index copies its inverses from inv_scan.
+// ------------------------------------------------------------------------------------------------
+namespace {
+enum ImageStep { kImageNone = 0, kImageDrop, kImageAlias, kImageRefill, kImageNew };
+struct RemovePrep {
+    vf_index* ix = nullptr;
+    std::vector<long long> rem;        // the rows that leave: local row numbers, ascending, distinct, not empty
+    CompactPlan plan{};
+    bool to_small = false;             // the row count crosses kSmallN downward: the scan copy goes, the cache of normalised rows comes
+    bool scan_moves = false;           // an owned scan copy that stays
+    int image = kImageNone;
+    float* new_cn = nullptr;           // allocations the commit hands to the handle
+    unsigned char* new_img = nullptr;
+    float* new_iimg = nullptr;
+    void release() {
+        if (new_cn) (void)hipFree(new_cn);
+        if (new_img) (void)hipFree(new_img);
+        if (new_iimg) (void)hipFree(new_iimg);
+        new_cn = nullptr; new_img = nullptr; new_iimg = nullptr;
+    }
+};
+}  // namespace
+
+
+// p.ix (a plain handle: its mutex is held, no search is pending) and p.rem are set
+static int remove_prepare(RemovePrep& p) {
+    vf_index* ix = p.ix;
+    const int64_t n0 = ix->n, m = (int64_t)p.rem.size(), n1 = n0 - m;
+    const size_t esz = dtype_bytes(ix->dtype), scan_esz = byte_rows(ix->dtype) ? 1 : 2;
+    VF_HIP(hipSetDevice(ix->device));
+    VF_HIP(hipDeviceSynchronize());   // every reader of the arrays is done
+    if (!ix->owns_rows) VF_TRY(regrow(ix, ix->cap));   // the caller's memory is never written
+    p.to_small = n0 > kSmallN && n1 <= kSmallN;
+    p.scan_moves = ix->rows_scan && ix->owns_scan && !p.to_small;
+    long long widest = (long long)ix->d * (long long)esz;
+    if (p.scan_moves) widest = std::max(widest, (long long)ix->dp * (long long)scan_esz);
+    p.plan = compact_plan(n0, m, p.rem[0], ix->compact_chunk_rows > 0 ? ix->compact_chunk_rows : compact_auto_rows(widest));
+    if (p.plan.chunks) {
+        VF_TRY(ix->st_cmp.ensure((size_t)p.plan.chunk_rows * (size_t)widest));
+        VF_TRY(ix->st_rem.ensure((size_t)m * sizeof(long long)));
+    }
+    if (n1 > 0 && n1 <= kSmallN && !ix->cn_cache &&
+        hipMalloc((void**)&p.new_cn, (size_t)std::min<int64_t>(ix->cap, kSmallN) * ix->d * sizeof(float)) != hipSuccess) {
+        (void)hipGetLastError();
+        p.new_cn = nullptr;
+        return fail(VF_ENOMEM, "remove: the cache of normalised rows does not fit in device memory");
+    }
+    // the image a fresh build of the remaining rows would hold
+    RouteIn in = route_in(ix);
+    in.n = n1; in.has_scan = in.has_scan && !p.to_small;
+    const bool eligible = ix->scan_image != 0 && image_eligible(in, ix->scan_image);
+    if (ix->rows_img) p.image = !eligible ? kImageDrop : ix->owns_img ? kImageRefill : kImageAlias;
+    else if (eligible && ix->dtype != VF_DTYPE_INT8) {   // (it had refused its image, or had found no room for it)
+        int rc = image_alloc(ix, ix->scan_image);
+        p.new_img = ix->rows_img; p.new_iimg = ix->inv_img;   // kept aside until the rows have moved
+        ix->rows_img = nullptr; ix->inv_img = nullptr; ix->owns_img = false;
+        if (rc != VF_OK) { p.release(); return rc; }
+        if (p.new_img) p.image = kImageNew;
+    }
+    if (p.image == kImageRefill || p.image == kImageNew) {
+        const int rc = ix->st_rho.ensure(2 * sizeof(u32));
+        if (rc != VF_OK) { p.release(); return rc; }
+    }
+    return VF_OK;
+}
+
+static int remove_run(RemovePrep& p) {
+    vf_index* ix = p.ix;
+    const int dt = ix->dtype;
+    const int64_t n0 = ix->n, m = (int64_t)p.rem.size(), n1 = n0 - m, first = p.plan.first;
+    const size_t esz = dtype_bytes(dt), scan_esz = byte_rows(dt) ? 1 : 2;
+    hipError_t e = hipSetDevice(ix->device);
+    const long long* d_rem = ix->st_rem.as<long long>();
+    if (e == hipSuccess && p.plan.chunks) e = hipMemcpy(ix->st_rem.p, p.rem.data(), (size_t)m * sizeof(long long), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {   // nothing has moved yet
+        p.release();
+        return fail(VF_EHIP, std::string("remove: ") + hipGetErrorString(e));
+    }
+    // ---- from here on a failure cannot be undone ----
+    // Each array moves under a plan of its own: what the staging buffer (sized for the widest array's chunk) holds of ITS rows, so the
+    // 4-byte arrays go in one chunk where the rows take many.  Option compact_chunk_rows fixes the rows per chunk for every array.
+    auto move = [&](void* base, size_t row_bytes) {
+        if (!base) return;
+        const CompactPlan plan = compact_plan(n0, m, p.rem[0], ix->compact_chunk_rows > 0 ? p.plan.chunk_rows : (long long)(ix->st_cmp.bytes / row_bytes));
+        for (long long c = 0; c < plan.chunks && e == hipSuccess; ++c) {
+            const CompactChunk k = compact_chunk(plan, c);
+            e = launch_compact_rows(base, ix->st_cmp.p, (long long)row_bytes, k.lo, k.hi - k.lo, d_rem, m, 0, k.lo, nullptr);    // gather
+            if (e == hipSuccess) e = launch_compact_rows(ix->st_cmp.p, base, (long long)row_bytes, k.lo, k.hi - k.lo, nullptr, 0, k.lo, 0, nullptr);   // scatter
+        }
+    };
+    // the vacated entries [n1, n0) of a per-row float array: the zeroes a fresh build with room to spare leaves there
+    auto vacate = [&](float* a) { if (e == hipSuccess && a) e = hipMemsetAsync(a + n1, 0, (size_t)m * sizeof(float), nullptr); };
+    move(ix->rows_orig, (size_t)ix->d * esz);
+    if (p.scan_moves) move(ix->rows_scan, (size_t)ix->dp * scan_esz);
+    move(ix->norm, sizeof(float));
+    move(ix->inv_scan, sizeof(float));
+    vacate(ix->norm);
+    vacate(ix->inv_scan);
+    if (p.image == kImageAlias) {   // an int8 index: inv_img = inv_scan, offsets 0
+        if (e == hipSuccess && n1 > first)
+            e = hipMemcpyAsync(ix->inv_img + first, ix->inv_scan + first, (size_t)(n1 - first) * sizeof(float), hipMemcpyDeviceToDevice, nullptr);
+        vacate(ix->inv_img);
+    }
+    if (e == hipSuccess && p.new_cn) e = launch_normalize_rows(ix->rows_orig, dt, 0, n1, ix->d, ix->norm, p.new_cn, nullptr);
+    else if (e == hipSuccess && ix->cn_cache && n1 > first)
+        e = launch_normalize_rows(ix->rows_orig, dt, first, n1 - first, ix->d, ix->norm, ix->cn_cache + (size_t)first * ix->d, nullptr);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        p.release();
+        ix->damaged = true;
+        return fail(VF_EHIP, std::string("remove: ") + hipGetErrorString(e) + " -- " + kDamagedMsg);
+    }
+    // commit: the row count last among the arrays, then what a fresh build of n1 rows holds and does not hold
+    ix->n = n1;
+    if (p.to_small) {
+        if (ix->owns_scan && ix->rows_scan) (void)hipFree(ix->rows_scan);
+        ix->rows_scan = nullptr; ix->owns_scan = false;
+    }
+    if (p.new_cn) { ix->cn_cache = p.new_cn; p.new_cn = nullptr; }
+    if (n1 == 0 && ix->cn_cache) { (void)hipFree(ix->cn_cache); ix->cn_cache = nullptr; }   // (a handle created empty holds none)
+    ix->image_refused = false;
+    if (p.image == kImageDrop) free_image(ix);
+    if (p.image == kImageNew) {
+        ix->rows_img = p.new_img; ix->inv_img = p.new_iimg; ix->owns_img = true;
+        p.new_img = nullptr; p.new_iimg = nullptr;
+    }
+    if (p.image == kImageNew || p.image == kImageRefill) {
+        const int rc = image_fill(ix);   // (a row that leaves too much residual: no image, as a fresh build decides)
+        if (rc != VF_OK) { ix->damaged = true; g_err += std::string(" -- ") + kDamagedMsg; return VF_EHIP; }
+    }
+    if (ix->st_cmp.bytes > (size_t)kCompactStageBytes) ix->st_cmp.release();
+    return VF_OK;
+}
+
+// vf_index_create with dtype == VF_INDEX_REMOVE.  Every argument error is reported before the first HIP call.
+static int remove_entry(vf_index** out, const int64_t* ids, int64_t n_ids, int32_t d, int32_t device_id) {
+    if (!out) return fail(VF_EINVAL, "vf_index_create: null out");
+    vf_index* ix = *out;
+    if (!ix) return fail(VF_EINVAL, "vf_index_create: VF_INDEX_REMOVE needs a live handle in *out");
+    if (d != ix->d) return fail(VF_EINVAL, "vf_index_create: VF_INDEX_REMOVE: d must be the handle's (" + std::to_string(ix->d) + ")");
+    if (device_id != ix->device) return fail(VF_EINVAL, "vf_index_create: VF_INDEX_REMOVE: device_id must be the handle's device " + std::to_string(ix->device));
+    if (n_ids < 0 || (n_ids > 0 && !ids)) return fail(VF_EINVAL, "vf_index_create: VF_INDEX_REMOVE: bad ids/n_ids");
+    std::lock_guard<std::mutex> g(ix->mu);
+    if (ix->damaged) return fail(VF_EHIP, std::string("vf_index_create: VF_INDEX_REMOVE: ") + kDamagedMsg);
+    if (search_pending(ix)) return fail(VF_EINVAL, "vf_index_create: VF_INDEX_REMOVE: search pending (a slot is between _begin and _end)");
+    if (n_ids == 0) return VF_OK;
+    const int64_t lo = ix->id_offset, hi = ix->id_offset + ix->n;
+    for (int64_t i = 0; i < n_ids; ++i)
+        if (ids[i] < lo || ids[i] >= hi)
+            return fail(VF_EINVAL, "vf_index_create: VF_INDEX_REMOVE: ids[" + std::to_string(i) + "] = " + std::to_string(ids[i]) +
+                                       " is outside the handle's ids [" + std::to_string(lo) + ", " + std::to_string(hi) + "): nothing was removed");
+    std::vector<long long> all(ids, ids + n_ids);
+    std::sort(all.begin(), all.end());
+    all.erase(std::unique(all.begin(), all.end()), all.end());
+    DeviceGuard restore_callers_device;
+    if (ix->shards.empty()) {
+        RemovePrep p;
+        p.ix = ix;
+        p.rem = std::move(all);
+        for (long long& r : p.rem) r -= lo;
+        VF_TRY(remove_prepare(p));
+        return remove_run(p);
+    }
+    // a group: each id to the shard that holds it; every shard is validated and prepared before any is changed
+    const size_t G = ix->shards.size();
+    std::vector<RemovePrep> preps(G);
+    size_t at = 0;
+    for (size_t s = 0; s < G; ++s) {
+        vf_index* sh = ix->shards[s];
+        preps[s].ix = sh;
+        while (at < all.size() && all[at] < sh->id_offset + sh->n) preps[s].rem.push_back(all[at++] - sh->id_offset);
+        if (!preps[s].rem.empty() && (int64_t)preps[s].rem.size() == sh->n)
+            return fail(VF_EUNSUPPORTED, "vf_index_create: VF_INDEX_REMOVE: the removal would leave shard " + std::to_string(s) +
+                                             " of the group without rows (nothing re-balances a group): nothing was removed");
+    }
+    std::vector<std::unique_lock<std::mutex>> locks;
+    for (vf_index* sh : ix->shards) locks.emplace_back(sh->mu);
+    for (size_t s = 0; s < G; ++s) {
+        if (preps[s].rem.empty()) continue;
+        const int rc = remove_prepare(preps[s]);
+        if (rc != VF_OK) {
+            const std::string keep = g_err;
+            for (RemovePrep& q : preps) q.release();
+            g_err = keep;
+            return rc;
+        }
+    }
+    int64_t gone = 0;
+    for (size_t s = 0; s < G; ++s) {
+        vf_index* sh = ix->shards[s];
+        sh->id_offset -= gone;   // ids stay one contiguous range
+        if (preps[s].rem.empty()) continue;
+        const int rc = remove_run(preps[s]);
+        if (rc != VF_OK) {       // (shards before this one have changed: the group cannot be searched as one range any more)
+            const std::string keep = g_err;
+            for (RemovePrep& q : preps) q.release();
+            ix->damaged = sh->damaged || gone > 0;
+            g_err = keep;
+            return rc;
+        }
+        gone += (int64_t)preps[s].rem.size();
+        ix->n -= (int64_t)preps[s].rem.size();
+    }
+    return VF_OK;
+}
+
 extern "C" int vf_index_create(vf_index** out, const void* rows, int64_t n, int32_t d, int32_t dtype,
                                int32_t device_id, int64_t id_offset) {
+    if (dtype == VF_INDEX_REMOVE) return remove_entry(out, (const int64_t*)rows, n, d, device_id);
     if (dtype >= 0 && (dtype & VF_INDEX_APPEND)) return append_entry(out, rows, false, n, d, dtype, device_id);
     DeviceGuard restore_callers_device;
     return create_impl(out, rows, false, n, d, dtype, device_id, id_offset);
@@ -917,6 +1156,7 @@ extern "C" int vf_index_set_option(vf_index* ix, const char* name, int64_t value
     else if (s == "overlap_scans") { if (!in_range(-1, 1)) return fail(VF_EINVAL, "overlap_scans must be -1 (auto), 0 or 1"); ix->overlap_scans = value; }
     else if (s == "scan_image") {
         if (!in_range(0, 2)) return fail(VF_EINVAL, "scan_image must be 0 (off), 1 (auto: when it fits with headroom) or 2 (force)");
+        if (ix->damaged) return fail(VF_EHIP, std::string("scan_image: ") + kDamagedMsg);
         if (!ix->shards.empty()) { ix->scan_image = value; return VF_OK; }   // (the shards have built or dropped theirs above)
         for (const Slot& sl : ix->slots) if (sl.pending) return fail(VF_EINVAL, "scan_image cannot change while a search is pending");
         DeviceGuard restore_callers_device;
@@ -929,6 +1169,7 @@ extern "C" int vf_index_set_option(vf_index* ix, const char* name, int64_t value
     }
     else if (s == "image_mfma") { if (!in_range(-1, 2)) return fail(VF_EINVAL, "image_mfma must be -1 (auto), 0 (the int8 row image on the fp16 matrix instruction, fp16 queries), 1 (on the int8 matrix instruction, the queries as one int8 plane) or 2 (as two planes, hi + lo: the band of 0)"); ix->image_mfma = value; }
     else if (s == "wide_rows") { if (!in_range(0, 2)) return fail(VF_EINVAL, std::string("wide_rows must be 0 (rows of more than 2432 padded elements never take the fused path), 1 (auto: from ") + std::to_string(kWideRowsMinRows) + " rows, e4m3 rows from " + std::to_string(kWideRowsMinRows8) + ", int8 rows from " + std::to_string(kWideRowsMinRowsI8) + ") or 2 (wherever k_scan_ksplit / k_scan_ksplit8 serve them; int8 rows: from " + std::to_string(kWideRowsMinRowsI8) + " rows)"); ix->wide_rows = value; }
+    else if (s == "compact_chunk_rows") { if (!in_range(0, kMaxShardRows)) return fail(VF_EINVAL, "compact_chunk_rows must be 0 (auto: 64 MB of staging) or the destination rows a removal moves per chunk"); ix->compact_chunk_rows = value; }
     else if (s == "debug") ix->debug = value;
     else if (s == "profile") {
         ix->profile = value != 0; ix->prof_scan_ms = ix->prof_pipe_ms = 0.0; ix->prof_launches = 0;
@@ -1519,6 +1760,7 @@ static int group_end(vf_index* ix, int slot_id) {
 
 static int search_begin_locked(vf_index* ix, int slot, const float* d_queries, int nq, int k, int64_t* d_ids,
                                float* d_scores, hipStream_t stream) {
+    if (ix->damaged) return fail(VF_EHIP, std::string("vf_index_search: ") + kDamagedMsg);
     if (!ix->shards.empty()) return group_begin(ix, slot, d_queries, nq, k, d_ids, d_scores, stream);
     VF_HIP(hipSetDevice(ix->device));
     int rc = begin_impl(ix, slot, d_queries, nq, k, d_ids, d_scores, stream);
@@ -1840,6 +2082,7 @@ static int cosine_matrix_rows_impl(vf_index* ix, const int64_t* ids, int32_t n, 
                                    const char* who) {
     DeviceGuard restore_callers_device;
     if (!ix) return fail(VF_EINVAL, std::string(who) + ": null handle");
+    if (ix->damaged) return fail(VF_EHIP, std::string(who) + ": " + kDamagedMsg);
     if (n < 0 || n_extra < 0) return fail(VF_EINVAL, std::string(who) + ": negative n");
     if (n == 0) return VF_OK;
     if (!ids || !out) return fail(VF_EINVAL, std::string(who) + ": null buffer");

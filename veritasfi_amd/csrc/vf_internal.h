@@ -10,6 +10,7 @@
 #include <string>
 
 #include "vf_ksplit_geom.h"   // + vf_scan_lds.h: the design constants, RowForm and every scan kernel's LDS budget
+#include "vf_compact.h"       // the plan of a removal's row compaction
 
 namespace vf {
 
@@ -160,6 +161,18 @@ struct AppendArgs {
     u32* rho_max_bits; float* rho_sum;    // with `img`: largest residual of the new rows (float bits) and their sum, zeroed by the caller
 };
 hipError_t launch_append_rows(const AppendArgs& a, hipStream_t s);
+// k_compact_rows: one step of a removal's chunk (VF_INDEX_REMOVE; the plan: vf_compact.h).  Row j = j0 + t, t < count, is read at
+// src + (source(j) - src_row0) * row_bytes and written at dst + (j - dst_row0) * row_bytes, where source(j) = compact_src(j, rem, m), or j
+// itself when rem is null.  The launcher picks `unit` (compact_unit) and `rows_per_block` (compact_rows_per_block).
+struct CompactArgs {
+    const char* src; char* dst;
+    long long row_bytes, j0, count;
+    const long long* rem;    // device: the sorted removed rows [m], or null
+    long long m, src_row0, dst_row0;
+    int unit, rows_per_block;
+};
+hipError_t launch_compact_rows(const void* src, void* dst, long long row_bytes, long long j0, long long count, const long long* rem /*device*/,
+                               long long m, long long src_row0, long long dst_row0, hipStream_t s);
 hipError_t launch_prep_queries(const float* q, int nq, int d, int dp, int qn_tile /*32 or 64*/,
                                float* qn, _Float16* qimg, hipStream_t s);
 hipError_t launch_normalize_rows(const void* rows, int dt /* VF_DTYPE_* */, long long row0, long long nrows, int d,

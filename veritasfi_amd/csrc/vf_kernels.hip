@@ -479,6 +479,75 @@ hipError_t launch_append_rows(const AppendArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------
+// k_compact_rows: the mover of a removal (VF_INDEX_REMOVE; the plan: vf_compact.h).  One launch copies `count` rows: row j = j0 + t of
+// the plan is read at src + (compact_src(j) - src_row0) rows and written at dst + (j - dst_row0) rows.  The gather step of a chunk reads
+// the array (src_row0 = 0) into the staging buffer (dst_row0 = j0); the scatter step reads the buffer back (rem = null: source row j,
+// src_row0 = j0) onto the array (dst_row0 = 0).  Source and destination of ONE launch never overlap, and no workgroup waits for another.
+// A workgroup takes compact_rows_per_block rows: their source rows go to LDS once (one binary search per row), then the threads
+// copy the rows' units -- 16 bytes wherever the addresses and the row size allow (every fused-path shape), narrower otherwise -- four
+// loads in flight before the first store.  The loads are non-temporal (a row is read once); the stores are plain, so that the staging
+// buffer the next launch reads stays in L2.
+// ------------------------------------------------------------------------------------------------
+typedef unsigned int cu32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int cu32x2 __attribute__((ext_vector_type(2)));
+
+template <class V>
+__device__ __forceinline__ void compact_units(const CompactArgs& a, const long long* s_src, long long j_first, int rows_here) {
+    const u32 upr = (u32)(a.row_bytes / (long long)sizeof(V));   // units per row (the launcher keeps rows_here * upr below 2^31)
+    const u32 total = (u32)rows_here * upr;
+    for (u32 i0 = threadIdx.x; i0 < total; i0 += 4 * 256) {
+        V v[4];
+        u32 row[4], unit[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const u32 i = i0 + e * 256;
+            if (i < total) {
+                row[e] = i / upr; unit[e] = i - row[e] * upr;
+                v[e] = __builtin_nontemporal_load((const V*)(a.src + (s_src[row[e]] - a.src_row0) * a.row_bytes) + unit[e]);
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (i0 + e * 256 < total) ((V*)(a.dst + (j_first + row[e] - a.dst_row0) * a.row_bytes))[unit[e]] = v[e];
+    }
+}
+
+__global__ __launch_bounds__(256) void k_compact_rows(CompactArgs a) {
+    __shared__ long long s_src[256];
+    const long long t0 = (long long)blockIdx.x * a.rows_per_block;
+    const long long left = a.count - t0;
+    const int rows_here = left < a.rows_per_block ? (int)left : a.rows_per_block;
+    const long long j_first = a.j0 + t0;
+    if ((int)threadIdx.x < rows_here) {
+        const long long j = j_first + threadIdx.x;
+        s_src[threadIdx.x] = a.rem ? compact_src(j, a.rem, a.m) : j;
+    }
+    __syncthreads();
+    switch (a.unit) {
+    case 16: compact_units<cu32x4>(a, s_src, j_first, rows_here); break;
+    case 8: compact_units<cu32x2>(a, s_src, j_first, rows_here); break;
+    case 4: compact_units<u32>(a, s_src, j_first, rows_here); break;
+    case 2: compact_units<unsigned short>(a, s_src, j_first, rows_here); break;
+    default: compact_units<unsigned char>(a, s_src, j_first, rows_here); break;
+    }
+}
+
+hipError_t launch_compact_rows(const void* src, void* dst, long long row_bytes, long long j0, long long count, const long long* rem,
+                               long long m, long long src_row0, long long dst_row0, hipStream_t s) {
+    if (count <= 0) return hipSuccess;
+    if (row_bytes <= 0 || row_bytes > (1ll << 30)) return hipErrorInvalidValue;
+    CompactArgs a;
+    a.src = (const char*)src; a.dst = (char*)dst; a.row_bytes = row_bytes; a.j0 = j0; a.count = count; a.rem = rem; a.m = m;
+    a.src_row0 = src_row0; a.dst_row0 = dst_row0;
+    a.unit = compact_unit((unsigned long long)(uintptr_t)src, (unsigned long long)(uintptr_t)dst, row_bytes);
+    a.rows_per_block = compact_rows_per_block(row_bytes);
+    const long long blocks = (count + a.rows_per_block - 1) / a.rows_per_block;
+    if (blocks > 0x7FFFFFFFll) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_compact_rows, dim3((unsigned)blocks), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
 // the same for rows PICKED by index: out[i] = canonical normalisation of row sel[i] (vf_cosine_matrix_rows)
 __global__ __launch_bounds__(256) void k_normalize_rows_gather(const void* rows, int dt, const long long* sel, int nsel, int d,
                                                                 const float* norm, float* out) {

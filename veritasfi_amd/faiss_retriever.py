@@ -108,6 +108,14 @@ class FaissRetriever:
         vectors = embed_docs(texts) if embed_docs is not None else [self.embeddings.embed_query(t) for t in texts]
         return self.add_embeddings(np.asarray(vectors, dtype=np.float32).reshape(len(texts), -1))
 
+    def remove_ids(self, ids) -> int:
+        """Remove rows by id (``faiss.IndexFlat.remove_ids``): later rows shift down, so ids stay positions -- delete the same entries
+        from any list kept beside the index.  Returns the number removed.  Refused where ``add_embeddings`` is: a retriever that wraps
+        an index it did not build changes it only when told how that index holds its rows."""
+        if getattr(self, "corpus_dtype", None) is None:
+            raise ValueError("this retriever wraps an index it did not build: pass corpus_dtype to from_index to remove from it")
+        return int(self.index.remove(np.asarray(ids, dtype=np.int64).ravel()))
+
     def invoke(self, querys: list, k: int):
         """(I, D) = ids and cosine scores, best first, shape [len(querys), k]; -1 / -FLT_MAX pad a corpus with fewer than k rows
         (reference :28-38: embed each string, fp32, L2-normalise, IndexFlatIP.search).  An embedder with a batched

@@ -266,6 +266,29 @@ class DenseIndex:
             self._keepalive = None   # the index holds its own copy of the rows now
         return first
 
+    def remove(self, ids) -> int:
+        """Remove rows from the live index by id (``faiss.IndexFlat.remove_ids``) and return how many left (distinct ids; duplicates in
+        ``ids`` count once).  Every later row moves down, so ids stay the positions ``id_offset .. id_offset + n - 1``: a host list
+        indexed by id stays aligned after ``del lst[i]`` for the same rows (highest first).  An id outside the index raises ValueError
+        and removes nothing; a pending search raises RuntimeError.  Afterwards the index is what a fresh one over the remaining rows
+        would be.  Capacity does not shrink: a later ``add`` uses the room.  An index that borrowed a CUDA tensor takes its own copy
+        first and lets the tensor go (it is never written).  A group removes in every shard that holds one of the ids and refuses
+        (RuntimeError, rc=-4) a removal that would empty a shard.  ``remove`` then ``add`` replaces a row (the new one gets a new id)."""
+        ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int64).ravel())
+        if ids.size == 0:
+            return 0
+        lo, hi = self.id_offset, self.id_offset + self.n
+        bad = np.flatnonzero((ids < lo) | (ids >= hi))
+        if bad.size:
+            raise ValueError(f"remove: ids[{int(bad[0])}] = {int(ids[bad[0]])} is outside the index's ids [{lo}, {hi})")
+        m = int(np.unique(ids).size)
+        _ffi.check(_ffi.lib().vf_index_create(ctypes.byref(self._h), ids.ctypes.data, int(ids.size), self.d, _ffi.VF_INDEX_REMOVE,
+                                              self.device_id, 0), "vf_index_create (remove)")
+        self.n -= m
+        if self.device_ids is None:
+            self._keepalive = None   # the index holds its own copy of the rows now
+        return m
+
     def reserve(self, total: int) -> None:
         """Room for ``total`` rows now (option ``reserve_rows``), so that ``add`` up to that count moves nothing."""
         self.set_option("reserve_rows", int(total))
