@@ -444,6 +444,50 @@ typedef struct vf_bm25 vf_bm25;
  * arguments ignored; *out is set to NULL) -- the exported surface stays two entry points. */
 int vf_bm25_create(const int64_t* indptr, int64_t vocab, const int32_t* indices, const float* data, int64_t nnz,
                    int64_t n_docs, int32_t device_id, vf_bm25** out, int32_t* slots);
+
+/* ---- a live BM25 index: documents are added and removed without a rebuild (no new entry point: the update rides on the create) ----
+ * A posting's score depends on the document count and the mean document length, so one added or removed document changes every
+ * score.  A live handle therefore keeps each posting's term frequency (int32) and each document's length beside the index, and an
+ * update rewrites the whole index on the device: removed rows leave, later rows move down (ids stay the positions 0 .. n - 1), new
+ * documents get the ids n .. n + m - 1, columns the vocabulary lacks are appended (columns never disappear), and every posting is
+ * re-scored by the Lucene recipe in float64, rounded once: (idf*tf) / (tf + k1*((1.0-b) + (b*dl)/avgdl)).  The result is, bit for
+ * bit, the index a build over the surviving documents followed by the new ones would be.
+ * The call: vf_bm25_create((const int64_t*)&delta, 0, NULL, NULL, 0, 0, device_id | PHASE, &h, &slots), with exactly one PHASE flag.
+ * An update is two calls, because idf needs a logarithm and the library takes none: idf[vocab] is the caller's, computed from the
+ * counts the first call returns, by the very expression that built the index.
+ *   VF_BM25_LIVE     stage: validates the delta (rows in range and strictly ascending per column, tf >= 1; every remove[i] in
+ *                    0 .. n - 1 else VF_EINVAL naming i; duplicates count once; at least one document must remain), allocates
+ *                    ALL the update needs, and fills counts[vocab] (postings per column after the update) and n_removed.  With
+ *                    *out == NULL it starts a live handle from the delta alone; that handle serves nothing until its commit, and a
+ *                    failed or discarded creation leaves *out NULL.  A stage discards an earlier stage that was not committed.
+ *   VF_BM25_COMMIT   reads idf, avgdl, k1, b: writes the new arrays from the old ones and the delta and swaps them in last.
+ *   VF_BM25_DISCARD  drops a staged update (release does too).
+ *   VF_BM25_FETCH    copies the handle's arrays to the non-NULL out_* pointers (sized by the caller from the counts it was given).
+ * Any failure leaves the handle exactly as it was: an update writes a SECOND set of arrays and never moves anything in place, so
+ * between a stage and its commit the device holds the postings twice (12 B per posting each, plus the 4 B per document row map).
+ * Searches are unchanged and may run between the two calls (they see the old index); each call holds the handle's lock.  After an
+ * update that changes n_docs the per-query scratch is dropped and made again by the next search.  A handle created without
+ * VF_BM25_LIVE keeps no term frequencies and refuses these calls; without a flag nothing about vf_bm25_create changes.
+ * Only Lucene scoring is live.  `chunk` (0 = 2048, else 1 .. 2048) is the number of postings one workgroup rewrites: tests lower it. */
+#define VF_BM25_LIVE 0x1000
+#define VF_BM25_COMMIT 0x2000
+#define VF_BM25_DISCARD 0x4000
+#define VF_BM25_FETCH 0x8000
+typedef struct vf_bm25_delta {
+    int64_t vocab;            /* V' >= the handle's vocabulary: columns of the delta and of the index after the update */
+    int64_t n_new;            /* documents added */
+    const int64_t* indptr;    /* [vocab + 1] the new documents' CSC ... */
+    const int32_t* rows;      /* ... rows 0 .. n_new - 1, strictly ascending per column */
+    const int32_t* tf;        /* ... term frequencies >= 1 */
+    const int64_t* remove;    /* [n_remove] ids that leave, any order (host) */
+    int64_t n_remove;
+    int64_t* counts;          /* out of the stage: [vocab] */
+    int64_t n_removed;        /* out of the stage: distinct ids removed */
+    const double* idf;        /* commit: [vocab] */
+    double avgdl, k1, b;      /* commit: total tokens / n_docs after the update, and the index's parameters */
+    int32_t chunk;
+    int64_t* out_indptr; int32_t* out_indices; float* out_data; int32_t* out_tf; int32_t* out_doc_len;   /* fetch */
+} vf_bm25_delta;
 /* q_offsets [nq + 1] (q_offsets[0] = 0, non-decreasing), q_terms [q_offsets[nq]] token columns in query order (repeats count
  * again; a query with no token ranks every row at score 0), 1 <= k <= n_docs (else VF_EINVAL)
  * -> out_ids [nq, k] rows, out_scores [nq, k] (host) */

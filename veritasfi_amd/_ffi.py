@@ -22,6 +22,21 @@ p_i32, p_i64, p_f32 = ctypes.POINTER(c_i32), ctypes.POINTER(c_i64), ctypes.POINT
 vp = ctypes.c_void_p
 
 
+# phases of a live BM25 update, or'ed into the device_id of vf_bm25_create (whose first argument is then a Bm25Delta)
+VF_BM25_LIVE, VF_BM25_COMMIT, VF_BM25_DISCARD, VF_BM25_FETCH = 0x1000, 0x2000, 0x4000, 0x8000
+
+
+class Bm25Delta(ctypes.Structure):
+    """vf_bm25_delta of include/veritasfi_hip.h."""
+    _fields_ = [
+        ("vocab", c_i64), ("n_new", c_i64), ("indptr", ctypes.POINTER(c_i64)), ("rows", ctypes.POINTER(c_i32)),
+        ("tf", ctypes.POINTER(c_i32)), ("remove", ctypes.POINTER(c_i64)), ("n_remove", c_i64), ("counts", ctypes.POINTER(c_i64)),
+        ("n_removed", c_i64), ("idf", ctypes.POINTER(ctypes.c_double)), ("avgdl", ctypes.c_double), ("k1", ctypes.c_double),
+        ("b", ctypes.c_double), ("chunk", c_i32), ("out_indptr", ctypes.POINTER(c_i64)), ("out_indices", ctypes.POINTER(c_i32)),
+        ("out_data", ctypes.POINTER(c_f32)), ("out_tf", ctypes.POINTER(c_i32)), ("out_doc_len", ctypes.POINTER(c_i32)),
+    ]
+
+
 class EncoderConfig(ctypes.Structure):
     _fields_ = [
         ("vocab", c_i32), ("hidden", c_i32), ("layers", c_i32), ("heads", c_i32), ("ffn", c_i32), ("max_pos", c_i32),

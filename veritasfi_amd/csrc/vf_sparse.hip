@@ -17,10 +17,15 @@
 //   k_bitonic_*        k > 4096 (the reference's k = num_chunk call): bitonic sort of the selected keys in global memory
 //   k_bm25_tail_*      the zero-score tail: untouched rows in ascending order (prefix sum over the bitmap's zero bits)
 //   k_bm25_reset       clear what the query touched: its postings' score entries and bitmap words (O(postings), not O(N))
+//   k_bm25_live_*      a live handle's update: documents leave and arrive, every posting is re-scored into a second set of
+//                      arrays (described where they stand; the index arithmetic is vf_bm25_live.h)
 #include "vf_internal.h"
+#include "vf_bm25_live.h"
 
 #include <float.h>
+#include <algorithm>
 #include <mutex>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -339,6 +344,180 @@ __global__ __launch_bounds__(kBmThreads) void k_bm25_emit(BmArgs a) {
     for (long long i = (long long)blockIdx.x * kBmThreads + threadIdx.x; i < n; i += (long long)gridDim.x * kBmThreads) bm_emit(a, 0, i, a.sel[i]);
 }
 
+// ---- the live index: one update = remove rows, renumber, append documents, re-score every posting (vf_bm25_live.h) -----------------
+// A second set of arrays is written from the old set and the delta; nothing is moved in place.  One workgroup per chunk of C flat
+// postings (C <= kLiveMaxChunk), whatever columns they belong to.  Every output element has exactly one writer: no float atomics,
+// and the LDS atomicMax that marks column starts is on integers.
+//   k_bm25_live_rowmap   old row -> new row or -1 (binary search in the removed rows); document lengths compacted, new ones appended
+//   k_bm25_live_count    survivors per chunk
+//   k_bm25_live_scan     exclusive prefix of the chunk counts (one workgroup)
+//   k_bm25_live_indptr   S(start(c)) + dptr[c] for the column starts each chunk owns: the new indptr
+//   k_bm25_live_rewrite  every survivor to S(p) + dptr[col(p)] with its new row, its tf and its new score
+//   k_bm25_live_append   the delta's postings behind their columns' survivors
+struct LiveArgs {
+    const long long* indptr; const int* indices; const int* tf;   // the old set
+    long long V, Vn, nnz, n0, n1, n_new; int C;
+    const int* rem; long long m;                                  // rows that leave, ascending and distinct
+    int* map;                                                     // [n0] new row or -1
+    const int* doclen0; int* doclen1; const int* delta_dl;        // [n0], [n1 + n_new], [n_new]
+    long long* csum;                                              // [chunks + 1] survivors per chunk, then their exclusive prefix
+    const long long* dptr; const int* drows; const int* dtf; long long dnnz;   // the delta CSC over Vn columns, local rows
+    long long* newptr;                                            // [Vn + 1]
+    int* indices1; int* tf1; float* data1;                        // the new set
+    const double* idf; double avgdl, k1, b, one_minus_b;
+};
+
+// exclusive prefix over the workgroup's kBmThreads values (Op: sum, or maximum with identity `id`); total = the whole workgroup's
+template <typename T, bool kMax>
+__device__ __forceinline__ T live_block_scan(T v, T id, T* part, T* total) {
+    const int t = threadIdx.x;
+    part[t] = v;
+    __syncthreads();
+    for (int d = 1; d < kBmThreads; d <<= 1) {
+        const T x = t >= d ? part[t - d] : id;
+        __syncthreads();
+        part[t] = kMax ? (x > part[t] ? x : part[t]) : part[t] + x;
+        __syncthreads();
+    }
+    const T excl = t > 0 ? part[t - 1] : id;
+    *total = part[kBmThreads - 1];
+    __syncthreads();
+    return excl;
+}
+
+// rows[i] = the new row of the chunk's posting i (or -1); rank[i] = survivors among the postings below i, rank[cnt] = all of them
+__device__ __forceinline__ void live_chunk_ranks(const LiveArgs& a, long long lo, int cnt, int* rows, int* rank, int* part) {
+    const int t = threadIdx.x;
+    for (int i = t; i < cnt; i += kBmThreads) {
+        const int r = a.map[a.indices[lo + i]];
+        if (rows) rows[i] = r;
+        rank[i] = r >= 0;
+    }
+    __syncthreads();
+    const int L = (cnt + kBmThreads - 1) / kBmThreads;
+    const int b0 = min(t * L, cnt), b1 = min(b0 + L, cnt);
+    int s = 0;
+    for (int i = b0; i < b1; ++i) s += rank[i];
+    int total;
+    int run = live_block_scan<int, false>(s, 0, part, &total);
+    for (int i = b0; i < b1; ++i) {
+        const int f = rank[i];
+        rank[i] = run;
+        run += f;
+    }
+    if (t == 0) rank[cnt] = total;
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(kBmThreads) void k_bm25_live_rowmap(LiveArgs a) {
+    const long long top = a.n0 > a.n_new ? a.n0 : a.n_new;
+    for (long long r = (long long)blockIdx.x * kBmThreads + threadIdx.x; r < top; r += (long long)gridDim.x * kBmThreads) {
+        if (r < a.n0) {
+            const long long nr = live_new_row(r, a.rem, a.m);
+            a.map[r] = (int)nr;
+            if (nr >= 0) a.doclen1[nr] = a.doclen0[r];
+        }
+        if (r < a.n_new) a.doclen1[a.n1 + r] = a.delta_dl[r];
+    }
+}
+
+__global__ __launch_bounds__(kBmThreads) void k_bm25_live_count(LiveArgs a) {
+    __shared__ int wsum[kBmThreads / 64];
+    const LiveChunk ch = live_chunk(a.nnz, a.C, blockIdx.x);
+    int s = 0;
+    for (long long p = ch.lo + threadIdx.x; p < ch.hi; p += kBmThreads) s += a.map[a.indices[p]] >= 0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);   // a sum only: one wave reduction and one barrier
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int total = 0;
+        for (int w = 0; w < kBmThreads / 64; ++w) total += wsum[w];
+        a.csum[blockIdx.x] = total;
+    }
+}
+
+__global__ __launch_bounds__(kBmThreads) void k_bm25_live_scan(LiveArgs a, long long chunks) {
+    __shared__ long long part[kBmThreads];
+    const long long L = (chunks + kBmThreads - 1) / kBmThreads;
+    const long long b0 = min((long long)threadIdx.x * L, chunks), b1 = min(b0 + L, chunks);
+    long long s = 0;
+    for (long long i = b0; i < b1; ++i) s += a.csum[i];
+    long long total;
+    long long run = live_block_scan<long long, false>(s, 0ll, part, &total);
+    for (long long i = b0; i < b1; ++i) {
+        const long long f = a.csum[i];
+        a.csum[i] = run;
+        run += f;
+    }
+    if (threadIdx.x == 0) a.csum[chunks] = total;
+}
+
+__global__ __launch_bounds__(kBmThreads) void k_bm25_live_indptr(LiveArgs a) {
+    __shared__ int rank[kLiveMaxChunk + 1];
+    __shared__ int part[kBmThreads];
+    const LiveChunk ch = live_chunk(a.nnz, a.C, blockIdx.x);
+    live_chunk_ranks(a, ch.lo, (int)(ch.hi - ch.lo), nullptr, rank, part);
+    const long long c0 = live_owned_first(a.indptr, a.V, a.Vn, a.nnz, ch), c1 = live_owned_end(a.indptr, a.V, a.Vn, a.nnz, ch);
+    const long long below = a.csum[blockIdx.x];
+    for (long long c = c0 + threadIdx.x; c < c1; c += kBmThreads)
+        a.newptr[c] = live_dest(below + rank[live_old_start(a.indptr, a.V, a.nnz, c) - ch.lo], a.dptr[c]);
+}
+
+__global__ __launch_bounds__(kBmThreads) void k_bm25_live_rewrite(LiveArgs a) {
+    __shared__ int rank[kLiveMaxChunk + 1];
+    __shared__ int rows[kLiveMaxChunk];
+    __shared__ int col[kLiveMaxChunk];
+    __shared__ int part[kBmThreads];
+    const LiveChunk ch = live_chunk(a.nnz, a.C, blockIdx.x);
+    const int cnt = (int)(ch.hi - ch.lo), t = threadIdx.x;
+    if (cnt == 0) return;
+    // the column of every posting: the one that holds the chunk's first posting, then the last column that starts at or below it
+    const long long cfirst = live_col_of(a.indptr, a.V, a.Vn, a.nnz, ch.lo), cend = live_col_lower(a.indptr, a.V, a.Vn, a.nnz, ch.hi);
+    for (int i = t; i < cnt; i += kBmThreads) col[i] = i == 0 ? (int)cfirst : -1;
+    __syncthreads();
+    for (long long c = cfirst + 1 + t; c < cend; c += kBmThreads) atomicMax(&col[a.indptr[c] - ch.lo], (int)c);   // c < cend <= V: starts in (lo, hi)
+    __syncthreads();
+    {
+        const int L = (cnt + kBmThreads - 1) / kBmThreads;
+        const int b0 = min(t * L, cnt), b1 = min(b0 + L, cnt);
+        int mx = -1;
+        for (int i = b0; i < b1; ++i) mx = max(mx, col[i]);
+        int total;
+        int run = live_block_scan<int, true>(mx, -1, part, &total);
+        for (int i = b0; i < b1; ++i) {
+            run = max(run, col[i]);
+            col[i] = run;
+        }
+    }
+    live_chunk_ranks(a, ch.lo, cnt, rows, rank, part);
+    const long long below = a.csum[blockIdx.x];
+    for (int i = t; i < cnt; i += kBmThreads) {
+        const int r = rows[i];
+        if (r < 0) continue;
+        const int c = col[i], f = a.tf[ch.lo + i];
+        const long long d = live_dest(below + rank[i], a.dptr[c]);
+        a.indices1[d] = r;
+        a.tf1[d] = f;
+        a.data1[d] = live_score(a.idf[c], f, a.doclen1[r], a.avgdl, a.k1, a.b, a.one_minus_b);
+    }
+}
+
+__global__ __launch_bounds__(kBmThreads) void k_bm25_live_append(LiveArgs a) {
+    for (long long q = (long long)blockIdx.x * kBmThreads + threadIdx.x; q < a.dnnz; q += (long long)gridDim.x * kBmThreads) {
+        long long lo = 0, hi = a.Vn;   // the delta column of q: the last c with dptr[c] <= q
+        while (lo < hi) {
+            const long long mid = lo + (hi - lo) / 2;
+            if (a.dptr[mid + 1] <= q) lo = mid + 1; else hi = mid;
+        }
+        const long long d = live_delta_dest(a.newptr[lo + 1], a.dptr[lo + 1], q);
+        const int r = (int)(a.n1 + a.drows[q]), f = a.dtf[q];
+        a.indices1[d] = r;
+        a.tf1[d] = f;
+        a.data1[d] = live_score(a.idf[lo], f, a.doclen1[r], a.avgdl, a.k1, a.b, a.one_minus_b);
+    }
+}
+
 }  // namespace vf
 
 using namespace vf;
@@ -379,7 +558,25 @@ struct vf_bm25 {
     long long* d_qoff = nullptr;
     int* d_qterms = nullptr;
     const int32_t* qterms_host = nullptr;   // the caller's q_terms during a search (grid sizes)
+    // a live handle (VF_BM25_LIVE) also keeps what a re-scoring needs
+    bool live = false;
+    bool born = true;                       // false between the stage and the commit that create a live handle
+    int* d_tf = nullptr;                    // [nnz] term frequency of each posting
+    int* d_doclen = nullptr;                // [n] tokens per document
+    struct BmStage* stage = nullptr;        // a staged update: the second set of arrays, not yet swapped in
     std::mutex mu;
+};
+
+// What a stage leaves for its commit.  Everything an update allocates is allocated here, before the first kernel.
+struct BmStage {
+    long long n1 = 0, n_new = 0, Vn = 0, dnnz = 0, cap = 0, chunks = 0;
+    int C = kLiveMaxChunk;
+    int* d_rem = nullptr; int* d_map = nullptr; int* d_doclen1 = nullptr; int* d_delta_dl = nullptr;
+    long long* d_csum = nullptr; long long* d_dptr = nullptr; int* d_drows = nullptr; int* d_dtf = nullptr;
+    long long* d_newptr = nullptr; int* d_indices1 = nullptr; int* d_tf1 = nullptr; float* d_data1 = nullptr;
+    double* d_idf = nullptr;
+    long long m = 0;
+    std::vector<long long> newptr;          // host copy of the new indptr
 };
 
 static long long bm_pow2(long long v) {
@@ -449,18 +646,259 @@ static unsigned bm_grid(long long work, long long per_block, long long cap) {
     return (unsigned)(g < 1 ? 1 : (g > cap ? cap : g));
 }
 
+static void bm_drop_stage(vf_bm25* h) {
+    BmStage* s = h->stage;
+    if (!s) return;
+    void* ps[] = {s->d_rem, s->d_map, s->d_doclen1, s->d_delta_dl, s->d_csum, s->d_dptr, s->d_drows, s->d_dtf, s->d_newptr, s->d_indices1,
+                  s->d_tf1, s->d_data1, s->d_idf};
+    for (void* p : ps)
+        if (p) (void)hipFree(p);
+    delete s;
+    h->stage = nullptr;
+}
+
+static LiveArgs bm_live_args(const vf_bm25* h, const BmStage* s) {
+    LiveArgs a{};
+    a.indptr = h->d_indptr; a.indices = h->d_indices; a.tf = h->d_tf;
+    a.V = h->V; a.Vn = s->Vn; a.nnz = h->nnz; a.n0 = h->n; a.n1 = s->n1; a.n_new = s->n_new; a.C = s->C;
+    a.rem = s->d_rem; a.m = s->m; a.map = s->d_map;
+    a.doclen0 = h->d_doclen; a.doclen1 = s->d_doclen1; a.delta_dl = s->d_delta_dl;
+    a.csum = s->d_csum;
+    a.dptr = s->d_dptr; a.drows = s->d_drows; a.dtf = s->d_dtf; a.dnnz = s->dnnz;
+    a.newptr = s->d_newptr; a.indices1 = s->d_indices1; a.tf1 = s->d_tf1; a.data1 = s->d_data1;
+    return a;
+}
+
 static int bm_destroy(vf_bm25* h) {
     if (!h) return VF_OK;
     DeviceGuard guard;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     bm_free_slots(h);
-    void* ps[] = {h->d_indptr, h->d_indices, h->d_data, h->d_big, h->d_big_tblk, h->d_big_ids, h->d_big_out, h->d_qoff, h->d_qterms};
+    bm_drop_stage(h);
+    void* ps[] = {h->d_indptr, h->d_indices, h->d_data, h->d_big, h->d_big_tblk, h->d_big_ids, h->d_big_out, h->d_qoff, h->d_qterms,
+                  h->d_tf, h->d_doclen};
     for (void* p : ps)
         if (p) (void)hipFree(p);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return VF_OK;
+}
+
+static void bm_free_big(vf_bm25* h) {
+    void* ps[] = {h->d_big, h->d_big_tblk, h->d_big_ids, h->d_big_out};
+    for (void* p : ps)
+        if (p) (void)hipFree(p);
+    h->d_big = nullptr; h->d_big_tblk = nullptr; h->d_big_ids = nullptr; h->d_big_out = nullptr;
+}
+
+static void bm_set_docs(vf_bm25* h, long long n) {   // what depends on the document count
+    h->n = n;
+    h->words = (int)(((n + 31) / 32 + kBmWordsPerBlock - 1) / kBmWordsPerBlock * kBmWordsPerBlock);
+    h->slot_cap = (int)std::max(1ll, std::min((long long)kBmMaxSlots, kBmScratchBudget / bm_slot_bytes(h)));
+}
+
+// ---- live updates (include/veritasfi_hip.h: VF_BM25_LIVE) ---------------------------------------------------------------------
+// Phase 1.  Validates, allocates all the update needs, uploads the delta, runs the row map, the survivor count and the scan, and
+// returns the new per-column counts.  The handle's arrays are only read.
+static int bm_live_stage(vf_bm25* h, vf_bm25_delta* d) {
+    bm_drop_stage(h);
+    if (!h->live) return bm_fail(VF_EINVAL, "vf_bm25_create: VF_BM25_LIVE on a handle that was not created live (it keeps no term frequencies)");
+    const long long Vn = d->vocab, n_new = d->n_new, n0 = h->n;
+    if (Vn < h->V) return bm_fail(VF_EINVAL, "vf_bm25_create: the delta's vocabulary is smaller than the handle's (columns never disappear)");
+    if (Vn > 0x7FFFFFFEll) return bm_fail(VF_EINVAL, "vf_bm25_create: the vocabulary must stay below 2^31 - 1 columns (the kernels keep columns as int32)");
+    if (n_new > 0x7FFFFFFFll) return bm_fail(VF_EINVAL, "vf_bm25_create: n_docs must stay in [1, 2^31 - 1]");
+    if (n_new < 0 || d->n_remove < 0 || !d->indptr || !d->counts || (d->n_remove > 0 && !d->remove))
+        return bm_fail(VF_EINVAL, "vf_bm25_create: null or negative field in vf_bm25_delta");
+    const int C = d->chunk == 0 ? kLiveMaxChunk : d->chunk;
+    if (C < 1 || C > kLiveMaxChunk) return bm_fail(VF_EINVAL, "vf_bm25_create: vf_bm25_delta.chunk must be 0 or in [1, " + std::to_string(kLiveMaxChunk) + "]");
+    const long long dnnz = d->indptr[Vn];
+    if (d->indptr[0] != 0 || dnnz < 0 || (dnnz > 0 && (!d->rows || !d->tf))) return bm_fail(VF_EINVAL, "vf_bm25_create: the delta's indptr must start at 0 and end at its posting count");
+    std::vector<int> delta_dl((size_t)n_new, 0);
+    for (long long c = 0; c < Vn; ++c) {   // what vf_bm25_create checks of an index, with tf >= 1 in place of score > 0
+        if (d->indptr[c + 1] < d->indptr[c] || d->indptr[c + 1] > dnnz) return bm_fail(VF_EINVAL, "vf_bm25_create: the delta's indptr is not non-decreasing");
+        for (long long p = d->indptr[c]; p < d->indptr[c + 1]; ++p) {
+            if (d->rows[p] < 0 || d->rows[p] >= n_new) return bm_fail(VF_EINVAL, "vf_bm25_create: a document row of the delta is out of range");
+            if (p > d->indptr[c] && d->rows[p] <= d->rows[p - 1])
+                return bm_fail(VF_EINVAL, "vf_bm25_create: rows of a delta column must be strictly ascending (one posting per document)");
+            if (d->tf[p] < 1) return bm_fail(VF_EINVAL, "vf_bm25_create: a term frequency of the delta is below 1");
+            if ((long long)delta_dl[d->rows[p]] + d->tf[p] > 0x7FFFFFFFll) return bm_fail(VF_EINVAL, "vf_bm25_create: a document of the delta is longer than 2^31 - 1 tokens");
+            delta_dl[d->rows[p]] += d->tf[p];
+        }
+    }
+    std::vector<int> rem((size_t)d->n_remove);
+    for (long long i = 0; i < d->n_remove; ++i) {
+        if (d->remove[i] < 0 || d->remove[i] >= n0)
+            return bm_fail(VF_EINVAL, "vf_bm25_create: remove[" + std::to_string(i) + "] = " + std::to_string(d->remove[i]) + " is outside 0 .. " + std::to_string(n0 - 1));
+        rem[i] = (int)d->remove[i];
+    }
+    std::sort(rem.begin(), rem.end());
+    rem.erase(std::unique(rem.begin(), rem.end()), rem.end());
+    const long long m = (long long)rem.size(), n1 = n0 - m;
+    if (n1 + n_new < 1) return bm_fail(VF_EINVAL, "vf_bm25_create: the update would leave no document (n_docs >= 1)");
+    if (n1 + n_new > 0x7FFFFFFFll) return bm_fail(VF_EINVAL, "vf_bm25_create: n_docs must stay in [1, 2^31 - 1]");
+
+    BmStage* s = new (std::nothrow) BmStage();
+    if (!s) return bm_fail(VF_ENOMEM, "host allocation failed");
+    h->stage = s;
+    s->n1 = n1; s->n_new = n_new; s->Vn = Vn; s->dnnz = dnnz; s->C = C; s->m = m;
+    s->cap = h->nnz + dnnz;                       // survivors <= nnz: known exactly only after the count, and allocations come first
+    s->chunks = live_chunks(h->nnz, C);
+    try { s->newptr.resize((size_t)Vn + 1); } catch (const std::bad_alloc&) { bm_drop_stage(h); return bm_fail(VF_ENOMEM, "host allocation failed"); }
+    const size_t one = 1;
+    hipError_t e = hipMalloc((void**)&s->d_rem, std::max(one, (size_t)m) * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&s->d_map, std::max(one, (size_t)n0) * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&s->d_doclen1, (size_t)(n1 + n_new) * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&s->d_delta_dl, std::max(one, (size_t)n_new) * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&s->d_csum, (size_t)(s->chunks + 1) * 8);
+    if (e == hipSuccess) e = hipMalloc((void**)&s->d_dptr, (size_t)(Vn + 1) * 8);
+    if (e == hipSuccess) e = hipMalloc((void**)&s->d_drows, std::max(one, (size_t)dnnz) * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&s->d_dtf, std::max(one, (size_t)dnnz) * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&s->d_newptr, (size_t)(Vn + 1) * 8);
+    if (e == hipSuccess) e = hipMalloc((void**)&s->d_indices1, std::max(one, (size_t)s->cap) * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&s->d_tf1, std::max(one, (size_t)s->cap) * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&s->d_data1, std::max(one, (size_t)s->cap) * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&s->d_idf, std::max(one, (size_t)Vn) * 8);
+    hipStream_t st = h->stream;
+    if (e == hipSuccess && m) e = hipMemcpyAsync(s->d_rem, rem.data(), (size_t)m * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && n_new) e = hipMemcpyAsync(s->d_delta_dl, delta_dl.data(), (size_t)n_new * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(s->d_dptr, d->indptr, (size_t)(Vn + 1) * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && dnnz) e = hipMemcpyAsync(s->d_drows, d->rows, (size_t)dnnz * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && dnnz) e = hipMemcpyAsync(s->d_dtf, d->tf, (size_t)dnnz * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        LiveArgs a = bm_live_args(h, s);
+        hipLaunchKernelGGL(k_bm25_live_rowmap, dim3(bm_grid(std::max(n0, n_new), kBmThreads, 8192)), dim3(kBmThreads), 0, st, a);
+        hipLaunchKernelGGL(k_bm25_live_count, dim3((unsigned)s->chunks), dim3(kBmThreads), 0, st, a);
+        hipLaunchKernelGGL(k_bm25_live_scan, dim3(1), dim3(kBmThreads), 0, st, a, s->chunks);
+        hipLaunchKernelGGL(k_bm25_live_indptr, dim3((unsigned)s->chunks), dim3(kBmThreads), 0, st, a);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(s->newptr.data(), s->d_newptr, (size_t)(Vn + 1) * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+        const std::string msg = std::string("vf_bm25_create (stage): ") + hipGetErrorString(e);
+        bm_drop_stage(h);
+        return bm_fail(e == hipErrorOutOfMemory ? VF_ENOMEM : VF_EHIP, msg);
+    }
+    for (long long c = 0; c < Vn; ++c) d->counts[c] = s->newptr[c + 1] - s->newptr[c];
+    d->n_removed = m;
+    return VF_OK;
+}
+
+// Phase 2.  Re-scores and rewrites every posting into the staged arrays, then swaps them in.
+static int bm_live_commit(vf_bm25* h, const vf_bm25_delta* d) {
+    BmStage* s = h->stage;
+    if (!s) return bm_fail(VF_EINVAL, "vf_bm25_create: VF_BM25_COMMIT without a staged update");
+    if (!d->idf || d->vocab != s->Vn || !(d->avgdl > 0.0) || !(d->k1 >= 0.0) || !(d->b >= 0.0 && d->b <= 1.0)) {
+        bm_drop_stage(h);
+        return bm_fail(VF_EINVAL, "vf_bm25_create: the commit needs idf[vocab] of the staged vocabulary, avgdl > 0, k1 >= 0 and b in [0, 1]");
+    }
+    hipStream_t st = h->stream;
+    LiveArgs a = bm_live_args(h, s);
+    a.idf = s->d_idf; a.avgdl = d->avgdl; a.k1 = d->k1; a.b = d->b; a.one_minus_b = 1.0 - d->b;
+    hipError_t e = hipSuccess;
+    if (s->Vn) e = hipMemcpyAsync(s->d_idf, d->idf, (size_t)s->Vn * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        if (h->nnz) hipLaunchKernelGGL(k_bm25_live_rewrite, dim3((unsigned)s->chunks), dim3(kBmThreads), 0, st, a);
+        if (s->dnnz) hipLaunchKernelGGL(k_bm25_live_append, dim3(bm_grid(s->dnnz, kBmThreads, 8192)), dim3(kBmThreads), 0, st, a);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+        const std::string msg = std::string("vf_bm25_create (commit): ") + hipGetErrorString(e);
+        bm_drop_stage(h);
+        return bm_fail(VF_EHIP, msg);
+    }
+    // the swap: from here nothing can fail
+    void* old[] = {h->d_indptr, h->d_indices, h->d_data, h->d_tf, h->d_doclen};
+    for (void* p : old)
+        if (p) (void)hipFree(p);
+    h->d_indptr = s->d_newptr; h->d_indices = s->d_indices1; h->d_data = s->d_data1; h->d_tf = s->d_tf1; h->d_doclen = s->d_doclen1;
+    s->d_newptr = nullptr; s->d_indices1 = nullptr; s->d_data1 = nullptr; s->d_tf1 = nullptr; s->d_doclen1 = nullptr;
+    h->indptr.swap(s->newptr);
+    h->V = s->Vn; h->nnz = h->indptr[(size_t)s->Vn];
+    const long long n = s->n1 + s->n_new;
+    if (n != h->n) {   // the per-query scratch is sized by n: dropped, and made again (zeroed) by the next search
+        bm_free_slots(h);
+        bm_free_big(h);
+        bm_set_docs(h, n);
+    }
+    h->born = true;
+    bm_drop_stage(h);
+    return VF_OK;
+}
+
+static int bm_live_fetch(vf_bm25* h, const vf_bm25_delta* d) {
+    if (!h->live || !h->born) return bm_fail(VF_EINVAL, "vf_bm25_create: VF_BM25_FETCH needs a live handle");
+    hipStream_t st = h->stream;
+    if (d->out_indptr) VFS_HIP(hipMemcpyAsync(d->out_indptr, h->d_indptr, (size_t)(h->V + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (d->out_indices && h->nnz) VFS_HIP(hipMemcpyAsync(d->out_indices, h->d_indices, (size_t)h->nnz * 4, hipMemcpyDeviceToHost, st));
+    if (d->out_data && h->nnz) VFS_HIP(hipMemcpyAsync(d->out_data, h->d_data, (size_t)h->nnz * 4, hipMemcpyDeviceToHost, st));
+    if (d->out_tf && h->nnz) VFS_HIP(hipMemcpyAsync(d->out_tf, h->d_tf, (size_t)h->nnz * 4, hipMemcpyDeviceToHost, st));
+    if (d->out_doc_len) VFS_HIP(hipMemcpyAsync(d->out_doc_len, h->d_doclen, (size_t)h->n * 4, hipMemcpyDeviceToHost, st));
+    VFS_HIP(hipStreamSynchronize(st));
+    return VF_OK;
+}
+
+static int bm_live_call(vf_bm25_delta* d, int32_t device_id, vf_bm25** out, int32_t* slots) {
+    const int phase = device_id & (VF_BM25_LIVE | VF_BM25_COMMIT | VF_BM25_DISCARD | VF_BM25_FETCH);
+    const int dev = device_id & 0xFFF;
+    if (phase != VF_BM25_LIVE && phase != VF_BM25_COMMIT && phase != VF_BM25_DISCARD && phase != VF_BM25_FETCH)
+        return bm_fail(VF_EINVAL, "vf_bm25_create: exactly one of VF_BM25_LIVE, VF_BM25_COMMIT, VF_BM25_DISCARD and VF_BM25_FETCH");
+    vf_bm25* h = *out;
+    if (!h) {   // a stage on no handle starts one: it is born by its commit
+        if (phase != VF_BM25_LIVE) return bm_fail(VF_EINVAL, "vf_bm25_create: null handle");
+        int ndev = 0;
+        VFS_HIP(hipGetDeviceCount(&ndev));
+        if (dev >= ndev) return bm_fail(VF_EINVAL, "vf_bm25_create: bad device_id");
+        DeviceGuard guard;
+        VFS_HIP(hipSetDevice(dev));
+        h = new (std::nothrow) vf_bm25();
+        if (!h) return bm_fail(VF_ENOMEM, "host allocation failed");
+        h->device = dev; h->live = true; h->born = false;
+        hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+        if (e == hipSuccess) e = hipMalloc((void**)&h->d_indptr, 8);
+        if (e == hipSuccess) e = hipMemset(h->d_indptr, 0, 8);
+        if (e != hipSuccess) {
+            const std::string msg = std::string("vf_bm25_create: ") + hipGetErrorString(e);
+            bm_destroy(h);
+            return bm_fail(e == hipErrorOutOfMemory ? VF_ENOMEM : VF_EHIP, msg);
+        }
+        int rc;
+        try {   // the host vectors of a stage allocate: no exception leaves the C ABI
+            h->indptr.assign(1, 0);
+            rc = bm_live_stage(h, d);
+        } catch (const std::bad_alloc&) {
+            rc = bm_fail(VF_ENOMEM, "host allocation failed");
+        }
+        if (rc != VF_OK) { bm_destroy(h); return rc; }
+        *out = h;
+        return VF_OK;
+    }
+    if (dev != h->device) return bm_fail(VF_EINVAL, "vf_bm25_create: device_id is not the handle's device");
+    int rc;
+    {
+        std::lock_guard<std::mutex> lk(h->mu);
+        DeviceGuard guard;
+        VFS_HIP(hipSetDevice(h->device));
+        if (phase == VF_BM25_LIVE) {
+            try {
+                rc = bm_live_stage(h, d);
+            } catch (const std::bad_alloc&) {   // as every refusal of a stage: the handle is as it was
+                bm_drop_stage(h);
+                rc = bm_fail(VF_ENOMEM, "host allocation failed");
+            }
+        } else if (phase == VF_BM25_COMMIT) rc = bm_live_commit(h, d);
+        else if (phase == VF_BM25_FETCH) rc = bm_live_fetch(h, d);
+        else { bm_drop_stage(h); rc = VF_OK; }
+        if (rc == VF_OK && slots) *slots = h->slot_cap;
+        if (h->born) return rc;
+    }
+    if (rc != VF_OK || phase == VF_BM25_DISCARD) {   // a handle that was never born does not outlive its failed or discarded creation
+        bm_destroy(h);
+        *out = nullptr;
+    }
+    return rc;
 }
 
 extern "C" int vf_bm25_create(const int64_t* indptr, int64_t V, const int32_t* indices, const float* data, int64_t nnz,
@@ -471,6 +909,8 @@ extern "C" int vf_bm25_create(const int64_t* indptr, int64_t V, const int32_t* i
         *out = nullptr;
         return VF_OK;
     }
+    if (device_id >= 0 && (device_id & ~0xFFF))   // a live update: `indptr` is a vf_bm25_delta
+        return bm_live_call((vf_bm25_delta*)(void*)indptr, device_id, out, slots);
     *out = nullptr;
     if (!indptr || V < 0 || nnz < 0 || (nnz > 0 && (!indices || !data))) return bm_fail(VF_EINVAL, "vf_bm25_create: null or negative argument");
     if (n_docs <= 0 || n_docs > 0x7FFFFFFFll) return bm_fail(VF_EINVAL, "vf_bm25_create: n_docs must be in [1, 2^31 - 1]");
@@ -566,6 +1006,7 @@ extern "C" int vf_bm25_search(vf_bm25* h, const int64_t* q_offsets, const int32_
     if (nq < 0) return bm_fail(VF_EINVAL, "vf_bm25_search: negative nq");
     if (nq == 0) return VF_OK;
     if (!q_offsets || !out_ids || !out_scores) return bm_fail(VF_EINVAL, "vf_bm25_search: null buffer");
+    std::lock_guard<std::mutex> lk(h->mu);   // before n_docs and the vocabulary are read: a live handle's update changes both
     if (k < 1 || (long long)k > h->n) return bm_fail(VF_EINVAL, "vf_bm25_search: k must be in [1, n_docs]");
     if (q_offsets[0] != 0) return bm_fail(VF_EINVAL, "vf_bm25_search: q_offsets[0] must be 0");
     for (int q = 0; q < nq; ++q)
@@ -574,7 +1015,6 @@ extern "C" int vf_bm25_search(vf_bm25* h, const int64_t* q_offsets, const int32_
     if (T > 0 && !q_terms) return bm_fail(VF_EINVAL, "vf_bm25_search: null q_terms");
     for (long long t = 0; t < T; ++t)
         if (q_terms[t] < 0 || q_terms[t] >= h->V) return bm_fail(VF_EINVAL, "vf_bm25_search: a token column is out of range");
-    std::lock_guard<std::mutex> lk(h->mu);
     DeviceGuard guard;
     VFS_HIP(hipSetDevice(h->device));
     hipStream_t st = h->stream;

@@ -112,12 +112,7 @@ class EnsembleRetriever:
         self.docid2idx: Dict[str, int] = {}
         self._bundle_rows: Dict[object, List[int]] = {}
         self._title_rows: Dict[str, List[int]] = {}
-        for row, md in enumerate(self.chunk_metadata):
-            self.docid2idx[md["doc_id"]] = row
-            b = md.get("bundle_id", None)
-            if b is not None:
-                self._bundle_rows.setdefault(b, []).append(row)
-            self._title_rows.setdefault(md.get("title_summary", ""), []).append(row)
+        self._build_maps()
         self._text_rows = _TextRows()
         self.similarity_from_rows = self._rows_serve_similarity() if similarity_from_rows is None else bool(similarity_from_rows)
 
@@ -131,6 +126,130 @@ class EnsembleRetriever:
             if getattr(self.embeddings, name, None):
                 return False
         return True
+
+    # -- a live corpus --------------------------------------------------------------------------------
+    def _build_maps(self) -> None:
+        self.docid2idx, self._bundle_rows, self._title_rows = {}, {}, {}
+        for row, md in enumerate(self.chunk_metadata):
+            self.docid2idx[md["doc_id"]] = row
+            b = md.get("bundle_id", None)
+            if b is not None:
+                self._bundle_rows.setdefault(b, []).append(row)
+            self._title_rows.setdefault(md.get("title_summary", ""), []).append(row)
+
+    def _check_live(self, need_bm25: str, need_dense: str) -> None:
+        """What can be known to refuse before any leg is asked: the BM25 leg is the live one and in step, the dense retriever has the
+        call and -- where it is this package's -- was told how its index holds the rows (``FaissRetriever.from_index`` without
+        ``corpus_dtype`` refuses every change)."""
+        if self.bm25_retriever is not None:
+            bm = self.bm25_retriever
+            if not (getattr(bm, "live", False) is True and hasattr(bm, need_bm25)):
+                raise ValueError("EnsembleRetriever: the BM25 leg cannot follow an added or removed chunk -- it must be this package's "
+                                 "live one, bm25_retriever=veritasfi_amd.BM25Retriever(bm25_dir, live=True)")
+            if bm.num_docs != self.num_chunk:
+                raise ValueError(f"EnsembleRetriever: the BM25 leg holds {bm.num_docs} documents, the corpus {self.num_chunk}")
+        dense = self.faiss_retriever
+        if not hasattr(dense, need_dense):
+            raise ValueError(f"EnsembleRetriever: the dense retriever has no {need_dense}(): it cannot follow an added or removed chunk")
+        if getattr(dense, "corpus_dtype", "") is None:
+            raise ValueError("EnsembleRetriever: the dense retriever wraps an index it did not build and was not told how that index "
+                             "holds its rows (FaissRetriever.from_index(..., corpus_dtype=...)): it cannot follow an added or removed chunk")
+
+    def add_documents(self, texts, metadatas, embeddings=None) -> List[int]:
+        """Append chunks to every leg together; returns their rows (num_chunk .. num_chunk + m - 1 before the call).
+        ``embeddings`` [m, d] are the chunks' vectors; without them ``texts`` are embedded here, as ``FaissRetriever.add_texts`` embeds
+        them (``embed_documents``, or ``embed_query`` per text).  The BM25 leg tokenises the texts with its own tokeniser;
+        ``chunk_metadata``, ``num_chunk``, the prefetched documents and the three maps follow.  Each metadata needs a ``doc_id`` no
+        chunk has yet.
+        Nothing changes when the call raises.  Checked before any leg is asked: the doc_ids, a BM25 leg that is not this package's
+        live one or is out of step, a dense retriever that cannot append, the embedder (it runs first), the vectors' width.  Then the
+        dense leg appends -- if IT refuses, nothing has changed -- and the BM25 leg follows; should that fail, the dense leg's new
+        rows are removed again (the newest rows: nothing moves) before the error is passed on.
+        Chroma itself (``self.chroma``: ``_fetch`` reads new chunks' texts from it unless documents are prefetched) and the
+        title-summary index are the caller's: add the chunks to the store first, and a ``title_summary`` the title index does not
+        hold is found by the other two branches only."""
+        texts, metadatas = list(texts), list(metadatas)
+        if len(texts) != len(metadatas):
+            raise ValueError("add_documents: one metadata per text")
+        if embeddings is not None and len(embeddings) != len(texts):
+            raise ValueError("add_documents: one embedding per text")
+        ids = [md["doc_id"] for md in metadatas]
+        if len(set(ids)) != len(ids) or any(i in self.docid2idx for i in ids):
+            raise ValueError("add_documents: a doc_id is repeated or already in the corpus")
+        dense = self.faiss_retriever
+        by_vectors = hasattr(dense, "add_embeddings")     # a retriever with add_texts alone embeds for itself
+        if embeddings is not None and not by_vectors:
+            raise ValueError("EnsembleRetriever: the dense retriever has no add_embeddings(): pass the texts without embeddings")
+        self._check_live("update", "add_embeddings" if by_vectors else "add_texts")
+        first = self.num_chunk
+        if not texts:
+            return []
+        if by_vectors:
+            if embeddings is None:
+                embed_docs = getattr(self.embeddings, "embed_documents", None)
+                embeddings = embed_docs(texts) if embed_docs is not None else [self.embeddings.embed_query(t) for t in texts]
+            embeddings = np.asarray(embeddings)
+            if embeddings.ndim != 2 or embeddings.shape[0] != len(texts):
+                raise ValueError(f"add_documents: embeddings must be [{len(texts)}, d], got {embeddings.shape}")
+            d = getattr(getattr(dense, "index", None), "d", None)
+            if d is not None and embeddings.shape[1] != d:
+                raise ValueError(f"add_documents: embeddings of width {embeddings.shape[1]} for an index of width {d}")
+            dense.add_embeddings(embeddings)
+        else:
+            dense.add_texts(texts)
+        if self.bm25_retriever is not None:
+            try:
+                self.bm25_retriever.update([], texts, doc_ids=ids)
+            except Exception:
+                if hasattr(dense, "remove_ids"):
+                    dense.remove_ids(np.arange(first, first + len(texts), dtype=np.int64))
+                raise
+        self.chunk_metadata = list(self.chunk_metadata) + metadatas
+        self.num_chunk = len(self.chunk_metadata)
+        if self._documents is not None:
+            self._documents = list(self._documents) + texts
+        for row, md in enumerate(metadatas, start=first):
+            self.docid2idx[md["doc_id"]] = row
+            b = md.get("bundle_id", None)
+            if b is not None:
+                self._bundle_rows.setdefault(b, []).append(row)
+            self._title_rows.setdefault(md.get("title_summary", ""), []).append(row)
+        return list(range(first, self.num_chunk))
+
+    def remove_documents(self, doc_ids) -> int:
+        """Remove chunks by ``doc_id`` from every leg together; later rows move down in all of them (faiss ``remove_ids``), so the
+        maps are rebuilt and the remembered text rows forgotten.  Returns the number removed.
+        Refused with nothing changed: an unknown ``doc_id``, removing every chunk, a BM25 leg that is not this package's live one or
+        is out of step, a dense retriever that cannot remove -- and whatever the dense leg itself refuses (a search in flight, a shard
+        of a group that would be emptied), because it is asked FIRST.  The BM25 leg follows with rows that were checked here (in
+        range, not all of them), so only a device failure can stop it; a removal cannot be undone in place, so that error is passed
+        on as a RuntimeError saying that the legs are out of step and the retriever must be constructed again.
+        Chroma itself and the title-summary index are the caller's."""
+        doc_ids = list(doc_ids)
+        unknown = [i for i in doc_ids if i not in self.docid2idx]
+        if unknown:
+            raise ValueError(f"remove_documents: unknown doc_id {unknown[0]!r}")
+        rows = sorted({self.docid2idx[i] for i in doc_ids})
+        if len(rows) >= self.num_chunk and rows:
+            raise ValueError("remove_documents: at least one chunk must remain")
+        self._check_live("remove", "remove_ids")
+        if not rows:
+            return 0
+        self.faiss_retriever.remove_ids(np.asarray(rows, dtype=np.int64))
+        if self.bm25_retriever is not None:
+            try:
+                self.bm25_retriever.remove(rows)
+            except Exception as e:
+                raise RuntimeError(f"remove_documents: the dense leg removed {len(rows)} rows and the BM25 leg then failed ({e}): the "
+                                   "legs are out of step, construct the EnsembleRetriever again") from e
+        gone = set(rows)
+        self.chunk_metadata = [md for r, md in enumerate(self.chunk_metadata) if r not in gone]
+        self.num_chunk = len(self.chunk_metadata)
+        if self._documents is not None:
+            self._documents = [t for r, t in enumerate(self._documents) if r not in gone]
+        self._build_maps()
+        self._text_rows = _TextRows()
+        return len(rows)
 
     # -- pieces -------------------------------------------------------------------------------------
     def _bundle_of(self, row: int, seen: set) -> List[int]:
