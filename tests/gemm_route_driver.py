@@ -100,6 +100,14 @@ static void check(const GemmIn& in) {
     // no cut of any kind without a workspace, with the tail off, or under an epilogue no co-operative finish serves
     if (!in.has_ws || in.knobs.splitk_tail == 0 || in.epi == 3 || in.epi == 11) CHECK(r.slices == 0 && r.kernel != kGemm9Split);
     if (in.epi == 3 || in.epi == 11) CHECK(r.kernel != kGemm9StreamK);
+    // ... so under those two a workspace changes nothing at all: a caller may pass one to every product (the pre-LayerNorm layer loop does)
+    if ((in.epi == 3 || in.epi == 11) && in.has_ws) {
+        GemmIn bare = in;
+        bare.has_ws = false; bare.ws_bytes = 0;
+        const GemmRoute b = route_gemm(bare);
+        CHECK(b.kernel == r.kernel && b.grid == r.grid && b.slices == r.slices && b.tail_tiles == r.tail_tiles && b.full_tiles == r.full_tiles &&
+              b.stagger_ticks == r.stagger_ticks);
+    }
     // stream-K only where it is compiled in AND asked for
     if (r.kernel == kGemm9StreamK) CHECK(in.knobs.experiments && (in.knobs.gemm9_streamk || in.knobs.kind == 12));
 }

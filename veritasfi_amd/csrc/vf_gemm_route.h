@@ -190,7 +190,8 @@ inline GemmRoute route_gemm(const GemmIn& in) {
             // Round 5, after the relaxed arrival made the finish cheaper: between one and two rounds, when the remainder can be cut at least
             // in two (<= half the CUs), the 8-phase kernel's tail wins as well -- 300 tiles at K = 3072 (FFN-down of 50 pairs) 136 vs
             // 145-147 us; a remainder too large to cut stays here (450 tiles: 180-183 vs 186-187; profiles/r05_tail8p_vs_gemm9.log)
-            if (kind == 10 || K < kLongK || tiles % G == 0 || (tiles <= 2 * ncu8 && !tail_cuttable(in, tiles, ncu8))) {
+            // (under an epilogue no co-operative finish serves there is no tail to win with: a workspace then changes nothing)
+            if (kind == 10 || K < kLongK || tiles % G == 0 || (tiles <= 2 * ncu8 && !(epi_cut && tail_cuttable(in, tiles, ncu8)))) {
                 // a tile's time in ticks of the 100 MHz real-time counter: ~1.5 us per K-tile + 2 (the stagger spreads the workgroups over it)
                 r.kernel = kGemm9; r.grid = G;
                 r.stagger_ticks = tiles > ncu8 ? (int)((150ll * nkt + 200) * kn.stagger_pct / 100) : 0;

@@ -3118,12 +3118,89 @@ static hipError_t handle_stream(hipStream_t* s) {
     return *s ? hipSuccess : hipStreamCreateWithFlags(s, hipStreamNonBlocking);
 }
 
-struct vf_encoder {
+// ------------------------------------------------------------------------------------------------
+// What the four model handles (vf_encoder, vf_decoder, vf_vit, vf_clip_text) share: the state, the create / destroy steps, the size
+// formulas and the configuration check of the BERT-shaped layer.  Every entry point that selects a handle's device holds a
+// vf::DeviceGuard (vf_internal.h) while it does.
+// ------------------------------------------------------------------------------------------------
+namespace vft {
+
+// A handle's workspace: device buffers known by the address of the field that names each, so that one line allocates a buffer (and says
+// whether it starts zeroed) and free_all() frees and nulls them all -- no second list to keep in step.
+struct DevPool {
+    std::vector<void**> fields;
+    template <typename T>
+    hipError_t get(T** field, size_t bytes, bool zero, hipStream_t st) {   // zero: filled on the handle's stream, in front of its forward
+        const hipError_t e = hipMalloc((void**)field, bytes);
+        if (e != hipSuccess) return e;
+        fields.push_back((void**)field);
+        return zero ? hipMemsetAsync(*field, 0, bytes, st) : hipSuccess;
+    }
+    void free_all() {   // the owner has synchronised its device
+        for (void** f : fields) { (void)hipFree(*f); *f = nullptr; }
+        fields.clear();
+    }
+};
+
+struct ModelBase {
+    hipStream_t stream = nullptr;   // this handle's own stream (handle_stream)
     GemmWs gws;
-    vf_encoder_config cfg{};
     int device = 0;
     half_t* w16 = nullptr;   // all fp16 matrices
-    float* w32 = nullptr;    // all fp32 vectors (biases, LayerNorm)
+    float* w32 = nullptr;    // all fp32 vectors (biases, norms)
+    DevPool ws;              // the workspace, grown on demand (*_ensure_ws)
+    std::mutex mu;
+};
+
+static int model_check_device(int device_id, const std::string& who) {
+    int ndev = 0;
+    VFT_HIP(hipGetDeviceCount(&ndev));
+    if (device_id < 0 || device_id >= ndev) return fail(VF_EINVAL, who + ": bad device_id");
+    return VF_OK;
+}
+// the two weight blobs onto the current device (= m.device), and every kernel opted into its LDS
+static hipError_t model_upload(ModelBase& m, const void* w16, int64_t n16, const float* w32, int64_t n32) {
+    hipError_t er = hipMalloc((void**)&m.w16, (size_t)n16 * 2);
+    if (er == hipSuccess) er = hipMalloc((void**)&m.w32, (size_t)n32 * 4);
+    if (er == hipSuccess) er = hipMemcpy(m.w16, w16, (size_t)n16 * 2, hipMemcpyHostToDevice);
+    if (er == hipSuccess) er = hipMemcpy(m.w32, w32, (size_t)n32 * 4, hipMemcpyHostToDevice);
+    if (er == hipSuccess) er = configure_once();
+    return er;
+}
+// a create that failed on the device: the message is built before the destroy's own HIP calls
+template <typename H>
+static int model_create_failed(H* h, int (*destroy)(H*), const char* who, hipError_t er) {
+    const std::string msg = std::string(who) + ": " + hipGetErrorString(er);
+    destroy(h);
+    return fail(VF_EHIP, msg);
+}
+// everything ModelBase owns (current device = m.device); a handle that never ran a forward has no stream and an empty pool
+static void model_release(ModelBase& m) {
+    (void)hipDeviceSynchronize();
+    m.ws.free_all();
+    gws_free(m.gws);
+    if (m.stream) (void)hipStreamDestroy(m.stream);
+    if (m.w16) (void)hipFree(m.w16);
+    if (m.w32) (void)hipFree(m.w32);
+}
+
+// elements of one BERT-shaped layer (encoder, vision tower, CLIP text tower): fp16 Wqkv, Wo, W1, W2; the fp32 vectors in the order of the
+// post-LayerNorm layer (bqkv, bo, LN1, b1, b2, LN2) and of the pre-LayerNorm one (LN1, bqkv, bo, LN2, b1, b2)
+static size_t bert_layer16(size_t H, size_t F) { return 3 * H * H + H * H + F * H + H * F; }
+static size_t postln_layer32(size_t H, size_t F) { return 3 * H + H + 2 * H + F + H + 2 * H; }
+static size_t preln_layer32(size_t H, size_t F) { return 2 * H + 3 * H + H + 2 * H + F + H; }
+// ... and what the kernels ask of its widths; prefix: "", "vit: " or "clip text: "
+static int bert_check_dims(int hidden, int heads, int ffn, const std::string& prefix) {
+    if (hidden <= 0 || hidden % 128 != 0 || hidden > 1024) return fail(VF_EUNSUPPORTED, prefix + "hidden must be a multiple of 128, <= 1024");
+    if (heads <= 0 || hidden % heads || hidden / heads != 64) return fail(VF_EUNSUPPORTED, prefix + "head dim must be 64");
+    if (ffn <= 0 || ffn % 128 != 0) return fail(VF_EUNSUPPORTED, prefix + "ffn must be a multiple of 128");
+    return VF_OK;
+}
+
+}  // namespace vft
+
+struct vf_encoder : ModelBase {
+    vf_encoder_config cfg{};
     bool q_folded = true;    // log2(e) / sqrt(dh) folded into the query projection (k_scale_half at load)
     // fp16 offsets (elements)
     size_t o_word = 0, o_pos = 0, o_type = 0, o_layers = 0, o_head_dense = 0, o_head_out = 0, layer16 = 0;
@@ -3151,20 +3228,18 @@ struct vf_encoder {
     struct GraphKey { int B, T, Tv, tt, pooling, normalize; bool operator==(const GraphKey& o) const { return B == o.B && T == o.T && Tv == o.Tv && tt == o.tt && pooling == o.pooling && normalize == o.normalize; } };
     struct GraphEntry { GraphKey key; hipGraphExec_t exec; };
     std::vector<GraphEntry> graphs;
-    hipStream_t gstream = nullptr;
-    std::mutex mu;
 };
 
 static size_t enc_n16(const vf_encoder_config& c) {
     const size_t H = c.hidden, F = c.ffn;
     size_t n = (size_t)c.vocab * H + (size_t)c.max_pos * H + (size_t)c.type_vocab * H;
-    n += (size_t)c.layers * (3 * H * H + H * H + F * H + H * F);
+    n += (size_t)c.layers * bert_layer16(H, F);
     if (c.head == 1) n += H * H + H;
     return n;
 }
 static size_t enc_n32(const vf_encoder_config& c) {
     const size_t H = c.hidden, F = c.ffn;
-    size_t n = 2 * H + (size_t)c.layers * (3 * H + H + 2 * H + F + H + 2 * H);
+    size_t n = 2 * H + (size_t)c.layers * postln_layer32(H, F);
     if (c.head == 1) n += H + 1;
     return n;
 }
@@ -3181,26 +3256,13 @@ static void enc_drop_graphs(vf_encoder* e) {
     e->graphs.clear();
 }
 
-static void enc_free_ws(vf_encoder* e) {
-    enc_drop_graphs(e);   // captured launches hold the workspace pointers
-    void* p[] = {e->x, e->y, e->qkv, e->ctx, e->hbuf, e->d_ids, e->d_mask, e->d_tt, e->d_pos, e->d_out, e->d_hidden, e->d_seq, e->stats_a, e->stats_b};
-    for (void* q : p) if (q) (void)hipFree(q);
-    e->x = e->y = e->qkv = e->ctx = e->hbuf = nullptr;
-    e->stats_a = e->stats_b = nullptr;
-    e->d_ids = e->d_mask = e->d_tt = e->d_pos = e->d_seq = nullptr;
-    e->d_out = nullptr; e->d_hidden = nullptr;
-    e->cap_tokens = 0; e->cap_b = 0;
-}
-
 extern "C" int vf_encoder_destroy(vf_encoder* e) {
     if (!e) return VF_OK;
+    vf::DeviceGuard guard;
     (void)hipSetDevice(e->device);
     (void)hipDeviceSynchronize();
-    enc_free_ws(e);
-    gws_free(e->gws);
-    if (e->gstream) (void)hipStreamDestroy(e->gstream);
-    if (e->w16) (void)hipFree(e->w16);
-    if (e->w32) (void)hipFree(e->w32);
+    enc_drop_graphs(e);   // before the workspace goes: captured launches hold its pointers
+    model_release(*e);
     if (e->d_flag) (void)hipFree(e->d_flag);
     if (e->sk_part) (void)hipFree(e->sk_part);
     if (e->sk_cnt) (void)hipFree(e->sk_cnt);
@@ -3216,16 +3278,13 @@ extern "C" int vf_encoder_create(vf_encoder** out, const vf_encoder_config* cfg,
     *out = nullptr;
     if (!cfg || !w16 || !w32) return fail(VF_EINVAL, "vf_encoder_create: null argument");
     const vf_encoder_config& c = *cfg;
-    if (c.hidden <= 0 || c.hidden % 128 != 0 || c.hidden > 1024) return fail(VF_EUNSUPPORTED, "hidden must be a multiple of 128, <= 1024");
-    if (c.heads <= 0 || c.hidden / c.heads != 64 || c.hidden % c.heads) return fail(VF_EUNSUPPORTED, "head dim must be 64");
-    if (c.ffn <= 0 || c.ffn % 128 != 0) return fail(VF_EUNSUPPORTED, "ffn must be a multiple of 128");
+    VFT_TRY(bert_check_dims(c.hidden, c.heads, c.ffn, ""));
     if (c.layers <= 0 || c.vocab <= 0 || c.max_pos <= 0 || c.type_vocab <= 0) return fail(VF_EINVAL, "bad encoder config");
     if (c.pooling < 0 || c.pooling > 3 || c.head < 0 || c.head > 1) return fail(VF_EINVAL, "bad pooling / head");
     if ((size_t)n16 != enc_n16(c) || (size_t)n32 != enc_n32(c))
         return fail(VF_EINVAL, "vf_encoder_create: weight blob sizes do not match the config (see vf_encoder_weight_sizes)");
-    int ndev = 0;
-    VFT_HIP(hipGetDeviceCount(&ndev));
-    if (device_id < 0 || device_id >= ndev) return fail(VF_EINVAL, "vf_encoder_create: bad device_id");
+    VFT_TRY(model_check_device(device_id, "vf_encoder_create"));
+    vf::DeviceGuard guard;
     VFT_HIP(hipSetDevice(device_id));
     vf_encoder* e = new (std::nothrow) vf_encoder();
     if (!e) return fail(VF_ENOMEM, "host allocation failed");
@@ -3233,26 +3292,22 @@ extern "C" int vf_encoder_create(vf_encoder** out, const vf_encoder_config* cfg,
     const size_t H = c.hidden, F = c.ffn;
     e->o_word = 0; e->o_pos = e->o_word + (size_t)c.vocab * H; e->o_type = e->o_pos + (size_t)c.max_pos * H;
     e->o_layers = e->o_type + (size_t)c.type_vocab * H;
-    e->layer16 = 3 * H * H + H * H + F * H + H * F;
+    e->layer16 = bert_layer16(H, F);
     e->o_head_dense = e->o_layers + (size_t)c.layers * e->layer16;
     e->o_head_out = e->o_head_dense + H * H;
     e->f_emb_g = 0; e->f_emb_b = H; e->f_layers = 2 * H;
-    e->layer32 = 3 * H + H + 2 * H + F + H + 2 * H;
+    e->layer32 = postln_layer32(H, F);
     e->f_head_bd = e->f_layers + (size_t)c.layers * e->layer32;
     e->f_head_bp = e->f_head_bd + H;
-    hipError_t er = hipMalloc((void**)&e->w16, (size_t)n16 * 2);
-    if (er == hipSuccess) er = hipMalloc((void**)&e->w32, (size_t)n32 * 4);
+    hipError_t er = model_upload(*e, w16, n16, w32, n32);
     if (er == hipSuccess) er = hipMalloc((void**)&e->d_flag, 4);
     {
         const size_t nmax = std::max<size_t>(3 * (size_t)cfg->hidden, (size_t)cfg->ffn);
         if (er == hipSuccess) er = hipMalloc((void**)&e->sk_part, (size_t)kSplitMax * kSplitMaxRows * nmax * sizeof(float));
         if (er == hipSuccess) er = hipMalloc((void**)&e->sk_cnt, 4096 * sizeof(unsigned));
-        if (er == hipSuccess) er = handle_stream(&e->gstream);
-        if (er == hipSuccess) er = hipMemsetAsync(e->sk_cnt, 0, 4096 * sizeof(unsigned), e->gstream);   // (not the legacy stream: see handle_stream)
+        if (er == hipSuccess) er = handle_stream(&e->stream);
+        if (er == hipSuccess) er = hipMemsetAsync(e->sk_cnt, 0, 4096 * sizeof(unsigned), e->stream);   // (not the legacy stream: see handle_stream)
     }
-    if (er == hipSuccess) er = hipMemcpy(e->w16, w16, (size_t)n16 * 2, hipMemcpyHostToDevice);
-    if (er == hipSuccess) er = hipMemcpy(e->w32, w32, (size_t)n32 * 4, hipMemcpyHostToDevice);
-    if (er == hipSuccess) er = configure_once();
     if (er == hipSuccess && e->q_folded) {
         const float qs = 0.125f * 1.4426950408889634f;   // log2(e) / sqrt(64)
         for (int l = 0; l < c.layers; ++l) {
@@ -3263,51 +3318,46 @@ extern "C" int vf_encoder_create(vf_encoder** out, const vf_encoder_config* cfg,
         }
         er = hipDeviceSynchronize();
     }
-    if (er != hipSuccess) {
-        const std::string msg = std::string("vf_encoder_create: ") + hipGetErrorString(er);
-        vf_encoder_destroy(e);
-        return fail(VF_EHIP, msg);
-    }
+    if (er != hipSuccess) return model_create_failed(e, vf_encoder_destroy, "vf_encoder_create", er);
     *out = e;
     return VF_OK;
 }
 
+// Every *_ensure_ws below: the zero fills run on the handle's stream, in front of its forward; the capacity is set once every buffer
+// exists, so a call after an allocation that failed half-way frees what there is and starts over.
 static int enc_ensure_ws(vf_encoder* e, int B, int T) {
-    VFT_HIP(handle_stream(&e->gstream));   // (the zero fills below run on the handle's stream, in front of its forward)
+    VFT_HIP(handle_stream(&e->stream));
     int tokens = (B * T + 255) / 256 * 256;
     if (tokens <= e->cap_tokens && B <= e->cap_b) return VF_OK;
     // grow monotonically on BOTH axes: alternating call shapes (100 x 512 re-rank, then 256 x 64 embed) must not free and
     // rebuild the workspace -- and drop every captured graph -- on each call
     tokens = std::max(tokens, e->cap_tokens); B = std::max(B, e->cap_b);
-    enc_free_ws(e);
+    enc_drop_graphs(e);   // captured launches hold the workspace pointers
+    e->ws.free_all();
+    e->cap_tokens = e->cap_b = 0;
     const size_t H = e->cfg.hidden, F = e->cfg.ffn, Mp = tokens;
     const int out_dim = e->cfg.head == 1 ? 1 : (int)H;
-    VFT_HIP(hipMalloc((void**)&e->x, Mp * H * 2));
-    VFT_HIP(hipMalloc((void**)&e->y, Mp * H * 2));
-    VFT_HIP(hipMalloc((void**)&e->qkv, Mp * 3 * H * 2));
-    VFT_HIP(hipMalloc((void**)&e->ctx, Mp * H * 2));
-    VFT_HIP(hipMalloc((void**)&e->hbuf, Mp * F * 2));
-    VFT_HIP(hipMalloc((void**)&e->d_ids, Mp * 4));
-    VFT_HIP(hipMalloc((void**)&e->d_mask, Mp * 4));
-    VFT_HIP(hipMalloc((void**)&e->d_tt, Mp * 4));
-    VFT_HIP(hipMalloc((void**)&e->d_pos, Mp * 4));
-    VFT_HIP(hipMalloc((void**)&e->d_seq, ((size_t)B + 1) * 4));
-    VFT_HIP(hipMalloc((void**)&e->d_out, (size_t)B * out_dim * 4));
-    VFT_HIP(hipMalloc((void**)&e->d_hidden, Mp * H * 4));
+    DevPool& ws = e->ws;
+    hipStream_t st = e->stream;
+    // (zeroed: padded rows are read by the GEMMs, keep them finite)
+    VFT_HIP(ws.get(&e->x, Mp * H * 2, true, st));
+    VFT_HIP(ws.get(&e->y, Mp * H * 2, true, st));
+    VFT_HIP(ws.get(&e->qkv, Mp * 3 * H * 2, true, st));
+    VFT_HIP(ws.get(&e->ctx, Mp * H * 2, true, st));
+    VFT_HIP(ws.get(&e->hbuf, Mp * F * 2, true, st));
+    VFT_HIP(ws.get(&e->d_ids, Mp * 4, false, st));
+    VFT_HIP(ws.get(&e->d_mask, Mp * 4, false, st));
+    VFT_HIP(ws.get(&e->d_tt, Mp * 4, false, st));
+    VFT_HIP(ws.get(&e->d_pos, Mp * 4, false, st));
+    VFT_HIP(ws.get(&e->d_seq, ((size_t)B + 1) * 4, false, st));
+    VFT_HIP(ws.get(&e->d_out, (size_t)B * out_dim * 4, false, st));
+    VFT_HIP(ws.get(&e->d_hidden, Mp * H * 4, false, st));
     if (H % 256 == 0) {
-        VFT_HIP(hipMalloc((void**)&e->stats_a, (H / 256) * Mp * 2 * sizeof(float)));
-        VFT_HIP(hipMalloc((void**)&e->stats_b, (H / 256) * Mp * 2 * sizeof(float)));
-        VFT_HIP(hipMemsetAsync(e->stats_a, 0, (H / 256) * Mp * 2 * sizeof(float), e->gstream));
-        VFT_HIP(hipMemsetAsync(e->stats_b, 0, (H / 256) * Mp * 2 * sizeof(float), e->gstream));
+        VFT_HIP(ws.get(&e->stats_a, (H / 256) * Mp * 2 * sizeof(float), true, st));
+        VFT_HIP(ws.get(&e->stats_b, (H / 256) * Mp * 2 * sizeof(float), true, st));
     }
-    // padded rows are read by the GEMMs: keep them finite
-    VFT_HIP(hipMemsetAsync(e->x, 0, Mp * H * 2, e->gstream));
-    VFT_HIP(hipMemsetAsync(e->y, 0, Mp * H * 2, e->gstream));
-    VFT_HIP(hipMemsetAsync(e->qkv, 0, Mp * 3 * H * 2, e->gstream));
-    VFT_HIP(hipMemsetAsync(e->ctx, 0, Mp * H * 2, e->gstream));
-    VFT_HIP(hipMemsetAsync(e->hbuf, 0, Mp * F * 2, e->gstream));
     e->cap_tokens = tokens; e->cap_b = B;
-    VFT_HIP(gws_ensure(e->gws, e->gstream));
+    VFT_HIP(gws_ensure(e->gws, st));
     return VF_OK;
 }
 
@@ -3783,14 +3833,15 @@ static int forward_impl(vf_encoder* e, const int32_t* ids, const int32_t* mask, 
     } restore{e->cfg, e->cfg.pooling, e->cfg.normalize};
     if (pooling >= 0) e->cfg.pooling = pooling;
     if (normalize >= 0) e->cfg.normalize = normalize;
+    vf::DeviceGuard guard;
     VFT_HIP(hipSetDevice(e->device));
     int rc = enc_ensure_ws(e, b, t);
     if (rc != VF_OK) return rc;
     const size_t n = (size_t)b * t;
     const int out_dim = e->cfg.head == 1 ? 1 : e->cfg.hidden;
     static const bool no_graph = getenv("VF_NO_GRAPH") != nullptr;   // A/B switch
-    VFT_HIP(handle_stream(&e->gstream));
-    hipStream_t es = e->gstream;
+    VFT_HIP(handle_stream(&e->stream));
+    hipStream_t es = e->stream;
     if (!no_graph && n <= 256 && e->cfg.pooling != 2) {   // (last-token pooling reads a flag back mid-forward: not capturable)
         hipStream_t gs = es;
         const vf_encoder::GraphKey key{b, t, t_valid, type_ids != nullptr, e->cfg.pooling, e->cfg.normalize};
@@ -3914,12 +3965,13 @@ extern "C" int vf_encoder_forward_hidden(vf_encoder* e, const int32_t* ids, cons
         if (badt >= 0) return fail(VF_EINVAL, "vf_encoder_forward_hidden: token type id " + std::to_string(type_ids[badt]) + " is outside [0, " + std::to_string(e->cfg.type_vocab) + ")");
     }
     std::lock_guard<std::mutex> g(e->mu);
+    vf::DeviceGuard guard;
     VFT_HIP(hipSetDevice(e->device));
     int rc = enc_ensure_ws(e, b, t);
     if (rc != VF_OK) return rc;
     const size_t n = (size_t)b * t;
-    VFT_HIP(handle_stream(&e->gstream));
-    hipStream_t es = e->gstream;
+    VFT_HIP(handle_stream(&e->stream));
+    hipStream_t es = e->stream;
     VFT_HIP(hipMemcpyAsync(e->d_ids, ids, n * 4, hipMemcpyHostToDevice, es));
     VFT_HIP(hipMemcpyAsync(e->d_mask, mask, n * 4, hipMemcpyHostToDevice, es));
     if (type_ids) VFT_HIP(hipMemcpyAsync(e->d_tt, type_ids, n * 4, hipMemcpyHostToDevice, es));
@@ -3958,13 +4010,8 @@ extern "C" int vf_reranker_destroy(vf_encoder* e) { return vf_encoder_destroy(e)
 // ------------------------------------------------------------------------------------------------
 constexpr int kDecMaxT = 4096;  // the reference truncates at max_length=4096 (step3_mul.py:200); streaming attention has no residency limit, the RoPE table is sized for this
 
-struct vf_decoder {
-    hipStream_t stream = nullptr;     // this handle's own stream (handle_stream)
-    GemmWs gws;
+struct vf_decoder : ModelBase {
     vf_decoder_config cfg{};
-    int device = 0;
-    half_t* w16 = nullptr;
-    float* w32 = nullptr;
     size_t o_embed = 0, o_layers = 0, layer16 = 0, o_head_row = 0;  // fp16 offsets (elements)
     size_t f_layers = 0, layer32 = 0, f_final = 0;                   // fp32 offsets
     int cap_tokens = 0, cap_b = 0, rope_T = 0;
@@ -3976,7 +4023,6 @@ struct vf_decoder {
     float* d_out = nullptr;
     float* d_hidden = nullptr;   // [cap_tokens, H] fp32 final hidden states (vf_decoder_forward_hidden)
     float2* rope = nullptr;
-    std::mutex mu;
 };
 
 static size_t dec_qd(const vf_decoder_config& c) { return (size_t)c.heads * c.head_dim; }
@@ -4016,24 +4062,11 @@ extern "C" int vf_decoder_weight_sizes(const vf_decoder_config* cfg, int64_t* n_
     return VF_OK;
 }
 
-static void dec_free_ws(vf_decoder* d) {
-    void* p[] = {d->x, d->y, d->n, d->qkv, d->ctx, d->gu, d->act, d->d_ids, d->d_mask, d->d_out, d->rope, d->d_hidden, d->d_seq, d->d_pos};
-    for (void* q : p) if (q) (void)hipFree(q);
-    d->x = d->y = nullptr; d->d_hidden = nullptr;
-    d->n = d->qkv = d->ctx = d->gu = d->act = nullptr;
-    d->d_ids = d->d_mask = d->d_seq = d->d_pos = nullptr; d->d_out = nullptr; d->rope = nullptr;
-    d->cap_tokens = d->cap_b = d->rope_T = 0;
-}
-
 extern "C" int vf_decoder_destroy(vf_decoder* d) {
     if (!d) return VF_OK;
+    vf::DeviceGuard guard;
     (void)hipSetDevice(d->device);
-    (void)hipDeviceSynchronize();
-    dec_free_ws(d);
-    gws_free(d->gws);
-    if (d->stream) (void)hipStreamDestroy(d->stream);
-    if (d->w16) (void)hipFree(d->w16);
-    if (d->w32) (void)hipFree(d->w32);
+    model_release(*d);
     if (d->d_flag) (void)hipFree(d->d_flag);
     delete d;
     return VF_OK;
@@ -4047,9 +4080,8 @@ extern "C" int vf_decoder_create(vf_decoder** out, const vf_decoder_config* cfg,
     if (rc != VF_OK) return rc;
     if (!w16 || !w32 || n16 != (int64_t)dec_n16(*cfg) || n32 != (int64_t)dec_n32(*cfg))
         return fail(VF_EINVAL, "vf_decoder_create: weight blobs do not match vf_decoder_weight_sizes");
-    int ndev = 0;
-    VFT_HIP(hipGetDeviceCount(&ndev));
-    if (device_id < 0 || device_id >= ndev) return fail(VF_EINVAL, "vf_decoder_create: bad device_id");
+    VFT_TRY(model_check_device(device_id, "vf_decoder_create"));
+    vf::DeviceGuard guard;
     VFT_HIP(hipSetDevice(device_id));
     vf_decoder* d = new (std::nothrow) vf_decoder();
     if (!d) return fail(VF_ENOMEM, "vf_decoder_create: host allocation failed");
@@ -4059,17 +4091,9 @@ extern "C" int vf_decoder_create(vf_decoder** out, const vf_decoder_config* cfg,
     d->layer16 = dec_layer16(*cfg);
     d->o_head_row = d->o_layers + (size_t)cfg->layers * d->layer16;
     d->f_layers = 0; d->layer32 = dec_layer32(*cfg); d->f_final = (size_t)cfg->layers * d->layer32;
-    hipError_t er = hipMalloc((void**)&d->w16, (size_t)n16 * 2);
-    if (er == hipSuccess) er = hipMalloc((void**)&d->w32, (size_t)n32 * 4);
+    hipError_t er = model_upload(*d, w16, n16, w32, n32);
     if (er == hipSuccess) er = hipMalloc((void**)&d->d_flag, 4);
-    if (er == hipSuccess) er = hipMemcpy(d->w16, w16, (size_t)n16 * 2, hipMemcpyHostToDevice);
-    if (er == hipSuccess) er = hipMemcpy(d->w32, w32, (size_t)n32 * 4, hipMemcpyHostToDevice);
-    if (er == hipSuccess) er = configure_once();
-    if (er != hipSuccess) {
-        const std::string msg = std::string("vf_decoder_create: ") + hipGetErrorString(er);
-        vf_decoder_destroy(d);
-        return fail(VF_EHIP, msg);
-    }
+    if (er != hipSuccess) return model_create_failed(d, vf_decoder_destroy, "vf_decoder_create", er);
     *out = d;
     return VF_OK;
 }
@@ -4126,41 +4150,37 @@ static void dec_launch_pool(const half_t* x, const int* mask, int b, int T, int 
 }
 
 static int dec_ensure_ws(vf_decoder* d, int B, int T) {
-    VFT_HIP(handle_stream(&d->stream));   // (the zero fills below run on the handle's stream, in front of its forward)
+    VFT_HIP(handle_stream(&d->stream));
     int tokens = (B * T + 255) / 256 * 256;
     if (tokens <= d->cap_tokens && B <= d->cap_b && T <= d->rope_T) return VF_OK;
     tokens = std::max(tokens, d->cap_tokens); B = std::max(B, d->cap_b);   // monotone growth (see enc_ensure_ws)
-    dec_free_ws(d);
+    d->ws.free_all();
+    d->cap_tokens = d->cap_b = d->rope_T = 0;
     const vf_decoder_config& c = d->cfg;
     const size_t H = c.hidden, F = c.ffn, QKV = dec_qd(c) + 2 * dec_kd(c), QD = dec_qd(c), Mp = tokens;
-    VFT_HIP(hipMalloc((void**)&d->x, Mp * H * 4));
-    VFT_HIP(hipMalloc((void**)&d->y, Mp * H * 4));
-    VFT_HIP(hipMalloc((void**)&d->d_hidden, Mp * H * 4));
-    VFT_HIP(hipMalloc((void**)&d->n, Mp * H * 2));
-    VFT_HIP(hipMalloc((void**)&d->qkv, Mp * QKV * 2));
-    VFT_HIP(hipMalloc((void**)&d->ctx, Mp * QD * 2));
-    VFT_HIP(hipMalloc((void**)&d->gu, Mp * 2 * F * 2));
-    VFT_HIP(hipMalloc((void**)&d->act, Mp * F * 2));
-    VFT_HIP(hipMalloc((void**)&d->d_ids, Mp * 4));
-    VFT_HIP(hipMalloc((void**)&d->d_mask, Mp * 4));
-    VFT_HIP(hipMalloc((void**)&d->d_pos, Mp * 4));
-    VFT_HIP(hipMalloc((void**)&d->d_seq, ((size_t)B + 1) * 4));
-    VFT_HIP(hipMalloc((void**)&d->d_out, (size_t)B * (c.head == 2 ? 1 : H) * 4));
-    VFT_HIP(hipMalloc((void**)&d->rope, (size_t)kDecMaxT * (c.head_dim / 2) * sizeof(float2)));
-    // padded rows are read by the GEMMs: keep them finite
-    VFT_HIP(hipMemsetAsync(d->x, 0, Mp * H * 4, d->stream));
-    VFT_HIP(hipMemsetAsync(d->y, 0, Mp * H * 4, d->stream));
-    VFT_HIP(hipMemsetAsync(d->n, 0, Mp * H * 2, d->stream));
-    VFT_HIP(hipMemsetAsync(d->qkv, 0, Mp * QKV * 2, d->stream));
-    VFT_HIP(hipMemsetAsync(d->ctx, 0, Mp * QD * 2, d->stream));
-    VFT_HIP(hipMemsetAsync(d->gu, 0, Mp * 2 * F * 2, d->stream));
-    VFT_HIP(hipMemsetAsync(d->act, 0, Mp * F * 2, d->stream));
-    // on the handle's own stream, like the memsets above: the forwards run there, and a non-blocking stream does not order itself behind
+    DevPool& ws = d->ws;
+    hipStream_t st = d->stream;
+    // (zeroed: padded rows are read by the GEMMs, keep them finite)
+    VFT_HIP(ws.get(&d->x, Mp * H * 4, true, st));
+    VFT_HIP(ws.get(&d->y, Mp * H * 4, true, st));
+    VFT_HIP(ws.get(&d->d_hidden, Mp * H * 4, false, st));
+    VFT_HIP(ws.get(&d->n, Mp * H * 2, true, st));
+    VFT_HIP(ws.get(&d->qkv, Mp * QKV * 2, true, st));
+    VFT_HIP(ws.get(&d->ctx, Mp * QD * 2, true, st));
+    VFT_HIP(ws.get(&d->gu, Mp * 2 * F * 2, true, st));
+    VFT_HIP(ws.get(&d->act, Mp * F * 2, true, st));
+    VFT_HIP(ws.get(&d->d_ids, Mp * 4, false, st));
+    VFT_HIP(ws.get(&d->d_mask, Mp * 4, false, st));
+    VFT_HIP(ws.get(&d->d_pos, Mp * 4, false, st));
+    VFT_HIP(ws.get(&d->d_seq, ((size_t)B + 1) * 4, false, st));
+    VFT_HIP(ws.get(&d->d_out, (size_t)B * (c.head == 2 ? 1 : H) * 4, false, st));
+    VFT_HIP(ws.get(&d->rope, (size_t)kDecMaxT * (c.head_dim / 2) * sizeof(float2), false, st));
+    // on the handle's own stream, like the zero fills: the forwards run there, and a non-blocking stream does not order itself behind
     // the NULL stream (round-5 advisor: the first forward after a (re)allocation could read a table not written yet)
-    dec_launch_rope_table(c.rope_theta, kDecMaxT, c.head_dim, d->rope, d->stream);
+    dec_launch_rope_table(c.rope_theta, kDecMaxT, c.head_dim, d->rope, st);
     VFT_HIP(hipGetLastError());
     d->cap_tokens = tokens; d->cap_b = B; d->rope_T = kDecMaxT;
-    VFT_HIP(gws_ensure(d->gws, d->stream));
+    VFT_HIP(gws_ensure(d->gws, st));
     return VF_OK;
 }
 
@@ -4245,6 +4265,7 @@ static int dec_forward_impl(vf_decoder* d, const int32_t* ids, const int32_t* ma
         ~Restore() { c.normalize = n; }
     } restore{d->cfg, d->cfg.normalize};
     if (normalize >= 0 && d->cfg.head != 2) d->cfg.normalize = normalize;
+    vf::DeviceGuard guard;
     VFT_HIP(hipSetDevice(d->device));
     int rc = dec_ensure_ws(d, b, t);
     if (rc != VF_OK) return rc;
@@ -4345,6 +4366,7 @@ extern "C" int vf_decoder_forward_hidden(vf_decoder* d, const int32_t* ids, cons
     VFT_TRY(dec_check_call(d, ids, mask, b, t, out_hidden, "vf_decoder_forward_hidden"));
     if (b == 0) return VF_OK;
     std::lock_guard<std::mutex> g(d->mu);
+    vf::DeviceGuard guard;
     VFT_HIP(hipSetDevice(d->device));
     int rc = dec_ensure_ws(d, b, t);
     if (rc != VF_OK) return rc;
@@ -4375,14 +4397,9 @@ extern "C" int vf_decoder_forward_hidden(vf_decoder* d, const int32_t* ids, cons
 // assembly + first LayerNorm, the quick-GELU epilogue of the products (EPI_BIAS_QGELU: x sigmoid(1.702 x), CLIP's
 // activation), and the class-token head.
 // ------------------------------------------------------------------------------------------------
-struct vf_vit {
-    hipStream_t stream = nullptr;     // this handle's own stream (handle_stream)
-    GemmWs gws;
+struct vf_vit : ModelBase {
     vf_vit_config cfg{};
-    int device = 0;
     int P = 0, T = 0, Tp = 0, Kp = 0;     // patches per image, tokens (P + 1), tokens padded to 32, patch length padded to 64
-    half_t* w16 = nullptr;
-    float* w32 = nullptr;
     size_t o_patch = 0, o_cls = 0, o_pos = 0, o_layers = 0, o_proj = 0, layer16 = 0;
     size_t f_zero = 0, f_pre = 0, f_layers = 0, f_post = 0, layer32 = 0;
     int cap_b = 0;
@@ -4390,16 +4407,15 @@ struct vf_vit {
     half_t *patches = nullptr, *emb = nullptr, *x = nullptr, *y = nullptr, *t = nullptr, *qkv = nullptr, *ctx = nullptr, *hbuf = nullptr;
     int* d_mask = nullptr;
     float* d_out = nullptr;
-    std::mutex mu;
 };
 
 static size_t vit_n16(const vf_vit_config& c) {
     const size_t H = c.hidden, F = c.ffn, g = c.image / c.patch, P = g * g, Kp = ((size_t)c.channels * c.patch * c.patch + 63) / 64 * 64;
-    return H * Kp + H + (P + 1) * H + (size_t)c.layers * (3 * H * H + H * H + F * H + H * F) + (size_t)c.proj_dim * H;
+    return H * Kp + H + (P + 1) * H + (size_t)c.layers * bert_layer16(H, F) + (size_t)c.proj_dim * H;
 }
 static size_t vit_n32(const vf_vit_config& c) {
     const size_t H = c.hidden, F = c.ffn;
-    return 2 * H + (size_t)c.layers * (2 * H + 3 * H + H + 2 * H + F + H) + 2 * H;
+    return 2 * H + (size_t)c.layers * preln_layer32(H, F) + 2 * H;
 }
 extern "C" int vf_vit_weight_sizes(const vf_vit_config* cfg, int64_t* n_fp16, int64_t* n_fp32) {
     if (!cfg || !n_fp16 || !n_fp32) return fail(VF_EINVAL, "vf_vit_weight_sizes: null argument");
@@ -4515,26 +4531,12 @@ __global__ __launch_bounds__(256) void k_vit_head(const half_t* __restrict__ x, 
     for (int d = tid; d < D; d += 256) o_[d] *= inv;
 }
 
-static void vit_free_ws(vf_vit* v) {
-    void* p[] = {v->d_pix, v->patches, v->emb, v->x, v->y, v->t, v->qkv, v->ctx, v->hbuf, v->d_mask, v->d_out};
-    for (void* q : p) if (q) (void)hipFree(q);
-    v->d_pix = nullptr; v->patches = v->emb = v->x = v->y = v->t = v->qkv = v->ctx = v->hbuf = nullptr;
-    v->d_mask = nullptr; v->d_out = nullptr; v->cap_b = 0;
-}
-
 extern "C" int vf_vit_destroy(vf_vit* v) {
     if (!v) return VF_OK;
-    int prev = 0;
-    const bool have_prev = hipGetDevice(&prev) == hipSuccess;
+    vf::DeviceGuard guard;
     (void)hipSetDevice(v->device);
-    (void)hipDeviceSynchronize();
-    vit_free_ws(v);
-    gws_free(v->gws);
-    if (v->stream) (void)hipStreamDestroy(v->stream);
-    if (v->w16) (void)hipFree(v->w16);
-    if (v->w32) (void)hipFree(v->w32);
+    model_release(*v);
     delete v;
-    if (have_prev) (void)hipSetDevice(prev);
     return VF_OK;
 }
 
@@ -4544,21 +4546,15 @@ extern "C" int vf_vit_create(vf_vit** out, const vf_vit_config* cfg, const void*
     *out = nullptr;
     if (!cfg || !w16 || !w32) return fail(VF_EINVAL, "vf_vit_create: null argument");
     const vf_vit_config& c = *cfg;
-    if (c.hidden <= 0 || c.hidden % 128 != 0 || c.hidden > 1024) return fail(VF_EUNSUPPORTED, "vit: hidden must be a multiple of 128, <= 1024");
-    if (c.heads <= 0 || c.hidden % c.heads || c.hidden / c.heads != 64) return fail(VF_EUNSUPPORTED, "vit: head dim must be 64");
-    if (c.ffn <= 0 || c.ffn % 128 != 0) return fail(VF_EUNSUPPORTED, "vit: ffn must be a multiple of 128");
+    VFT_TRY(bert_check_dims(c.hidden, c.heads, c.ffn, "vit: "));
     if (c.layers <= 0 || c.channels <= 0 || c.patch <= 0 || c.image <= 0 || c.image % c.patch) return fail(VF_EINVAL, "vit: bad image / patch / layers");
     if (c.proj_dim <= 0 || c.act < 0 || c.act > 1 || c.normalize < 0 || c.normalize > 1) return fail(VF_EINVAL, "vit: bad proj_dim / act / normalize");
     const int g = c.image / c.patch, P = g * g, T = P + 1, Tp = (T + 31) / 32 * 32;
     if (Tp > kEncResidentT) return fail(VF_EUNSUPPORTED, "vit: more than 511 patches per image");
     if ((size_t)n16 != vit_n16(c) || (size_t)n32 != vit_n32(c))
         return fail(VF_EINVAL, "vf_vit_create: weight blob sizes do not match the config (see vf_vit_weight_sizes)");
-    int ndev = 0;
-    VFT_HIP(hipGetDeviceCount(&ndev));
-    if (device_id < 0 || device_id >= ndev) return fail(VF_EINVAL, "vf_vit_create: bad device_id");
-    int prev = 0;
-    VFT_HIP(hipGetDevice(&prev));
-    struct Back { int d; ~Back() { (void)hipSetDevice(d); } } back{prev};
+    VFT_TRY(model_check_device(device_id, "vf_vit_create"));
+    vf::DeviceGuard guard;
     VFT_HIP(hipSetDevice(device_id));
     vf_vit* v = new (std::nothrow) vf_vit();
     if (!v) return fail(VF_ENOMEM, "host allocation failed");
@@ -4566,15 +4562,11 @@ extern "C" int vf_vit_create(vf_vit** out, const vf_vit_config* cfg, const void*
     v->Kp = (c.channels * c.patch * c.patch + 63) / 64 * 64;
     const size_t H = c.hidden, F = c.ffn;
     v->o_patch = 0; v->o_cls = H * (size_t)v->Kp; v->o_pos = v->o_cls + H; v->o_layers = v->o_pos + (size_t)T * H;
-    v->layer16 = 3 * H * H + H * H + F * H + H * F;
+    v->layer16 = bert_layer16(H, F);
     v->o_proj = v->o_layers + (size_t)c.layers * v->layer16;
-    v->f_pre = 0; v->f_layers = 2 * H; v->layer32 = 2 * H + 3 * H + H + 2 * H + F + H;
+    v->f_pre = 0; v->f_layers = 2 * H; v->layer32 = preln_layer32(H, F);
     v->f_post = v->f_layers + (size_t)c.layers * v->layer32;
-    hipError_t er = hipMalloc((void**)&v->w16, (size_t)n16 * 2);
-    if (er == hipSuccess) er = hipMalloc((void**)&v->w32, (size_t)n32 * 4);
-    if (er == hipSuccess) er = hipMemcpy(v->w16, w16, (size_t)n16 * 2, hipMemcpyHostToDevice);
-    if (er == hipSuccess) er = hipMemcpy(v->w32, w32, (size_t)n32 * 4, hipMemcpyHostToDevice);
-    if (er == hipSuccess) er = configure_once();
+    hipError_t er = model_upload(*v, w16, n16, w32, n32);
     if (er == hipSuccess) {   // log2(e) / sqrt(64) into the query projection, as the text encoder does (k_attention2 expects it)
         const float qs = 0.125f * 1.4426950408889634f;
         for (int l = 0; l < c.layers; ++l) {
@@ -4583,43 +4575,58 @@ extern "C" int vf_vit_create(vf_vit** out, const vf_vit_config* cfg, const void*
         }
         er = hipDeviceSynchronize();
     }
-    if (er != hipSuccess) {
-        const std::string msg = std::string("vf_vit_create: ") + hipGetErrorString(er);
-        vf_vit_destroy(v);
-        return fail(VF_EHIP, msg);
-    }
+    if (er != hipSuccess) return model_create_failed(v, vf_vit_destroy, "vf_vit_create", er);
     *out = v;
     return VF_OK;
 }
 
 static int vit_ensure_ws(vf_vit* v, int B) {
-    VFT_HIP(handle_stream(&v->stream));   // (the zero fills below run on the handle's stream, in front of its forward)
+    VFT_HIP(handle_stream(&v->stream));
     if (B <= v->cap_b) return VF_OK;
-    vit_free_ws(v);
+    v->ws.free_all();
+    v->cap_b = 0;
     const vf_vit_config& c = v->cfg;
     const size_t H = c.hidden, F = c.ffn;
     const size_t Mp = ((size_t)B * v->Tp + 255) / 256 * 256, Rp = ((size_t)B * v->P + 255) / 256 * 256;
-    VFT_HIP(hipMalloc((void**)&v->d_pix, (size_t)B * c.channels * c.image * c.image * 4));
-    VFT_HIP(hipMalloc((void**)&v->patches, Rp * v->Kp * 2));
-    VFT_HIP(hipMalloc((void**)&v->emb, Rp * H * 2));
-    VFT_HIP(hipMalloc((void**)&v->x, Mp * H * 2));
-    VFT_HIP(hipMalloc((void**)&v->y, Mp * H * 2));
-    VFT_HIP(hipMalloc((void**)&v->t, Mp * H * 2));
-    VFT_HIP(hipMalloc((void**)&v->qkv, Mp * 3 * H * 2));
-    VFT_HIP(hipMalloc((void**)&v->ctx, Mp * H * 2));
-    VFT_HIP(hipMalloc((void**)&v->hbuf, Mp * F * 2));
-    VFT_HIP(hipMalloc((void**)&v->d_mask, Mp * 4));
-    VFT_HIP(hipMalloc((void**)&v->d_out, (size_t)B * c.proj_dim * 4));
-    // rows past B Tp are read by the products: keep them finite
-    VFT_HIP(hipMemsetAsync(v->x, 0, Mp * H * 2, v->stream));
-    VFT_HIP(hipMemsetAsync(v->y, 0, Mp * H * 2, v->stream));
-    VFT_HIP(hipMemsetAsync(v->t, 0, Mp * H * 2, v->stream));
-    VFT_HIP(hipMemsetAsync(v->qkv, 0, Mp * 3 * H * 2, v->stream));
-    VFT_HIP(hipMemsetAsync(v->ctx, 0, Mp * H * 2, v->stream));
-    VFT_HIP(hipMemsetAsync(v->hbuf, 0, Mp * F * 2, v->stream));
-    VFT_HIP(hipMemsetAsync(v->d_mask, 0, Mp * 4, v->stream));
+    DevPool& ws = v->ws;
+    hipStream_t st = v->stream;
+    // (zeroed: rows past B Tp are read by the products, keep them finite)
+    VFT_HIP(ws.get(&v->d_pix, (size_t)B * c.channels * c.image * c.image * 4, false, st));
+    VFT_HIP(ws.get(&v->patches, Rp * v->Kp * 2, false, st));
+    VFT_HIP(ws.get(&v->emb, Rp * H * 2, false, st));
+    VFT_HIP(ws.get(&v->x, Mp * H * 2, true, st));
+    VFT_HIP(ws.get(&v->y, Mp * H * 2, true, st));
+    VFT_HIP(ws.get(&v->t, Mp * H * 2, true, st));
+    VFT_HIP(ws.get(&v->qkv, Mp * 3 * H * 2, true, st));
+    VFT_HIP(ws.get(&v->ctx, Mp * H * 2, true, st));
+    VFT_HIP(ws.get(&v->hbuf, Mp * F * 2, true, st));
+    VFT_HIP(ws.get(&v->d_mask, Mp * 4, true, st));
+    VFT_HIP(ws.get(&v->d_out, (size_t)B * c.proj_dim * 4, false, st));
     v->cap_b = B;
-    VFT_HIP(gws_ensure(v->gws, v->stream));
+    VFT_HIP(gws_ensure(v->gws, st));
+    return VF_OK;
+}
+
+// The PRE-LayerNorm layers of a tower (vf_vit or vf_clip_text: same fields) over the M rows of v->x: x += Wo attn(LN1 x); x += W2 act(W1 LN2 x).
+// attention(): the tower's own launch, v->qkv -> v->ctx.
+template <typename Tower, typename Attention>
+static int preln_layers(Tower* v, int M, hipStream_t st, Attention attention) {
+    const auto& c = v->cfg;
+    const int H = c.hidden, F = c.ffn, Mp = (M + 255) / 256 * 256;
+    for (int l = 0; l < c.layers; ++l) {
+        const half_t* w = v->w16 + v->o_layers + (size_t)l * v->layer16;
+        const float* f = v->w32 + v->f_layers + (size_t)l * v->layer32;
+        const half_t *Wqkv = w, *Wo = Wqkv + (size_t)3 * H * H, *W1 = Wo + (size_t)H * H, *W2 = W1 + (size_t)F * H;
+        const float *g1 = f, *b1n = g1 + H, *bqkv = b1n + H, *bo = bqkv + 3 * H, *g2 = bo + H, *b2n = g2 + H, *b1 = b2n + H, *b2 = b1 + F;
+        hipLaunchKernelGGL(k_layernorm, dim3((M + 7) / 8), dim3(256), 0, st, v->x, g1, b1n, c.ln_eps, M, H, v->t);
+        VFT_HIP(gemm<EPI_BIAS>(v->t, Wqkv, bqkv, nullptr, v->qkv, Mp, 3 * H, H, st, 0, &v->gws));
+        attention();
+        VFT_HIP(gemm<EPI_BIAS_RESIDUAL>(v->ctx, Wo, bo, v->x, v->y, Mp, H, H, st, 0, &v->gws));
+        hipLaunchKernelGGL(k_layernorm, dim3((M + 7) / 8), dim3(256), 0, st, v->y, g2, b2n, c.ln_eps, M, H, v->t);
+        if (c.act == 0) VFT_HIP(gemm<EPI_BIAS_GELU>(v->t, W1, b1, nullptr, v->hbuf, Mp, F, H, st, 0, &v->gws));
+        else VFT_HIP(gemm<EPI_BIAS_QGELU>(v->t, W1, b1, nullptr, v->hbuf, Mp, F, H, st, 0, &v->gws));
+        VFT_HIP(gemm<EPI_BIAS_RESIDUAL>(v->hbuf, W2, b2, v->y, v->x, Mp, H, F, st, 0, &v->gws));
+    }
     return VF_OK;
 }
 
@@ -4640,14 +4647,12 @@ static int vit_forward_impl(vf_vit* v, const float* pixels, const unsigned char*
         }
     }
     std::lock_guard<std::mutex> lk(v->mu);
-    int prev = 0;
-    VFT_HIP(hipGetDevice(&prev));
-    struct Back { int d; ~Back() { (void)hipSetDevice(d); } } back{prev};
+    vf::DeviceGuard guard;
     VFT_HIP(hipSetDevice(v->device));
     VFT_TRY(vit_ensure_ws(v, b));
     const vf_vit_config& c = v->cfg;
-    const int H = c.hidden, F = c.ffn, P = v->P, Tp = v->Tp, Kp = v->Kp;
-    const int M = b * Tp, Mp = (M + 255) / 256 * 256, Rp = (b * P + 255) / 256 * 256;
+    const int H = c.hidden, P = v->P, Tp = v->Tp, Kp = v->Kp;
+    const int M = b * Tp, Rp = (b * P + 255) / 256 * 256;
     VFT_HIP(handle_stream(&v->stream));
     hipStream_t st = v->stream;
     const size_t npix = (size_t)b * c.channels * c.image * c.image;
@@ -4663,20 +4668,7 @@ static int vit_forward_impl(vf_vit* v, const float* pixels, const unsigned char*
     VFT_HIP(gemm<EPI_BIAS>(v->patches, v->w16 + v->o_patch, nullptr, nullptr, v->emb, Rp, H, Kp, st, 0, &v->gws));
     hipLaunchKernelGGL(k_vit_embed, dim3((M + 7) / 8), dim3(256), 0, st, v->emb, v->w16 + v->o_cls, v->w16 + v->o_pos, v->w32 + v->f_pre,
                        v->w32 + v->f_pre + H, c.ln_eps, b, P, Tp, H, v->x, v->d_mask);
-    for (int l = 0; l < c.layers; ++l) {
-        const half_t* w = v->w16 + v->o_layers + (size_t)l * v->layer16;
-        const float* f = v->w32 + v->f_layers + (size_t)l * v->layer32;
-        const half_t *Wqkv = w, *Wo = Wqkv + (size_t)3 * H * H, *W1 = Wo + (size_t)H * H, *W2 = W1 + (size_t)F * H;
-        const float *g1 = f, *b1n = g1 + H, *bqkv = b1n + H, *bo = bqkv + 3 * H, *g2 = bo + H, *b2n = g2 + H, *b1 = b2n + H, *b2 = b1 + F;
-        hipLaunchKernelGGL(k_layernorm, dim3((M + 7) / 8), dim3(256), 0, st, v->x, g1, b1n, c.ln_eps, M, H, v->t);
-        VFT_HIP(gemm<EPI_BIAS>(v->t, Wqkv, bqkv, nullptr, v->qkv, Mp, 3 * H, H, st, 0, &v->gws));
-        launch_attention2<0>(v->qkv, v->d_mask, b, Tp, c.heads, v->ctx, st);
-        VFT_HIP(gemm<EPI_BIAS_RESIDUAL>(v->ctx, Wo, bo, v->x, v->y, Mp, H, H, st, 0, &v->gws));
-        hipLaunchKernelGGL(k_layernorm, dim3((M + 7) / 8), dim3(256), 0, st, v->y, g2, b2n, c.ln_eps, M, H, v->t);
-        if (c.act == 0) VFT_HIP(gemm<EPI_BIAS_GELU>(v->t, W1, b1, nullptr, v->hbuf, Mp, F, H, st, 0, &v->gws));
-        else VFT_HIP(gemm<EPI_BIAS_QGELU>(v->t, W1, b1, nullptr, v->hbuf, Mp, F, H, st));
-        VFT_HIP(gemm<EPI_BIAS_RESIDUAL>(v->hbuf, W2, b2, v->y, v->x, Mp, H, F, st, 0, &v->gws));
-    }
+    VFT_TRY(preln_layers(v, M, st, [&] { launch_attention2<0>(v->qkv, v->d_mask, b, Tp, c.heads, v->ctx, st); }));
     hipLaunchKernelGGL(k_vit_head, dim3(b), dim3(256), (size_t)(H + 256) * sizeof(float), st, v->x, Tp, H, v->w32 + v->f_post, v->w32 + v->f_post + H,
                        c.ln_eps, v->w16 + v->o_proj, c.proj_dim, c.normalize, v->d_out, (const int*)nullptr);
     VFT_HIP(hipGetLastError());
@@ -4701,29 +4693,23 @@ extern "C" int vf_vit_forward_u8(vf_vit* v, const unsigned char* pixels, const f
 // streaming attention at head dim 64 (k_attention_stream2<64, true>: softmax scale passed, nothing folded into Wq), and
 // k_vit_head reading row eos[b] instead of row 0.
 // ------------------------------------------------------------------------------------------------
-struct vf_clip_text {
-    hipStream_t stream = nullptr;     // this handle's own stream (handle_stream)
-    GemmWs gws;
+struct vf_clip_text : ModelBase {
     vf_clip_text_config cfg{};
-    int device = 0;
-    half_t* w16 = nullptr;
-    float* w32 = nullptr;
     size_t o_tok = 0, o_pos = 0, o_layers = 0, o_proj = 0, layer16 = 0;
     size_t f_layers = 0, f_final = 0, layer32 = 0;
     int cap_tokens = 0, cap_b = 0;
     half_t *x = nullptr, *y = nullptr, *t = nullptr, *qkv = nullptr, *ctx = nullptr, *hbuf = nullptr;
     int *d_ids = nullptr, *d_mask_in = nullptr, *d_mask = nullptr, *d_eos = nullptr;
     float* d_out = nullptr;
-    std::mutex mu;
 };
 
 static size_t ct_n16(const vf_clip_text_config& c) {
     const size_t H = c.hidden, F = c.ffn;
-    return (size_t)c.vocab * H + (size_t)c.max_pos * H + (size_t)c.layers * (3 * H * H + H * H + F * H + H * F) + (size_t)c.proj_dim * H;
+    return (size_t)c.vocab * H + (size_t)c.max_pos * H + (size_t)c.layers * bert_layer16(H, F) + (size_t)c.proj_dim * H;
 }
 static size_t ct_n32(const vf_clip_text_config& c) {
     const size_t H = c.hidden, F = c.ffn;
-    return (size_t)c.layers * (2 * H + 3 * H + H + 2 * H + F + H) + 2 * H;
+    return (size_t)c.layers * preln_layer32(H, F) + 2 * H;
 }
 extern "C" int vf_clip_text_weight_sizes(const vf_clip_text_config* cfg, int64_t* n_fp16, int64_t* n_fp32) {
     if (!cfg || !n_fp16 || !n_fp32) return fail(VF_EINVAL, "vf_clip_text_weight_sizes: null argument");
@@ -4761,26 +4747,12 @@ __global__ __launch_bounds__(256) void k_clip_text_embed(const int* __restrict__
     }
 }
 
-static void ct_free_ws(vf_clip_text* v) {
-    void* p[] = {v->x, v->y, v->t, v->qkv, v->ctx, v->hbuf, v->d_ids, v->d_mask_in, v->d_mask, v->d_eos, v->d_out};
-    for (void* q : p) if (q) (void)hipFree(q);
-    v->x = v->y = v->t = v->qkv = v->ctx = v->hbuf = nullptr;
-    v->d_ids = v->d_mask_in = v->d_mask = v->d_eos = nullptr; v->d_out = nullptr; v->cap_tokens = v->cap_b = 0;
-}
-
 extern "C" int vf_clip_text_destroy(vf_clip_text* v) {
     if (!v) return VF_OK;
-    int prev = 0;
-    const bool have_prev = hipGetDevice(&prev) == hipSuccess;
+    vf::DeviceGuard guard;
     (void)hipSetDevice(v->device);
-    (void)hipDeviceSynchronize();
-    ct_free_ws(v);
-    gws_free(v->gws);
-    if (v->stream) (void)hipStreamDestroy(v->stream);
-    if (v->w16) (void)hipFree(v->w16);
-    if (v->w32) (void)hipFree(v->w32);
+    model_release(*v);
     delete v;
-    if (have_prev) (void)hipSetDevice(prev);
     return VF_OK;
 }
 
@@ -4790,71 +4762,53 @@ extern "C" int vf_clip_text_create(vf_clip_text** out, const vf_clip_text_config
     *out = nullptr;
     if (!cfg || !w16 || !w32) return fail(VF_EINVAL, "vf_clip_text_create: null argument");
     const vf_clip_text_config& c = *cfg;
-    if (c.hidden <= 0 || c.hidden % 128 != 0 || c.hidden > 1024) return fail(VF_EUNSUPPORTED, "clip text: hidden must be a multiple of 128, <= 1024");
-    if (c.heads <= 0 || c.hidden % c.heads || c.hidden / c.heads != 64) return fail(VF_EUNSUPPORTED, "clip text: head dim must be 64");
-    if (c.ffn <= 0 || c.ffn % 128 != 0) return fail(VF_EUNSUPPORTED, "clip text: ffn must be a multiple of 128");
+    VFT_TRY(bert_check_dims(c.hidden, c.heads, c.ffn, "clip text: "));
     if (c.layers <= 0 || c.vocab <= 0 || c.max_pos <= 0 || c.max_pos > 512) return fail(VF_EINVAL, "clip text: bad layers / vocab / max_pos (<= 512)");
     if (c.proj_dim <= 0 || c.act < 0 || c.act > 1 || c.normalize < 0 || c.normalize > 1) return fail(VF_EINVAL, "clip text: bad proj_dim / act / normalize");
     if ((size_t)n16 != ct_n16(c) || (size_t)n32 != ct_n32(c))
         return fail(VF_EINVAL, "vf_clip_text_create: weight blob sizes do not match the config (see vf_clip_text_weight_sizes)");
-    int ndev = 0;
-    VFT_HIP(hipGetDeviceCount(&ndev));
-    if (device_id < 0 || device_id >= ndev) return fail(VF_EINVAL, "vf_clip_text_create: bad device_id");
-    int prev = 0;
-    VFT_HIP(hipGetDevice(&prev));
-    struct Back { int d; ~Back() { (void)hipSetDevice(d); } } back{prev};
+    VFT_TRY(model_check_device(device_id, "vf_clip_text_create"));
+    vf::DeviceGuard guard;
     VFT_HIP(hipSetDevice(device_id));
     vf_clip_text* v = new (std::nothrow) vf_clip_text();
     if (!v) return fail(VF_ENOMEM, "host allocation failed");
     v->cfg = c; v->device = device_id;
     const size_t H = c.hidden, F = c.ffn;
     v->o_tok = 0; v->o_pos = (size_t)c.vocab * H; v->o_layers = v->o_pos + (size_t)c.max_pos * H;
-    v->layer16 = 3 * H * H + H * H + F * H + H * F;
+    v->layer16 = bert_layer16(H, F);
     v->o_proj = v->o_layers + (size_t)c.layers * v->layer16;
-    v->f_layers = 0; v->layer32 = 2 * H + 3 * H + H + 2 * H + F + H;
+    v->f_layers = 0; v->layer32 = preln_layer32(H, F);
     v->f_final = (size_t)c.layers * v->layer32;
-    hipError_t er = hipMalloc((void**)&v->w16, (size_t)n16 * 2);
-    if (er == hipSuccess) er = hipMalloc((void**)&v->w32, (size_t)n32 * 4);
-    if (er == hipSuccess) er = hipMemcpy(v->w16, w16, (size_t)n16 * 2, hipMemcpyHostToDevice);
-    if (er == hipSuccess) er = hipMemcpy(v->w32, w32, (size_t)n32 * 4, hipMemcpyHostToDevice);
-    if (er == hipSuccess) er = configure_once();
-    if (er != hipSuccess) {
-        const std::string msg = std::string("vf_clip_text_create: ") + hipGetErrorString(er);
-        vf_clip_text_destroy(v);
-        return fail(VF_EHIP, msg);
-    }
+    const hipError_t er = model_upload(*v, w16, n16, w32, n32);
+    if (er != hipSuccess) return model_create_failed(v, vf_clip_text_destroy, "vf_clip_text_create", er);
     *out = v;
     return VF_OK;
 }
 
 static int ct_ensure_ws(vf_clip_text* v, int B, int Tp) {
-    VFT_HIP(handle_stream(&v->stream));   // (the zero fills below run on the handle's stream, in front of its forward)
+    VFT_HIP(handle_stream(&v->stream));
     int tokens = (B * Tp + 255) / 256 * 256;
     if (tokens <= v->cap_tokens && B <= v->cap_b) return VF_OK;
     tokens = std::max(tokens, v->cap_tokens); B = std::max(B, v->cap_b);
-    ct_free_ws(v);
+    v->ws.free_all();
+    v->cap_tokens = v->cap_b = 0;
     const size_t H = v->cfg.hidden, F = v->cfg.ffn, Mp = tokens;
-    VFT_HIP(hipMalloc((void**)&v->x, Mp * H * 2));
-    VFT_HIP(hipMalloc((void**)&v->y, Mp * H * 2));
-    VFT_HIP(hipMalloc((void**)&v->t, Mp * H * 2));
-    VFT_HIP(hipMalloc((void**)&v->qkv, Mp * 3 * H * 2));
-    VFT_HIP(hipMalloc((void**)&v->ctx, Mp * H * 2));
-    VFT_HIP(hipMalloc((void**)&v->hbuf, Mp * F * 2));
-    VFT_HIP(hipMalloc((void**)&v->d_ids, Mp * 4));
-    VFT_HIP(hipMalloc((void**)&v->d_mask_in, Mp * 4));
-    VFT_HIP(hipMalloc((void**)&v->d_mask, Mp * 4));
-    VFT_HIP(hipMalloc((void**)&v->d_eos, (size_t)B * 4));
-    VFT_HIP(hipMalloc((void**)&v->d_out, (size_t)B * v->cfg.proj_dim * 4));
-    // rows past B Tp are read by the products: keep them finite
-    VFT_HIP(hipMemsetAsync(v->x, 0, Mp * H * 2, v->stream));
-    VFT_HIP(hipMemsetAsync(v->y, 0, Mp * H * 2, v->stream));
-    VFT_HIP(hipMemsetAsync(v->t, 0, Mp * H * 2, v->stream));
-    VFT_HIP(hipMemsetAsync(v->qkv, 0, Mp * 3 * H * 2, v->stream));
-    VFT_HIP(hipMemsetAsync(v->ctx, 0, Mp * H * 2, v->stream));
-    VFT_HIP(hipMemsetAsync(v->hbuf, 0, Mp * F * 2, v->stream));
-    VFT_HIP(hipMemsetAsync(v->d_mask, 0, Mp * 4, v->stream));
+    DevPool& ws = v->ws;
+    hipStream_t st = v->stream;
+    // (zeroed: rows past B Tp are read by the products, keep them finite)
+    VFT_HIP(ws.get(&v->x, Mp * H * 2, true, st));
+    VFT_HIP(ws.get(&v->y, Mp * H * 2, true, st));
+    VFT_HIP(ws.get(&v->t, Mp * H * 2, true, st));
+    VFT_HIP(ws.get(&v->qkv, Mp * 3 * H * 2, true, st));
+    VFT_HIP(ws.get(&v->ctx, Mp * H * 2, true, st));
+    VFT_HIP(ws.get(&v->hbuf, Mp * F * 2, true, st));
+    VFT_HIP(ws.get(&v->d_ids, Mp * 4, false, st));
+    VFT_HIP(ws.get(&v->d_mask_in, Mp * 4, false, st));
+    VFT_HIP(ws.get(&v->d_mask, Mp * 4, true, st));
+    VFT_HIP(ws.get(&v->d_eos, (size_t)B * 4, false, st));
+    VFT_HIP(ws.get(&v->d_out, (size_t)B * v->cfg.proj_dim * 4, false, st));
     v->cap_tokens = tokens; v->cap_b = B;
-    VFT_HIP(gws_ensure(v->gws, v->stream));
+    VFT_HIP(gws_ensure(v->gws, st));
     return VF_OK;
 }
 
@@ -4883,14 +4837,11 @@ extern "C" int vf_clip_text_forward(vf_clip_text* v, const int32_t* ids, const i
     }
     if (!mask) { ones.assign((size_t)b * t, 1); mask = ones.data(); }
     std::lock_guard<std::mutex> lk(v->mu);
-    int prev = 0;
-    VFT_HIP(hipGetDevice(&prev));
-    struct Back { int d; ~Back() { (void)hipSetDevice(d); } } back{prev};
+    vf::DeviceGuard guard;
     VFT_HIP(hipSetDevice(v->device));
     const int Tp = (t + 31) / 32 * 32;
     VFT_TRY(ct_ensure_ws(v, b, Tp));
-    const int H = c.hidden, F = c.ffn;
-    const int M = b * Tp, Mp = (M + 255) / 256 * 256;
+    const int H = c.hidden, M = b * Tp;
     VFT_HIP(handle_stream(&v->stream));
     hipStream_t st = v->stream;
     VFT_HIP(hipMemcpyAsync(v->d_ids, ids, (size_t)b * t * 4, hipMemcpyHostToDevice, st));
@@ -4899,21 +4850,10 @@ extern "C" int vf_clip_text_forward(vf_clip_text* v, const int32_t* ids, const i
     hipLaunchKernelGGL(k_clip_text_embed, dim3((M + 7) / 8), dim3(256), 0, st, v->d_ids, v->d_mask_in, v->w16 + v->o_tok, v->w16 + v->o_pos, b, t,
                        Tp, H, c.vocab, v->x, v->d_mask);
     const dim3 agrid((Tp + 127) / 128, c.heads, b);
-    for (int l = 0; l < c.layers; ++l) {
-        const half_t* w = v->w16 + v->o_layers + (size_t)l * v->layer16;
-        const float* f = v->w32 + v->f_layers + (size_t)l * v->layer32;
-        const half_t *Wqkv = w, *Wo = Wqkv + (size_t)3 * H * H, *W1 = Wo + (size_t)H * H, *W2 = W1 + (size_t)F * H;
-        const float *g1 = f, *b1n = g1 + H, *bqkv = b1n + H, *bo = bqkv + 3 * H, *g2 = bo + H, *b2n = g2 + H, *b1 = b2n + H, *b2 = b1 + F;
-        hipLaunchKernelGGL(k_layernorm, dim3((M + 7) / 8), dim3(256), 0, st, v->x, g1, b1n, c.ln_eps, M, H, v->t);
-        VFT_HIP(gemm<EPI_BIAS>(v->t, Wqkv, bqkv, nullptr, v->qkv, Mp, 3 * H, H, st, 0, &v->gws));
+    VFT_TRY(preln_layers(v, M, st, [&] {
         hipLaunchKernelGGL((k_attention_stream2<64, true>), agrid, dim3(256), sizeof(AttnStream2Lds<64>), st, v->qkv, v->d_mask, Tp, 3 * H, c.heads,
                            c.heads, 0.125f, v->ctx, H, (const int*)nullptr);
-        VFT_HIP(gemm<EPI_BIAS_RESIDUAL>(v->ctx, Wo, bo, v->x, v->y, Mp, H, H, st, 0, &v->gws));
-        hipLaunchKernelGGL(k_layernorm, dim3((M + 7) / 8), dim3(256), 0, st, v->y, g2, b2n, c.ln_eps, M, H, v->t);
-        if (c.act == 0) VFT_HIP(gemm<EPI_BIAS_GELU>(v->t, W1, b1, nullptr, v->hbuf, Mp, F, H, st, 0, &v->gws));
-        else VFT_HIP(gemm<EPI_BIAS_QGELU>(v->t, W1, b1, nullptr, v->hbuf, Mp, F, H, st, 0, &v->gws));
-        VFT_HIP(gemm<EPI_BIAS_RESIDUAL>(v->hbuf, W2, b2, v->y, v->x, Mp, H, F, st, 0, &v->gws));
-    }
+    }));
     hipLaunchKernelGGL(k_vit_head, dim3(b), dim3(256), (size_t)(H + 256) * sizeof(float), st, v->x, Tp, H, v->w32 + v->f_final, v->w32 + v->f_final + H,
                        c.ln_eps, v->w16 + v->o_proj, c.proj_dim, c.normalize, v->d_out, (const int*)v->d_eos);
     VFT_HIP(hipGetLastError());
