@@ -47,7 +47,7 @@ typedef struct vf_index vf_index;
 
 /* counters of the last search on a handle (for tests / benches; not part of the reference surface) */
 typedef struct vf_search_stats {
-    int64_t path;            /* 0 = small-N exact dense, 1 = fused MFMA scan, 2 = chunked exact */
+    int64_t path;            /* 0 = small-N exact dense, 1 = fused MFMA scan, 2 = chunked exact, 3 = subset scan (VF_SEARCH_SUBSET) */
     int64_t n_queries;
     int64_t candidates;      /* total candidates appended by the fused scan (all queries) */
     int64_t max_candidates;  /* largest per-query candidate count */
@@ -60,7 +60,8 @@ typedef struct vf_search_stats {
     int64_t scans_overlap;   /* 1 = main scans of consecutive slots were not ordered against each other */
     int64_t scan_kernel;     /* main-scan kernel of the call: 1 k_scan (register loads), 2 k_scan2 (whole-line LDS-DMA), 3 k_scan_wide, 4 k_scan_wide8 (fp8 matrix instruction), 5 k_scan2r (k_scan2, half the query image in registers), 6 k_scan_ksplit (rows of 2560 to 4096 padded elements: option "wide_rows"), 7 k_scan_ksplit8 (the same for e4m3 rows) or its int8 form k_scan_ksplit8i (int8 rows report 7 as the int8 forms of k_scan and k_scan_wide report 1 and 3) */
     int64_t scan_image;      /* 1 = the main scan read the int8 row image (option "scan_image"), 0 = the rows as stored */
-    int64_t reserved[3];
+    int64_t subset_rows;     /* path 3 only: rows the list of a subset search named (VF_SEARCH_SUBSET) */
+    int64_t reserved[2];
 } vf_search_stats;
 
 int vf_version(void);
@@ -193,6 +194,42 @@ int vf_index_slots(vf_index* idx, int32_t* out);
 int vf_index_search_begin(vf_index* idx, int32_t slot, const float* d_queries, int32_t nq, int32_t k,
                           int64_t* d_ids, float* d_scores, void* stream);
 int vf_index_search_end(vf_index* idx, int32_t slot);
+
+/* ---- search a chosen subset of rows: exact filtered top-k ------------------------------------------------------------------
+ * The reference promises metadata filtering ("compatible with LangChain that supports metadata filtering": FaissRetriever,
+ * BM25Retriever) and does not deliver it: BM25Retriever.invoke(metadata_filters=...) raises NotImplementedError
+ * (src/utils/bm25Retriever.py:54,70-72) and the sketch under its TODO (:91-132) ranks everything and masks on the host; in practice
+ * it keeps one index per company.  Here ONE index answers "only these rows": `ids` [n_ids] are global ids (id_offset ..
+ * id_offset + n - 1), STRICTLY ASCENDING, and the result is what vf_index_search over an index of those rows alone would return, ids
+ * mapped back -- same canonical scores bit for bit, descending, ties to the lower id, a zero score reported as +0.0, k > n_ids padded
+ * with (-1, -FLT_MAX).  Only the listed rows are read (k_scan_subset scores them as the index holds them: no copy of them is made),
+ * so a call costs what its rows cost, whatever the index holds.
+ * A list that is out of range, not ascending or repeats an id is VF_EINVAL and the message names the first offending position; the
+ * host form checks before any HIP call, the device form by a small kernel whose word is read at the one synchronisation the call
+ * makes (nothing has then been written to the output buffers).  A refused call changes nothing: the handle stays searchable.
+ * n_ids == 0 returns all padding; n_ids == n is the ordinary search (vf_search_stats.path says which); every other call reports
+ * path 3 and subset_rows = n_ids.  Limits: any k while n_ids <= 16 384; k <= 8192 beyond (VF_EUNSUPPORTED, the chunked exact path's own
+ * limit); n_ids <= 2^32 - 2.  Synchronous, under the handle's mutex; the workspace is leased from the pool of the small dense entry
+ * points (scores: up to 64 MB per launch, option "subset_super_rows" lowers the rows per launch), never from the search slots, so a
+ * search pending between _begin and _end is not disturbed.  A damaged handle returns VF_EHIP.
+ * Group handles take the host form only (the device form is VF_EUNSUPPORTED): the list is split at the shards' id ranges on the host,
+ * the shards are searched one after another -- NOT overlapped -- and the parts are merged on the home device; shards * k > 16384 is
+ * VF_EUNSUPPORTED as for every group search.
+ * Not in scope: a pipelined _begin / _end form, overlapped shards, a row filter inside the BM25 kernels (the ensemble filters that
+ * leg on the host), MixedModalIndex.
+ * The call (no new entry point: like appends and removals it rides on calls that exist, so the exported surface stays as it is):
+ *   vf_subset_query sq = {queries, ids, n_ids};
+ *   vf_index_search(idx, (const float*)&sq, nq | VF_SEARCH_SUBSET, k, out_ids, out_scores);                        host buffers
+ *   vf_index_search_device(idx, (const float*)&sq, nq | VF_SEARCH_SUBSET, k, d_out_ids, d_out_scores, stream);     device buffers
+ * `sq` itself is always in host memory; in the device form its `queries` and `ids` are device pointers on the index's device (a filter
+ * uploaded once serves every later call), work is enqueued on `stream` and the call returns after the results are final.  Without
+ * the flag nothing about the two calls changes. */
+#define VF_SEARCH_SUBSET 0x40000000   /* or'ed into `nq` of vf_index_search / vf_index_search_device: `queries` is a vf_subset_query */
+typedef struct vf_subset_query {
+    const float* queries;   /* [nq, d] fp32, not normalised */
+    const int64_t* ids;     /* [n_ids] global ids, strictly ascending */
+    int64_t n_ids;
+} vf_subset_query;
 
 int vf_index_info(vf_index* idx, int64_t* n, int32_t* d, int32_t* dtype, int32_t* device_id);
 int vf_index_stats(vf_index* idx, vf_search_stats* out);

@@ -64,8 +64,8 @@ def configure(hw_queues: int = 8, warn: bool = True) -> bool:
     return True
 
 
-from .index import (DenseIndex, cosine_matrix, cosine_scores, fuse_rank, merge_topk_device,  # noqa: F401
-                    merge_topk_packed_device, packed_part_bytes, packed_result_buffer, quantize_int8)
+from .index import (DenseIndex, RowSubset, cosine_matrix, cosine_scores, fuse_rank, merge_topk_device,  # noqa: F401
+                    merge_topk_packed_device, packed_part_bytes, packed_result_buffer, quantize_int8, subset_ids)
 from .faiss_retriever import FaissRetriever  # noqa: F401
 from .retrieval import get_embeddings, last_token_pool, select_top_chunks, select_top_chunks_batch  # noqa: F401
 from .similarity import compute_similarity, compute_similarity_mtx, fuse_and_rank, time_scores  # noqa: F401

@@ -17,6 +17,8 @@ VF_DTYPE_F32, VF_DTYPE_F16, VF_DTYPE_FP8_E4M3, VF_DTYPE_INT8 = 0, 1, 2, 3
 VF_INDEX_APPEND = 0x100   # or'ed into the dtype of vf_index_create / vf_index_create_device: append to the handle in *out
 VF_INDEX_REMOVE = 0x200   # the whole dtype of vf_index_create: `rows` are int64 ids to remove from the handle in *out
 
+VF_SEARCH_SUBSET = 0x40000000   # or'ed into nq of vf_index_search / vf_index_search_device: `queries` is then a SubsetQuery
+
 c_i32, c_i64, c_f32 = ctypes.c_int32, ctypes.c_int64, ctypes.c_float
 p_i32, p_i64, p_f32 = ctypes.POINTER(c_i32), ctypes.POINTER(c_i64), ctypes.POINTER(c_f32)
 vp = ctypes.c_void_p
@@ -35,6 +37,24 @@ class Bm25Delta(ctypes.Structure):
         ("b", ctypes.c_double), ("chunk", c_i32), ("out_indptr", ctypes.POINTER(c_i64)), ("out_indices", ctypes.POINTER(c_i32)),
         ("out_data", ctypes.POINTER(c_f32)), ("out_tf", ctypes.POINTER(c_i32)), ("out_doc_len", ctypes.POINTER(c_i32)),
     ]
+
+
+class SubsetQuery(ctypes.Structure):
+    """vf_subset_query of include/veritasfi_hip.h: what `queries` points to when nq carries VF_SEARCH_SUBSET (host memory; in the
+    device form the two pointers inside are device pointers)."""
+    _fields_ = [("queries", ctypes.c_void_p), ("ids", ctypes.c_void_p), ("n_ids", ctypes.c_int64)]
+
+
+def search_subset(L, handle, queries_ptr, nq, k, ids_ptr, n_ids, out_ids_ptr, out_scores_ptr) -> int:
+    """vf_index_search in its subset form; returns the code."""
+    sq = SubsetQuery(queries_ptr, ids_ptr, n_ids)
+    return L.vf_index_search(handle, ctypes.addressof(sq), int(nq) | VF_SEARCH_SUBSET, k, out_ids_ptr, out_scores_ptr)
+
+
+def search_subset_device(L, handle, d_queries_ptr, nq, k, d_ids_ptr, n_ids, d_out_ids_ptr, d_out_scores_ptr, stream) -> int:
+    """vf_index_search_device in its subset form; returns the code."""
+    sq = SubsetQuery(d_queries_ptr, d_ids_ptr, n_ids)
+    return L.vf_index_search_device(handle, ctypes.addressof(sq), int(nq) | VF_SEARCH_SUBSET, k, d_out_ids_ptr, d_out_scores_ptr, stream)
 
 
 class EncoderConfig(ctypes.Structure):
@@ -71,7 +91,7 @@ class SearchStats(ctypes.Structure):
     _fields_ = [
         ("path", c_i64), ("n_queries", c_i64), ("candidates", c_i64), ("max_candidates", c_i64),
         ("uncertified", c_i64), ("overflowed", c_i64), ("exact_reruns", c_i64), ("wide_launches", c_i64), ("wide_queries", c_i64),
-        ("aux_cus", c_i64), ("scans_overlap", c_i64), ("scan_kernel", c_i64), ("scan_image", c_i64), ("reserved", c_i64 * 3),
+        ("aux_cus", c_i64), ("scans_overlap", c_i64), ("scan_kernel", c_i64), ("scan_image", c_i64), ("subset_rows", c_i64), ("reserved", c_i64 * 2),
     ]
 
     def as_dict(self):

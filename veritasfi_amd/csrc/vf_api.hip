@@ -196,6 +196,7 @@ struct vf_index {
     DevBuf st_add, st_rho;            // appends: the new rows on their way in (host rows, rows of another device), the image's two residual words
     DevBuf st_cmp, st_rem;            // removals: the staging buffer of the row compaction, the sorted removed rows
     int64_t compact_chunk_rows = 0;   // option: destination rows per chunk of a removal's compaction (0 = auto: kCompactStageBytes of the widest array)
+    int64_t subset_super_rows = 0;    // option: listed rows a subset search scores per launch (0 = auto: kSubsetScoreBytes of scores; vf_subset.h)
     bool damaged = false;             // a HIP error struck a removal after its first row had moved: searches, appends and removals are refused from then on
     // ---- group handle (vf_index_create_sharded / vf_index_group): the corpus is row-sharded over `shards`, one per
     // device; this handle owns them.  device = the HOME device: queries arrive there and the merged result lands there.
@@ -1170,6 +1171,7 @@ extern "C" int vf_index_set_option(vf_index* ix, const char* name, int64_t value
     else if (s == "image_mfma") { if (!in_range(-1, 2)) return fail(VF_EINVAL, "image_mfma must be -1 (auto), 0 (the int8 row image on the fp16 matrix instruction, fp16 queries), 1 (on the int8 matrix instruction, the queries as one int8 plane) or 2 (as two planes, hi + lo: the band of 0)"); ix->image_mfma = value; }
     else if (s == "wide_rows") { if (!in_range(0, 2)) return fail(VF_EINVAL, std::string("wide_rows must be 0 (rows of more than 2432 padded elements never take the fused path), 1 (auto: from ") + std::to_string(kWideRowsMinRows) + " rows, e4m3 rows from " + std::to_string(kWideRowsMinRows8) + ", int8 rows from " + std::to_string(kWideRowsMinRowsI8) + ") or 2 (wherever k_scan_ksplit / k_scan_ksplit8 serve them; int8 rows: from " + std::to_string(kWideRowsMinRowsI8) + " rows)"); ix->wide_rows = value; }
     else if (s == "compact_chunk_rows") { if (!in_range(0, kMaxShardRows)) return fail(VF_EINVAL, "compact_chunk_rows must be 0 (auto: 64 MB of staging) or the destination rows a removal moves per chunk"); ix->compact_chunk_rows = value; }
+    else if (s == "subset_super_rows") { if (!in_range(0, kSubsetMaxRows)) return fail(VF_EINVAL, "subset_super_rows must be 0 (auto: 64 MB of scores) or the listed rows a subset search scores per launch"); ix->subset_super_rows = value; }
     else if (s == "debug") ix->debug = value;
     else if (s == "profile") {
         ix->profile = value != 0; ix->prof_scan_ms = ix->prof_pipe_ms = 0.0; ix->prof_launches = 0;
@@ -1802,8 +1804,14 @@ static int search_device_locked(vf_index* ix, const float* d_queries, int nq, in
     return search_end_locked(ix, 0);
 }
 
+// the subset forms of the two search entry points (nq carries VF_SEARCH_SUBSET, `queries` is a vf_subset_query): defined with the
+// subset search, below
+static int subset_entry_host(vf_index* ix, const vf_subset_query* sq, int32_t nq, int32_t k, int64_t* out_ids, float* out_scores);
+static int subset_entry_device(vf_index* ix, const vf_subset_query* sq, int32_t nq, int32_t k, int64_t* d_out_ids, float* d_out_scores, void* stream);
+
 extern "C" int vf_index_search_device(vf_index* ix, const float* d_queries, int32_t nq, int32_t k, int64_t* d_ids,
                                       float* d_scores, void* stream) {
+    if (nq >= 0 && (nq & VF_SEARCH_SUBSET)) return subset_entry_device(ix, (const vf_subset_query*)d_queries, nq & ~VF_SEARCH_SUBSET, k, d_ids, d_scores, stream);
     DeviceGuard restore_callers_device;
     VF_TRY(check_search_args(ix, d_queries, nq, k, d_ids, d_scores));
     std::lock_guard<std::mutex> g(ix->mu);
@@ -1813,12 +1821,7 @@ extern "C" int vf_index_search_device(vf_index* ix, const float* d_queries, int3
 // Host buffers in and out: what FaissRetriever.invoke hands over (NumPy arrays, src/utils/faissRetriever.py:34-38).
 // The device staging lives in the handle and is reused from call to call (no hipMalloc / hipFree per request); the
 // handle's mutex is held for the whole call, so concurrent request threads take turns on it.
-extern "C" int vf_index_search(vf_index* ix, const float* queries, int32_t nq, int32_t k, int64_t* out_ids,
-                               float* out_scores) {
-    DeviceGuard restore_callers_device;
-    VF_TRY(check_search_args(ix, queries, nq, k, out_ids, out_scores));
-    if (nq == 0 || k == 0) return VF_OK;
-    std::lock_guard<std::mutex> g(ix->mu);
+static int search_host_locked(vf_index* ix, const float* queries, int nq, int k, int64_t* out_ids, float* out_scores) {
     VF_HIP(hipSetDevice(ix->device));
     const size_t qb = (size_t)nq * ix->d * sizeof(float), ib = (size_t)nq * k * sizeof(int64_t), sb = (size_t)nq * k * sizeof(float);
     VF_TRY(ix->st_q.ensure(qb));
@@ -1831,6 +1834,16 @@ extern "C" int vf_index_search(vf_index* ix, const float* queries, int32_t nq, i
     VF_HIP(hipMemcpy(out_ids, ix->st_ids.p, ib, hipMemcpyDeviceToHost));
     VF_HIP(hipMemcpy(out_scores, ix->st_sc.p, sb, hipMemcpyDeviceToHost));
     return VF_OK;
+}
+
+extern "C" int vf_index_search(vf_index* ix, const float* queries, int32_t nq, int32_t k, int64_t* out_ids,
+                               float* out_scores) {
+    if (nq >= 0 && (nq & VF_SEARCH_SUBSET)) return subset_entry_host(ix, (const vf_subset_query*)queries, nq & ~VF_SEARCH_SUBSET, k, out_ids, out_scores);
+    DeviceGuard restore_callers_device;
+    VF_TRY(check_search_args(ix, queries, nq, k, out_ids, out_scores));
+    if (nq == 0 || k == 0) return VF_OK;
+    std::lock_guard<std::mutex> g(ix->mu);
+    return search_host_locked(ix, queries, nq, k, out_ids, out_scores);
 }
 
 static std::atomic<bool> g_force_no_peer{false};
@@ -2188,6 +2201,230 @@ extern "C" int vf_cosine_matrix_rows(vf_index* ix, const int64_t* ids, int32_t n
 
 extern "C" int vf_cosine_matrix_rows_mixed(vf_index* ix, const int64_t* ids, int32_t n, const float* extra, int32_t n_extra, float* out) {
     return cosine_matrix_rows_impl(ix, ids, n, extra, n_extra, out, "vf_cosine_matrix_rows_mixed");
+}
+
+// ------------------------------------------------------------------------------------------------
+// Search over a chosen subset of rows (round 16): vf_index_search / vf_index_search_device with VF_SEARCH_SUBSET in nq.  The reference promises metadata filtering and
+// never delivers it (BM25Retriever.invoke raises NotImplementedError, src/utils/bm25Retriever.py:70-72; its sketch ranks everything
+// and masks on the host, :91-132).  Here the listed rows alone are scored, by k_scan_subset, in the canonical arithmetic, so the
+// result is exactly what an index over those rows would return, ids mapped back; cost follows the rows listed, not the rows held.
+// The plan (super-chunks, rank chunks, merge rounds, limits, the two trivial routes): vf_subset.h.  The workspace is ONE lease of the
+// small entry points' pool, so the search slots -- and a search pending in one -- are not touched.
+// ------------------------------------------------------------------------------------------------
+static std::string subset_bad_message(const char* who, int64_t i, int64_t v, bool has_prev, int64_t prev, int64_t lo, int64_t hi) {
+    const std::string at = std::string(who) + ": ids[" + std::to_string(i) + "] = " + std::to_string(v);
+    if (v < lo || v >= hi) return at + " is outside the index's ids [" + std::to_string(lo) + ", " + std::to_string(hi) + ")";
+    if (has_prev && v == prev) return at + " is a duplicate of ids[" + std::to_string(i - 1) + "] (the list must be strictly ascending)";
+    return at + " is not ascending: ids[" + std::to_string(i - 1) + "] = " + std::to_string(prev) + " (the list must be strictly ascending)";
+}
+
+static int check_subset_args(vf_index* ix, const void* q, int nq, int k, const void* list, int64_t m, const void* ids, const void* sc, const char* who) {
+    if (!ix) return fail(VF_EINVAL, std::string(who) + ": null handle");
+    if (nq < 0 || k < 0 || m < 0) return fail(VF_EINVAL, std::string(who) + ": negative nq / k / n_ids");
+    if (m > 0 && !list) return fail(VF_EINVAL, std::string(who) + ": null id list");
+    if (nq > 0 && k > 0 && (!q || !ids || !sc)) return fail(VF_EINVAL, std::string(who) + ": null buffer");
+    return VF_OK;
+}
+
+static size_t subset_ws_bytes(const SubsetPlan& p, int d, int k) {
+    const size_t part = (size_t)p.batch * k, slots = p.parts > 1 ? (size_t)p.super_parts + 1 : 1;
+    size_t b = Lease::padded((size_t)p.batch * d * 4) + Lease::padded((size_t)p.score_bytes) + Lease::padded(slots * part * 8) + Lease::padded(slots * part * 4);
+    if (p.parts > 1) b += Lease::padded(part * 8) + Lease::padded(part * 4);
+    return b;
+}
+
+static void subset_stats(vf_index* ix, int nq, int64_t m) {
+    vf_search_stats stt{};
+    stt.path = 3; stt.n_queries = nq; stt.subset_rows = m;
+    ix->stats = stt;
+}
+
+// every result (-1, -FLT_MAX): the ranking kernel over no score at all
+static int subset_fill_empty(int nq, int k, int64_t* d_out_ids, float* d_out_sc, hipStream_t st) {
+    VF_HIP(launch_sort_rows(nullptr, 0, nq, 0, k, 0, (long long*)d_out_ids, d_out_sc, k, st));
+    return VF_OK;
+}
+
+// The scan route, enqueued on `st` (nothing is waited for): everything on the device of the plain handle ix, which is current.
+// d_list: the m listed ids; d_flag: the device form's check word (nothing reaches the outputs unless it reads ~0), or null.
+// Per super-chunk: one scan, one ranking launch over its whole chunks (+ one for a short last chunk), then the parts are folded into
+// the running result, fan_in slots per merge (vf_subset.h).
+static int subset_scan(vf_index* ix, const SubsetPlan& p, Lease& ws, const float* d_q, int nq, int k, const long long* d_list, int64_t m,
+                       const u64* d_flag, int64_t* d_out_ids, float* d_out_sc, hipStream_t st) {
+    const int d = ix->d;
+    const bool merging = p.parts > 1;
+    const size_t part = (size_t)p.batch * k, slots = merging ? (size_t)p.super_parts + 1 : 1;
+    float* qn = ws.take<float>((size_t)p.batch * d);
+    float* scores = ws.take<float>((size_t)p.score_bytes / 4);
+    long long* buf_ids = ws.take<long long>(slots * part);     // slot 0: the running result; slots 1 ..: the parts of a super-chunk
+    float* buf_sc = ws.take<float>(slots * part);
+    long long* mrg_ids = merging ? ws.take<long long>(part) : nullptr;
+    float* mrg_sc = merging ? ws.take<float>(part) : nullptr;
+    for (int b0 = 0; b0 < nq; b0 += p.batch) {
+        const int nb = std::min(p.batch, nq - b0);
+        const size_t pb = (size_t)nb * k;   // one slot of this pass
+        VF_HIP(launch_prep_queries(d_q + (size_t)b0 * d, nb, d, d, nb, qn, nullptr, st));
+        if (merging) VF_HIP(hipMemsetAsync(buf_ids, 0xFF, pb * 8, st));   // the running result starts as padding (ids -1: their scores are not read)
+        for (long long c = 0; c < p.supers; ++c) {
+            const SubsetSpan sup = subset_super(p, m, c);
+            const long long count = sup.hi - sup.lo;
+            SubsetArgs a{};
+            a.rows = ix->rows_orig; a.norm = ix->norm; a.n = ix->n; a.ids = d_list; a.id_base = ix->id_offset;
+            a.pos0 = sup.lo; a.count = count; a.qn = qn; a.nq = nb; a.d = d; a.scores = scores; a.rank_rows = p.rank_rows;
+            VF_HIP(launch_scan_subset(a, ix->dtype, st));
+            if (!merging) {   // one part: ranked straight into the result, any k
+                VF_HIP(launch_sort_rows(scores, p.rank_rows, nb, (int)count, k, 0, buf_ids, buf_sc, k, st));
+                break;
+            }
+            const long long chunks = subset_rank_chunks(p, sup), full = count / p.rank_rows, tail = count - full * p.rank_rows;
+            long long* part_ids = buf_ids + pb;
+            float* part_sc = buf_sc + pb;
+            // a "query" of the ranking launch is a (chunk, query) pair: the scores are [chunk][query][rank_rows], the parts come out [chunk][query][k]
+            if (full > 0) VF_HIP(launch_sort_rows(scores, p.rank_rows, (int)(full * nb), (int)p.rank_rows, k, 0, part_ids, part_sc, k, st));
+            if (tail > 0) VF_HIP(launch_sort_rows(scores + (size_t)full * nb * p.rank_rows, p.rank_rows, nb, (int)tail, k, 0, part_ids + (size_t)full * pb,
+                                                  part_sc + (size_t)full * pb, k, st));
+            VF_HIP(launch_subset_part_base(part_ids, chunks, (long long)pb, sup.lo, p.rank_rows, st));
+            long long first = 0;   // the slot that holds the running result
+            for (long long done = 0; done < chunks;) {
+                const long long take = std::min<long long>(p.fan_in - 1, chunks - done);
+                VF_HIP(launch_merge_topk(buf_ids + (size_t)first * pb, buf_sc + (size_t)first * pb, (int)take + 1, nb, k, mrg_ids, mrg_sc, st));
+                first += take; done += take;
+                // ... which moves to the last slot this merge consumed -- the first of the next merge -- or, at the end, back to slot 0
+                const long long to = done < chunks ? first : 0;
+                VF_HIP(hipMemcpyAsync(buf_ids + (size_t)to * pb, mrg_ids, pb * 8, hipMemcpyDeviceToDevice, st));
+                VF_HIP(hipMemcpyAsync(buf_sc + (size_t)to * pb, mrg_sc, pb * 4, hipMemcpyDeviceToDevice, st));
+                if (done >= chunks) first = 0;
+            }
+        }
+        VF_HIP(launch_subset_ids(buf_ids, buf_sc, (long long)pb, d_list, d_flag, (long long*)d_out_ids + (size_t)b0 * k, d_out_sc + (size_t)b0 * k, st));
+    }
+    return VF_OK;
+}
+
+// host buffers, a plain handle, the caller holds the lock
+static int subset_host_plain(vf_index* ix, const float* queries, int nq, int k, const int64_t* ids, int64_t m, int64_t* out_ids, float* out_sc,
+                             const char* who) {
+    if (ix->damaged) return fail(VF_EHIP, std::string(who) + ": " + kDamagedMsg);
+    const int64_t lo = ix->id_offset, hi = ix->id_offset + ix->n;
+    const long long bad = subset_first_bad((const long long*)ids, m, lo, hi);
+    if (bad >= 0) return fail(VF_EINVAL, subset_bad_message(who, bad, ids[bad], bad > 0, bad > 0 ? ids[bad - 1] : 0, lo, hi));
+    const SubsetPlan p = subset_plan(ix->n, m, nq, k, ix->subset_super_rows, 0);
+    if (p.route == kSubsetRefused) return fail(VF_EUNSUPPORTED, std::string(who) + ": " + p.why);
+    if (p.route == kSubsetAll) return search_host_locked(ix, queries, nq, k, out_ids, out_sc);
+    if (p.route == kSubsetEmpty) {
+        std::fill(out_ids, out_ids + (size_t)nq * k, (int64_t)-1);
+        std::fill(out_sc, out_sc + (size_t)nq * k, -FLT_MAX);
+        subset_stats(ix, nq, 0);
+        return VF_OK;
+    }
+    VF_HIP(hipSetDevice(ix->device));
+    const size_t qe = (size_t)nq * ix->d, oe = (size_t)nq * k;
+    Lease ws;
+    VF_TRY(ws.acquire(ix->device, subset_ws_bytes(p, ix->d, k) + Lease::padded(qe * 4) + Lease::padded((size_t)m * 8) + Lease::padded(oe * 8) + Lease::padded(oe * 4)));
+    float* dq = ws.take<float>(qe); long long* dlist = ws.take<long long>((size_t)m);
+    int64_t* dout_ids = ws.take<int64_t>(oe); float* dout_sc = ws.take<float>(oe);
+    VF_HIP(hipMemcpy(dq, queries, qe * 4, hipMemcpyHostToDevice));
+    VF_HIP(hipMemcpy(dlist, ids, (size_t)m * 8, hipMemcpyHostToDevice));
+    VF_TRY(subset_scan(ix, p, ws, dq, nq, k, dlist, m, nullptr, dout_ids, dout_sc, nullptr));
+    VF_HIP(hipStreamSynchronize(nullptr));
+    VF_HIP(hipMemcpy(out_ids, dout_ids, oe * 8, hipMemcpyDeviceToHost));
+    VF_HIP(hipMemcpy(out_sc, dout_sc, oe * 4, hipMemcpyDeviceToHost));
+    subset_stats(ix, nq, m);
+    return VF_OK;
+}
+
+// A group: the list is split at the shards' id ranges on the host and the shards are searched ONE AFTER ANOTHER (no overlap: each
+// call is the synchronous host form); a shard without a listed row gives an all-padding part.  The parts meet on the home device
+// and one k_merge_topk ranks them (shard order = ascending ids, which its tie rule relies on).
+static int subset_host_group(vf_index* ix, const float* queries, int nq, int k, const int64_t* ids, int64_t m, int64_t* out_ids, float* out_sc,
+                             const char* who) {
+    if (ix->damaged) return fail(VF_EHIP, std::string(who) + ": " + kDamagedMsg);
+    const size_t G = ix->shards.size();
+    if ((size_t)G * k > 16384) return fail(VF_EUNSUPPORTED, "sharded search: shards * k > 16384");
+    const int64_t lo = ix->id_offset, hi = ix->id_offset + ix->n;
+    const long long bad = subset_first_bad((const long long*)ids, m, lo, hi);
+    if (bad >= 0) return fail(VF_EINVAL, subset_bad_message(who, bad, ids[bad], bad > 0, bad > 0 ? ids[bad - 1] : 0, lo, hi));
+    const size_t oe = (size_t)nq * k;
+    std::vector<int64_t> part_ids(G * oe);
+    std::vector<float> part_sc(G * oe);
+    const int64_t* at = ids;
+    for (size_t g = 0; g < G; ++g) {
+        vf_index* sh = ix->shards[g];
+        const int64_t* end = std::lower_bound(at, ids + m, sh->id_offset + sh->n);
+        VF_TRY(subset_host_plain(sh, queries, nq, k, at, end - at, part_ids.data() + g * oe, part_sc.data() + g * oe, who));
+        at = end;
+    }
+    VF_HIP(hipSetDevice(ix->device));
+    VF_HIP(scan_configure());
+    Lease ws;
+    VF_TRY(ws.acquire(ix->device, Lease::padded(G * oe * 8) + Lease::padded(G * oe * 4) + Lease::padded(oe * 8) + Lease::padded(oe * 4)));
+    long long* dp_ids = ws.take<long long>(G * oe); float* dp_sc = ws.take<float>(G * oe);
+    long long* d_ids = ws.take<long long>(oe); float* d_sc = ws.take<float>(oe);
+    VF_HIP(hipMemcpy(dp_ids, part_ids.data(), G * oe * 8, hipMemcpyHostToDevice));
+    VF_HIP(hipMemcpy(dp_sc, part_sc.data(), G * oe * 4, hipMemcpyHostToDevice));
+    VF_HIP(launch_merge_topk(dp_ids, dp_sc, (int)G, nq, k, d_ids, d_sc, nullptr));
+    VF_HIP(hipStreamSynchronize(nullptr));
+    VF_HIP(hipMemcpy(out_ids, d_ids, oe * 8, hipMemcpyDeviceToHost));
+    VF_HIP(hipMemcpy(out_sc, d_sc, oe * 4, hipMemcpyDeviceToHost));
+    subset_stats(ix, nq, m);
+    return VF_OK;
+}
+
+static int subset_entry_host(vf_index* ix, const vf_subset_query* sq, int32_t nq, int32_t k, int64_t* out_ids, float* out_scores) {
+    static const char* who = "vf_index_search (VF_SEARCH_SUBSET)";
+    if (!sq) return fail(VF_EINVAL, std::string(who) + ": null vf_subset_query");
+    const float* queries = sq->queries; const int64_t* ids = sq->ids; const int64_t n_ids = sq->n_ids;
+    DeviceGuard restore_callers_device;
+    VF_TRY(check_subset_args(ix, queries, nq, k, ids, n_ids, out_ids, out_scores, who));
+    std::lock_guard<std::mutex> g(ix->mu);
+    if (nq == 0 || k == 0) {   // nothing to return, but a bad list is still a bad list
+        const long long bad = subset_first_bad((const long long*)ids, n_ids, ix->id_offset, ix->id_offset + ix->n);
+        if (bad >= 0) return fail(VF_EINVAL, subset_bad_message(who, bad, ids[bad], bad > 0, bad > 0 ? ids[bad - 1] : 0, ix->id_offset, ix->id_offset + ix->n));
+        return VF_OK;
+    }
+    if (!ix->shards.empty()) return subset_host_group(ix, queries, nq, k, ids, n_ids, out_ids, out_scores, who);
+    return subset_host_plain(ix, queries, nq, k, ids, n_ids, out_ids, out_scores, who);
+}
+
+static int subset_entry_device(vf_index* ix, const vf_subset_query* sq, int32_t nq, int32_t k, int64_t* d_out_ids, float* d_out_scores, void* stream) {
+    static const char* who = "vf_index_search_device (VF_SEARCH_SUBSET)";
+    if (!sq) return fail(VF_EINVAL, std::string(who) + ": null vf_subset_query");
+    const float* d_queries = sq->queries; const int64_t* d_ids = sq->ids; const int64_t n_ids = sq->n_ids;
+    DeviceGuard restore_callers_device;
+    VF_TRY(check_subset_args(ix, d_queries, nq, k, d_ids, n_ids, d_out_ids, d_out_scores, who));
+    std::lock_guard<std::mutex> g(ix->mu);
+    if (ix->damaged) return fail(VF_EHIP, std::string(who) + ": " + kDamagedMsg);
+    if (!ix->shards.empty()) return fail(VF_EUNSUPPORTED, std::string(who) + ": a group handle takes the host-buffer form only (vf_index_search with VF_SEARCH_SUBSET)");
+    if (n_ids > ix->n) return fail(VF_EINVAL, std::string(who) + ": " + std::to_string(n_ids) + " ids for an index of " + std::to_string(ix->n) + " rows (the list must be strictly ascending)");
+    const SubsetPlan p = subset_plan(ix->n, n_ids, nq, k, ix->subset_super_rows, 0);
+    if (p.route == kSubsetRefused) return fail(VF_EUNSUPPORTED, std::string(who) + ": " + p.why);
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t m = n_ids, lo = ix->id_offset, hi = ix->id_offset + ix->n;
+    VF_HIP(hipSetDevice(ix->device));
+    if (p.route == kSubsetEmpty) {
+        if (nq > 0 && k > 0) { VF_TRY(subset_fill_empty(nq, k, d_out_ids, d_out_scores, st)); VF_HIP(hipStreamSynchronize(st)); }
+        subset_stats(ix, nq, 0);
+        return VF_OK;
+    }
+    Lease ws;
+    VF_TRY(ws.acquire(ix->device, Lease::padded(8) + (p.route == kSubsetScan && nq > 0 && k > 0 ? subset_ws_bytes(p, ix->d, k) : 0)));
+    u64* d_flag = ws.take<u64>(1);
+    VF_HIP(hipMemsetAsync(d_flag, 0xFF, 8, st));
+    VF_HIP(launch_subset_check((const long long*)d_ids, m, lo, hi, d_flag, st));
+    const bool scan = p.route == kSubsetScan && nq > 0 && k > 0;
+    if (scan) VF_TRY(subset_scan(ix, p, ws, d_queries, nq, k, (const long long*)d_ids, m, d_flag, d_out_ids, d_out_scores, st));
+    u64 first_bad = 0;
+    VF_HIP(hipMemcpyAsync(&first_bad, d_flag, 8, hipMemcpyDeviceToHost, st));
+    VF_HIP(hipStreamSynchronize(st));   // the one wait of the call: the results are final and the check word is here
+    if (first_bad != ~0ull) {
+        int64_t v[2] = {0, 0};
+        const int64_t i = (int64_t)first_bad;
+        VF_HIP(hipMemcpy(v, d_ids + (i > 0 ? i - 1 : 0), (i > 0 ? 2 : 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+        return fail(VF_EINVAL, subset_bad_message(who, i, i > 0 ? v[1] : v[0], i > 0, v[0], lo, hi));
+    }
+    if (scan) { subset_stats(ix, nq, m); return VF_OK; }
+    if (nq == 0 || k == 0) return VF_OK;
+    return search_device_locked(ix, d_queries, nq, k, d_out_ids, d_out_scores, st);   // every row is listed: the ordinary search
 }
 
 extern "C" int vf_merge_topk_device(const int64_t* d_ids_parts, const float* d_score_parts, int32_t nparts, int32_t nq,

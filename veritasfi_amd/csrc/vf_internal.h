@@ -11,6 +11,7 @@
 
 #include "vf_ksplit_geom.h"   // + vf_scan_lds.h: the design constants, RowForm and every scan kernel's LDS budget
 #include "vf_compact.h"       // the plan of a removal's row compaction
+#include "vf_subset.h"        // the plan of a search over a chosen subset of rows
 
 namespace vf {
 
@@ -181,6 +182,22 @@ hipError_t launch_normalize_rows_gather(const void* rows, int dt, const long lon
                                         const float* norm, float* out, hipStream_t s);
 hipError_t launch_dense_dot16(const float* qn, int nq, const float* cn, long long nrows, int d,
                               float* out, long long out_stride, hipStream_t s);
+// k_scan_subset: canonical scores of the listed rows alone, read as the index holds them (VF_SEARCH_SUBSET; the plan: vf_subset.h)
+struct SubsetArgs {
+    const void* rows; const float* norm; long long n;   // the index: rows as held (rows_orig), canonical norms, row count
+    const long long* ids; long long id_base;             // the list (device; global ids, strictly ascending): row = ids[i] - id_base
+    long long pos0, count;                               // the positions [pos0, pos0 + count) of the list this launch scores
+    const float* qn; int nq, d;                          // canonical queries of the pass [nq][d] (k_prep_queries)
+    float* scores; long long rank_rows;                  // scores[subset_score_index(i, q, nq, rank_rows)], i = position - pos0: chunk-major
+};
+hipError_t launch_scan_subset(const SubsetArgs& a, int dt /* VF_DTYPE_* */, hipStream_t s);
+// ids[p][j] += base0 + p * rank_rows where >= 0: the parts of one ranking launch over `parts` chunks, [parts][per_part]
+hipError_t launch_subset_part_base(long long* ids, long long parts, long long per_part, long long base0, long long rank_rows, hipStream_t s);
+// the device form's list check: *first_bad (preset to ~0) = the lowest position that is out of [lo, hi) or not above its predecessor
+hipError_t launch_subset_check(const long long* ids, long long m, long long lo, long long hi, u64* first_bad, hipStream_t s);
+// ranked positions -> ids through the list (-1 stays), scores copied; nothing is written when *first_bad != ~0 (first_bad may be null)
+hipError_t launch_subset_ids(const long long* pos, const float* sc, long long total, const long long* ids, const u64* first_bad,
+                             long long* out_ids, float* out_scores, hipStream_t s);
 hipError_t launch_sort_rows(const float* scores, long long score_stride, int nq, int n, int k,
                             long long id_base, long long* out_ids, float* out_scores, int out_stride,
                             hipStream_t s);

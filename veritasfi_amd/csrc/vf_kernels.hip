@@ -4327,6 +4327,208 @@ tail:
     return (s4[0] + s4[2]) + (s4[1] + s4[3]);
 }
 
+// ------------------------------------------------------------------------------------------------
+// k_scan_subset: the exact scores of a chosen SUBSET of rows (VF_SEARCH_SUBSET; the plan: vf_subset.h).
+//   scores[subset_score_index(i, q)] = dot16(qn[q], cn(row(i))), row(i) = ids[pos0 + i] - id_base, cn[j] = load_elem(row, j) * canon_inv(norm[row])
+// -- bit for bit what k_normalize_rows_gather followed by k_dense_dot16 gives, without the fp32 copy of the rows in between: the rows
+// are read as the index holds them, once per tile of kSubsetQ queries, and normalised in registers.
+// It stands here and not beside k_dense_dot16 because it shares rescore_pair's row reading (RowVec / decode8 above): a row belongs to a
+// PAIR of lanes, lane half h owning the canonical partial sums 8h .. 8h + 7 (element j goes to sum j & 15, in ascending j), so a lane
+// reads 8 consecutive elements of every 16-element block with one vector load and the +8 step of the tree is one exchange inside the
+// pair; +4, +2, +1 are in-lane.  A pair holds kSubsetR rows x kSubsetQ queries x 8 sums in registers, so a query value read from LDS
+// feeds kSubsetR multiply-adds and a row value kSubsetQ.  The queries of the tile are staged in LDS in K-slices of kSubsetSlice
+// elements (16 KB whatever d is); slices are taken in ascending order, so the order inside every sum is the oracle's.
+// One wave per workgroup: 32 pairs x kSubsetR rows.  Every load is unconditional: a position past the launch's end is clamped to the
+// last one, a block index to the last whole block, an id to the index's rows (a list the device form has not yet seen refused must
+// not read outside the rows); the contribution is masked instead.
+// ------------------------------------------------------------------------------------------------
+template <int DT>
+__global__ __launch_bounds__(kSubsetThreads, 2) void k_scan_subset(SubsetArgs a) {   // two waves per SIMD: at most 256 registers (the e4m3 form took 258 without the bound)
+    constexpr int R = kSubsetR, Q = kSubsetQ;
+    constexpr int ESZ = DT == VF_DTYPE_F32 ? 4 : (DT == VF_DTYPE_F16 ? 2 : 1);
+    constexpr int kBlk = (DT == VF_DTYPE_F32 || DT == VF_DTYPE_FP8_E4M3) ? 2 : 4;   // 16-element blocks in flight per row and lane (e4m3: four spilled two registers)
+    typedef typename RowVec<DT>::type vec_t;
+    __shared__ __attribute__((aligned(16))) float qs[Q * kSubsetSlice];
+    const int lane = threadIdx.x, h = lane & 1, p = lane >> 1;
+    long long pos[R], row[R];
+    const char* base[R];
+    float inv[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        pos[r] = (long long)blockIdx.x * kSubsetRowsPerWg + r * (kSubsetThreads / 2) + p;
+        const long long c = pos[r] < a.count ? pos[r] : a.count - 1;
+        long long g = a.ids[a.pos0 + c] - a.id_base;
+        g = g < 0 ? 0 : (g < a.n ? g : a.n - 1);
+        row[r] = g;
+        base[r] = (const char*)a.rows + g * (long long)a.d * ESZ;
+        inv[r] = canon_inv(a.norm[g]);
+    }
+    const bool vec = ((((unsigned long long)(uintptr_t)a.rows) | ((unsigned long long)a.d * ESZ)) & 15) == 0;
+    for (int q0 = blockIdx.y * Q; q0 < a.nq; q0 += gridDim.y * Q) {   // (the launcher gives every query tile its own workgroups)
+        float acc[R][Q][8];
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+#pragma unroll
+            for (int qi = 0; qi < Q; ++qi)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) acc[r][qi][e] = 0.0f;
+        for (int k0 = 0; k0 < a.d; k0 += kSubsetSlice) {
+            const int len = a.d - k0 < kSubsetSlice ? a.d - k0 : kSubsetSlice;   // elements of this slice
+            const int len16 = (len + 15) & ~15;                                  // ... padded with zeros to whole blocks
+            __syncthreads();
+            for (int i = lane; i < Q * len16; i += kSubsetThreads) {
+                const int qi = i / len16, j = i - qi * len16;
+                qs[qi * kSubsetSlice + j] = (q0 + qi < a.nq && j < len) ? a.qn[(long long)(q0 + qi) * a.d + k0 + j] : 0.0f;
+            }
+            __syncthreads();
+            const int nfull = len >> 4;
+            // one 16-element block of the R rows (cn: the normalised values) against the Q queries of the tile
+            auto step = [&](const float (&cn)[R][8], int b, bool live, int valid) {
+#pragma unroll
+                for (int qi = 0; qi < Q; ++qi) {
+                    const float* qp = qs + qi * kSubsetSlice + b * 16 + 8 * h;
+                    const float4 q0v = *(const float4*)qp, q1v = *(const float4*)(qp + 4);
+                    const float qq[8] = {q0v.x, q0v.y, q0v.z, q0v.w, q1v.x, q1v.y, q1v.z, q1v.w};
+#pragma unroll
+                    for (int e = 0; e < 8; ++e)
+#pragma unroll
+                        for (int r = 0; r < R; ++r) {
+                            const float t = __builtin_fmaf(qq[e], cn[r][e], acc[r][qi][e]);
+                            acc[r][qi][e] = (live && e < valid) ? t : acc[r][qi][e];
+                        }
+                }
+            };
+            if (vec) {
+                for (int b0 = 0; b0 < nfull; b0 += kBlk) {
+                    vec_t v[R][kBlk];
+#pragma unroll
+                    for (int u = 0; u < kBlk; ++u) {
+                        const int b = b0 + u < nfull ? b0 + u : nfull - 1;
+#pragma unroll
+                        for (int r = 0; r < R; ++r) v[r][u] = *(const vec_t*)(base[r] + ((long long)k0 + b * 16 + 8 * h) * ESZ);
+                    }
+#pragma unroll
+                    for (int u = 0; u < kBlk; ++u) {
+                        const bool live = b0 + u < nfull;
+                        float cn[R][8];
+#pragma unroll
+                        for (int r = 0; r < R; ++r) {
+                            float x[8];
+                            decode8<DT>(v[r][u], x);
+#pragma unroll
+                            for (int e = 0; e < 8; ++e) cn[r][e] = x[e] * inv[r];
+                        }
+                        step(cn, live ? b0 + u : nfull - 1, live, 8);
+                    }
+                }
+            } else {   // rows that are not 16-byte aligned (odd d): element loads, same order
+                for (int b = 0; b < nfull; ++b) {
+                    float cn[R][8];
+#pragma unroll
+                    for (int r = 0; r < R; ++r)
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) cn[r][e] = load_elem(a.rows, DT, row[r] * (long long)a.d + k0 + b * 16 + 8 * h + e) * inv[r];
+                    step(cn, b, true, 8);
+                }
+            }
+            if (len & 15) {   // the tail block (the last slice alone has one): element j of it exists while j < len
+                const int j0 = nfull * 16 + 8 * h;
+                const int valid = len - j0 < 0 ? 0 : (len - j0 > 8 ? 8 : len - j0);
+                float cn[R][8];
+#pragma unroll
+                for (int r = 0; r < R; ++r)
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        const int j = e < valid ? j0 + e : 0;   // (a clamped, masked read)
+                        cn[r][e] = load_elem(a.rows, DT, row[r] * (long long)a.d + k0 + j) * inv[r];
+                    }
+                step(cn, nfull, true, valid);
+            }
+        }
+        // canonical tree: s8[l] = acc[l] + acc[l + 8] needs the partner half's sums; then 4, 2, 1 in-lane
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+#pragma unroll
+            for (int qi = 0; qi < Q; ++qi) {
+                float s8[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) s8[e] = acc[r][qi][e] + __shfl_xor(acc[r][qi][e], 1);
+                const float s4[4] = {s8[0] + s8[4], s8[1] + s8[5], s8[2] + s8[6], s8[3] + s8[7]};
+                const float s = (s4[0] + s4[2]) + (s4[1] + s4[3]);
+                if (h == 0 && pos[r] < a.count && q0 + qi < a.nq) a.scores[subset_score_index(pos[r], q0 + qi, a.nq, a.rank_rows)] = s;
+            }
+    }
+}
+
+hipError_t launch_scan_subset(const SubsetArgs& a, int dt, hipStream_t s) {
+    if (a.count <= 0 || a.nq <= 0) return hipSuccess;
+    if (a.n <= 0 || a.d <= 0) return hipErrorInvalidValue;
+    const long long blocks = (a.count + kSubsetRowsPerWg - 1) / kSubsetRowsPerWg;
+    if (blocks > 0x7FFFFFFFll) return hipErrorInvalidValue;
+    if (a.rank_rows <= 0) return hipErrorInvalidValue;
+    const int tiles = (a.nq + kSubsetQ - 1) / kSubsetQ;
+    const dim3 grid((unsigned)blocks, (unsigned)(tiles < 65535 ? tiles : 65535)), block(kSubsetThreads);
+    if (dt == VF_DTYPE_F16) hipLaunchKernelGGL(k_scan_subset<VF_DTYPE_F16>, grid, block, 0, s, a);
+    else if (dt == VF_DTYPE_FP8_E4M3) hipLaunchKernelGGL(k_scan_subset<VF_DTYPE_FP8_E4M3>, grid, block, 0, s, a);
+    else if (dt == VF_DTYPE_INT8) hipLaunchKernelGGL(k_scan_subset<VF_DTYPE_INT8>, grid, block, 0, s, a);
+    else if (dt == VF_DTYPE_F32) hipLaunchKernelGGL(k_scan_subset<VF_DTYPE_F32>, grid, block, 0, s, a);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+// the device form's list check: the lowest position the list may not hold (subset_bad_at), or ~0 when it is good (the caller's memset)
+__global__ __launch_bounds__(256) void k_subset_check(const long long* ids, long long m, long long lo, long long hi, u64* first_bad) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < m; i += (long long)gridDim.x * 256)
+        if (subset_bad_at(ids, i, lo, hi)) atomicMin(first_bad, (u64)i);
+}
+
+hipError_t launch_subset_check(const long long* ids, long long m, long long lo, long long hi, u64* first_bad, hipStream_t s) {
+    if (m <= 0) return hipSuccess;
+    long long blocks = (m + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(k_subset_check, dim3((unsigned)blocks), dim3(256), 0, s, ids, m, lo, hi, first_bad);
+    return hipGetLastError();
+}
+
+// one launch_sort_rows ranked `parts` chunks at once, so each part holds positions inside its own chunk: part p of [parts][per_part]
+// gets base0 + p * rank_rows added (padding stays -1)
+__global__ __launch_bounds__(256) void k_subset_part_base(long long* ids, long long parts, long long per_part, long long base0, long long rank_rows) {
+    const long long total = parts * per_part;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const long long v = ids[i];
+        if (v >= 0) ids[i] = v + base0 + (i / per_part) * rank_rows;
+    }
+}
+
+hipError_t launch_subset_part_base(long long* ids, long long parts, long long per_part, long long base0, long long rank_rows, hipStream_t s) {
+    if (parts <= 0 || per_part <= 0) return hipSuccess;
+    long long blocks = (parts * per_part + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(k_subset_part_base, dim3((unsigned)blocks), dim3(256), 0, s, ids, parts, per_part, base0, rank_rows);
+    return hipGetLastError();
+}
+
+// positions -> ids through the list, after the last merge: out_ids[i] = ids[pos[i]] (-1 stays), scores copied.  With a list the
+// device form found bad (*first_bad != ~0) nothing is written: the caller's buffers stay as they were.
+__global__ __launch_bounds__(256) void k_subset_ids(const long long* pos, const float* sc, long long total, const long long* ids,
+                                                      const u64* first_bad, long long* out_ids, float* out_scores) {
+    if (first_bad && *first_bad != ~0ull) return;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const long long p = pos[i];
+        out_ids[i] = p < 0 ? -1 : ids[p];
+        out_scores[i] = sc[i];
+    }
+}
+
+hipError_t launch_subset_ids(const long long* pos, const float* sc, long long total, const long long* ids, const u64* first_bad,
+                             long long* out_ids, float* out_scores, hipStream_t s) {
+    if (total <= 0) return hipSuccess;
+    long long blocks = (total + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(k_subset_ids, dim3((unsigned)blocks), dim3(256), 0, s, pos, sc, total, ids, first_bad, out_ids, out_scores);
+    return hipGetLastError();
+}
+
 __global__ __launch_bounds__(kFinalThreads) void k_final(FinalArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     u64* top = (u64*)smem_raw;                // [top_cap] ranked approx keys, then ranked canonical keys

@@ -130,6 +130,7 @@ class EnsembleRetriever:
     # -- a live corpus --------------------------------------------------------------------------------
     def _build_maps(self) -> None:
         self.docid2idx, self._bundle_rows, self._title_rows = {}, {}, {}
+        self._field_rows = {}   # rows_where's per-field dictionaries: built on first use, dropped whenever the corpus changes
         for row, md in enumerate(self.chunk_metadata):
             self.docid2idx[md["doc_id"]] = row
             b = md.get("bundle_id", None)
@@ -206,6 +207,7 @@ class EnsembleRetriever:
                 raise
         self.chunk_metadata = list(self.chunk_metadata) + metadatas
         self.num_chunk = len(self.chunk_metadata)
+        self._field_rows = {}
         if self._documents is not None:
             self._documents = list(self._documents) + texts
         for row, md in enumerate(metadatas, start=first):
@@ -251,13 +253,39 @@ class EnsembleRetriever:
         self._text_rows = _TextRows()
         return len(rows)
 
+    # -- metadata filters -----------------------------------------------------------------------------
+    def rows_where(self, where) -> np.ndarray:
+        """Sorted row numbers (int64) of the chunks whose metadata passes ``where``: a dict ``field -> value``, or ``field -> a
+        collection of values`` (list, tuple, set, frozenset: any of them passes); several fields must all pass.  A chunk without the
+        field passes only a filter that lists ``None``.  Served from one dictionary ``value -> rows`` per field, built on the first
+        use of that field and dropped by ``add_documents`` / ``remove_documents``."""
+        if not isinstance(where, dict):
+            raise TypeError("rows_where: `where` is a dict field -> value, or field -> a collection of values")
+        rows = None
+        for field, want in where.items():
+            index = self._field_rows.get(field)
+            if index is None:
+                index = {}
+                for row, md in enumerate(self.chunk_metadata):
+                    try:
+                        index.setdefault(md.get(field, None), []).append(row)
+                    except TypeError:      # an unhashable metadata value (a list): no filter value can equal it
+                        pass
+                self._field_rows[field] = index
+            values = list(want) if isinstance(want, (list, tuple, set, frozenset)) else [want]
+            hit = sorted({r for v in values for r in index.get(v, ())})
+            hit = np.asarray(hit, dtype=np.int64)
+            rows = hit if rows is None else np.intersect1d(rows, hit, assume_unique=True)
+        return np.arange(self.num_chunk, dtype=np.int64) if rows is None else rows
+
     # -- pieces -------------------------------------------------------------------------------------
-    def _bundle_of(self, row: int, seen: set) -> List[int]:
-        """Rows emitted for a hit: the whole bundle when the chunk has one (all marked seen), else the row."""
+    def _bundle_of(self, row: int, seen: set, allow=None) -> List[int]:
+        """Rows emitted for a hit: the whole bundle when the chunk has one (all marked seen), else the row.  allow: the rows a filter
+        lets through (a set), or None."""
         b = self.chunk_metadata[row].get("bundle_id", None)
         if b is None:
             return [row]
-        rows = list(self._bundle_rows[b])
+        rows = [r for r in self._bundle_rows[b] if allow is None or r in allow]
         seen.update(rows)
         return rows
 
@@ -275,17 +303,21 @@ class EnsembleRetriever:
             out.append({"retriever": name, "score": float(score), "page_content": text, "metadata": md,
                         "bundle_id": bundle_cnt})
 
-    def _expand(self, rows: List[int], hit_md: dict, score_map: dict, seen: set) -> None:
+    def _expand(self, rows: List[int], hit_md: dict, score_map: dict, seen: set, allow=None) -> None:
         prev_doc, next_doc = hit_md["prev_chunk_id"], hit_md["next_chunk_id"]
         while len(rows) < MAX_EXPANDED:
             grew = False
             p = self.docid2idx.get(prev_doc, -1) if prev_doc != "" else -1
+            if allow is not None and p not in allow:     # a store of the passing chunks alone would not know this neighbour
+                p = -1
             if p != -1 and score_map.get(p, 0) > NEIGHBOUR_SCORE and p not in seen:
                 grew = True
                 seen.add(p)
                 rows.insert(0, p)
                 prev_doc = self.chunk_metadata[p]["prev_chunk_id"]
             n = self.docid2idx.get(next_doc, -1) if next_doc != "" else -1
+            if allow is not None and n not in allow:
+                n = -1
             if n != -1 and score_map.get(n, 0) > NEIGHBOUR_SCORE and n not in seen:
                 grew = True
                 seen.add(n)
@@ -295,35 +327,48 @@ class EnsembleRetriever:
                 break
 
     # -- the reference's entry point ------------------------------------------------------------------
-    def invoke(self, input: str, hyde_chunks: List[str]) -> List[Dict]:
+    def invoke(self, input: str, hyde_chunks: List[str], where=None) -> List[Dict]:
         """Stage brackets as upstream (``"retrieve"`` around the call, one per branch, the ``retrieved_chunks`` metric): no-ops
-        unless ``veritasfi_amd.set_profiler`` was given the host's profiler (stages.py)."""
+        unless ``veritasfi_amd.set_profiler`` was given the host's profiler (stages.py).
+        where (``rows_where``'s argument; None = no filter, today's call): only chunks whose metadata passes are returned.  The rule:
+        the result is what ``invoke`` would return over a store that held the passing chunks alone -- the dense leg searches those
+        rows only (``FaissRetriever.invoke(subset=...)``: the retriever must take ``subset``), bundles and the neighbour expansion see
+        passing rows only, the title-summary leg's rows are filtered here.  ONE stated exception, the BM25 leg: it keeps the
+        whole corpus's statistics (idf, average length), as upstream's own sketch does (bm25Retriever.py:91-132) -- it is asked for
+        the full ranking, filtered here, and the first ``bm25_k`` survivors are used.  A filter nothing passes returns []."""
         with stages.stage("retrieve"):
-            out = self._invoke(input, hyde_chunks)
+            out = self._invoke(input, hyde_chunks, where)
         stages.metric("retrieved_chunks", len(out))
         return out
 
-    def _invoke(self, input: str, hyde_chunks: List[str]) -> List[Dict]:
+    def _invoke(self, input: str, hyde_chunks: List[str], where=None) -> List[Dict]:
         seen: set = set()
         out: list = []
         bundle_cnt = 0
+        passing = None if where is None else self.rows_where(where)
+        allow = None if passing is None else set(passing.tolist())
+        if passing is not None and passing.size == 0:
+            return out
         if self.faiss_k > 0:
             with stages.stage("retrieve_faiss"):
-                bundle_cnt = self._faiss_branch(input, hyde_chunks, seen, out, bundle_cnt)
+                bundle_cnt = self._faiss_branch(input, hyde_chunks, seen, out, bundle_cnt, passing, allow)
         if self.faiss_ts_k > 0:
             with stages.stage("retrieve_faiss_ts"):
-                bundle_cnt = self._title_branch(input, seen, out, bundle_cnt)
+                bundle_cnt = self._title_branch(input, seen, out, bundle_cnt, allow)
         if self.bm25_k > 0:
             with stages.stage("retrieve_bm25"):
-                bundle_cnt = self._bm25_branch(input, seen, out, bundle_cnt)
+                bundle_cnt = self._bm25_branch(input, seen, out, bundle_cnt, allow)
         return out
 
-    def _faiss_branch(self, input, hyde_chunks, seen, out, bundle_cnt):
+    def _faiss_branch(self, input, hyde_chunks, seen, out, bundle_cnt, passing=None, allow=None):
         inputs = [input] + list(hyde_chunks)
         # upstream always searches 2048 deep (:64-66) and reads the tail only as the neighbour expansion's score map (:85-107): without
         # enable_expand the first faiss_k entries are all that is looked at, and an exact search's top-k is a prefix of its top-2048
         depth = SEARCH_DEPTH if self.enable_expand else min(SEARCH_DEPTH, max(1, int(self.faiss_k)))
-        ids_list, scores_list = self.faiss_retriever.invoke(inputs, depth)
+        if passing is None:
+            ids_list, scores_list = self.faiss_retriever.invoke(inputs, depth)
+        else:   # rows are ids here (the retriever's index starts at 0, as upstream's does)
+            ids_list, scores_list = self.faiss_retriever.invoke(inputs, depth, subset=passing)
         for ids, scores in zip(ids_list, scores_list):
             ids = [int(i) for i in ids]
             score_map = dict(zip(ids, scores))
@@ -332,27 +377,38 @@ class EnsembleRetriever:
                     continue
                 seen.add(row)
                 md = self.chunk_metadata[row]
-                rows = self._bundle_of(row, seen)
+                rows = self._bundle_of(row, seen, allow)
                 if score > EXPAND_SCORE and self.enable_expand:
-                    self._expand(rows, md, score_map, seen)
+                    self._expand(rows, md, score_map, seen, allow)
                 self._emit(out, "FAISS", score, rows, bundle_cnt)
                 bundle_cnt += 1
         return bundle_cnt
 
-    def _title_branch(self, input, seen, out, bundle_cnt):
+    def _title_branch(self, input, seen, out, bundle_cnt, allow=None):
         t_ids, t_scores = self.title_summary_faiss_retriever.invoke([input], self.faiss_ts_k)
         for t, score in zip(t_ids[0], t_scores[0]):
             if t < 0:
                 continue
             for row in self._title_rows.get(self.title_summaries[int(t)], ()):
-                if row in seen:
+                if row in seen or (allow is not None and row not in allow):
                     continue
                 seen.add(row)
-                self._emit(out, "Title Summary", score, self._bundle_of(row, seen), bundle_cnt)
+                self._emit(out, "Title Summary", score, self._bundle_of(row, seen, allow), bundle_cnt)
                 bundle_cnt += 1
         return bundle_cnt
 
-    def _bm25_branch(self, input, seen, out, bundle_cnt):
+    def _bm25_branch(self, input, seen, out, bundle_cnt, allow=None):
+        if allow is not None:
+            # filtered: the full ranking (whole-corpus statistics: the stated exception), the first bm25_k rows that pass
+            b_ids, b_scores = self.bm25_retriever.invoke(input, self.num_chunk)
+            kept = [(int(r), s) for r, s in zip(b_ids, b_scores) if int(r) in allow][:self.bm25_k]
+            for row, score in kept:
+                if row in seen:
+                    continue
+                seen.add(row)
+                self._emit(out, "BM25", score, self._bundle_of(row, seen, allow), bundle_cnt)
+                bundle_cnt += 1
+            return bundle_cnt
         # upstream ranks every chunk (:188) and reads the first bm25_k; a retriever whose ranking is a total order
         # (exact_prefix, e.g. veritasfi_amd.BM25Retriever) returns exactly that prefix when asked for bm25_k rows -- min_score
         # included, since it keeps a prefix of a descending ranking.  Others keep the upstream call.

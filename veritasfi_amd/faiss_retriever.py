@@ -116,13 +116,18 @@ class FaissRetriever:
             raise ValueError("this retriever wraps an index it did not build: pass corpus_dtype to from_index to remove from it")
         return int(self.index.remove(np.asarray(ids, dtype=np.int64).ravel()))
 
-    def invoke(self, querys: list, k: int):
+    def invoke(self, querys: list, k: int, subset=None):
         """(I, D) = ids and cosine scores, best first, shape [len(querys), k]; -1 / -FLT_MAX pad a corpus with fewer than k rows
         (reference :28-38: embed each string, fp32, L2-normalise, IndexFlatIP.search).  An embedder with a batched
-        ``embed_queries`` -- ours has one -- gets ONE forward for all strings; any other is called per string, as upstream does."""
+        ``embed_queries`` -- ours has one -- gets ONE forward for all strings; any other is called per string, as upstream does.
+        subset: search these rows only (ids, a boolean mask or a ``RowSubset``: ``DenseIndex.search``) -- the metadata filtering the
+        reference class announces and does not have."""
         texts = list(querys)
         embed_many = getattr(self.embeddings, "embed_queries", None)
         vectors = embed_many(texts) if embed_many is not None else [self.embeddings.embed_query(t) for t in texts]
         q = np.asarray(vectors, dtype=np.float32).reshape(len(texts), -1)
-        ids, scores = self.index.search(q, k)      # normalisation happens on the device (k_prep_queries), canonical order
+        if subset is None:
+            ids, scores = self.index.search(q, k)      # normalisation happens on the device (k_prep_queries), canonical order
+        else:
+            ids, scores = self.index.search(q, k, subset=subset)
         return ids, scores

@@ -33,6 +33,49 @@ def quantize_int8(x) -> np.ndarray:
     return np.clip(np.rint(x / sc), -127.0, 127.0).astype(np.int8)
 
 
+def subset_ids(subset, n: int, id_offset: int = 0) -> np.ndarray:
+    """What ``DenseIndex.search(subset=...)`` hands to the library: a contiguous int64 array of global ids, strictly ascending.
+    ``subset`` is an int64 array-like of ids (any order, repeats count once) or a boolean mask of length ``n`` (True = row
+    ``id_offset + i`` is searched).  The ascending check runs first and costs one pass; only a list that fails it is sorted and made
+    distinct.  Ids outside ``[id_offset, id_offset + n)`` raise ValueError naming the first offender's position in the caller's list."""
+    a = np.asarray(subset)
+    if a.dtype == np.bool_:
+        if a.ndim != 1 or a.shape[0] != n:
+            raise ValueError(f"subset: a boolean mask must have one entry per row ({n}), got shape {a.shape}")
+        return np.flatnonzero(a).astype(np.int64) + np.int64(id_offset)
+    if a.size == 0:
+        return np.empty(0, dtype=np.int64)
+    if a.dtype.kind not in "iu":
+        raise TypeError(f"subset: ids must be integers or a boolean mask, got {a.dtype}")
+    if a.ndim != 1:
+        raise ValueError(f"subset: ids must be one-dimensional, got shape {a.shape}")
+    if a.dtype == np.uint64 and a.max() > np.uint64(np.iinfo(np.int64).max):
+        raise ValueError("subset: an id does not fit int64")
+    ids = np.ascontiguousarray(a, dtype=np.int64)
+    lo, hi = int(id_offset), int(id_offset) + int(n)
+    bad = np.flatnonzero((ids < lo) | (ids >= hi))
+    if bad.size:
+        raise ValueError(f"subset: ids[{int(bad[0])}] = {int(ids[bad[0]])} is outside the index's ids [{lo}, {hi})")
+    if ids.size > 1 and not bool((ids[1:] > ids[:-1]).all()):
+        ids = np.unique(ids)   # sorted, distinct
+    return ids
+
+
+class RowSubset:
+    """A list of row ids kept ON THE DEVICE for repeated subset searches (``DenseIndex.row_subset``): a tenant's filter is uploaded
+    once, not 8 bytes per row per query.  It holds ids, not rows: after ``DenseIndex.remove`` (ids shift) make a new one -- the
+    library's range check catches a stale one only when it reaches past the new end of the index."""
+
+    def __init__(self, ids: np.ndarray, device_id: int):
+        import torch
+        self.ids = ids                       # host copy (int64, strictly ascending)
+        self.device_id = int(device_id)
+        self.tensor = torch.from_numpy(ids).to(f"cuda:{self.device_id}")
+
+    def __len__(self) -> int:
+        return int(self.ids.size)
+
+
 def _dev_array(device_ids):
     ids = [int(x) for x in device_ids]
     if not ids:
@@ -296,18 +339,50 @@ class DenseIndex:
             self._keepalive = None
 
     # -- host buffers ------------------------------------------------------------------------------
-    def search(self, queries, k: int):
+    def search(self, queries, k: int, subset=None):
         """queries [nq, d] -> (ids int64 [nq, k], scores float32 [nq, k]); ids first, as
-        FaissRetriever.invoke returns them (faissRetriever.py:38)."""
+        FaissRetriever.invoke returns them (faissRetriever.py:38).
+        subset: search these rows only -- an int64 array-like of ids, a boolean mask of length n, or a ``RowSubset``.  The result is
+        what an index over those rows alone would return, ids mapped back (``vf_index_search`` with ``VF_SEARCH_SUBSET``: only the listed rows are
+        read).  An unsorted or repeating list is sorted and made distinct on the host first (``subset_ids``); fewer than k rows pad
+        with -1 / -FLT_MAX; an empty subset returns all padding."""
         q = np.ascontiguousarray(np.asarray(queries, dtype=np.float32))
         if q.ndim != 2 or q.shape[1] != self.d:
             raise ValueError(f"queries must be [nq, {self.d}], got {q.shape}")
         k = int(k)
         ids = np.empty((q.shape[0], k), dtype=np.int64)
         scores = np.empty((q.shape[0], k), dtype=np.float32)
+        if isinstance(subset, RowSubset):
+            return self._search_row_subset(q, k, subset)
+        if subset is not None:
+            sel = subset_ids(subset, self.n, self.id_offset)
+            _ffi.check(_ffi.search_subset(_ffi.lib(), self._h, q.ctypes.data, q.shape[0], k, sel.ctypes.data, int(sel.size),
+                                          ids.ctypes.data, scores.ctypes.data), "vf_index_search (subset)")
+            return ids, scores
         _ffi.check(_ffi.lib().vf_index_search(self._h, q.ctypes.data, q.shape[0], k, ids.ctypes.data,
                                               scores.ctypes.data), "vf_index_search")
         return ids, scores
+
+    def row_subset(self, ids_or_mask) -> RowSubset:
+        """The ids of ``ids_or_mask`` (as ``search(subset=...)`` takes them), sorted, made distinct and kept on the index's device for
+        ``search(..., subset=row_subset)``: the device entry point reads them where they are.  Single-device handles (a group
+        takes lists: its shards split them on the host)."""
+        if self.device_ids is not None:
+            raise ValueError("row_subset: a sharded handle takes id lists (search(subset=ids)), not a device-resident subset")
+        return RowSubset(subset_ids(ids_or_mask, self.n, self.id_offset), self.device_id)
+
+    def _search_row_subset(self, q: np.ndarray, k: int, rs: RowSubset):
+        import torch
+        if self.device_ids is not None or rs.device_id != self.device_id:
+            raise ValueError("search: the RowSubset lives on another device than the index (or the handle is sharded)")
+        dev = torch.device(f"cuda:{self.device_id}")
+        dq = torch.from_numpy(q).to(dev)
+        out_ids = torch.empty((q.shape[0], k), dtype=torch.int64, device=dev)
+        out_scores = torch.empty((q.shape[0], k), dtype=torch.float32, device=dev)
+        _ffi.check(_ffi.search_subset_device(_ffi.lib(), self._h, dq.data_ptr(), q.shape[0], k, rs.tensor.data_ptr(), len(rs),
+                                             out_ids.data_ptr(), out_scores.data_ptr(),
+                                             torch.cuda.current_stream(dev).cuda_stream), "vf_index_search_device (subset)")
+        return out_ids.cpu().numpy(), out_scores.cpu().numpy()
 
     # -- device buffers (torch CUDA tensors) ---------------------------------------------------------
     def _dev_args(self, queries, k, out_ids, out_scores):
