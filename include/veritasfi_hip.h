@@ -215,8 +215,8 @@ int vf_index_search_end(vf_index* idx, int32_t slot);
  * Group handles take the host form only (the device form is VF_EUNSUPPORTED): the list is split at the shards' id ranges on the host,
  * the shards are searched one after another -- NOT overlapped -- and the parts are merged on the home device; shards * k > 16384 is
  * VF_EUNSUPPORTED as for every group search.
- * Not in scope: a pipelined _begin / _end form, overlapped shards, a row filter inside the BM25 kernels (the ensemble filters that
- * leg on the host), MixedModalIndex.
+ * Not in scope: a pipelined _begin / _end form, overlapped shards, MixedModalIndex.  (The BM25 leg has its own row filter, inside its
+ * kernels: VF_BM25_FILTER below.)
  * The call (no new entry point: like appends and removals it rides on calls that exist, so the exported surface stays as it is):
  *   vf_subset_query sq = {queries, ids, n_ids};
  *   vf_index_search(idx, (const float*)&sq, nq | VF_SEARCH_SUBSET, k, out_ids, out_scores);                        host buffers
@@ -530,6 +530,29 @@ typedef struct vf_bm25_delta {
  * -> out_ids [nq, k] rows, out_scores [nq, k] (host) */
 int vf_bm25_search(vf_bm25* h, const int64_t* q_offsets, const int32_t* q_terms, int32_t nq, int32_t k, int64_t* out_ids,
                    float* out_scores);
+
+/* ---- a BM25 search restricted to a chosen set of rows (no new entry point: the filter rides on the search) -----------------------
+ * The call: vf_bm25_filter_query fq = {q_offsets, allow, n_docs};
+ *           vf_bm25_search(h, (const int64_t*)&fq, q_terms, nq | VF_BM25_FILTER, k, out_ids, out_scores);
+ * `allow` is a bitmap of the rows that may be returned, ONE for all nq queries of the call.  Scores keep the whole corpus's
+ * statistics (the postings' scores are what they are): the result is the first k entries of the unfiltered canonical ranking --
+ * score descending, ties to the lower row, then the untouched rows at score 0 in ascending row order -- after the rows outside the
+ * set are struck out.  Ids are the original rows and score bits those of the unfiltered call.  With m rows allowed and k > m the
+ * ranks m .. k - 1 are padding, (-1, -FLT_MAX), as in the dense leg's subset search; k itself stays in [1, n_docs].
+ * Checked under the handle's lock before any device work, VF_EINVAL each: a null `allow`; n_docs that is not the handle's document
+ * count (a live handle may have changed since the bitmap was made); a bit set at or past n_docs (the message names the first such
+ * row).  m == 0 returns all padding without a launch.  A refused call changes nothing.
+ * The filter acts at the scatter: a posting whose row is outside the set is neither added nor marked, so the select and the sort see
+ * allowed rows only, and the zero-score tail takes allowed untouched rows from every block of the bitmap.  The bitmap, n_docs / 8
+ * bytes, is uploaded with every filtered call (no filter is kept on the device between calls); the handle allocates its device copy
+ * and 4 B per 32 768 rows and query slot of tail scratch on the first filtered call.  Without the flag nothing about the call changes.
+ * Not in scope: a filter per query, a filter that stays on the device across calls, statistics (idf, average length) over the set. */
+#define VF_BM25_FILTER 0x40000000      /* or'ed into `nq` of vf_bm25_search: `q_offsets` is a vf_bm25_filter_query */
+typedef struct vf_bm25_filter_query {
+    const int64_t*  q_offsets;   /* what q_offsets was */
+    const uint32_t* allow;       /* host, (n_docs + 31) / 32 words: bit (r & 31) of word r >> 5 set = row r may be returned */
+    int64_t         n_docs;      /* the document count the bitmap was made for */
+} vf_bm25_filter_query;
 
 #ifdef __cplusplus
 }

@@ -39,6 +39,15 @@ class Bm25Delta(ctypes.Structure):
     ]
 
 
+VF_BM25_FILTER = 0x40000000   # or'ed into nq of vf_bm25_search: `q_offsets` is then a Bm25FilterQuery
+
+
+class Bm25FilterQuery(ctypes.Structure):
+    """vf_bm25_filter_query of include/veritasfi_hip.h (host memory): the query offsets, the bitmap of the rows that may be returned
+    (uint32 words, bit r & 31 of word r >> 5) and the document count the bitmap was made for."""
+    _fields_ = [("q_offsets", ctypes.POINTER(c_i64)), ("allow", ctypes.POINTER(ctypes.c_uint32)), ("n_docs", c_i64)]
+
+
 class SubsetQuery(ctypes.Structure):
     """vf_subset_query of include/veritasfi_hip.h: what `queries` points to when nq carries VF_SEARCH_SUBSET (host memory; in the
     device form the two pointers inside are device pointers)."""

@@ -36,6 +36,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _ffi
+from .index import RowSubset, subset_ids
 
 _TOKEN = re.compile(r"(?u)\b\w\w+\b")
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -221,6 +222,29 @@ def load_bm25_index(dir_path: str, load_corpus: bool = True) -> BM25Index:
     return BM25Index(params, vocab, indptr, indices, data, num_docs, corpus, tf)
 
 
+def filter_words(subset, n: int):
+    """(words, m): the bitmap ``vf_bm25_search`` takes with VF_BM25_FILTER -- uint32 [(n + 31) // 32], bit ``r & 31`` of word
+    ``r >> 5`` set = row r may be returned -- and the number of rows it allows.  ``subset`` is what the dense leg's
+    ``search(subset=...)`` takes: an integer array-like of ids (any order, repeats count once; an id outside [0, n) is a ValueError
+    naming it), a boolean mask of length ``n``, or a ``RowSubset`` (its host ids are read).  Packed by numpy, no loop over rows."""
+    n = int(n)
+    if isinstance(subset, RowSubset) or hasattr(subset, "tensor"):
+        ids = getattr(subset, "ids", None)
+        if ids is None:
+            raise TypeError("subset: this RowSubset does not expose its host ids (.ids); pass the ids or a boolean mask instead")
+        subset = ids
+    a = np.asarray(subset)
+    mask = np.zeros((n + 31) // 32 * 32, dtype=np.bool_)
+    if a.dtype == np.bool_:
+        if a.ndim != 1 or a.shape[0] != n:
+            raise ValueError(f"subset: a boolean mask must have one entry per row ({n}), got shape {a.shape}")
+        mask[:n] = a
+    else:
+        mask[subset_ids(a, n)] = True
+    words = np.ascontiguousarray(np.packbits(mask, bitorder="little").view(np.dtype("<u4")), dtype=np.uint32)
+    return words, int(np.count_nonzero(mask))
+
+
 # ---- the retriever ---------------------------------------------------------------------------------------------------------
 class BM25Retriever:
     """The reference's constructor and ``invoke(query, k) -> (ids, scores)``; scoring and ranking run on the GPU.
@@ -231,6 +255,12 @@ class BM25Retriever:
     ``exact_prefix`` tells ``EnsembleRetriever`` it may ask for ``bm25_k`` rows instead of all of them.  A handle may be
     shared across threads (the device handle serialises its calls).
 
+    ``subset=`` (``invoke``, ``invoke_batch``, ``search_columns``): only these rows may be returned -- ids, a boolean mask or a
+    ``RowSubset``, as the dense leg takes them.  Scores keep the WHOLE corpus's statistics: the result is the unfiltered ranking with
+    the other rows struck out, cut to k, filtered inside the device's kernels (``vf_bm25_search`` with VF_BM25_FILTER; the bitmap,
+    n / 8 bytes, goes up with every call).  ``filtered_prefix`` tells ``EnsembleRetriever`` it may ask a filtered request for
+    ``bm25_k`` rows with ``subset=`` instead of ranking every row and filtering on the host.
+
     ``live=True``: documents can be added and removed without a rebuild (``add_texts``, ``add_token_ids``, ``remove``, ``update``,
     ``save``).  Ids stay the positions: removed rows leave and later rows move down, new documents get the ids n .. n + m - 1, a
     token the vocabulary lacks gets a new column at the end, columns never disappear.  After every update the device holds, bit
@@ -240,6 +270,7 @@ class BM25Retriever:
     the device holds the postings twice."""
 
     exact_prefix = True
+    filtered_prefix = True
 
     def __init__(self, dir_path: str, load_corpus: bool = True, min_score: Optional[float] = None, stemmer="english",
                  device_id: int = 0, stopwords=None, live: bool = False, live_chunk: int = 0):
@@ -436,8 +467,9 @@ class BM25Retriever:
         v = self.vocab
         return np.asarray([v[w] for w in tokenize(query, self._stem, self._stopwords) if w in v], dtype=np.int32)
 
-    def search_columns(self, columns: Sequence[np.ndarray], k: int):
-        """Token-column lists -> (ids int64 [nq, k], scores float32 [nq, k]) in one device call."""
+    def search_columns(self, columns: Sequence[np.ndarray], k: int, subset=None):
+        """Token-column lists -> (ids int64 [nq, k], scores float32 [nq, k]) in one device call.  subset (``filter_words``' argument):
+        one set of rows for all the queries; with m rows allowed and k > m the ranks m .. k - 1 are padding, id -1 and score -FLT_MAX."""
         cols = [np.asarray(c, dtype=np.int32).ravel() for c in columns]
         nq, k = len(cols), int(k)
         offsets = np.zeros(nq + 1, dtype=np.int64)
@@ -452,27 +484,37 @@ class BM25Retriever:
                 return ids, scores
             if not self._h.value:
                 raise RuntimeError("BM25Retriever is closed")
-            _ffi.check(_ffi.lib().vf_bm25_search(self._h, offsets.ctypes.data_as(_ffi.p_i64), terms.ctypes.data_as(_ffi.p_i32),
+            q_arg = offsets.ctypes.data_as(_ffi.p_i64)
+            if subset is not None:   # packed under the lock: the mask's length is held to the count the device has now
+                words, _ = filter_words(subset, self.num_docs)
+                fq = _ffi.Bm25FilterQuery(q_arg, words.ctypes.data_as(_ffi.ctypes.POINTER(_ffi.ctypes.c_uint32)), self.num_docs)
+                q_arg, nq = _ffi.ctypes.cast(_ffi.ctypes.byref(fq), _ffi.p_i64), nq | _ffi.VF_BM25_FILTER
+            _ffi.check(_ffi.lib().vf_bm25_search(self._h, q_arg, terms.ctypes.data_as(_ffi.p_i32),
                                                  nq, k, ids.ctypes.data_as(_ffi.p_i64), scores.ctypes.data_as(_ffi.p_f32)),
                        "vf_bm25_search")
         return ids, scores
 
     def _result(self, ids_row: np.ndarray, scores_row: np.ndarray):
+        if ids_row.size and ids_row[-1] < 0:   # a filter of fewer than k rows: the padding is a suffix, and is not returned
+            keep = int(np.count_nonzero(ids_row >= 0))
+            ids_row, scores_row = ids_row[:keep], scores_row[:keep]
         ids = [int(i) for i in ids_row]
         if self.min_score is not None:
             ids = [i for i, s in zip(ids, scores_row) if s >= self.min_score]
         return ids, scores_row
 
-    def invoke(self, query: str, k: int, metadata_filters=None):
-        """(ids, scores) of the k best rows (bm25Retriever.py:50-87)."""
+    def invoke(self, query: str, k: int, metadata_filters=None, subset=None):
+        """(ids, scores) of the k best rows (bm25Retriever.py:50-87); with ``subset`` the k best of those rows, min(k, rows allowed)
+        of them.  The retriever holds no metadata: ``metadata_filters`` raises as upstream, ``EnsembleRetriever.rows_where`` turns
+        a metadata filter into the rows ``subset`` takes."""
         if metadata_filters:
             raise NotImplementedError("Metadata filtering is not supported yet.")   # as upstream (:69-72)
-        ids, scores = self.search_columns([self.query_columns(query)], k)
+        ids, scores = self.search_columns([self.query_columns(query)], k, subset=subset)
         return self._result(ids[0], scores[0])
 
-    def invoke_batch(self, queries: Sequence[str], k: int):
-        """[(ids, scores)] per query, all in one device call."""
-        ids, scores = self.search_columns([self.query_columns(q) for q in queries], k)
+    def invoke_batch(self, queries: Sequence[str], k: int, subset=None):
+        """[(ids, scores)] per query, all in one device call; ``subset``: one set of rows for all of them."""
+        ids, scores = self.search_columns([self.query_columns(q) for q in queries], k, subset=subset)
         return [self._result(ids[i], scores[i]) for i in range(len(ids))]
 
     def info(self) -> dict:

@@ -17,10 +17,13 @@
 //   k_bitonic_*        k > 4096 (the reference's k = num_chunk call): bitonic sort of the selected keys in global memory
 //   k_bm25_tail_*      the zero-score tail: untouched rows in ascending order (prefix sum over the bitmap's zero bits)
 //   k_bm25_reset       clear what the query touched: its postings' score entries and bitmap words (O(postings), not O(N))
+//   k_bm25_*_f, k_bm25_pad_out   a search restricted to a set of rows (VF_BM25_FILTER; the word arithmetic is vf_bm25_filter.h): the scatter
+//                      skips rows outside the set, the tail takes allowed rows only from every bitmap block, ranks past the set are padded
 //   k_bm25_live_*      a live handle's update: documents leave and arrive, every posting is re-scored into a second set of
 //                      arrays (described where they stand; the index arithmetic is vf_bm25_live.h)
 #include "vf_internal.h"
 #include "vf_bm25_live.h"
+#include "vf_bm25_filter.h"
 
 #include <float.h>
 #include <algorithm>
@@ -38,6 +41,7 @@ constexpr int kBmSmallK = 4096;                                     // k up to t
 constexpr int kBmMaxSlots = 64;                                     // queries in flight per group
 constexpr long long kBmScratchBudget = 3ll << 30;                   // bytes of per-query scratch a handle may hold
 constexpr int kBmSortChunk = 4096;                                  // keys per LDS chunk of the global bitonic sort
+static_assert(kBmWordsPerBlock == kBm25FilterBlockWords, "vf_bm25_filter.h plans the tail over blocks of kBmWordsPerBlock words");
 
 struct BmState {          // per slot, rewritten by pass 0 of every query
     u64 prefix;           // selected keys are those >= prefix
@@ -67,7 +71,9 @@ __device__ __forceinline__ u64 bm_key(const float* sc, u32 row) {
     return ((u64)orderkey(sc[row]) << 32) | (u64)(0xFFFFFFFFu - row);
 }
 
-__global__ __launch_bounds__(kBmThreads) void k_bm25_accum(BmArgs a, int t) {
+// kFilt: `allow` is the filter's bitmap; a posting whose row is out is skipped, so it is neither scored nor marked as touched
+template <bool kFilt>
+__device__ __forceinline__ void bm_accum(const BmArgs& a, int t, const u32* allow) {
     const int s = blockIdx.y, q = a.q0 + s;
     const long long b = a.q_off[q], e = a.q_off[q + 1];
     if (b + t >= e) return;
@@ -77,10 +83,14 @@ __global__ __launch_bounds__(kBmThreads) void k_bm25_accum(BmArgs a, int t) {
     u32* bits = a.bits + s * a.bits_stride;
     for (long long p = p0 + (long long)blockIdx.x * kBmThreads + threadIdx.x; p < p1; p += (long long)gridDim.x * kBmThreads) {
         const u32 row = (u32)a.indices[p];
+        if (kFilt && !bm25f_row_allowed(allow, row)) continue;
         sc[row] = sc[row] + a.data[p];
         atomicOr(&bits[row >> 5], 1u << (row & 31u));
     }
 }
+
+__global__ __launch_bounds__(kBmThreads) void k_bm25_accum(BmArgs a, int t) { bm_accum<false>(a, t, nullptr); }
+__global__ __launch_bounds__(kBmThreads) void k_bm25_accum_f(BmArgs a, int t, const u32* allow) { bm_accum<true>(a, t, allow); }
 
 // histogram of digit (key >> shift) & 255 over the touched keys whose upper digits equal the prefix
 __global__ __launch_bounds__(kBmThreads) void k_bm25_hist(BmArgs a, int pass) {
@@ -206,17 +216,17 @@ __global__ __launch_bounds__(512) void k_bm25_sort_small(BmArgs a, int Pk) {
     for (int i = tid; i < (int)n; i += 512) bm_emit(a, s, i, keys[i]);
 }
 
-// zero bits (untouched rows < n) of the four words a thread owns in bitmap block b
-__device__ __forceinline__ void bm_zero_words(const BmArgs& a, int s, int b, int tid, u32 z[4]) {
-    const uint4 w4 = *(const uint4*)(a.bits + s * a.bits_stride + (long long)b * kBmWordsPerBlock + tid * 4);
-    const u32 wv[4] = {w4.x, w4.y, w4.z, w4.w};
+// zero bits (untouched rows < n) of the four words a thread owns in bitmap block b; kFilt: those of them `allow` [words] lets through
+template <bool kFilt>
+__device__ __forceinline__ void bm_zero_words(const BmArgs& a, int s, int b, int tid, const u32* allow, u32 z[4]) {
     const long long w0 = (long long)b * kBmWordsPerBlock + tid * 4;
+    const uint4 w4 = *(const uint4*)(a.bits + s * a.bits_stride + w0);
+    const u32 wv[4] = {w4.x, w4.y, w4.z, w4.w};
+    uint4 f4 = make_uint4(~0u, ~0u, ~0u, ~0u);
+    if (kFilt) f4 = *(const uint4*)(allow + w0);
+    const u32 fv[4] = {f4.x, f4.y, f4.z, f4.w};
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const long long r0 = (w0 + j) * 32;
-        const u32 valid = r0 >= a.n ? 0u : (a.n - r0 >= 32 ? 0xFFFFFFFFu : ((1u << (u32)(a.n - r0)) - 1u));
-        z[j] = ~wv[j] & valid;
-    }
+    for (int j = 0; j < 4; ++j) z[j] = bm25f_allowed_untouched(wv[j], bm25f_valid_mask((w0 + j) * 32, a.n), fv[j]);
 }
 
 __device__ __forceinline__ u32 block_excl_scan(u32 v, u32* lds /* [kBmThreads / 64] */, u32* total) {
@@ -240,16 +250,20 @@ __device__ __forceinline__ u32 block_excl_scan(u32 v, u32* lds /* [kBmThreads / 
 }
 
 // the zero-score tail, only when fewer than k rows were touched: untouched rows per bitmap block ...
-__global__ __launch_bounds__(kBmThreads) void k_bm25_tail_count(BmArgs a) {
+template <bool kFilt>
+__device__ __forceinline__ void bm_tail_count(const BmArgs& a, const u32* allow) {
     const int s = blockIdx.y, tid = threadIdx.x;
     if (a.st[s].nsel >= (u32)a.k) return;
     u32 z[4];
-    bm_zero_words(a, s, blockIdx.x, tid, z);
+    bm_zero_words<kFilt>(a, s, blockIdx.x, tid, allow, z);
     __shared__ u32 lds[kBmThreads / 64];
     u32 total;
     block_excl_scan(__popc(z[0]) + __popc(z[1]) + __popc(z[2]) + __popc(z[3]), lds, &total);
     if (tid == 0) a.tblk[s * a.tblk_stride + blockIdx.x] = total;
 }
+
+__global__ __launch_bounds__(kBmThreads) void k_bm25_tail_count(BmArgs a) { bm_tail_count<false>(a, nullptr); }
+__global__ __launch_bounds__(kBmThreads) void k_bm25_tail_count_f(BmArgs a, const u32* allow) { bm_tail_count<true>(a, allow); }
 
 // ... their exclusive prefix over the blocks (one workgroup per slot) ...
 __global__ __launch_bounds__(kBmThreads) void k_bm25_tail_scan(BmArgs a, int nblk) {
@@ -268,14 +282,15 @@ __global__ __launch_bounds__(kBmThreads) void k_bm25_tail_scan(BmArgs a, int nbl
 }
 
 // ... and the rows themselves, in ascending order, at ranks nsel + (untouched rows before them), while < k
-__global__ __launch_bounds__(kBmThreads) void k_bm25_tail_write(BmArgs a) {
+template <bool kFilt>
+__device__ __forceinline__ void bm_tail_write(const BmArgs& a, const u32* allow) {
     const int s = blockIdx.y, tid = threadIdx.x;
     const long long nsel = a.st[s].nsel;
     if (nsel >= a.k) return;
     const long long start = nsel + a.tblk[s * a.tblk_stride + blockIdx.x];
     if (start >= a.k) return;
     u32 z[4];
-    bm_zero_words(a, s, blockIdx.x, tid, z);
+    bm_zero_words<kFilt>(a, s, blockIdx.x, tid, allow, z);
     __shared__ u32 lds[kBmThreads / 64];
     u32 total;
     long long pos = start + block_excl_scan(__popc(z[0]) + __popc(z[1]) + __popc(z[2]) + __popc(z[3]), lds, &total);
@@ -286,6 +301,18 @@ __global__ __launch_bounds__(kBmThreads) void k_bm25_tail_write(BmArgs a) {
             a.out_ids[s * a.out_stride + pos] = (w0 + j) * 32 + (__ffs(m) - 1);
             a.out_scores[s * a.out_stride + pos] = 0.0f;
         }
+}
+
+__global__ __launch_bounds__(kBmThreads) void k_bm25_tail_write(BmArgs a) { bm_tail_write<false>(a, nullptr); }
+__global__ __launch_bounds__(kBmThreads) void k_bm25_tail_write_f(BmArgs a, const u32* allow) { bm_tail_write<true>(a, allow); }
+
+// a filter that allows fewer than k rows: ranks from .. k - 1 of every slot are padding, written before the sort and the tail write theirs
+__global__ __launch_bounds__(kBmThreads) void k_bm25_pad_out(BmArgs a, long long from) {
+    const int s = blockIdx.y;
+    for (long long i = from + (long long)blockIdx.x * kBmThreads + threadIdx.x; i < a.k; i += (long long)gridDim.x * kBmThreads) {
+        a.out_ids[s * a.out_stride + i] = -1;
+        a.out_scores[s * a.out_stride + i] = -FLT_MAX;
+    }
 }
 
 // every score entry and bitmap word the query touched back to zero (writes of zero only: overlaps are harmless)
@@ -558,6 +585,9 @@ struct vf_bm25 {
     long long* d_qoff = nullptr;
     int* d_qterms = nullptr;
     const int32_t* qterms_host = nullptr;   // the caller's q_terms during a search (grid sizes)
+    // a filtered search (VF_BM25_FILTER) also holds these from the first such call on; they go with the slots
+    u32* d_allow = nullptr;                 // [words] the filter of the call in flight, zero past n
+    u32* d_ftblk = nullptr;                 // [slots][words / kBmWordsPerBlock]: the filtered small-k tail counts every bitmap block
     // a live handle (VF_BM25_LIVE) also keeps what a re-scoring needs
     bool live = false;
     bool born = true;                       // false between the stage and the commit that create a live handle
@@ -590,12 +620,29 @@ static long long bm_slot_bytes(const vf_bm25* h) {
 }
 
 static void bm_free_slots(vf_bm25* h) {
-    void* ps[] = {h->d_scores, h->d_bits, h->d_hist, h->d_st, h->d_sel, h->d_tblk, h->d_ids, h->d_out};
+    void* ps[] = {h->d_scores, h->d_bits, h->d_hist, h->d_st, h->d_sel, h->d_tblk, h->d_ids, h->d_out, h->d_allow, h->d_ftblk};
     for (void* p : ps)
         if (p) (void)hipFree(p);
     h->d_scores = nullptr; h->d_bits = nullptr; h->d_hist = nullptr; h->d_st = nullptr; h->d_sel = nullptr;
     h->d_tblk = nullptr; h->d_ids = nullptr; h->d_out = nullptr;
+    h->d_allow = nullptr; h->d_ftblk = nullptr;   // sized by the slots and the words that go here: the next filtered call makes them again
     h->slots = 0;
+}
+
+// what a filtered call holds beyond the slots (after bm_ensure_slots: h->slots and h->words are the call's)
+static int bm_ensure_filter(vf_bm25* h) {
+    hipError_t e = hipSuccess;
+    if (!h->d_allow) {
+        e = hipMalloc((void**)&h->d_allow, (size_t)h->words * 4);
+        if (e == hipSuccess) e = hipMemsetAsync(h->d_allow, 0, (size_t)h->words * 4, h->stream);   // the words past n stay zero
+    }
+    if (e == hipSuccess && !h->d_ftblk) e = hipMalloc((void**)&h->d_ftblk, (size_t)h->slots * (size_t)(h->words / kBmWordsPerBlock) * 4);
+    if (e != hipSuccess) {
+        if (h->d_allow) (void)hipFree(h->d_allow);
+        h->d_allow = nullptr; h->d_ftblk = nullptr;   // d_ftblk was the allocation that failed, or was never reached
+        return bm_fail(e == hipErrorOutOfMemory ? VF_ENOMEM : VF_EHIP, std::string("vf_bm25: filter scratch: ") + hipGetErrorString(e));
+    }
+    return VF_OK;
 }
 
 // the per-query scratch of `want` slots, zeroed (the reset keeps it zero between queries)
@@ -953,8 +1000,9 @@ extern "C" int vf_bm25_create(const int64_t* indptr, int64_t V, const int32_t* i
     return VF_OK;
 }
 
-// the scoring and the radix select of the group's queries (slots 0 .. g-1); sel / tblk / out set by the caller
-static int bm_score_select(vf_bm25* h, BmArgs& a, const int64_t* q_off, int g) {
+// the scoring and the radix select of the group's queries (slots 0 .. g-1); sel / tblk / out set by the caller.  allow: the device
+// bitmap of a filtered call (the scatter skips the rows outside it), or null
+static int bm_score_select(vf_bm25* h, BmArgs& a, const int64_t* q_off, int g, const u32* allow) {
     hipStream_t st = h->stream;
     long long maxlen = 0;
     for (int s = 0; s < g; ++s) maxlen = std::max<long long>(maxlen, q_off[a.q0 + s + 1] - q_off[a.q0 + s]);
@@ -968,7 +1016,8 @@ static int bm_score_select(vf_bm25* h, BmArgs& a, const int64_t* q_off, int g) {
             }
         }
         if (post == 0) continue;
-        hipLaunchKernelGGL(k_bm25_accum, dim3(bm_grid(post, kBmThreads, 4096), g), dim3(kBmThreads), 0, st, a, (int)t);
+        if (allow) hipLaunchKernelGGL(k_bm25_accum_f, dim3(bm_grid(post, kBmThreads, 4096), g), dim3(kBmThreads), 0, st, a, (int)t, allow);
+        else hipLaunchKernelGGL(k_bm25_accum, dim3(bm_grid(post, kBmThreads, 4096), g), dim3(kBmThreads), 0, st, a, (int)t);
         VFS_HIP(hipGetLastError());
     }
     const unsigned wblk = (unsigned)(h->words / kBmWordsPerBlock);
@@ -981,11 +1030,13 @@ static int bm_score_select(vf_bm25* h, BmArgs& a, const int64_t* q_off, int g) {
     return VF_OK;
 }
 
-static int bm_tail_and_reset(vf_bm25* h, BmArgs& a, const int64_t* q_off, int g, int tail_blocks) {
+static int bm_tail_and_reset(vf_bm25* h, BmArgs& a, const int64_t* q_off, int g, int tail_blocks, const u32* allow) {
     hipStream_t st = h->stream;
-    hipLaunchKernelGGL(k_bm25_tail_count, dim3(tail_blocks, g), dim3(kBmThreads), 0, st, a);
+    if (allow) hipLaunchKernelGGL(k_bm25_tail_count_f, dim3(tail_blocks, g), dim3(kBmThreads), 0, st, a, allow);
+    else hipLaunchKernelGGL(k_bm25_tail_count, dim3(tail_blocks, g), dim3(kBmThreads), 0, st, a);
     hipLaunchKernelGGL(k_bm25_tail_scan, dim3(1, g), dim3(kBmThreads), 0, st, a, tail_blocks);
-    hipLaunchKernelGGL(k_bm25_tail_write, dim3(tail_blocks, g), dim3(kBmThreads), 0, st, a);
+    if (allow) hipLaunchKernelGGL(k_bm25_tail_write_f, dim3(tail_blocks, g), dim3(kBmThreads), 0, st, a, allow);
+    else hipLaunchKernelGGL(k_bm25_tail_write, dim3(tail_blocks, g), dim3(kBmThreads), 0, st, a);
     long long post = 0;
     for (int s = 0; s < g; ++s) {
         long long p = 0;
@@ -1004,6 +1055,13 @@ extern "C" int vf_bm25_search(vf_bm25* h, const int64_t* q_offsets, const int32_
                               int64_t* out_ids, float* out_scores) {
     if (!h) return bm_fail(VF_EINVAL, "vf_bm25_search: null handle");
     if (nq < 0) return bm_fail(VF_EINVAL, "vf_bm25_search: negative nq");
+    const vf_bm25_filter_query* fq = nullptr;   // VF_BM25_FILTER: one set of rows for every query of the call
+    if (nq & VF_BM25_FILTER) {
+        fq = (const vf_bm25_filter_query*)(const void*)q_offsets;
+        if (!fq) return bm_fail(VF_EINVAL, "vf_bm25_search: VF_BM25_FILTER with a null vf_bm25_filter_query");
+        q_offsets = fq->q_offsets;
+        nq &= ~VF_BM25_FILTER;
+    }
     if (nq == 0) return VF_OK;
     if (!q_offsets || !out_ids || !out_scores) return bm_fail(VF_EINVAL, "vf_bm25_search: null buffer");
     std::lock_guard<std::mutex> lk(h->mu);   // before n_docs and the vocabulary are read: a live handle's update changes both
@@ -1015,6 +1073,22 @@ extern "C" int vf_bm25_search(vf_bm25* h, const int64_t* q_offsets, const int32_
     if (T > 0 && !q_terms) return bm_fail(VF_EINVAL, "vf_bm25_search: null q_terms");
     for (long long t = 0; t < T; ++t)
         if (q_terms[t] < 0 || q_terms[t] >= h->V) return bm_fail(VF_EINVAL, "vf_bm25_search: a token column is out of range");
+    Bm25FilterPlan fp{};
+    if (fq) {
+        if (!fq->allow) return bm_fail(VF_EINVAL, "vf_bm25_search: VF_BM25_FILTER with a null allow bitmap");
+        if (fq->n_docs != h->n)
+            return bm_fail(VF_EINVAL, "vf_bm25_search: the filter was made for " + std::to_string(fq->n_docs) + " documents, the handle holds " +
+                                          std::to_string(h->n) + " (a live handle may have changed since the bitmap was made: make it again)");
+        const Bm25FilterCheck fc = bm25f_check(fq->allow, h->n);
+        if (fc.bad_row >= 0)
+            return bm_fail(VF_EINVAL, "vf_bm25_search: the filter allows row " + std::to_string(fc.bad_row) + ", at or past n_docs = " + std::to_string(h->n));
+        fp = bm25f_plan(h->words, fc.m, k);
+        if (fc.m == 0) {   // nothing may be returned: all padding, no launch
+            std::fill(out_ids, out_ids + (size_t)nq * k, (int64_t)-1);
+            std::fill(out_scores, out_scores + (size_t)nq * k, -FLT_MAX);
+            return VF_OK;
+        }
+    }
     DeviceGuard guard;
     VFS_HIP(hipSetDevice(h->device));
     hipStream_t st = h->stream;
@@ -1049,6 +1123,14 @@ extern "C" int vf_bm25_search(vf_bm25* h, const int64_t* q_offsets, const int32_
         const int rc = bm_ensure_big(h);
         if (rc != VF_OK) return rc;
     }
+    const u32* allow = nullptr;
+    if (fq) {   // the bitmap goes up with every filtered call (n / 8 bytes): no filter is kept on the device between calls
+        const int rc = bm_ensure_filter(h);
+        if (rc != VF_OK) return rc;
+        VFS_HIP(hipMemcpyAsync(h->d_allow, fq->allow, (size_t)bm25f_words(h->n) * 4, hipMemcpyHostToDevice, st));
+        allow = h->d_allow;
+    }
+    const unsigned pad_grid = bm_grid(k - fp.pad_from, kBmThreads, 64);   // a filtered call of fewer than k rows pads ranks pad_from .. k - 1
     a.scores = h->d_scores; a.score_stride = h->n;
     a.bits = h->d_bits; a.bits_stride = h->words;
     a.hist = h->d_hist; a.st = h->d_st;
@@ -1058,20 +1140,24 @@ extern "C" int vf_bm25_search(vf_bm25* h, const int64_t* q_offsets, const int32_
         if (small) {
             a.sel = h->d_sel; a.sel_stride = kBmSmallK; a.sel_cap = kBmSmallK;
             a.tblk = h->d_tblk; a.tblk_stride = 1;
+            if (fq) { a.tblk = h->d_ftblk; a.tblk_stride = fp.tblk_entries; }
             a.out_ids = h->d_ids; a.out_scores = h->d_out; a.out_stride = k;
-            int rc = bm_score_select(h, a, q_offsets, g);
+            int rc = bm_score_select(h, a, q_offsets, g, allow);
             if (rc != VF_OK) return rc;
+            if (fq && fp.pad_from < k) hipLaunchKernelGGL(k_bm25_pad_out, dim3(pad_grid, g), dim3(kBmThreads), 0, st, a, fp.pad_from);
             const int Pk = (int)bm_pow2(k);
             hipLaunchKernelGGL(k_bm25_sort_small, dim3(1, g), dim3(512), (size_t)Pk * 8, st, a, Pk);
-            // fewer than k touched rows means fewer than kBmSmallK: the tail lies in the first 2 * kBmSmallK rows, one bitmap block
-            rc = bm_tail_and_reset(h, a, q_offsets, g, 1);
+            // fewer than k touched rows means fewer than kBmSmallK: the tail lies in the first 2 * kBmSmallK rows, one bitmap block --
+            // unless a filter strikes rows out: then the allowed untouched rows can lie in any block, and every block is counted
+            rc = bm_tail_and_reset(h, a, q_offsets, g, fq ? fp.tail_blocks : 1, allow);
             if (rc != VF_OK) return rc;
         } else {
             a.sel = h->d_big; a.sel_stride = 0; a.sel_cap = bm_pow2(h->n);
             a.tblk = h->d_big_tblk; a.tblk_stride = 0;
             a.out_ids = h->d_big_ids; a.out_scores = h->d_big_out; a.out_stride = 0;
-            int rc = bm_score_select(h, a, q_offsets, 1);
+            int rc = bm_score_select(h, a, q_offsets, 1, allow);
             if (rc != VF_OK) return rc;
+            if (fq && fp.pad_from < k) hipLaunchKernelGGL(k_bm25_pad_out, dim3(pad_grid, 1), dim3(kBmThreads), 0, st, a, fp.pad_from);
             BmState bs;
             VFS_HIP(hipMemcpyAsync(&bs, h->d_st, sizeof(bs), hipMemcpyDeviceToHost, st));
             VFS_HIP(hipStreamSynchronize(st));
@@ -1086,7 +1172,7 @@ extern "C" int vf_bm25_search(vf_bm25* h, const int64_t* q_offsets, const int32_
             }
             if (bs.nsel > 0) hipLaunchKernelGGL(k_bm25_emit, dim3(bm_grid(bs.nsel, kBmThreads, 8192)), dim3(kBmThreads), 0, st, a);
             VFS_HIP(hipGetLastError());
-            rc = bm_tail_and_reset(h, a, q_offsets, 1, h->words / kBmWordsPerBlock);
+            rc = bm_tail_and_reset(h, a, q_offsets, 1, h->words / kBmWordsPerBlock, allow);
             if (rc != VF_OK) return rc;
         }
         VFS_HIP(hipMemcpyAsync(out_ids + (size_t)q0 * k, a.out_ids, (size_t)g * k * 8, hipMemcpyDeviceToHost, st));

@@ -334,8 +334,11 @@ class EnsembleRetriever:
         the result is what ``invoke`` would return over a store that held the passing chunks alone -- the dense leg searches those
         rows only (``FaissRetriever.invoke(subset=...)``: the retriever must take ``subset``), bundles and the neighbour expansion see
         passing rows only, the title-summary leg's rows are filtered here.  ONE stated exception, the BM25 leg: it keeps the
-        whole corpus's statistics (idf, average length), as upstream's own sketch does (bm25Retriever.py:91-132) -- it is asked for
-        the full ranking, filtered here, and the first ``bm25_k`` survivors are used.  A filter nothing passes returns []."""
+        whole corpus's statistics (idf, average length), as upstream's own sketch does (bm25Retriever.py:91-132) -- its result is
+        the first ``bm25_k`` passing rows of the full ranking.  A retriever that declares ``filtered_prefix`` (this package's
+        ``BM25Retriever``) is asked for exactly those, ``invoke(input, min(bm25_k, passing rows), subset=passing)``, and filters
+        inside its kernels, so the exception costs nothing; any other retriever is asked for the full ranking, which is
+        filtered here.  A filter nothing passes returns []."""
         with stages.stage("retrieve"):
             out = self._invoke(input, hyde_chunks, where)
         stages.metric("retrieved_chunks", len(out))
@@ -357,7 +360,7 @@ class EnsembleRetriever:
                 bundle_cnt = self._title_branch(input, seen, out, bundle_cnt, allow)
         if self.bm25_k > 0:
             with stages.stage("retrieve_bm25"):
-                bundle_cnt = self._bm25_branch(input, seen, out, bundle_cnt, allow)
+                bundle_cnt = self._bm25_branch(input, seen, out, bundle_cnt, allow, passing)
         return out
 
     def _faiss_branch(self, input, hyde_chunks, seen, out, bundle_cnt, passing=None, allow=None):
@@ -397,11 +400,16 @@ class EnsembleRetriever:
                 bundle_cnt += 1
         return bundle_cnt
 
-    def _bm25_branch(self, input, seen, out, bundle_cnt, allow=None):
+    def _bm25_branch(self, input, seen, out, bundle_cnt, allow=None, passing=None):
         if allow is not None:
-            # filtered: the full ranking (whole-corpus statistics: the stated exception), the first bm25_k rows that pass
-            b_ids, b_scores = self.bm25_retriever.invoke(input, self.num_chunk)
-            kept = [(int(r), s) for r, s in zip(b_ids, b_scores) if int(r) in allow][:self.bm25_k]
+            # filtered: the first bm25_k passing rows of the full ranking (whole-corpus statistics: the stated exception) -- from a
+            # retriever that filters on its own (filtered_prefix), else from the full ranking, filtered here
+            if passing is not None and getattr(self.bm25_retriever, "filtered_prefix", False) is True:
+                b_ids, b_scores = self.bm25_retriever.invoke(input, max(1, min(int(self.bm25_k), len(passing))), subset=passing)
+                kept = [(int(r), s) for r, s in zip(b_ids, b_scores)]
+            else:
+                b_ids, b_scores = self.bm25_retriever.invoke(input, self.num_chunk)
+                kept = [(int(r), s) for r, s in zip(b_ids, b_scores) if int(r) in allow][:self.bm25_k]
             for row, score in kept:
                 if row in seen:
                     continue
