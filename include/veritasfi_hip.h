@@ -233,8 +233,8 @@ typedef struct vf_subset_query {
 
 int vf_index_info(vf_index* idx, int64_t* n, int32_t* d, int32_t* dtype, int32_t* device_id);
 int vf_index_stats(vf_index* idx, vf_search_stats* out);
-/* tuning knobs, by name ("force_path", "sample_rows", "margin", "cap", "waves" ...); tests use
- * force_path to exercise every path on the same data.  Unknown name -> VF_EINVAL.
+/* tuning knobs, by name: every name, its default and its accepted values are the table in veritasfi_amd/csrc/vf_options.h (tests use
+ * "force_path" to exercise every path on the same data).  Unknown name or refused value -> VF_EINVAL; vf_last_error says what is accepted.
  * "wide_mfma": matrix instruction of the wide scan (batches of >= 129 queries) over e4m3 rows: -1 auto (= 1; = 0 for rows of 2560
  *   to 4096 padded elements, where the hi + lo query's wider bound costs repairs), 1 the fp8
  *   instruction on the row bytes as stored (k_scan_wide8: the query goes in as a hi + lo pair of e4m3 codes and its exactly

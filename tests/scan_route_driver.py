@@ -1,7 +1,7 @@
-"""A host-compiled driver of the scan route (veritasfi_amd/csrc/vf_route.h + vf_scan_lds.h), shared by tests/test_scan_route.py (no GPU)
+"""A host-compiled driver of the scan route (veritasfi_amd/csrc/vf_route.h + vf_options.h + vf_scan_lds.h), shared by tests/test_scan_route.py (no GPU)
 and tests/test_gpu_scan_route.py (the library's reported values against the driver's prediction).
 
-The two headers are plain C++17 without HIP, so the host compiler reads them as they stand (the way tests/test_wide_rows_geometry.py
+The headers are plain C++17 without HIP, so the host compiler reads them as they stand (the way tests/test_wide_rows_geometry.py
 compiles its header), under UBSan.  The program is stand-alone:
 
   driver eval    reads one search per line of stdin ("key=value key=value ..."), prints its route as one line of "key=value"
@@ -35,7 +35,7 @@ struct Routed {
     SearchRoute r; SplitReport split{0, 0};
     int passes = 0, wide_launches = 0, wide_queries = 0, scan_kernel = 0;
     BatchRoute first{}, last{};   // passes of a search that is not wide
-    WidePass wlast{};
+    WidePass wfirst{}, wlast{};
 };
 
 static Routed route(Case c) {
@@ -54,7 +54,7 @@ static Routed route(Case c) {
         // (a pass's route depends on its query count only: the first and the last pass stand for all)
         if (b0 != 0 && b0 + o.r.per_pass < c.nq) { ++o.passes; if (o.r.wide) { ++o.wide_launches; o.wide_queries += nb; } continue; }
         ++o.passes;
-        if (o.r.wide) { o.wlast = route_wide_pass(in, o.r.plan, nb); ++o.wide_launches; o.wide_queries += nb; o.scan_kernel = o.wlast.main; }
+        if (o.r.wide) { o.wlast = route_wide_pass(in, o.r.plan, nb); if (b0 == 0) o.wfirst = o.wlast; ++o.wide_launches; o.wide_queries += nb; o.scan_kernel = o.wlast.main; }
         else { o.last = route_batch(in, o.r, nb); if (b0 == 0) o.first = o.last; o.scan_kernel = o.last.main; }
     }
     return o;
@@ -79,20 +79,24 @@ static int eval_lines() {
         in.has_scan = get("has_scan", in.n > kSmallN) != 0; in.has_image = get("has_image", 0) != 0; in.rho_mean = (float)get("rho_mean", 0.0);
         in.group = get("group", 0) != 0;
         c.nq = (int)get("nq", 1); c.k = (int)get("k", 100); c.masking = get("masking", 1) != 0; c.aux_applied = (long long)get("aux_applied", -1);
-#define OPT(f) in.f = (int64_t)get(#f, (double)in.f);
-        OPT(force_path) OPT(wide) OPT(wide_mfma) OPT(wide8_waves) OPT(wide8_stage) OPT(wide_rows) OPT(scan_impl) OPT(sample_impl) OPT(sample_grid)
-        OPT(steal) OPT(scan_image) OPT(image_mfma) OPT(aux_cus) OPT(overlap_scans) OPT(margin) OPT(cap) OPT(waves) OPT(sample_rows) OPT(debug)
+#define OPT(f, ...) in.f = (int64_t)get(#f, (double)in.f);   // every option of the table (vf_options.h), by its name
+        VF_OPTIONS(OPT)
 #undef OPT
         if (!kv.empty()) { std::printf("error=unknown-key:%s\n", kv.begin()->first.c_str()); return 2; }
         const Routed o = route(c);
         const bool fused = o.r.path == 1, narrow = fused && !o.r.wide && o.passes > 0;
         std::printf("path=%d wide=%d per_pass=%d passes=%d scan_image=%d planes=%d aux_cus=%d scans_overlap=%d scan_kernel=%d wide_launches=%d "
-                    "wide_queries=%d tile=%d sample=%d sample_grid=%d sample_rows=%d main_rows=%d stage_cap=%d kprime=%d cap=%d grid=%d samp=%d total_waves=%d\n",
+                    "wide_queries=%d tile=%d sample=%d sample_grid=%d sample_rows=%d main_rows=%d stage_cap=%d kprime=%d cap=%d grid=%d samp=%d total_waves=%d "
+                    "refresh_every=%d clear_sample=%d scan_bytes=%lld\n",
                     o.r.path, (int)o.r.wide, o.r.per_pass, o.passes, fused && o.r.image ? 1 : 0, o.r.planes, o.split.aux_cus, o.split.scans_overlap,
                     o.scan_kernel, o.wide_launches, o.wide_queries, narrow ? o.first.tile : 0, narrow ? (int)o.first.sample : 0,
                     narrow ? o.first.sample_grid : 0, narrow ? (int)o.first.sample_rows : -1,
                     narrow ? (int)o.last.main_rows : (fused && o.passes ? (int)o.wlast.rows : -1), narrow ? o.last.stage_cap : (fused && o.passes ? o.wlast.stage_cap : 0),
-                    fused ? o.r.plan.kprime : 0, fused ? (o.r.wide && o.passes ? o.wlast.cap : o.r.plan.cap) : 0, fused ? o.r.plan.grid : 0, fused ? o.r.plan.samp : 0, fused ? o.r.plan.total_waves : 0);
+                    fused ? o.r.plan.kprime : 0, fused ? (o.r.wide && o.passes ? o.wlast.cap : o.r.plan.cap) : 0, fused ? o.r.plan.grid : 0, fused ? o.r.plan.samp : 0, fused ? o.r.plan.total_waves : 0,
+                    // the first pass's (the one a profiled search times)
+                    narrow ? o.first.refresh_every : (fused && o.passes ? o.wfirst.refresh_every : 0),
+                    narrow ? (int)o.first.clear_sample : (fused && o.passes ? (int)o.wfirst.clear_sample : 0),
+                    narrow ? (long long)o.first.scan_bytes : (fused && o.passes ? (long long)o.wfirst.scan_bytes : 0ll));
     }
     return 0;
 }

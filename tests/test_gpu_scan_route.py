@@ -1,5 +1,6 @@
 """What the library reports of a search against the route the host-compiled driver (tests/scan_route_driver.py, vf_route.h) predicts for
-the same inputs: path, scan_kernel, scan_image, wide_launches, wide_queries, aux_cus and scans_overlap.
+the same inputs: path, scan_kernel, scan_image, wide_launches, wide_queries, aux_cus and scans_overlap -- and, with the profile on, the
+bytes the library says a timed main scan reads (scan_bytes_per_launch) against the driver's scan_bytes of the search's first pass.
 
 20 000 rows (the smallest kind of index the fused path serves on its own) of 768 elements as fp16, e4m3 and int8 (scan_image = 2: the
 index is its own image), and of 2560 elements as fp16 and e4m3 under wide_rows = 2, each with 1, 33, 65 and 130 queries: every branch of
@@ -51,15 +52,18 @@ def test_reported_route_is_the_predicted_one(vf, driver, dtype, d, options):
     with _index(vf, dtype, d, rng) as ix:
         for name, value in options.items():
             ix.set_option(name, value)
-        got = []
+        ix.set_option("profile", 1)
+        got, got_bytes = [], []
         for nq in (1, 33, 65, 130):
             ix.search(rng.standard_normal((nq, d), dtype=np.float32), K)
             got.append(ix.stats())
+            got_bytes.append(ix.profile()["scan_bytes_per_launch"])   # (of the latest timed search's first pass)
     has_image = 1 if options.get("scan_image") == 2 else 0   # (the int8 index is its own image; 20 000 rows of fp16 / e4m3 build none)
     cases = [dict(dtype=dtype, n=N, d=d, nq=nq, k=K, n_cu=n_cu, has_image=has_image, aux_applied=g["aux_cus"], **options)
              for nq, g in zip((1, 33, 65, 130), got)]
     want = drv.evaluate(driver, cases)
-    for nq, g, w in zip((1, 33, 65, 130), got, want):
-        print(dtype, d, nq, {k: g[k] for k in KEYS}, w)
+    for nq, g, gb, w in zip((1, 33, 65, 130), got, got_bytes, want):
+        print(dtype, d, nq, {k: g[k] for k in KEYS}, "scan_bytes_per_launch", gb, w)
         assert {k: g[k] for k in KEYS} == {k: w[k] for k in KEYS}, f"{dtype} {N} x {d}, {nq} queries"
+        assert gb == w["scan_bytes"] and gb > 0, f"{dtype} {N} x {d}, {nq} queries: scan bytes"
         assert g["path"] == 1   # every one of these searches is the fused path's: the comparison above is about its kernels

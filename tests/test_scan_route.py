@@ -72,6 +72,42 @@ TABLE = [
     ("int8 17000 x 2560, force_path 1", dict(dtype="int8", n=17000, d=2560, force_path=1), dict(path=-1)),
 ]
 
+# What a pass is launched with beside its kernels -- refresh_every, clear_sample, scan_bytes of the search's FIRST pass -- derived by hand
+# from the expressions as they stood in vf_api.hip's begin_impl (narrow passes) and wide_pass before they moved into the header.
+#   narrow refresh_every = min(256, max(4, max(1, option) * nb / 64)) rounded down to a power of two
+#   wide   refresh_every = the largest power of two <= min(256, max(1, option))
+#   narrow clear_sample  = n / total_waves < samp            wide clear_sample = n / rgroups < samp * 8
+#   scan_bytes = (n - sampled rows) x bytes per row: d x (1 or 2) + 4, the int8 image dp + 8;
+#     sampled = total_waves x min(samp, n / total_waves), wide: rgroups x min(samp * 8, n / rgroups)
+F16_1M_WIDE = dict(dtype="f16", n=M, d=768, nq=65)          # one wide pass: 65 queries pad to one tile of 256, 256 CUs / 1 tile = 256 row groups,
+                                                            # one query tile samples 32 x 8 = 256 rows per group
+F16_WAVES = dict(dtype="f16", d=768, nq=1, waves=320, sample_rows=64)   # waves = 320: 40 workgroups of 8 waves; 64 sample rows per wave
+TABLE += [
+    ("refresh 128, 64 queries", dict(F16_17K, refresh_every=128), dict(wide=0, refresh_every=128)),        # 128 * 64 / 64 = 128
+    ("refresh 128, 33 queries", dict(F16_17K, nq=33, refresh_every=128), dict(wide=0, refresh_every=64)),  # 128 * 33 / 64 = 66 -> 64
+    ("refresh 128, 1 query", dict(F16_17K, nq=1, refresh_every=128), dict(refresh_every=4)),               # 128 * 1 / 64 = 2 -> the floor of 4
+    ("refresh 1, 64 queries", dict(F16_17K, refresh_every=1), dict(refresh_every=4)),                      # 1 -> the floor of 4
+    ("refresh 256, 64 queries", dict(F16_17K, refresh_every=256), dict(refresh_every=256)),                # 256 * 64 / 64 = 256, the ceiling
+    ("wide, refresh 128", dict(F16_1M_WIDE, refresh_every=128), dict(wide=1, refresh_every=128)),
+    ("wide, refresh 100", dict(F16_1M_WIDE, refresh_every=100), dict(wide=1, refresh_every=64)),           # largest power of two <= 100
+    ("wide, refresh 1", dict(F16_1M_WIDE, refresh_every=1), dict(wide=1, refresh_every=1)),                # no floor on a wide pass
+    # 320 waves: 20480 / 320 = 64 rows per wave, not fewer than the 64 sampled; one row less and 20479 / 320 = 63 < 64
+    ("clear_sample, narrow, at the boundary", dict(F16_WAVES, n=20480), dict(path=1, total_waves=320, samp=64, clear_sample=0)),
+    ("clear_sample, narrow, below it", dict(F16_WAVES, n=20479), dict(path=1, total_waves=320, samp=64, clear_sample=1)),
+    # 256 row groups sampling 256 rows each: 65536 / 256 = 256 is enough, 65535 / 256 = 255 is not
+    ("clear_sample, wide, at the boundary", dict(F16_1M_WIDE, n=65536), dict(wide=1, clear_sample=0)),
+    ("clear_sample, wide, below it", dict(F16_1M_WIDE, n=65535), dict(wide=1, clear_sample=1)),
+    # fp16 17000 x 768: 224 scan CUs but 17000 / 512 = 33 workgroups = 264 waves sampling 8 rows each (64 per wave are there):
+    # (17000 - 264 * 8) * (768 * 2 + 4) = 14888 * 1540
+    ("scan_bytes, fp16", F16_17K, dict(grid=33, total_waves=264, samp=8, scan_bytes=22_927_520)),
+    # e4m3 1M x 768: 224 workgroups = 1792 waves x 8 sample rows: (1000000 - 14336) * (768 + 4) = 985664 * 772
+    ("scan_bytes, e4m3", dict(E4M3_1M, nq=64), dict(grid=224, total_waves=1792, samp=8, scan_bytes=760_932_608)),
+    # the int8 image of 1M x 768: the same grid and sample, dp + 8 = 776 bytes per row: 985664 * 776
+    ("scan_bytes, image", I8_IMG, dict(scan_image=1, grid=224, total_waves=1792, samp=8, scan_bytes=764_875_264)),
+    # wide, fp16 1M x 768: 256 row groups x 256 sample rows: (1000000 - 65536) * 1540 = 934464 * 1540
+    ("scan_bytes, wide", F16_1M_WIDE, dict(wide=1, scan_bytes=1_439_074_560)),
+]
+
 
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):

@@ -15,7 +15,6 @@ CONFIGS = [
     {"scan_g": 1}, {"scan_g": 3},
     {"sample_rows": 32}, {"margin": 16},
 ]
-DEFAULTS = {"debug": 0, "scan_g": 0, "sample_rows": 16, "refresh_every": 32, "waves": 0, "margin": -1}
 
 def run(ix, q, k, steps, outs):
     pend = []
@@ -35,14 +34,14 @@ def main():
         corpus = make_shard(torch, 0, rows, 768, dev)
         g = torch.Generator(device=dev); g.manual_seed(4321)
         q = torch.randn((64, 768), generator=g, device=dev)
-        ix = vf.DenseIndex(corpus)
         outs = [(torch.empty((64, 100), dtype=torch.int64, device=dev), torch.empty((64, 100), dtype=torch.float32, device=dev)) for _ in range(2)]
         steps = 40 if rows <= 2_000_000 else 12
         print(f"== rows={rows} steps={steps}")
         for rep in range(2):
             for cfg in CONFIGS:
-                for kname, v in DEFAULTS.items():
-                    ix.set_option(kname, cfg.get(kname, v))
+                ix = vf.DenseIndex(corpus)   # a fresh handle per setting: every other option is what the library starts with
+                for kname, v in cfg.items():
+                    ix.set_option(kname, v)
                 run(ix, q, 100, 4, outs)
                 ix.set_option("profile", 1)
                 t0 = time.perf_counter()
@@ -52,7 +51,8 @@ def main():
                 scan_ms = p["scan_ms_total"] / max(1, p["scan_launches"])
                 gbs = p["scan_bytes_per_launch"] / (scan_ms * 1e-3) / 1e9 if scan_ms > 0 else 0
                 print(f"rep{rep} {json.dumps(cfg):28s} step {dt*1e3:7.3f} ms  scan {scan_ms:7.3f} ms {gbs:7.0f} GB/s  pipe {p['pipeline_ms_total']/max(1,p['scan_launches']):7.3f} ms  cand/q {st['candidates']/64:7.0f} reruns {st['exact_reruns']}", flush=True)
-        ix.close(); del corpus
+                ix.close()
+        del corpus
         torch.cuda.empty_cache()
 
 if __name__ == "__main__":

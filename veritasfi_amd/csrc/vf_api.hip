@@ -180,10 +180,7 @@ struct vf_index {
     float rho_sum = 0.0f;             // ... and their sum, which appended rows add to (rho_mean = rho_sum / n, as a fresh build forms it)
     std::mutex mu;
     Slot slots[kSlots];
-    // options
-    int64_t force_path = -1, sample_rows = -1, margin = -1, cap_opt = 0, waves_opt = 0, scan_g = 0,
-            refresh_every = 128, debug = 0, steal_opt = 0, wide_opt = 1, wide_sync = -1, wide_mfma = -1, wide8_waves = 8, wide8_stage = 0,
-            aux_cus = -1, sample_grid = -1, overlap_scans = -1, scan_impl = 2, sample_impl = -1, scan_image = 1, wide_rows = 1, image_mfma = -1;   // aux_cus / overlap_scans: -1 = auto (route_aux_cus / route_overlap)   // scan_impl: 1 k_scan, 2 auto (k_scan2 for fp16 rows, k_scan2r where it measured faster), 3 k_scan2 wherever it fits, 4 never k_scan2r, 5 k_scan2r wherever a shape exists (veritasfi_hip.h; the rule: vf_route.h)   // aux_cus: CUs the main scan leaves to the small kernels of the other slots (0 = no split)   // wide_sync: -1 siblings of a wide row group run free (default: fastest), >= 0 = the slack in super-tiles  // steal_opt: cross-workgroup tile pool in the main scan (measured slower: DESIGN.md 5)  // wide_opt: 0 never, 1 auto (from kWideMinQueries* queries: vf_route.h), > 1 = from that many queries
+    Options opt;                // every integer option, at the defaults of the table they are generated from (vf_options.h)
     vf_search_stats stats{};
     bool profile = false;
     double prof_scan_ms = 0.0, prof_pipe_ms = 0.0;
@@ -195,8 +192,6 @@ struct vf_index {
     DevBuf st_q, st_ids, st_sc;
     DevBuf st_add, st_rho;            // appends: the new rows on their way in (host rows, rows of another device), the image's two residual words
     DevBuf st_cmp, st_rem;            // removals: the staging buffer of the row compaction, the sorted removed rows
-    int64_t compact_chunk_rows = 0;   // option: destination rows per chunk of a removal's compaction (0 = auto: kCompactStageBytes of the widest array)
-    int64_t subset_super_rows = 0;    // option: listed rows a subset search scores per launch (0 = auto: kSubsetScoreBytes of scores; vf_subset.h)
     bool damaged = false;             // a HIP error struck a removal after its first row had moved: searches, appends and removals are refused from then on
     // ---- group handle (vf_index_create_sharded / vf_index_group): the corpus is row-sharded over `shards`, one per
     // device; this handle owns them.  device = the HOME device: queries arrive there and the merged result lands there.
@@ -231,17 +226,13 @@ static size_t dtype_bytes(int dtype) { return dtype == VF_DTYPE_F32 ? 4 : (dtype
 // stream is CU-masked.  Every routing question below goes through this.
 static RouteIn route_in(const vf_index* ix, const Slot* s = nullptr) {
     RouteIn in;
+    static_cast<Options&>(in) = ix->opt;
     in.n = ix->n; in.d = ix->d; in.dp = ix->dp; in.dtype = ix->dtype; in.n_cu = ix->n_cu;
     in.has_scan = ix->rows_scan && ix->inv_scan;
     in.has_image = ix->rows_img != nullptr; in.rho_mean = ix->rho_mean;
     in.group = !ix->shards.empty();
     in.aux_applied = ix->aux_applied;
     in.masked = s && s->scan_stream && s->scan_stream != s->stream;
-    in.force_path = ix->force_path; in.wide = ix->wide_opt; in.wide_mfma = ix->wide_mfma; in.wide8_waves = ix->wide8_waves;
-    in.wide8_stage = ix->wide8_stage; in.wide_rows = ix->wide_rows; in.scan_impl = ix->scan_impl; in.sample_impl = ix->sample_impl;
-    in.sample_grid = ix->sample_grid; in.steal = ix->steal_opt; in.scan_image = ix->scan_image; in.image_mfma = ix->image_mfma;
-    in.aux_cus = ix->aux_cus; in.overlap_scans = ix->overlap_scans; in.margin = ix->margin; in.cap = ix->cap_opt; in.waves = ix->waves_opt;
-    in.sample_rows = ix->sample_rows; in.debug = ix->debug;
     return in;
 }
 
@@ -272,7 +263,7 @@ static int build_common(vf_index* ix) {
         }
     }
     VF_HIP(launch_prep_rows(ix->rows_orig, dt, ix->n, ix->d, ix->dp, scan_out, ix->norm, ix->inv_scan, nullptr));
-    VF_TRY(build_image(ix, ix->scan_image));
+    VF_TRY(build_image(ix, ix->opt.scan_image));
     if (ix->n > 0 && ix->n <= kSmallN) {
         VF_HIP(hipMalloc((void**)&ix->cn_cache, (size_t)std::min<int64_t>(ix->cap, kSmallN) * ix->d * sizeof(float)));
         VF_HIP(launch_normalize_rows(ix->rows_orig, dt, 0, ix->n, ix->d, ix->norm, ix->cn_cache, nullptr));
@@ -632,7 +623,7 @@ static int append_rows(vf_index* ix, const void* rows, int src_device, int64_t m
     }
     // the image a fresh build of this many rows would hold (it appears at a row count: image_eligible)
     if (!ix->rows_img && !ix->image_refused) {
-        const int rc = build_image(ix, ix->scan_image);
+        const int rc = build_image(ix, ix->opt.scan_image);
         if (rc != VF_OK) {   // back to the handle as it was
             const std::string keep = g_err;
             free_image(ix);
@@ -738,7 +729,7 @@ static int remove_prepare(RemovePrep& p) {
     p.scan_moves = ix->rows_scan && ix->owns_scan && !p.to_small;
     long long widest = (long long)ix->d * (long long)esz;
     if (p.scan_moves) widest = std::max(widest, (long long)ix->dp * (long long)scan_esz);
-    p.plan = compact_plan(n0, m, p.rem[0], ix->compact_chunk_rows > 0 ? ix->compact_chunk_rows : compact_auto_rows(widest));
+    p.plan = compact_plan(n0, m, p.rem[0], ix->opt.compact_chunk_rows > 0 ? ix->opt.compact_chunk_rows : compact_auto_rows(widest));
     if (p.plan.chunks) {
         VF_TRY(ix->st_cmp.ensure((size_t)p.plan.chunk_rows * (size_t)widest));
         VF_TRY(ix->st_rem.ensure((size_t)m * sizeof(long long)));
@@ -752,10 +743,10 @@ static int remove_prepare(RemovePrep& p) {
     // the image a fresh build of the remaining rows would hold
     RouteIn in = route_in(ix);
     in.n = n1; in.has_scan = in.has_scan && !p.to_small;
-    const bool eligible = ix->scan_image != 0 && image_eligible(in, ix->scan_image);
+    const bool eligible = ix->opt.scan_image != 0 && image_eligible(in, ix->opt.scan_image);
     if (ix->rows_img) p.image = !eligible ? kImageDrop : ix->owns_img ? kImageRefill : kImageAlias;
     else if (eligible && ix->dtype != VF_DTYPE_INT8) {   // (it had refused its image, or had found no room for it)
-        int rc = image_alloc(ix, ix->scan_image);
+        int rc = image_alloc(ix, ix->opt.scan_image);
         p.new_img = ix->rows_img; p.new_iimg = ix->inv_img;   // kept aside until the rows have moved
         ix->rows_img = nullptr; ix->inv_img = nullptr; ix->owns_img = false;
         if (rc != VF_OK) { p.release(); return rc; }
@@ -785,7 +776,7 @@ static int remove_run(RemovePrep& p) {
     // 4-byte arrays go in one chunk where the rows take many.  Option compact_chunk_rows fixes the rows per chunk for every array.
     auto move = [&](void* base, size_t row_bytes) {
         if (!base) return;
-        const CompactPlan plan = compact_plan(n0, m, p.rem[0], ix->compact_chunk_rows > 0 ? p.plan.chunk_rows : (long long)(ix->st_cmp.bytes / row_bytes));
+        const CompactPlan plan = compact_plan(n0, m, p.rem[0], ix->opt.compact_chunk_rows > 0 ? p.plan.chunk_rows : (long long)(ix->st_cmp.bytes / row_bytes));
         for (long long c = 0; c < plan.chunks && e == hipSuccess; ++c) {
             const CompactChunk k = compact_chunk(plan, c);
             e = launch_compact_rows(base, ix->st_cmp.p, (long long)row_bytes, k.lo, k.hi - k.lo, d_rem, m, 0, k.lo, nullptr);    // gather
@@ -1118,67 +1109,37 @@ extern "C" int vf_index_slots(vf_index* ix, int32_t* out) {
     return VF_OK;
 }
 
+static_assert(kMaxShardRows == 0xFFFFFFFFll && kSubsetMaxRows == 0xFFFFFFFEll, "vf_options.h: the upper ends of compact_chunk_rows and subset_super_rows");
 extern "C" int vf_index_set_option(vf_index* ix, const char* name, int64_t value) {
     if (!ix || !name) return fail(VF_EINVAL, "vf_index_set_option: null argument");
     if (strcmp(name, "reserve_rows") == 0) return reserve_rows(ix, value);
     for (vf_index* sh : ix->shards) VF_TRY(vf_index_set_option(sh, name, value));  // a group forwards to every shard
     std::lock_guard<std::mutex> g(ix->mu);
-    const std::string s(name);
-    auto in_range = [&](int64_t lo, int64_t hi) { return value >= lo && value <= hi; };
-    if (s == "force_path") { if (!in_range(-1, 2)) return fail(VF_EINVAL, "force_path must be -1 (auto), 0, 1 or 2"); ix->force_path = value; }
-    else if (s == "sample_rows") { if (!in_range(-1, 64) || value == 0) return fail(VF_EINVAL, "sample_rows must be -1 (auto) or in [1, 64]"); ix->sample_rows = value; }
-    else if (s == "margin") { if (!in_range(-1, 2048)) return fail(VF_EINVAL, "margin must be -1 (auto) or in [0, 2048]"); ix->margin = value; }
-    else if (s == "cap") { if (!in_range(0, 16384)) return fail(VF_EINVAL, "cap must be in [0, 16384]"); ix->cap_opt = value; }
-    else if (s == "waves") { if (!in_range(0, 8 * 1024)) return fail(VF_EINVAL, "waves must be in [0, 8192]"); ix->waves_opt = value; }
-    else if (s == "scan_g") { if (!in_range(0, 4)) return fail(VF_EINVAL, "scan_g must be in [0, 4]"); ix->scan_g = value; }
-    else if (s == "refresh_every") { if (!in_range(1, 256)) return fail(VF_EINVAL, "refresh_every must be in [1, 256]"); ix->refresh_every = value; }
-    else if (s == "steal") { if (!in_range(0, 1)) return fail(VF_EINVAL, "steal must be 0 or 1"); ix->steal_opt = value; }
-    else if (s == "wide") { if (!in_range(0, 4096)) return fail(VF_EINVAL, "wide must be 0 (off), 1 (auto) or a query count"); ix->wide_opt = value; }
-    else if (s == "wide8_stage") { if (value != 0 && !in_range(64, 3584)) return fail(VF_EINVAL, "wide8_stage must be 0 (auto) or 64..3584 candidate-stage entries"); ix->wide8_stage = value; }
-    else if (s == "wide8_waves") {
-#ifdef VF_EXPERIMENTS
-        if (value != 4 && value != 8) return fail(VF_EINVAL, "wide8_waves must be 8 (one 512-thread workgroup per CU, 256-query tiles: the default) or 4 (two 256-thread workgroups, 128-query tiles: measured slower, DESIGN.md 4)");
-#else
-        if (value != 8) return fail(VF_EINVAL, "wide8_waves must be 8 (the 4-wave form was measured slower and is built with -DVF_EXPERIMENTS only: DESIGN.md 4)");
-#endif
-        ix->wide8_waves = value;
-    }
-    else if (s == "wide_mfma") { if (!in_range(-1, 1)) return fail(VF_EINVAL, "wide_mfma must be -1 (auto: the fp8 instruction for e4m3 rows), 0 (fp16 matrix instruction on converted rows) or 1 (the fp8 instruction on the e4m3 row bytes: k_scan_wide8)"); ix->wide_mfma = value; }
-    else if (s == "wide_sync") { if (!in_range(-1, 8)) return fail(VF_EINVAL, "wide_sync must be -1 (off) or a slack of 0..8 super-tiles"); ix->wide_sync = value; }
-    else if (s == "aux_cus") {   // takes effect for slots created afterwards (set it before the first search)
-        if (!in_range(-1, 128)) return fail(VF_EINVAL, "aux_cus must be -1 (auto) or in [0, 128]");
-        if (ix->aux_applied >= 0 && value != ix->aux_cus)
-            return fail(VF_EINVAL, "aux_cus is fixed once the first search has created the scan streams: set it before searching");
-        ix->aux_cus = value;
-    }
-    else if (s == "sample_grid") { if (!in_range(-1, 1024)) return fail(VF_EINVAL, "sample_grid must be -1 (auto), 0 (one workgroup per range) or a workgroup count"); ix->sample_grid = value; }
-    else if (s == "scan_impl") { if (!in_range(1, 5)) return fail(VF_EINVAL, "scan_impl must be 1 (k_scan), 2 (auto: k_scan2 for fp16 rows, k_scan2r where it measured faster), 3 (k_scan2 wherever it fits, e4m3 rows converted), 4 (k_scan2 for fp16 rows, never k_scan2r) or 5 (k_scan2r wherever a shape of it exists: fp16 rows of 384 / 512 / 768 / 1024 elements, e4m3 rows of 768 / 1024)"); ix->scan_impl = value; }
-    else if (s == "sample_impl") { if (!in_range(-1, 1)) return fail(VF_EINVAL, "sample_impl must be -1 (auto: k_scan2r's operand path for the sample pass where it exists and the CU split is on), 0 (k_scan) or 1 (k_scan2r wherever it fits)"); ix->sample_impl = value; }
-    else if (s == "overlap_scans") { if (!in_range(-1, 1)) return fail(VF_EINVAL, "overlap_scans must be -1 (auto), 0 or 1"); ix->overlap_scans = value; }
-    else if (s == "scan_image") {
-        if (!in_range(0, 2)) return fail(VF_EINVAL, "scan_image must be 0 (off), 1 (auto: when it fits with headroom) or 2 (force)");
-        if (ix->damaged) return fail(VF_EHIP, std::string("scan_image: ") + kDamagedMsg);
-        if (!ix->shards.empty()) { ix->scan_image = value; return VF_OK; }   // (the shards have built or dropped theirs above)
-        for (const Slot& sl : ix->slots) if (sl.pending) return fail(VF_EINVAL, "scan_image cannot change while a search is pending");
-        DeviceGuard restore_callers_device;
-        VF_HIP(hipSetDevice(ix->device));
-        VF_HIP(hipDeviceSynchronize());
-        ix->image_refused = false;
-        if (value == 0) free_image(ix);
-        else VF_TRY(build_image(ix, value));
-        ix->scan_image = value;
-    }
-    else if (s == "image_mfma") { if (!in_range(-1, 2)) return fail(VF_EINVAL, "image_mfma must be -1 (auto), 0 (the int8 row image on the fp16 matrix instruction, fp16 queries), 1 (on the int8 matrix instruction, the queries as one int8 plane) or 2 (as two planes, hi + lo: the band of 0)"); ix->image_mfma = value; }
-    else if (s == "wide_rows") { if (!in_range(0, 2)) return fail(VF_EINVAL, std::string("wide_rows must be 0 (rows of more than 2432 padded elements never take the fused path), 1 (auto: from ") + std::to_string(kWideRowsMinRows) + " rows, e4m3 rows from " + std::to_string(kWideRowsMinRows8) + ", int8 rows from " + std::to_string(kWideRowsMinRowsI8) + ") or 2 (wherever k_scan_ksplit / k_scan_ksplit8 serve them; int8 rows: from " + std::to_string(kWideRowsMinRowsI8) + " rows)"); ix->wide_rows = value; }
-    else if (s == "compact_chunk_rows") { if (!in_range(0, kMaxShardRows)) return fail(VF_EINVAL, "compact_chunk_rows must be 0 (auto: 64 MB of staging) or the destination rows a removal moves per chunk"); ix->compact_chunk_rows = value; }
-    else if (s == "subset_super_rows") { if (!in_range(0, kSubsetMaxRows)) return fail(VF_EINVAL, "subset_super_rows must be 0 (auto: 64 MB of scores) or the listed rows a subset search scores per launch"); ix->subset_super_rows = value; }
-    else if (s == "debug") ix->debug = value;
-    else if (s == "profile") {
+    if (strcmp(name, "profile") == 0) {
         ix->profile = value != 0; ix->prof_scan_ms = ix->prof_pipe_ms = 0.0; ix->prof_launches = 0;
         ix->span_started = false;
         for (bool& b : ix->span_slot) b = false;
+        return VF_OK;
     }
-    else return fail(VF_EINVAL, "vf_index_set_option: unknown option " + s);
+    // the table's check (vf_options.h) runs on a copy: the handle takes the value once what it has to do for it has succeeded
+    Options o = ix->opt;
+    std::string msg;
+    if (option_set(o, name, value, &msg) != kOptionStored) return fail(VF_EINVAL, msg);
+    if (o.aux_cus != ix->opt.aux_cus && ix->aux_applied >= 0)   // takes effect for slots created afterwards (set it before the first search)
+        return fail(VF_EINVAL, "aux_cus is fixed once the first search has created the scan streams: set it before searching");
+    if (strcmp(name, "scan_image") == 0) {
+        if (ix->damaged) return fail(VF_EHIP, std::string("scan_image: ") + kDamagedMsg);
+        if (ix->shards.empty()) {   // (a group's shards have built or dropped theirs above)
+            for (const Slot& sl : ix->slots) if (sl.pending) return fail(VF_EINVAL, "scan_image cannot change while a search is pending");
+            DeviceGuard restore_callers_device;
+            VF_HIP(hipSetDevice(ix->device));
+            VF_HIP(hipDeviceSynchronize());
+            ix->image_refused = false;
+            if (value == 0) free_image(ix);
+            else VF_TRY(build_image(ix, value));
+        }
+    }
+    ix->opt = o;
     return VF_OK;
 }
 
@@ -1258,169 +1219,162 @@ extern "C" int vf_debug_image_q8_bound(float rho_q, float eps_img, int32_t tau_b
     return VF_OK;
 }
 
-// ---- wide passes (k_scan_wide): up to 1024 queries share ONE read of the shard --------------------------------------
-static int wide_pass(vf_index* ix, Slot& s, const RouteIn& in, const FusedPlan& p0, const float* d_queries, int nb, int k, int64_t* d_ids,
-                     float* d_scores, int flag_off, float* qn_b, bool timed, hipStream_t st, int slot_id) {
-    const WidePass w = route_wide_pass(in, p0, nb);
-    const int qtot = w.qtot, J = w.jtiles, RG = w.rgroups, samp = w.samp;
-    const bool w8 = w.main == kKernelWide8;
-    FusedPlan p = p0;
-    p.cap = w.cap;
-    const size_t slen = (size_t)RG * samp * 8;
-    VF_TRY(s.qimg.ensure((size_t)ix->dp * qtot * 2));
-    VF_TRY(s.s0.ensure((size_t)qtot * slen * sizeof(float)));
-    VF_TRY(s.cnt.ensure((size_t)qtot * kCntStride * sizeof(u32)));
-    VF_TRY(s.tau.ensure((size_t)qtot * sizeof(int)));
-    VF_TRY(s.hist.ensure((size_t)qtot * kHistBins * sizeof(u32)));
-    VF_TRY(s.hist_coarse.ensure((size_t)qtot * 64 * sizeof(u32)));
-    VF_TRY(s.cand.ensure((size_t)qtot * p.cap * sizeof(u64)));
-    if (s.wgbase_n != ix->n || s.wgbase_grid != -RG) {   // negative grid tag: the row-group table of the wide scan
-        std::vector<long long> base(RG);
-        for (int w = 0; w < RG; ++w) base[w] = ix->n * (long long)w / RG;
-        VF_TRY(s.wgbase.ensure((size_t)RG * sizeof(long long)));
-        VF_HIP(hipMemcpyAsync(s.wgbase.p, base.data(), (size_t)RG * sizeof(long long), hipMemcpyHostToDevice, st));
-        VF_HIP(hipStreamSynchronize(st));
-        s.wgbase_n = ix->n; s.wgbase_grid = -RG;
-    }
-    VF_HIP(launch_prep_queries(d_queries, nb, ix->d, ix->dp, qtot, qn_b, s.qimg.as<_Float16>(), st));
-    if (w8) {
-        VF_TRY(s.qimg8.ensure((size_t)ix->dp * qtot * 2));
-        VF_TRY(s.epsq.ensure((size_t)qtot * sizeof(float)));
-        VF_HIP(launch_prep_wide8(qn_b, nb, ix->d, ix->dp, qtot, (unsigned char*)s.qimg8.p, s.epsq.as<float>(), st));
-    }
-    const RowForm f8 = w.rows;
-    ScanArgs a{};
-    a.rows = (const char*)ix->rows_scan; a.inv_scan = ix->inv_scan; a.qimg = s.qimg.as<_Float16>();
-    a.n = ix->n; a.dp = ix->dp; a.row_bytes = (long long)ix->dp * (f8 ? 1 : 2);
-    a.total_waves = RG * 8; a.samp = samp;
-    a.s0 = s.s0.as<float>(); a.wg_base = s.wgbase.as<long long>(); a.cnt = s.cnt.as<u32>(); a.tau_bin = s.tau.as<int>();
-    a.hist = s.hist.as<u32>(); a.hist_coarse = s.hist_coarse.as<u32>(); a.cand = s.cand.as<u64>(); a.cap = p.cap; a.kprime = p.kprime;
-    a.stage_cap = kWideStageCap; a.dbg = nullptr; a.debug = (int)ix->debug;
-    a.refresh_every = 1;   // a power of two on this path (block completion is tested with a mask)
-    while (a.refresh_every * 2 <= (int)std::min<int64_t>(256, std::max<int64_t>(1, ix->refresh_every))) a.refresh_every *= 2;
-    a.nq = nb; a.qn_total = qtot; a.jtiles = J; a.rgroups = RG;
-    if (ix->n / RG < (int64_t)samp * 8)   // sample slots no wave writes must read as empty (NaN)
-        VF_HIP(hipMemsetAsync(a.s0, 0xFF, (size_t)qtot * slen * sizeof(float), st));
-    VF_HIP(launch_scan_wide(a, kModeSample, f8, st));
-    VF_HIP(launch_sel0(a, qtot, st));
-    for (int o = 0; o < kSlots; ++o)
-        if (o != slot_id && ix->slots[o].ev_scan) VF_HIP(hipStreamWaitEvent(st, ix->slots[o].ev_scan, 0));
-    const int w8_waves = w.waves, J8 = w.main_jtiles;
-    if (J8 > 1 && ix->wide_sync >= 0) {   // sibling progress words of the main pass (see k_scan_wide; eight per row group)
-        VF_TRY(s.sib.ensure((size_t)RG * 8 * sizeof(u32)));
-        VF_HIP(hipMemsetAsync(s.sib.p, 0, (size_t)RG * 8 * sizeof(u32), st));
-        a.sib = s.sib.as<u32>(); a.sib_slack = (int)ix->wide_sync;
-    }
-    if (timed) VF_HIP(hipEventRecord(s.ev_t[0], st));
-    if (w8) {
-        ScanArgs a8 = a;
-        a8.qimg = (const _Float16*)s.qimg8.p;
-        a8.jtiles = J8;
-        a8.stage_cap = w.stage_cap;
-        if (ix->debug & 128) {   // per-wave phase times of k_scan_wide8 (vf_index_debug_read)
-            VF_TRY(s.dbg.ensure((size_t)8 * J8 * ((RG + 7) / 8) * w8_waves * 16 * sizeof(u64)));
-            VF_HIP(hipMemsetAsync(s.dbg.p, 0, s.dbg.bytes, st));
-            a8.dbg = s.dbg.as<u64>();
-        }
-        VF_HIP(launch_scan_wide8(a8, w8_waves, st));
-    } else
-        VF_HIP(launch_scan_wide(a, kModeMain, f8, st));
-    VF_HIP(hipEventRecord(s.ev_scan, st));
-    if (timed) {
-        VF_HIP(hipEventRecord(s.ev_t[1], st));
-        const int64_t sampled = std::min<int64_t>(ix->n, (int64_t)RG * std::min<int64_t>((int64_t)samp * 8, ix->n / RG));
-        ix->prof_bytes = (ix->n - sampled) * ((int64_t)ix->d * (f8 ? 1 : 2) + 4);
-    }
-    FinalArgs f{};
-    f.cnt = a.cnt; f.cand = a.cand; f.cap = p.cap; f.tau_bin = a.tau_bin; f.rows_orig = ix->rows_orig;
-    f.orig_dtype = ix->dtype; f.orig_row_elems = ix->d; f.norm = ix->norm; f.qn = qn_b;
-    f.d = ix->d; f.k = k; f.kprime = p.kprime; f.eps = p.eps; f.n_rows = ix->n; f.id_offset = ix->id_offset;
-    f.eps_q = w8 ? s.epsq.as<float>() : nullptr;   // (the sample pass scored with fp16 queries: its bound is the smaller one)
-    f.out_ids = (long long*)d_ids; f.out_scores = d_scores;
-    f.flags = s.d_flags + flag_off; f.cand_count_out = s.d_counts + flag_off;
-    f.dbg = nullptr;
-    if (ix->debug & 256) { VF_TRY(s.dbg.ensure((size_t)qtot * 8 * sizeof(u64))); f.dbg = s.dbg.as<u64>(); }
-    VF_HIP(launch_final(f, nb, st));
-    s.scan_kernel = w.main;
+// ---- what the passes of a fused search share -----------------------------------------------------------------------------
+// The fused path's per-query state for `slots` query slots: `slen` sample scores and a candidate list of `cap` entries each.
+static int ensure_fused_bufs(Slot& s, size_t slots, size_t slen, size_t cap) {
+    VF_TRY(s.s0.ensure(slots * slen * sizeof(float)));
+    VF_TRY(s.cnt.ensure(slots * kCntStride * sizeof(u32)));
+    VF_TRY(s.tau.ensure(slots * sizeof(int)));
+    VF_TRY(s.hist.ensure(slots * kHistBins * sizeof(u32)));
+    VF_TRY(s.hist_coarse.ensure(slots * 64 * sizeof(u32)));
+    return s.cand.ensure(slots * cap * sizeof(u64));
+}
+
+// First row of every scan workgroup (k_sel0 maps sample slots back to rows) or, tagged with the negative count, of every row group of a
+// wide pass: uploaded when (n, groups) changed.  The copy goes on the slot's stream, which is then synchronised (`base` is host memory):
+// consecutive wide passes of one search can have different row-group counts, so the copy must be ordered behind the previous pass.
+// The narrow passes keep one grid for the whole search and need no such order -- they used a blocking hipMemcpy here; for them only the
+// synchronising call differs, on the first search after n or the grid changed.
+static int upload_row_bases(vf_index* ix, Slot& s, int groups, bool wide, hipStream_t st) {
+    const int tag = wide ? -groups : groups;
+    if (s.wgbase_n == ix->n && s.wgbase_grid == tag) return VF_OK;
+    std::vector<long long> base(groups);
+    for (int w = 0; w < groups; ++w) base[w] = ix->n * (long long)w / groups;
+    VF_TRY(s.wgbase.ensure((size_t)groups * sizeof(long long)));
+    VF_HIP(hipMemcpyAsync(s.wgbase.p, base.data(), (size_t)groups * sizeof(long long), hipMemcpyHostToDevice, st));
+    VF_HIP(hipStreamSynchronize(st));
+    s.wgbase_n = ix->n; s.wgbase_grid = tag;
     return VF_OK;
 }
 
-static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq, int k, int64_t* d_ids,
-                      float* d_scores, hipStream_t user) {
-    Slot& s = ix->slots[slot_id];
-    if (s.pending) return fail(VF_EINVAL, "vf_index_search_begin: slot already has a pending search");
-    const int path = route_path(route_in(ix), k);
-    if (path < 0) return fail(VF_EUNSUPPORTED, "forced fused path is not possible for this n / k / d");
-    if (path != 1 && ix->n > kSmallN && k > 8192)  // checked before anything is enqueued (k_merge_topk's LDS sort)
-        return fail(VF_EUNSUPPORTED, "exact chunked search supports k <= 8192 when n > 16384");
-    VF_TRY(ensure_slot(ix, s));
-    VF_HIP(hipEventRecord(s.ev_in, user));
-    VF_HIP(hipStreamWaitEvent(s.stream, s.ev_in, 0));
+// What every kernel of a pass of nb queries is given alike, wide or not: the rows as stored and their inverse norms, the fp16 query image,
+// the slot's counters, thresholds, histograms and candidate lists.  The caller adds its geometry and the operands that are its own.
+static ScanArgs scan_args(const vf_index* ix, const Slot& s, const FusedPlan& p, int nb) {
+    ScanArgs a{};
+    a.rows = (const char*)ix->rows_scan; a.inv_scan = ix->inv_scan; a.qimg = s.qimg.as<_Float16>();
+    a.n = ix->n; a.dp = ix->dp; a.row_bytes = (long long)ix->dp * (byte_rows(ix->dtype) ? 1 : 2);
+    a.s0 = s.s0.as<float>(); a.wg_base = s.wgbase.as<long long>(); a.cnt = s.cnt.as<u32>(); a.tau_bin = s.tau.as<int>();
+    a.hist = s.hist.as<u32>(); a.hist_coarse = s.hist_coarse.as<u32>(); a.cand = s.cand.as<u64>(); a.cap = p.cap; a.kprime = p.kprime;
+    a.nq = nb; a.debug = (int)ix->opt.debug;
+    return a;
+}
+
+// ... and k_final: the candidate lists, the rows as given for the re-score, the pass's queries, where its results and flags go
+static FinalArgs final_args(const vf_index* ix, const Slot& s, const FusedPlan& p, int k, const float* qn_b, int64_t* d_ids, float* d_scores,
+                            int flag_off) {
+    FinalArgs f{};
+    f.cnt = s.cnt.as<u32>(); f.cand = s.cand.as<u64>(); f.cap = p.cap; f.tau_bin = s.tau.as<int>(); f.rows_orig = ix->rows_orig;
+    f.orig_dtype = ix->dtype; f.orig_row_elems = ix->d; f.norm = ix->norm; f.qn = qn_b;
+    f.d = ix->d; f.k = k; f.kprime = p.kprime; f.eps = p.eps; f.n_rows = ix->n; f.id_offset = ix->id_offset;
+    f.out_ids = (long long*)d_ids; f.out_scores = d_scores;
+    f.flags = s.d_flags + flag_off; f.cand_count_out = s.d_counts + flag_off;
+    return f;
+}
+
+// The three ways a pending search (the slot's d_queries, nq, k, d_ids, d_scores) is enqueued on the slot's streams; begin_impl records
+// ev_done behind whichever ran.
+static int begin_exact(vf_index* ix, Slot& s, int per_pass) {
     hipStream_t st = s.stream;
-    // (after ensure_slot: the plan's grid and the sample pass follow the CU split as it was applied to this slot's streams)
-    const RouteIn in = route_in(ix, &s);
-    const SearchRoute r = route_search(in, nq, k);
-    const int bl = r.per_pass;
-    VF_TRY(s.qn.ensure((size_t)std::max(nq, 1) * ix->d * sizeof(float)));
-    VF_TRY(s.qimg.ensure(scan_lds_bytes(ix->dp, kMaxBatch)));
-    VF_TRY(ensure_pinned(s, (size_t)nq));
-    s.pending = true; s.d_queries = d_queries; s.nq = nq; s.k = k; s.d_ids = d_ids; s.d_scores = d_scores;
-    s.path = path; s.user_stream = user; s.wide_launches = 0; s.wide_queries = 0; s.scan_kernel = 0;
-    if (nq == 0 || k == 0) { VF_HIP(hipEventRecord(s.ev_done, st)); return VF_OK; }
-
-    if (path != 1) {
-        for (int b0 = 0; b0 < nq; b0 += bl) {
-            const int nb = std::min(bl, nq - b0);
-            VF_HIP(launch_prep_queries(d_queries + (size_t)b0 * ix->d, nb, ix->d, ix->dp, qn_tile_for(nb),
-                                       s.qn.as<float>() + (size_t)b0 * ix->d, s.qimg.as<_Float16>(), st));
-            VF_TRY(exact_search(ix, s, s.qn.as<float>() + (size_t)b0 * ix->d, nb, k, d_ids + (size_t)b0 * k,
-                                d_scores + (size_t)b0 * k, st));
-        }
-        VF_HIP(hipEventRecord(s.ev_done, st));
-        return VF_OK;
+    for (int b0 = 0; b0 < s.nq; b0 += per_pass) {
+        const int nb = std::min(per_pass, s.nq - b0);
+        float* qn_b = s.qn.as<float>() + (size_t)b0 * ix->d;
+        VF_HIP(launch_prep_queries(s.d_queries + (size_t)b0 * ix->d, nb, ix->d, ix->dp, qn_tile_for(nb), qn_b, s.qimg.as<_Float16>(), st));
+        VF_TRY(exact_search(ix, s, qn_b, nb, s.k, s.d_ids + (size_t)b0 * s.k, s.d_scores + (size_t)b0 * s.k, st));
     }
+    return VF_OK;
+}
 
+// ---- wide passes (k_scan_wide): up to 1024 queries share ONE read of the shard --------------------------------------
+static int begin_wide(vf_index* ix, int slot_id, const RouteIn& in, const SearchRoute& r) {
+    Slot& s = ix->slots[slot_id];
+    hipStream_t st = s.stream;
+    const int64_t debug = ix->opt.debug;
+    s.timed = ix->profile;
+    if (s.timed) VF_HIP(hipEventRecord(s.ev_t[2], st));
+    for (int b0 = 0; b0 < s.nq; b0 += r.per_pass) {
+        const int nb = std::min(r.per_pass, s.nq - b0);
+        const bool timed = s.timed && b0 == 0;
+        const float* q_b = s.d_queries + (size_t)b0 * ix->d;
+        float* qn_b = s.qn.as<float>() + (size_t)b0 * ix->d;
+        const WidePass w = route_wide_pass(in, r.plan, nb);
+        const int qtot = w.qtot, RG = w.rgroups;
+        const bool w8 = w.main == kKernelWide8;
+        FusedPlan p = r.plan;
+        p.cap = w.cap;
+        const size_t slen = (size_t)RG * w.samp * 8;
+        VF_TRY(s.qimg.ensure((size_t)ix->dp * qtot * 2));
+        VF_TRY(ensure_fused_bufs(s, (size_t)qtot, slen, (size_t)p.cap));
+        VF_TRY(upload_row_bases(ix, s, RG, true, st));
+        VF_HIP(launch_prep_queries(q_b, nb, ix->d, ix->dp, qtot, qn_b, s.qimg.as<_Float16>(), st));
+        if (w8) {
+            VF_TRY(s.qimg8.ensure((size_t)ix->dp * qtot * 2));
+            VF_TRY(s.epsq.ensure((size_t)qtot * sizeof(float)));
+            VF_HIP(launch_prep_wide8(qn_b, nb, ix->d, ix->dp, qtot, (unsigned char*)s.qimg8.p, s.epsq.as<float>(), st));
+        }
+        ScanArgs a = scan_args(ix, s, p, nb);
+        a.total_waves = RG * 8; a.samp = w.samp; a.stage_cap = kWideStageCap; a.refresh_every = w.refresh_every;
+        a.qn_total = qtot; a.jtiles = w.jtiles; a.rgroups = RG;
+        if (w.clear_sample)   // sample slots no wave writes must read as empty (NaN)
+            VF_HIP(hipMemsetAsync(a.s0, 0xFF, (size_t)qtot * slen * sizeof(float), st));
+        VF_HIP(launch_scan_wide(a, kModeSample, w.rows, st));
+        VF_HIP(launch_sel0(a, qtot, st));
+        for (int o = 0; o < kSlots; ++o)
+            if (o != slot_id && ix->slots[o].ev_scan) VF_HIP(hipStreamWaitEvent(st, ix->slots[o].ev_scan, 0));
+        if (w.main_jtiles > 1 && ix->opt.wide_sync >= 0) {   // sibling progress words of the main pass (see k_scan_wide; eight per row group)
+            VF_TRY(s.sib.ensure((size_t)RG * 8 * sizeof(u32)));
+            VF_HIP(hipMemsetAsync(s.sib.p, 0, (size_t)RG * 8 * sizeof(u32), st));
+            a.sib = s.sib.as<u32>(); a.sib_slack = (int)ix->opt.wide_sync;
+        }
+        if (timed) VF_HIP(hipEventRecord(s.ev_t[0], st));
+        if (w8) {
+            ScanArgs a8 = a;
+            a8.qimg = (const _Float16*)s.qimg8.p;
+            a8.jtiles = w.main_jtiles;
+            a8.stage_cap = w.stage_cap;
+            if (debug & 128) {   // per-wave phase times of k_scan_wide8 (vf_index_debug_read)
+                VF_TRY(s.dbg.ensure((size_t)8 * w.main_jtiles * ((RG + 7) / 8) * w.waves * 16 * sizeof(u64)));
+                VF_HIP(hipMemsetAsync(s.dbg.p, 0, s.dbg.bytes, st));
+                a8.dbg = s.dbg.as<u64>();
+            }
+            VF_HIP(launch_scan_wide8(a8, w.waves, st));
+        } else
+            VF_HIP(launch_scan_wide(a, kModeMain, w.rows, st));
+        VF_HIP(hipEventRecord(s.ev_scan, st));
+        if (timed) {
+            VF_HIP(hipEventRecord(s.ev_t[1], st));
+            ix->prof_bytes = w.scan_bytes;
+        }
+        FinalArgs f = final_args(ix, s, p, s.k, qn_b, s.d_ids + (size_t)b0 * s.k, s.d_scores + (size_t)b0 * s.k, b0);
+        f.eps_q = w8 ? s.epsq.as<float>() : nullptr;   // (the sample pass scored with fp16 queries: its bound is the smaller one)
+        if (debug & 256) { VF_TRY(s.dbg.ensure((size_t)qtot * 8 * sizeof(u64))); f.dbg = s.dbg.as<u64>(); }
+        VF_HIP(launch_final(f, nb, st));
+        s.scan_kernel = w.main;
+        ++s.wide_launches; s.wide_queries += nb;
+    }
+    if (s.timed) VF_HIP(hipEventRecord(s.ev_t[3], st));
+    return VF_OK;
+}
+
+// ---- passes of up to 64 queries: sample pass, threshold seed, main scan (on the scan stream), k_final ---------------------------
+static int begin_narrow(vf_index* ix, int slot_id, const RouteIn& in, const SearchRoute& r) {
+    Slot& s = ix->slots[slot_id];
+    hipStream_t st = s.stream, sst = s.scan_stream;
     const FusedPlan& p = r.plan;
-    s.scan_image = r.image ? 1 : 0;
-    s.image_i8 = r.planes;
-    if (r.wide) {
-        s.timed = ix->profile;
-        if (s.timed) VF_HIP(hipEventRecord(s.ev_t[2], st));
-        for (int b0 = 0; b0 < nq; b0 += bl) {
-            const int nb = std::min(bl, nq - b0);
-            VF_TRY(wide_pass(ix, s, in, p, d_queries + (size_t)b0 * ix->d, nb, k, d_ids + (size_t)b0 * k, d_scores + (size_t)b0 * k,
-                             b0, s.qn.as<float>() + (size_t)b0 * ix->d, s.timed && b0 == 0, st, slot_id));
-            ++s.wide_launches; s.wide_queries += nb;
-        }
-        if (s.timed) VF_HIP(hipEventRecord(s.ev_t[3], st));
-        VF_HIP(hipEventRecord(s.ev_done, st));
-        return VF_OK;
-    }
-    VF_TRY(s.s0.ensure((size_t)kMaxBatch * p.total_waves * p.samp * sizeof(float)));
-    VF_TRY(s.cnt.ensure((size_t)kMaxBatch * kCntStride * sizeof(u32)));
-    VF_TRY(s.tau.ensure(kMaxBatch * sizeof(int)));
-    VF_TRY(s.hist.ensure((size_t)kMaxBatch * kHistBins * sizeof(u32)));
-    VF_TRY(s.hist_coarse.ensure((size_t)kMaxBatch * 64 * sizeof(u32)));
-    VF_TRY(s.cand.ensure((size_t)kMaxBatch * p.cap * sizeof(u64)));
+    const int64_t debug = ix->opt.debug;
+    VF_TRY(ensure_fused_bufs(s, kMaxBatch, (size_t)p.total_waves * p.samp, (size_t)p.cap));
     VF_TRY(s.tilecnt.ensure((size_t)p.grid * sizeof(u32)));
     s.timed = ix->profile;
     if (s.timed) VF_HIP(hipEventRecord(s.ev_t[2], st));
-    if (s.wgbase_n != ix->n || s.wgbase_grid != p.grid) {  // first row of every scan workgroup (k_sel0 maps sample slots back to rows)
-        std::vector<long long> base(p.grid);
-        for (int w = 0; w < p.grid; ++w) base[w] = ix->n * (long long)w / p.grid;
-        VF_TRY(s.wgbase.ensure((size_t)p.grid * sizeof(long long)));
-        VF_HIP(hipMemcpy(s.wgbase.p, base.data(), (size_t)p.grid * sizeof(long long), hipMemcpyHostToDevice));
-        s.wgbase_n = ix->n; s.wgbase_grid = p.grid;
-    }
-    for (int b0 = 0; b0 < nq; b0 += bl) {
-        const int nb = std::min(bl, nq - b0);
+    VF_TRY(upload_row_bases(ix, s, p.grid, false, st));
+    for (int b0 = 0; b0 < s.nq; b0 += r.per_pass) {
+        const int nb = std::min(r.per_pass, s.nq - b0);
+        const bool timed = s.timed && b0 == 0;
         const BatchRoute b = route_batch(in, r, nb);
         const int qt = b.tile;
         float* qn_b = s.qn.as<float>() + (size_t)b0 * ix->d;
         // (the int8 plane replaces the fp16 image: that one is not built)
-        VF_HIP(launch_prep_queries(d_queries + (size_t)b0 * ix->d, nb, ix->d, ix->dp, qt, qn_b, s.image_i8 ? nullptr : s.qimg.as<_Float16>(), st));
-        ScanArgs a{};
-        a.rows = (const char*)ix->rows_scan; a.inv_scan = ix->inv_scan; a.qimg = s.qimg.as<_Float16>();
+        VF_HIP(launch_prep_queries(s.d_queries + (size_t)b0 * ix->d, nb, ix->d, ix->dp, qt, qn_b, s.image_i8 ? nullptr : s.qimg.as<_Float16>(), st));
+        ScanArgs a = scan_args(ix, s, p, nb);
         if (s.image_i8) {
             VF_TRY(s.qimg8.ensure((size_t)ix->dp * kMaxBatch * 2));
             VF_TRY(s.epsq.ensure(kMaxBatch * sizeof(float)));
@@ -1430,26 +1384,13 @@ static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq,
                                   p.eps, p.tau_band, p.fine_band, st));
             a.qimg = (const _Float16*)s.qimg8.p; a.q_scale = s.qscale.as<float>(); a.band_q = s.bandq.as<int>();
         }
-        a.n = ix->n; a.dp = ix->dp; a.row_bytes = (long long)ix->dp * (byte_rows(ix->dtype) ? 1 : 2); a.total_waves = p.total_waves; a.samp = p.samp;
         if (p.image) { a.rows = (const char*)ix->rows_img; a.inv_scan = ix->inv_img; a.off_scan = image_offsets(ix); a.row_bytes = ix->dp; }   // every pass of the batch: sample, seed, main
-        a.s0 = s.s0.as<float>(); a.wg_base = s.wgbase.as<long long>(); a.cnt = s.cnt.as<u32>(); a.tau_bin = s.tau.as<int>(); a.hist = s.hist.as<u32>();
-        a.cand = s.cand.as<u64>(); a.cap = p.cap; a.kprime = p.kprime; a.tau_band = p.tau_band;
-        a.hist_coarse = s.hist_coarse.as<u32>(); a.stage_cap = b.stage_cap;
-        a.tile_cnt = ix->steal_opt ? s.tilecnt.as<u32>() : nullptr; a.scan_grid = p.grid;
-        a.dbg = nullptr;
-        if (ix->debug & 128) { VF_TRY(s.dbg.ensure((size_t)p.total_waves * ((ix->debug & 512) ? 72 : 4) * sizeof(u64))); a.dbg = s.dbg.as<u64>(); if (ix->debug & 512) VF_HIP(hipMemsetAsync(s.dbg.p, 0, s.dbg.bytes, st)); }
-        // A workgroup publishes its staged candidates (and refreshes one threshold) per BLOCK of refresh_every staged entries,
-        // whatever query they belong to: the option is stated for a full 64-query batch and scales with the batch's query
-        // count, so that a query sees the same publication granularity at nq = 1 as at nq = 64.  (Unscaled, a single
-        // query over 5M rows staged ~76 entries per workgroup, never completed a 128-entry block, never raised its
-        // threshold above the sample's and overflowed its candidate list: exact re-run, 38 ms instead of 1.5.)
-        // (rounded down to a power of two: the kernels find a block's number with a shift)
-        a.refresh_every = (int)std::min<int64_t>(256, std::max<int64_t>(4, std::max<int64_t>(1, ix->refresh_every) * nb / kMaxBatch));
-        while (a.refresh_every & (a.refresh_every - 1)) a.refresh_every &= a.refresh_every - 1;
-        a.nq = nb; a.debug = (int)ix->debug;
+        a.total_waves = p.total_waves; a.samp = p.samp; a.tau_band = p.tau_band; a.stage_cap = b.stage_cap; a.refresh_every = b.refresh_every;
+        a.tile_cnt = ix->opt.steal ? s.tilecnt.as<u32>() : nullptr; a.scan_grid = p.grid;
+        if (debug & 128) { VF_TRY(s.dbg.ensure((size_t)p.total_waves * ((debug & 512) ? 72 : 4) * sizeof(u64))); a.dbg = s.dbg.as<u64>(); if (debug & 512) VF_HIP(hipMemsetAsync(s.dbg.p, 0, s.dbg.bytes, st)); }
         // sample slots no wave writes (a wave range shorter than samp) must read as empty: 0xFF bytes
-        // are a NaN, which k_sel0's "v > -inf" test skips.  Never needed once n >= TW * samp.
-        if (ix->n / p.total_waves < p.samp)
+        // are a NaN, which k_sel0's "v > -inf" test skips.
+        if (b.clear_sample)
             VF_HIP(hipMemsetAsync(a.s0, 0xFF, (size_t)qt * p.total_waves * p.samp * sizeof(float), st));
         switch (b.sample) {
         case kKernelKsplit: VF_HIP(launch_scan_ksplit(a, kModeSample, b.sample_grid, st)); break;
@@ -1460,10 +1401,9 @@ static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq,
             VF_HIP(launch_scan2r_sample(as, qt, b.sample_grid, b.sample_rows, st));
             break;
         }
-        default: VF_HIP(launch_scan(a, kModeSample, qt, b.sample_grid, (int)ix->scan_g, b.sample_rows, st));
+        default: VF_HIP(launch_scan(a, kModeSample, qt, b.sample_grid, (int)ix->opt.scan_g, b.sample_rows, st));
         }
         VF_HIP(launch_sel0(a, qt, st));
-        hipStream_t sst = s.scan_stream;
         if (sst != st) {   // the main scan runs on the CU-masked stream, behind this slot's prologue
             VF_HIP(hipEventRecord(s.ev_pro, st));
             VF_HIP(hipStreamWaitEvent(sst, s.ev_pro, 0));
@@ -1474,7 +1414,7 @@ static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq,
         if (!route_overlap(in))
             for (int o = 0; o < kSlots; ++o)
                 if (o != slot_id && ix->slots[o].ev_scan) VF_HIP(hipStreamWaitEvent(sst, ix->slots[o].ev_scan, 0));
-        if (s.timed && b0 == 0) {
+        if (timed) {
             if (!ix->span_started) {   // makespan of the timed launches: from here to the last launch's end (vf_index_profile_span)
                 if (!ix->ev_span) VF_HIP(hipEventCreate(&ix->ev_span));
                 VF_HIP(hipEventRecord(ix->ev_span, sst));
@@ -1490,7 +1430,7 @@ static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq,
         case kKernelScan2: {
             ScanArgs a2 = a;
 #ifdef VF_EXPERIMENTS
-            if (ix->debug & 32) {   // timing experiment: compute unit -> range table (k_scan2, debug bit 5)
+            if (debug & 32) {   // timing experiment: compute unit -> range table (k_scan2, debug bit 5)
                 const bool fresh = s.sib.bytes < 4096;
                 VF_TRY(s.sib.ensure(4096));
                 if (fresh) VF_HIP(hipMemsetAsync(s.sib.p, 0xFF, 4096, st));
@@ -1500,31 +1440,80 @@ static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq,
             VF_HIP(launch_scan2(a2, qt, p.grid, b.main_rows, sst));
             break;
         }
-        default: VF_HIP(launch_scan(a, kModeMain, qt, p.grid, (int)ix->scan_g, b.main_rows, sst));
+        default: VF_HIP(launch_scan(a, kModeMain, qt, p.grid, (int)ix->opt.scan_g, b.main_rows, sst));
         }
         s.scan_kernel = b.main;
         VF_HIP(hipEventRecord(s.ev_scan, sst));
-        if (s.timed && b0 == 0) {
+        if (timed) {
             VF_HIP(hipEventRecord(s.ev_t[1], sst));
-            const int64_t per_wave = ix->n / p.total_waves;
-            const int64_t sampled = std::min<int64_t>(ix->n, (int64_t)p.total_waves * std::min<int64_t>(p.samp, per_wave));
-            ix->prof_bytes = (ix->n - sampled) * (p.image ? (int64_t)ix->dp + 8 : (int64_t)ix->d * (byte_rows(ix->dtype) ? 1 : 2) + 4);
+            ix->prof_bytes = b.scan_bytes;
         }
         if (sst != st) VF_HIP(hipStreamWaitEvent(st, s.ev_scan, 0));
-        FinalArgs f{};
-        f.cnt = a.cnt; f.cand = a.cand; f.cap = p.cap; f.tau_bin = a.tau_bin; f.rows_orig = ix->rows_orig;
-        f.orig_dtype = ix->dtype; f.orig_row_elems = ix->d; f.norm = ix->norm; f.qn = qn_b;
-        f.d = ix->d; f.k = k; f.kprime = p.kprime; f.eps = p.eps; f.n_rows = ix->n; f.id_offset = ix->id_offset;
+        FinalArgs f = final_args(ix, s, p, s.k, qn_b, s.d_ids + (size_t)b0 * s.k, s.d_scores + (size_t)b0 * s.k, b0);
         f.band = p.fine_band;
         if (s.image_i8) { f.eps_q = s.epsq.as<float>(); f.band_q = s.bandq.as<int>() + qt; }
-        f.out_ids = (long long*)(d_ids + (size_t)b0 * k); f.out_scores = d_scores + (size_t)b0 * k;
-        f.flags = s.d_flags + b0; f.cand_count_out = s.d_counts + b0;
-        f.dbg = nullptr;
-        if (ix->debug & 256) { VF_TRY(s.dbg.ensure((size_t)std::max(p.total_waves * 4, 64 * 8) * sizeof(u64))); f.dbg = s.dbg.as<u64>(); }
+        if (debug & 256) { VF_TRY(s.dbg.ensure((size_t)std::max(p.total_waves * 4, 64 * 8) * sizeof(u64))); f.dbg = s.dbg.as<u64>(); }
         VF_HIP(launch_final(f, nb, st));
     }
     if (s.timed) VF_HIP(hipEventRecord(s.ev_t[3], st));
+    return VF_OK;
+}
+
+static int begin_impl(vf_index* ix, int slot_id, const float* d_queries, int nq, int k, int64_t* d_ids,
+                      float* d_scores, hipStream_t user) {
+    Slot& s = ix->slots[slot_id];
+    if (s.pending) return fail(VF_EINVAL, "vf_index_search_begin: slot already has a pending search");
+    const int path = route_path(route_in(ix), k);
+    if (path < 0) return fail(VF_EUNSUPPORTED, "forced fused path is not possible for this n / k / d");
+    if (path != 1 && ix->n > kSmallN && k > 8192)  // checked before anything is enqueued (k_merge_topk's LDS sort)
+        return fail(VF_EUNSUPPORTED, "exact chunked search supports k <= 8192 when n > 16384");
+    VF_TRY(ensure_slot(ix, s));
+    VF_HIP(hipEventRecord(s.ev_in, user));
+    VF_HIP(hipStreamWaitEvent(s.stream, s.ev_in, 0));
+    // (after ensure_slot: the plan's grid and the sample pass follow the CU split as it was applied to this slot's streams)
+    const RouteIn in = route_in(ix, &s);
+    const SearchRoute r = route_search(in, nq, k);
+    VF_TRY(s.qn.ensure((size_t)std::max(nq, 1) * ix->d * sizeof(float)));
+    VF_TRY(s.qimg.ensure(scan_lds_bytes(ix->dp, kMaxBatch)));
+    VF_TRY(ensure_pinned(s, (size_t)nq));
+    s.pending = true; s.d_queries = d_queries; s.nq = nq; s.k = k; s.d_ids = d_ids; s.d_scores = d_scores;
+    s.path = path; s.user_stream = user; s.wide_launches = 0; s.wide_queries = 0; s.scan_kernel = 0;
+    if (nq > 0 && k > 0) {
+        if (path != 1) VF_TRY(begin_exact(ix, s, r.per_pass));
+        else {
+            s.scan_image = r.image ? 1 : 0;
+            s.image_i8 = r.planes;
+            VF_TRY(r.wide ? begin_wide(ix, slot_id, in, r) : begin_narrow(ix, slot_id, in, r));
+        }
+    }
+    VF_HIP(hipEventRecord(s.ev_done, s.stream));
+    return VF_OK;
+}
+
+// repair: exact chunked search for the flagged queries `redo` of the slot's search only (still on the GPU), waited for
+static int repair_flagged(vf_index* ix, Slot& s, const std::vector<int>& redo) {
+    const int m = (int)redo.size();
+    hipStream_t st = s.stream;
+    VF_TRY(s.qsel.ensure((size_t)m * ix->d * sizeof(float) + (size_t)m * s.k * (sizeof(long long) + sizeof(float))));
+    float* qsel = s.qsel.as<float>();
+    long long* rid = (long long*)(qsel + (size_t)m * ix->d);
+    float* rsc = (float*)(rid + (size_t)m * s.k);
+    for (int i = 0; i < m; ++i)
+        VF_HIP(hipMemcpyAsync(qsel + (size_t)i * ix->d, s.qn.as<float>() + (size_t)redo[i] * ix->d,
+                              (size_t)ix->d * sizeof(float), hipMemcpyDeviceToDevice, st));
+    for (int i0 = 0; i0 < m; i0 += kMaxBatch) {
+        const int nb = std::min(kMaxBatch, m - i0);
+        VF_TRY(exact_search(ix, s, qsel + (size_t)i0 * ix->d, nb, s.k, (int64_t*)(rid + (size_t)i0 * s.k),
+                            rsc + (size_t)i0 * s.k, st));
+    }
+    for (int i = 0; i < m; ++i) {
+        VF_HIP(hipMemcpyAsync(s.d_ids + (size_t)redo[i] * s.k, rid + (size_t)i * s.k, (size_t)s.k * sizeof(long long),
+                              hipMemcpyDeviceToDevice, st));
+        VF_HIP(hipMemcpyAsync(s.d_scores + (size_t)redo[i] * s.k, rsc + (size_t)i * s.k, (size_t)s.k * sizeof(float),
+                              hipMemcpyDeviceToDevice, st));
+    }
     VF_HIP(hipEventRecord(s.ev_done, st));
+    VF_HIP(hipEventSynchronize(s.ev_done));
     return VF_OK;
 }
 
@@ -1559,30 +1548,8 @@ static int end_impl(vf_index* ix, int slot_id) {
             if (s.h_flags[q] != 0) redo.push_back(q);
         }
         if (!redo.empty()) {
-            // repair: exact chunked search for the flagged queries only (still on the GPU)
-            const int m = (int)redo.size();
-            hipStream_t st = s.stream;
-            VF_TRY(s.qsel.ensure((size_t)m * ix->d * sizeof(float) + (size_t)m * s.k * (sizeof(long long) + sizeof(float))));
-            float* qsel = s.qsel.as<float>();
-            long long* rid = (long long*)(qsel + (size_t)m * ix->d);
-            float* rsc = (float*)(rid + (size_t)m * s.k);
-            for (int i = 0; i < m; ++i)
-                VF_HIP(hipMemcpyAsync(qsel + (size_t)i * ix->d, s.qn.as<float>() + (size_t)redo[i] * ix->d,
-                                      (size_t)ix->d * sizeof(float), hipMemcpyDeviceToDevice, st));
-            for (int i0 = 0; i0 < m; i0 += kMaxBatch) {
-                const int nb = std::min(kMaxBatch, m - i0);
-                VF_TRY(exact_search(ix, s, qsel + (size_t)i0 * ix->d, nb, s.k, (int64_t*)(rid + (size_t)i0 * s.k),
-                                    rsc + (size_t)i0 * s.k, st));
-            }
-            for (int i = 0; i < m; ++i) {
-                VF_HIP(hipMemcpyAsync(s.d_ids + (size_t)redo[i] * s.k, rid + (size_t)i * s.k, (size_t)s.k * sizeof(long long),
-                                      hipMemcpyDeviceToDevice, st));
-                VF_HIP(hipMemcpyAsync(s.d_scores + (size_t)redo[i] * s.k, rsc + (size_t)i * s.k, (size_t)s.k * sizeof(float),
-                                      hipMemcpyDeviceToDevice, st));
-            }
-            VF_HIP(hipEventRecord(s.ev_done, st));
-            VF_HIP(hipEventSynchronize(s.ev_done));
-            stt.exact_reruns = m;
+            VF_TRY(repair_flagged(ix, s, redo));
+            stt.exact_reruns = (int)redo.size();
         }
     }
     // later work on the caller's stream sees the results
@@ -2308,7 +2275,7 @@ static int subset_host_plain(vf_index* ix, const float* queries, int nq, int k, 
     const int64_t lo = ix->id_offset, hi = ix->id_offset + ix->n;
     const long long bad = subset_first_bad((const long long*)ids, m, lo, hi);
     if (bad >= 0) return fail(VF_EINVAL, subset_bad_message(who, bad, ids[bad], bad > 0, bad > 0 ? ids[bad - 1] : 0, lo, hi));
-    const SubsetPlan p = subset_plan(ix->n, m, nq, k, ix->subset_super_rows, 0);
+    const SubsetPlan p = subset_plan(ix->n, m, nq, k, ix->opt.subset_super_rows, 0);
     if (p.route == kSubsetRefused) return fail(VF_EUNSUPPORTED, std::string(who) + ": " + p.why);
     if (p.route == kSubsetAll) return search_host_locked(ix, queries, nq, k, out_ids, out_sc);
     if (p.route == kSubsetEmpty) {
@@ -2396,7 +2363,7 @@ static int subset_entry_device(vf_index* ix, const vf_subset_query* sq, int32_t 
     if (ix->damaged) return fail(VF_EHIP, std::string(who) + ": " + kDamagedMsg);
     if (!ix->shards.empty()) return fail(VF_EUNSUPPORTED, std::string(who) + ": a group handle takes the host-buffer form only (vf_index_search with VF_SEARCH_SUBSET)");
     if (n_ids > ix->n) return fail(VF_EINVAL, std::string(who) + ": " + std::to_string(n_ids) + " ids for an index of " + std::to_string(ix->n) + " rows (the list must be strictly ascending)");
-    const SubsetPlan p = subset_plan(ix->n, n_ids, nq, k, ix->subset_super_rows, 0);
+    const SubsetPlan p = subset_plan(ix->n, n_ids, nq, k, ix->opt.subset_super_rows, 0);
     if (p.route == kSubsetRefused) return fail(VF_EUNSUPPORTED, std::string(who) + ": " + p.why);
     hipStream_t st = (hipStream_t)stream;
     const int64_t m = n_ids, lo = ix->id_offset, hi = ix->id_offset + ix->n;

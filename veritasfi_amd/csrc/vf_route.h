@@ -1,6 +1,7 @@
 // vf_route.h -- which kernels serve a search: the one decision every search makes, as a pure function of the handle's shape and options.
 // vf_api.hip fills a RouteIn from the handle (route_in), asks route_path / route_search once per search, route_batch or route_wide_pass
-// once per pass, and switches on the answer; allocation, streams, events and launches stay there.  Every threshold the choice rests on is
+// once per pass (their answers carry what the pass is launched with beside its kernels: the publication block, whether the sample slots
+// need clearing, the bytes a timed scan reads), and switches on the answer; allocation, streams, events and launches stay there.  Every threshold the choice rests on is
 // defined here, beside the record of where it was measured.  Plain C++17: no HIP and no vf_index, so a host-compiled driver
 // (tests/test_scan_route.py: UBSan, a table of pinned routes and an option sweep) evaluates it without a GPU.
 #pragma once
@@ -11,11 +12,12 @@
 
 #include "../../include/veritasfi_hip.h"  // VF_DTYPE_*
 #include "vf_ksplit_geom.h"               // + vf_scan_lds.h: the design constants, RowForm, every scan kernel's LDS budget
+#include "vf_options.h"                   // the option table: names, defaults, accepted values
 
 namespace vf {
 
-// What the choice depends on.  The option fields hold the option values as set (vf_index_set_option; -1 = auto where an option has one).
-struct RouteIn {
+// What the choice depends on: the option values as set (vf_options.h; -1 = auto where an option has one) and the handle's shape.
+struct RouteIn : Options {
     int64_t n = 0;
     int d = 0, dp = 0, dtype = 0, n_cu = 256;
     bool has_scan = false;      // the scan copy and its inverse norms exist (corpora of up to kSmallN rows are built without them)
@@ -24,9 +26,6 @@ struct RouteIn {
     bool group = false;         // a group handle (its shards route for themselves)
     int64_t aux_applied = -1;   // the CU split the first slot's streams were created with (-1: no slot yet)
     bool masked = false;        // this slot's scan stream is CU-masked
-    int64_t force_path = -1, wide = 1, wide_mfma = -1, wide8_waves = 8, wide8_stage = 0, wide_rows = 1, scan_impl = 2, sample_impl = -1,
-            sample_grid = -1, steal = 0, scan_image = 1, image_mfma = -1, aux_cus = -1, overlap_scans = -1, margin = -1, cap = 0, waves = 0,
-            sample_rows = -1, debug = 0;
 };
 
 // the scan kernels, by the code vf_search_stats.scan_kernel reports (veritasfi_hip.h); a sample pass is named by the same codes
@@ -62,6 +61,9 @@ struct BatchRoute {
     ScanKernel main;         // the main scan
     RowForm main_rows;
     int stage_cap;           // its LDS candidate stage, in entries
+    int refresh_every;       // staged entries per published block: a power of two (the kernels find a block's number with a shift)
+    bool clear_sample;       // a wave range is shorter than the sample: the slots no wave writes must be cleared first
+    int64_t scan_bytes;      // what the main scan reads from HBM (vf_index_profile's scan_bytes_per_launch)
 };
 
 // One wide pass of nb <= kWideMaxQueries queries.
@@ -74,6 +76,9 @@ struct WidePass {
     int samp;                // sample rows per row group = samp * 8: 32768 / 65536 rows in all
     int stage_cap;           // the main pass's LDS candidate stage
     int cap;                 // candidate slots per query (the plan's, raised for deep k)
+    int refresh_every;       // staged entries per published block: a power of two (block completion is tested with a mask)
+    bool clear_sample;       // a row group is shorter than its sample: the slots no wave writes must be cleared first
+    int64_t scan_bytes;      // what the main pass reads from HBM (vf_index_profile's scan_bytes_per_launch)
 };
 
 // One byte per element in HBM (e4m3 codes, or the biased bytes of an int8 index): scanned as bytes with the e4m3 geometry, converted in
@@ -148,6 +153,9 @@ constexpr int64_t kWideRowsMinRows8 = 32768;
 // there), and below it the behaviour of int8 rows is pinned by tests/test_gpu_int8_rows.py::
 // test_int8_chunked_exact_path_and_rows_of_2560_elements (17 000 x 2560: path 2 under wide_rows = 1 and 2, force_path = 1 refused).
 constexpr int64_t kWideRowsMinRowsI8 = 32768;
+inline std::string wide_rows_refusal() {   // (declared in vf_options.h: the wide_rows row of the table)
+    return std::string("wide_rows must be 0 (rows of more than 2432 padded elements never take the fused path), 1 (auto: from ") + std::to_string(kWideRowsMinRows) + " rows, e4m3 rows from " + std::to_string(kWideRowsMinRows8) + ", int8 rows from " + std::to_string(kWideRowsMinRowsI8) + ") or 2 (wherever k_scan_ksplit / k_scan_ksplit8 serve them; int8 rows: from " + std::to_string(kWideRowsMinRowsI8) + " rows)";
+}
 inline int ksplit_stage_cap(const RouteIn& in) { return byte_rows(in.dtype) ? ks8_stage_cap(in.dp) : scan_ksplit_stage_cap(in.dp); }
 inline bool ksplit_serves(const RouteIn& in, bool forced) {
     if (in.wide_rows == 0 || ksplit_stage_cap(in) < kStageMinEntries) return false;
@@ -231,7 +239,7 @@ inline int image_planes(const RouteIn& in, int qt) {   // 0: the fp16 instructio
 }
 
 // the int8 image serves a fused batch when it exists, k is within kImageMaxK and the scans are k_scan2r's (the options that pick another
-// kernel, the tile pool or k_scan's sample pass keep the rows as stored); wide passes never reach it (wide_pass returns before)
+// kernel, the tile pool or k_scan's sample pass keep the rows as stored); wide passes never reach it (route_search decides them first)
 inline bool image_serves(const RouteIn& in, int k, int qt) {
     return in.has_image && k <= kImageMaxK && (in.scan_impl == 2 || in.scan_impl == 5) && !in.steal && in.sample_impl != 0 &&
            scan2r_stage_cap(in.dp, qt, kRowsI8) >= kStageMinEntries;
@@ -365,6 +373,12 @@ inline WidePass route_wide_pass(const RouteIn& in, const FusedPlan& p, int nb) {
     w.main_jtiles = w8 && w.waves == 4 ? (nb + 127) / 128 : w.jtiles;
     w.stage_cap = !w8 ? kWideStageCap
                       : in.wide8_stage > 0 ? (int)std::min<int64_t>(in.wide8_stage, scan_wide8_stage_cap(w.waves)) : scan_wide8_stage_cap(w.waves);
+    w.refresh_every = 1;
+    while (w.refresh_every * 2 <= (int)std::min<int64_t>(256, std::max<int64_t>(1, in.refresh_every))) w.refresh_every *= 2;
+    const int64_t group_rows = in.n / w.rgroups, group_samp = (int64_t)w.samp * 8;
+    w.clear_sample = group_rows < group_samp;
+    const int64_t sampled = std::min<int64_t>(in.n, (int64_t)w.rgroups * std::min(group_samp, group_rows));
+    w.scan_bytes = (in.n - sampled) * ((int64_t)in.d * (row_form_bytes(w.rows) ? 1 : 2) + 4);
     return w;
 }
 
@@ -392,6 +406,18 @@ inline BatchRoute route_batch(const RouteIn& in, const SearchRoute& r, int nb) {
     const int qt = b.tile = qn_tile_for(nb);
     const bool ks = ksplit_width(in.dp);
     const int64_t steal = in.steal, scan_impl = in.scan_impl;
+    // A workgroup publishes its staged candidates (and refreshes one threshold) per BLOCK of refresh_every staged entries,
+    // whatever query they belong to: the option is stated for a full 64-query batch and scales with the batch's query
+    // count, so that a query sees the same publication granularity at nq = 1 as at nq = 64.  (Unscaled, a single
+    // query over 5M rows staged ~76 entries per workgroup, never completed a 128-entry block, never raised its
+    // threshold above the sample's and overflowed its candidate list: exact re-run, 38 ms instead of 1.5.)
+    // (rounded down to a power of two: the kernels find a block's number with a shift)
+    b.refresh_every = (int)std::min<int64_t>(256, std::max<int64_t>(4, std::max<int64_t>(1, in.refresh_every) * nb / kMaxBatch));
+    while (b.refresh_every & (b.refresh_every - 1)) b.refresh_every &= b.refresh_every - 1;
+    const int64_t per_wave = in.n / p.total_waves;   // (from n >= total_waves * samp on, no wave's range is shorter than its sample)
+    b.clear_sample = per_wave < p.samp;
+    const int64_t sampled = std::min<int64_t>(in.n, (int64_t)p.total_waves * std::min<int64_t>(p.samp, per_wave));
+    b.scan_bytes = (in.n - sampled) * (p.image ? (int64_t)in.dp + 8 : (int64_t)in.d * (byte_rows(in.dtype) ? 1 : 2) + 4);
     // sample pass: a FEW workgroups walk the sample parts of all ranges (each stages the query image once)
     // (auto: 4 workgroups per spare CU when the CU split is on, one per range otherwise)
     // Round 6: where k_scan2r's operand path is the default (scan2r_auto_width) the sample pass takes it too -- ONE workgroup per spare
