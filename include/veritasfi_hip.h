@@ -546,13 +546,57 @@ int vf_bm25_search(vf_bm25* h, const int64_t* q_offsets, const int32_t* q_terms,
  * allowed rows only, and the zero-score tail takes allowed untouched rows from every block of the bitmap.  The bitmap, n_docs / 8
  * bytes, is uploaded with every filtered call (no filter is kept on the device between calls); the handle allocates its device copy
  * and 4 B per 32 768 rows and query slot of tail scratch on the first filtered call.  Without the flag nothing about the call changes.
- * Not in scope: a filter per query, a filter that stays on the device across calls, statistics (idf, average length) over the set. */
+ * Not in scope: a filter per query, a filter that stays on the device across calls.  (Statistics over the set: VF_BM25_SUBSTATS below.) */
 #define VF_BM25_FILTER 0x40000000      /* or'ed into `nq` of vf_bm25_search: `q_offsets` is a vf_bm25_filter_query */
 typedef struct vf_bm25_filter_query {
     const int64_t*  q_offsets;   /* what q_offsets was */
     const uint32_t* allow;       /* host, (n_docs + 31) / 32 words: bit (r & 31) of word r >> 5 set = row r may be returned */
     int64_t         n_docs;      /* the document count the bitmap was made for */
 } vf_bm25_filter_query;
+
+/* ---- a filtered BM25 search scored by the SUBSET's own statistics (no new entry point: the mode rides on the filtered search) --------
+ * With VF_BM25_FILTER alone a filtered search keeps the whole corpus's N, df and mean length.  With VF_BM25_SUBSTATS or'ed in as well
+ * the result is, bit for bit in ids and score bits, what a handle over the index built from the allowed documents ALONE returns
+ * (Lucene scoring, the same vocabulary size, the allowed rows in ascending order, its row i mapped back to the i-th allowed row):
+ * N = m, df[c] = the allowed postings of column c, avgdl = the allowed rows' tokens / m (1.0 when they hold none).  Ranking, padding
+ * (m < k: ranks m .. k - 1 are (-1, -FLT_MAX)) and the one-filter-per-call rule are the filtered search's.  A query token without an
+ * allowed posting adds nothing; a repeated token counts again.
+ * A request is TWO calls with the caller's logarithm between them (the library takes none, as for a live update):
+ *   vf_bm25_substats_query sq = {q_offsets, allow, n_docs, PHASE, ...};
+ *   vf_bm25_search(h, (const int64_t*)&sq, q_terms, nq | VF_BM25_FILTER | VF_BM25_SUBSTATS, k, out_ids, out_scores);
+ *   VF_BM25_SUBSTATS_STAGE   counts on the device and fills df [q_offsets[nq]] (one count per q_terms position), total_len (tokens of
+ *                            the allowed rows), m (rows allowed) and generation (the handle's update generation).  k, out_ids and
+ *                            out_scores are not read (with m == 0 and non-NULL outputs and k >= 1 they are filled with padding).
+ *   the caller               idf[t] = log(1.0 + (m - df[t] + 0.5) / (df[t] + 0.5)) in float64, the expression that built the index;
+ *                            avgdl = (double)total_len / m, or 1.0 when total_len == 0.
+ *   VF_BM25_SUBSTATS_SEARCH  reads idf [q_offsets[nq]], avgdl, k1, b and generation, scores every allowed posting from its term
+ *                            frequency -- float64, (idf*tf) / (tf + k1*((1.0-b) + (b*dl)/avgdl)), rounded once, the live update's own
+ *                            arithmetic -- and ranks as the filtered search does.
+ * Checked under the handle's lock before any device work, on top of the filtered search's checks: the handle must be live (it keeps
+ * term frequencies and lengths), else VF_EUNSUPPORTED; a phase that is neither of the two, a null df (stage) or idf (search) with a
+ * token in the batch, an idf that is not finite or is negative, avgdl <= 0, k1 < 0 or b outside [0, 1] are VF_EINVAL; so is a
+ * generation that is no longer the handle's: the index was updated between the two calls (n_docs alone cannot tell: a removal plus an
+ * addition keeps it), and what the stage counted is stale.  A refused call changes nothing, neither the outputs nor the struct.  m == 0
+ * returns all padding without a launch.
+ * The bitmap goes up once per request: the stage leaves its device copy for the search that follows, which uploads it again only if
+ * its `allow` differs from the staged words or another filtered call came between.  The handle allocates 8 B per q_terms position and
+ * 8 B per distinct column on the first such call; a handle that never uses the mode allocates nothing.  Without the flag nothing
+ * about vf_bm25_search changes.  Not in scope: a filter per query, statistics kept on the device across requests. */
+#define VF_BM25_SUBSTATS 0x20000000    /* or'ed into `nq` beside VF_BM25_FILTER: `q_offsets` is a vf_bm25_substats_query */
+#define VF_BM25_SUBSTATS_STAGE 1
+#define VF_BM25_SUBSTATS_SEARCH 2
+typedef struct vf_bm25_substats_query {
+    const int64_t*  q_offsets;   /* the three members of vf_bm25_filter_query ... */
+    const uint32_t* allow;
+    int64_t         n_docs;
+    int32_t         phase;       /* ... and, read only under VF_BM25_SUBSTATS: VF_BM25_SUBSTATS_STAGE or VF_BM25_SUBSTATS_SEARCH */
+    int64_t*        df;          /* out of the stage: [q_offsets[nq]] allowed postings of each q_terms position's column */
+    int64_t         total_len;   /* out of the stage: tokens of the allowed rows */
+    int64_t         m;           /* out of the stage: rows allowed */
+    uint64_t        generation;  /* out of the stage, into the search: the handle's update generation */
+    const double*   idf;         /* search: [q_offsets[nq]] */
+    double          avgdl, k1, b;   /* search: the subset's mean length and the index's parameters */
+} vf_bm25_substats_query;
 
 #ifdef __cplusplus
 }

@@ -48,6 +48,19 @@ class Bm25FilterQuery(ctypes.Structure):
     _fields_ = [("q_offsets", ctypes.POINTER(c_i64)), ("allow", ctypes.POINTER(ctypes.c_uint32)), ("n_docs", c_i64)]
 
 
+# or'ed into nq beside VF_BM25_FILTER: `q_offsets` is then a Bm25SubstatsQuery, and the request is two calls (its two phases)
+VF_BM25_SUBSTATS, VF_BM25_SUBSTATS_STAGE, VF_BM25_SUBSTATS_SEARCH = 0x20000000, 1, 2
+
+
+class Bm25SubstatsQuery(ctypes.Structure):
+    """vf_bm25_substats_query of include/veritasfi_hip.h: Bm25FilterQuery's three members, the phase, what the stage writes (df per
+    q_terms position, the allowed rows' tokens, their number, the handle's update generation) and what the search reads (idf per
+    position, avgdl, k1, b and that generation)."""
+    _fields_ = [("q_offsets", ctypes.POINTER(c_i64)), ("allow", ctypes.POINTER(ctypes.c_uint32)), ("n_docs", c_i64),
+                ("phase", c_i32), ("df", ctypes.POINTER(c_i64)), ("total_len", c_i64), ("m", c_i64), ("generation", ctypes.c_uint64),
+                ("idf", ctypes.POINTER(ctypes.c_double)), ("avgdl", ctypes.c_double), ("k1", ctypes.c_double), ("b", ctypes.c_double)]
+
+
 class SubsetQuery(ctypes.Structure):
     """vf_subset_query of include/veritasfi_hip.h: what `queries` points to when nq carries VF_SEARCH_SUBSET (host memory; in the
     device form the two pointers inside are device pointers)."""

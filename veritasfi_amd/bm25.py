@@ -26,6 +26,7 @@ list; that it equals bm25s's ``"english"`` list is unpinned, as is PyStemmer's E
 """
 from __future__ import annotations
 
+import contextlib
 import json
 import os
 import re
@@ -43,6 +44,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 FILES = {"params": "params.index.json", "vocab": "vocab.index.json", "data": "data.csc.index.npy",
          "indices": "indices.csc.index.npy", "indptr": "indptr.csc.index.npy", "corpus": "corpus.jsonl", "tf": "tf.csc.index.npy"}
 SERVED_METHODS = ("lucene", "robertson", "atire")
+_NO_LOCK = contextlib.nullcontext()
 
 
 def _load_stopwords_en() -> frozenset:
@@ -261,6 +263,11 @@ class BM25Retriever:
     n / 8 bytes, goes up with every call).  ``filtered_prefix`` tells ``EnsembleRetriever`` it may ask a filtered request for
     ``bm25_k`` rows with ``subset=`` instead of ranking every row and filtering on the host.
 
+    ``stats="subset"`` beside ``subset=`` (a live retriever only): the scores are those of an index built from the allowed rows ALONE --
+    N, df and the mean length are the subset's (one index per company, as upstream deploys) -- bit for bit what ``BM25Retriever`` over
+    ``bm25_index_arrays`` of those documents returns, rows mapped back.  The device counts (``subset_statistics``), numpy takes the
+    logarithm, the device scores each allowed posting from its term frequency (VF_BM25_SUBSTATS).  ``stats="corpus"`` is the default.
+
     ``live=True``: documents can be added and removed without a rebuild (``add_texts``, ``add_token_ids``, ``remove``, ``update``,
     ``save``).  Ids stay the positions: removed rows leave and later rows move down, new documents get the ids n .. n + m - 1, a
     token the vocabulary lacks gets a new column at the end, columns never disappear.  After every update the device holds, bit
@@ -467,15 +474,61 @@ class BM25Retriever:
         v = self.vocab
         return np.asarray([v[w] for w in tokenize(query, self._stem, self._stopwords) if w in v], dtype=np.int32)
 
-    def search_columns(self, columns: Sequence[np.ndarray], k: int, subset=None):
-        """Token-column lists -> (ids int64 [nq, k], scores float32 [nq, k]) in one device call.  subset (``filter_words``' argument):
-        one set of rows for all the queries; with m rows allowed and k > m the ranks m .. k - 1 are padding, id -1 and score -FLT_MAX."""
+    def _need_subset_stats(self, subset, stats: str) -> bool:
+        """True for ``stats="subset"``; refuses a value that is neither mode, the mode without rows and a retriever that is not live."""
+        if stats not in ("corpus", "subset"):
+            raise ValueError(f"stats={stats!r}: 'corpus' (the whole index's N, df and mean length) or 'subset' (the allowed rows' own)")
+        if stats == "corpus":
+            return False
+        if subset is None:
+            raise ValueError("stats='subset' needs subset=: the statistics are those of the rows that may be returned")
+        if not self.live:
+            raise ValueError("stats='subset' needs a live retriever, BM25Retriever(dir, live=True): only it keeps the term "
+                             "frequencies and the document lengths on the device")
+        return True
+
+    @staticmethod
+    def _columns_args(columns):
         cols = [np.asarray(c, dtype=np.int32).ravel() for c in columns]
-        nq, k = len(cols), int(k)
-        offsets = np.zeros(nq + 1, dtype=np.int64)
+        offsets = np.zeros(len(cols) + 1, dtype=np.int64)
         np.cumsum([c.size for c in cols], out=offsets[1:])
-        terms = np.ascontiguousarray(np.concatenate(cols) if nq else np.zeros(0, np.int32), dtype=np.int32)
-        with self._mu:   # the check of k included: a live retriever's update changes the count
+        terms = np.ascontiguousarray(np.concatenate(cols) if cols else np.zeros(0, np.int32), dtype=np.int32)
+        return cols, offsets, terms
+
+    def _substats_stage(self, sq, terms, nq: int) -> np.ndarray:
+        """The stage call (``self._mu`` held): fills sq.m, sq.total_len and sq.generation, returns df per q_terms position."""
+        df = np.zeros(max(int(terms.size), 1), np.int64)
+        sq.phase, sq.df = _ffi.VF_BM25_SUBSTATS_STAGE, df.ctypes.data_as(_ffi.p_i64)
+        _ffi.check(_ffi.lib().vf_bm25_search(self._h, _ffi.ctypes.cast(_ffi.ctypes.byref(sq), _ffi.p_i64), terms.ctypes.data_as(_ffi.p_i32),
+                                             nq | _ffi.VF_BM25_FILTER | _ffi.VF_BM25_SUBSTATS, 1, None, None), "vf_bm25_search")
+        return df[:terms.size]
+
+    # The attribute ``subset_statistics`` declares that ``invoke`` takes stats="subset" (EnsembleRetriever(where_statistics="subset") asks
+    # for a truthy one; a retriever of another make sets ``subset_statistics = True``).  Here it is the method that exposes the counts.
+    def subset_statistics(self, subset, columns):
+        """(m, total_len, df): the rows ``subset`` allows, the tokens they hold, and per query of ``columns`` an int64 array with, for
+        each token position, the allowed postings of its column -- what ``stats="subset"`` scores by, counted on the device (the
+        stage call alone)."""
+        self._need_subset_stats(subset, "subset")
+        cols, offsets, terms = self._columns_args(columns if len(columns) else [np.zeros(0, np.int32)])
+        with self._update_mu, self._mu:
+            if not self._h.value:
+                raise RuntimeError("BM25Retriever is closed")
+            words, _ = filter_words(subset, self.num_docs)
+            sq = _ffi.Bm25SubstatsQuery(offsets.ctypes.data_as(_ffi.p_i64), words.ctypes.data_as(_ffi.ctypes.POINTER(_ffi.ctypes.c_uint32)), self.num_docs)
+            df = self._substats_stage(sq, terms, len(cols))
+        return int(sq.m), int(sq.total_len), [df[offsets[i]:offsets[i + 1]].copy() for i in range(len(columns))]
+
+    def search_columns(self, columns: Sequence[np.ndarray], k: int, subset=None, stats: str = "corpus"):
+        """Token-column lists -> (ids int64 [nq, k], scores float32 [nq, k]) in one device call.  subset (``filter_words``' argument):
+        one set of rows for all the queries; with m rows allowed and k > m the ranks m .. k - 1 are padding, id -1 and score -FLT_MAX.
+        stats="subset" (a live retriever, with ``subset``): scored by the allowed rows' own N, df and mean length -- bit for bit what a
+        retriever over ``bm25_index_arrays`` of those documents alone returns, its rows mapped back.  Two device calls (the counts, then
+        the search) with numpy's log between them, as an update, and under the update lock, so that no update lands between them."""
+        by_subset = self._need_subset_stats(subset, stats)
+        cols, offsets, terms = self._columns_args(columns)
+        nq, k = len(cols), int(k)
+        with (self._update_mu if by_subset else _NO_LOCK), self._mu:   # the check of k included: a live retriever's update changes the count
             if not 1 <= k <= self.num_docs:
                 raise ValueError(f"k={k}: must be in [1, {self.num_docs}] (the number of documents)")
             ids = np.empty((nq, k), dtype=np.int64)
@@ -485,6 +538,25 @@ class BM25Retriever:
             if not self._h.value:
                 raise RuntimeError("BM25Retriever is closed")
             q_arg = offsets.ctypes.data_as(_ffi.p_i64)
+            if by_subset:
+                t0 = time.perf_counter()
+                words, _ = filter_words(subset, self.num_docs)
+                sq = _ffi.Bm25SubstatsQuery(q_arg, words.ctypes.data_as(_ffi.ctypes.POINTER(_ffi.ctypes.c_uint32)), self.num_docs)
+                t1 = time.perf_counter()
+                df = self._substats_stage(sq, terms, nq).astype(np.float64)
+                t2 = time.perf_counter()
+                m = int(sq.m)
+                idf = np.ascontiguousarray(np.log(1.0 + (m - df + 0.5) / (df + 0.5)))      # as bm25_index_arrays, N = m
+                sq.idf = idf.ctypes.data_as(_ffi.ctypes.POINTER(_ffi.ctypes.c_double))
+                sq.avgdl = float(int(sq.total_len)) / m if m and sq.total_len else 1.0
+                sq.k1, sq.b, sq.phase = self._k1, self._b, _ffi.VF_BM25_SUBSTATS_SEARCH
+                t3 = time.perf_counter()
+                _ffi.check(_ffi.lib().vf_bm25_search(self._h, _ffi.ctypes.cast(_ffi.ctypes.byref(sq), _ffi.p_i64), terms.ctypes.data_as(_ffi.p_i32),
+                                                     nq | _ffi.VF_BM25_FILTER | _ffi.VF_BM25_SUBSTATS, k, ids.ctypes.data_as(_ffi.p_i64),
+                                                     scores.ctypes.data_as(_ffi.p_f32)), "vf_bm25_search")
+                # where the request's time went (tools/bench_bm25_substats.py): pack = the bitmap; host = idf and avgdl
+                self.last_subset_ms = {"pack": 1e3 * (t1 - t0), "stage": 1e3 * (t2 - t1), "host": 1e3 * (t3 - t2), "search": 1e3 * (time.perf_counter() - t3)}
+                return ids, scores
             if subset is not None:   # packed under the lock: the mask's length is held to the count the device has now
                 words, _ = filter_words(subset, self.num_docs)
                 fq = _ffi.Bm25FilterQuery(q_arg, words.ctypes.data_as(_ffi.ctypes.POINTER(_ffi.ctypes.c_uint32)), self.num_docs)
@@ -503,18 +575,18 @@ class BM25Retriever:
             ids = [i for i, s in zip(ids, scores_row) if s >= self.min_score]
         return ids, scores_row
 
-    def invoke(self, query: str, k: int, metadata_filters=None, subset=None):
+    def invoke(self, query: str, k: int, metadata_filters=None, subset=None, stats: str = "corpus"):
         """(ids, scores) of the k best rows (bm25Retriever.py:50-87); with ``subset`` the k best of those rows, min(k, rows allowed)
-        of them.  The retriever holds no metadata: ``metadata_filters`` raises as upstream, ``EnsembleRetriever.rows_where`` turns
+        of them, scored by the whole corpus's statistics or, with stats="subset", by those rows' own (``search_columns``).  The retriever holds no metadata: ``metadata_filters`` raises as upstream, ``EnsembleRetriever.rows_where`` turns
         a metadata filter into the rows ``subset`` takes."""
         if metadata_filters:
             raise NotImplementedError("Metadata filtering is not supported yet.")   # as upstream (:69-72)
-        ids, scores = self.search_columns([self.query_columns(query)], k, subset=subset)
+        ids, scores = self.search_columns([self.query_columns(query)], k, subset=subset, stats=stats)
         return self._result(ids[0], scores[0])
 
-    def invoke_batch(self, queries: Sequence[str], k: int, subset=None):
-        """[(ids, scores)] per query, all in one device call; ``subset``: one set of rows for all of them."""
-        ids, scores = self.search_columns([self.query_columns(q) for q in queries], k, subset=subset)
+    def invoke_batch(self, queries: Sequence[str], k: int, subset=None, stats: str = "corpus"):
+        """[(ids, scores)] per query, all in one device call; ``subset``: one set of rows for all of them, ``stats`` as ``search_columns``."""
+        ids, scores = self.search_columns([self.query_columns(q) for q in queries], k, subset=subset, stats=stats)
         return [self._result(ids[i], scores[i]) for i in range(len(ids))]
 
     def info(self) -> dict:

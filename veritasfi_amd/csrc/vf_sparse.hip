@@ -19,11 +19,15 @@
 //   k_bm25_reset       clear what the query touched: its postings' score entries and bitmap words (O(postings), not O(N))
 //   k_bm25_*_f, k_bm25_pad_out   a search restricted to a set of rows (VF_BM25_FILTER; the word arithmetic is vf_bm25_filter.h): the scatter
 //                      skips rows outside the set, the tail takes allowed rows only from every bitmap block, ranks past the set are padded
+//   k_bm25_sub_len, k_bm25_sub_df, k_bm25_accum_s   a filtered search scored by the subset's own statistics (VF_BM25_SUBSTATS; the index
+//                      arithmetic is vf_bm25_substats.h): the allowed rows' lengths summed and the allowed postings of each distinct query
+//                      column counted (the stage), then a scatter that scores each posting from its tf by the caller's idf and avgdl
 //   k_bm25_live_*      a live handle's update: documents leave and arrive, every posting is re-scored into a second set of
 //                      arrays (described where they stand; the index arithmetic is vf_bm25_live.h)
 #include "vf_internal.h"
 #include "vf_bm25_live.h"
 #include "vf_bm25_filter.h"
+#include "vf_bm25_substats.h"
 
 #include <float.h>
 #include <algorithm>
@@ -42,6 +46,7 @@ constexpr int kBmMaxSlots = 64;                                     // queries i
 constexpr long long kBmScratchBudget = 3ll << 30;                   // bytes of per-query scratch a handle may hold
 constexpr int kBmSortChunk = 4096;                                  // keys per LDS chunk of the global bitonic sort
 static_assert(kBmWordsPerBlock == kBm25FilterBlockWords, "vf_bm25_filter.h plans the tail over blocks of kBmWordsPerBlock words");
+static_assert(kBmThreads == kBm25SubThreads && kBmWordsPerThread == kBm25SubWordsPerThread, "vf_bm25_substats.h plans the counting kernels");
 
 struct BmState {          // per slot, rewritten by pass 0 of every query
     u64 prefix;           // selected keys are those >= prefix
@@ -91,6 +96,78 @@ __device__ __forceinline__ void bm_accum(const BmArgs& a, int t, const u32* allo
 
 __global__ __launch_bounds__(kBmThreads) void k_bm25_accum(BmArgs a, int t) { bm_accum<false>(a, t, nullptr); }
 __global__ __launch_bounds__(kBmThreads) void k_bm25_accum_f(BmArgs a, int t, const u32* allow) { bm_accum<true>(a, t, allow); }
+
+// ---- a filtered search by the subset's own statistics (vf_bm25_substats.h) ----------------------------------------------------------
+struct SubArgs {
+    const long long* indptr; const int* indices; const int* tf; const int* doclen;   // the live handle's arrays
+    const u32* allow; long long n;                                                    // the filter, [words], zero past n
+    const int* dcols; int* df;                                                        // the batch's distinct columns and their counts
+    unsigned long long* total;                                                        // the allowed rows' lengths, summed
+    const double* idf; double avgdl, k1, b, one_minus_b;                              // the search: idf per q_terms position
+};
+
+// the lengths of the allowed rows: one bitmap block per workgroup, a wave reduction, one integer atomic per workgroup (exact: any order)
+__global__ __launch_bounds__(kBmThreads) void k_bm25_sub_len(SubArgs a) {
+    const int tid = threadIdx.x;
+    const long long w0 = bm25s_len_word0(blockIdx.x, tid);
+    const uint4 f4 = *(const uint4*)(a.allow + w0);
+    const u32 fv[4] = {f4.x, f4.y, f4.z, f4.w};
+    unsigned long long s = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) s += bm25s_word_len(fv[j], (w0 + j) * 32, a.n, a.doclen);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+    __shared__ unsigned long long wsum[kBmThreads / 64];
+    if ((tid & 63) == 0) wsum[tid >> 6] = s;
+    __syncthreads();
+    if (tid == 0) {
+        unsigned long long t = 0;
+        for (int w = 0; w < kBmThreads / 64; ++w) t += wsum[w];
+        if (t) atomicAdd(a.total, t);
+    }
+}
+
+// the allowed postings of distinct column d0 + blockIdx.y: a wave counts by ballot, a workgroup adds once
+__global__ __launch_bounds__(kBmThreads) void k_bm25_sub_df(SubArgs a, int d0) {
+    const int tid = threadIdx.x, d = d0 + blockIdx.y;
+    const int col = a.dcols[d];
+    const long long p0 = a.indptr[col], p1 = a.indptr[col + 1];
+    int cnt = 0;   // lane 0 of each wave holds the wave's count
+    for (long long i = 0;; ++i) {
+        const long long base = bm25s_df_base(p0, blockIdx.x, gridDim.x, i);   // the same for the whole workgroup: every lane votes
+        if (base >= p1) break;
+        const long long p = base + tid;
+        const bool in = p < p1 && bm25f_row_allowed(a.allow, (u32)a.indices[p]);
+        cnt += __popcll(__ballot(in));
+    }
+    __shared__ int wsum[kBmThreads / 64];
+    if ((tid & 63) == 0) wsum[tid >> 6] = cnt;
+    __syncthreads();
+    if (tid == 0) {
+        int t = 0;
+        for (int w = 0; w < kBmThreads / 64; ++w) t += wsum[w];
+        if (t) atomicAdd(&a.df[d], t);
+    }
+}
+
+// k_bm25_accum_f with the posting's score computed from its tf by the subset's statistics in place of the stored one; idf is indexed
+// by the token's position in q_terms.  The same plain read-add-write, one launch per position: the fp32 order is fixed.
+__global__ __launch_bounds__(kBmThreads) void k_bm25_accum_s(BmArgs a, int t, SubArgs sa) {
+    const int s = blockIdx.y, q = a.q0 + s;
+    const long long b = a.q_off[q], e = a.q_off[q + 1];
+    if (b + t >= e) return;
+    const int col = a.q_terms[b + t];
+    const double idf = sa.idf[b + t];
+    const long long p0 = a.indptr[col], p1 = a.indptr[col + 1];
+    float* sc = a.scores + s * a.score_stride;
+    u32* bits = a.bits + s * a.bits_stride;
+    for (long long p = p0 + (long long)blockIdx.x * kBmThreads + threadIdx.x; p < p1; p += (long long)gridDim.x * kBmThreads) {
+        const u32 row = (u32)a.indices[p];
+        if (!bm25f_row_allowed(sa.allow, row)) continue;
+        sc[row] = sc[row] + live_score(idf, sa.tf[p], sa.doclen[row], sa.avgdl, sa.k1, sa.b, sa.one_minus_b);
+        atomicOr(&bits[row >> 5], 1u << (row & 31u));
+    }
+}
 
 // histogram of digit (key >> shift) & 255 over the touched keys whose upper digits equal the prefix
 __global__ __launch_bounds__(kBmThreads) void k_bm25_hist(BmArgs a, int pass) {
@@ -594,6 +671,14 @@ struct vf_bm25 {
     int* d_tf = nullptr;                    // [nnz] term frequency of each posting
     int* d_doclen = nullptr;                // [n] tokens per document
     struct BmStage* stage = nullptr;        // a staged update: the second set of arrays, not yet swapped in
+    unsigned long long gen = 1;             // the update generation: every commit makes it the next one
+    // a search by the subset's statistics (VF_BM25_SUBSTATS) also holds these from the first such call on
+    unsigned long long* d_sub = nullptr;    // the stage's counts: the length sum (8 B), then df [sub_cap] and the distinct columns [sub_cap]
+    long long sub_cap = 0;
+    double* d_sidf = nullptr;               // [sidf_cap] the search's idf per q_terms position
+    long long sidf_cap = 0;
+    std::vector<u32> staged_allow;          // the bitmap the last stage left in d_allow, while allow_staged: its search does not upload it again
+    bool allow_staged = false;
     std::mutex mu;
 };
 
@@ -626,6 +711,7 @@ static void bm_free_slots(vf_bm25* h) {
     h->d_scores = nullptr; h->d_bits = nullptr; h->d_hist = nullptr; h->d_st = nullptr; h->d_sel = nullptr;
     h->d_tblk = nullptr; h->d_ids = nullptr; h->d_out = nullptr;
     h->d_allow = nullptr; h->d_ftblk = nullptr;   // sized by the slots and the words that go here: the next filtered call makes them again
+    h->allow_staged = false;
     h->slots = 0;
 }
 
@@ -724,7 +810,7 @@ static int bm_destroy(vf_bm25* h) {
     bm_free_slots(h);
     bm_drop_stage(h);
     void* ps[] = {h->d_indptr, h->d_indices, h->d_data, h->d_big, h->d_big_tblk, h->d_big_ids, h->d_big_out, h->d_qoff, h->d_qterms,
-                  h->d_tf, h->d_doclen};
+                  h->d_tf, h->d_doclen, h->d_sub, h->d_sidf};
     for (void* p : ps)
         if (p) (void)hipFree(p);
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -871,6 +957,8 @@ static int bm_live_commit(vf_bm25* h, const vf_bm25_delta* d) {
         bm_set_docs(h, n);
     }
     h->born = true;
+    ++h->gen;                  // what a VF_BM25_SUBSTATS stage counted is no longer this index's
+    h->allow_staged = false;
     bm_drop_stage(h);
     return VF_OK;
 }
@@ -1000,9 +1088,79 @@ extern "C" int vf_bm25_create(const int64_t* indptr, int64_t V, const int32_t* i
     return VF_OK;
 }
 
+// ---- a search by the subset's own statistics (include/veritasfi_hip.h: VF_BM25_SUBSTATS) --------------------------------------------
+static int bm_ensure_sidf(vf_bm25* h, long long T) {
+    const long long want = std::max<long long>(T, 1);
+    if (want <= h->sidf_cap) return VF_OK;
+    if (h->d_sidf) (void)hipFree(h->d_sidf);
+    h->d_sidf = nullptr; h->sidf_cap = 0;
+    const hipError_t e = hipMalloc((void**)&h->d_sidf, (size_t)want * 8);
+    if (e != hipSuccess) return bm_fail(e == hipErrorOutOfMemory ? VF_ENOMEM : VF_EHIP, std::string("vf_bm25: idf of the query positions: ") + hipGetErrorString(e));
+    h->sidf_cap = want;
+    return VF_OK;
+}
+
+// The stage.  Every check has passed and m > 0.  Uploads the bitmap (it stays for the search that follows), sums the allowed rows'
+// lengths, counts the allowed postings of the batch's distinct columns, and writes the struct's out members last.
+static int bm_substats_stage(vf_bm25* h, vf_bm25_substats_query* sq, const uint32_t* allow_host, long long m, const int32_t* q_terms, int nq, long long T) {
+    std::vector<int32_t> distinct, pos2d;
+    std::vector<unsigned long long> back;   // the length sum, then the counts (two int32 per word)
+    long long D = 0;
+    const size_t aw = (size_t)bm25f_words(h->n);
+    try {
+        D = bm25s_dedupe(q_terms, T, distinct, pos2d);
+        back.assign((size_t)(1 + (D + 1) / 2), 0ull);
+        h->staged_allow.assign(allow_host, allow_host + aw);
+    } catch (const std::bad_alloc&) {
+        h->allow_staged = false;
+        return bm_fail(VF_ENOMEM, "host allocation failed");
+    }
+    h->allow_staged = false;
+    DeviceGuard guard;
+    VFS_HIP(hipSetDevice(h->device));
+    hipStream_t st = h->stream;
+    {   // the slots of the search that follows, so that it does not make d_allow again
+        const int rc = bm_ensure_slots(h, std::max(std::min<int>(nq, h->slot_cap), h->slots));
+        if (rc != VF_OK) return rc;
+        const int rc2 = bm_ensure_filter(h);
+        if (rc2 != VF_OK) return rc2;
+    }
+    if (std::max<long long>(D, 1) > h->sub_cap) {
+        if (h->d_sub) (void)hipFree(h->d_sub);
+        h->d_sub = nullptr; h->sub_cap = 0;
+        const long long cap = std::max<long long>(D, 1) + (std::max<long long>(D, 1) & 1);   // even: the columns start on 8 bytes as well
+        const hipError_t e = hipMalloc((void**)&h->d_sub, 8 + (size_t)cap * 8);
+        if (e != hipSuccess) return bm_fail(e == hipErrorOutOfMemory ? VF_ENOMEM : VF_EHIP, std::string("vf_bm25: subset counts: ") + hipGetErrorString(e));
+        h->sub_cap = cap;
+    }
+    SubArgs sa{};
+    sa.indptr = h->d_indptr; sa.indices = h->d_indices; sa.tf = h->d_tf; sa.doclen = h->d_doclen;
+    sa.allow = h->d_allow; sa.n = h->n;
+    sa.total = h->d_sub; sa.df = (int*)(h->d_sub + 1); sa.dcols = sa.df + h->sub_cap;
+    VFS_HIP(hipMemcpyAsync(h->d_allow, allow_host, aw * 4, hipMemcpyHostToDevice, st));
+    VFS_HIP(hipMemsetAsync(h->d_sub, 0, 8 + (size_t)h->sub_cap * 4, st));
+    if (D > 0) VFS_HIP(hipMemcpyAsync((void*)sa.dcols, distinct.data(), (size_t)D * 4, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_bm25_sub_len, dim3((unsigned)(h->words / kBmWordsPerBlock)), dim3(kBmThreads), 0, st, sa);
+    long long most = 0;
+    for (long long d = 0; d < D; ++d) most = std::max(most, h->indptr[(size_t)distinct[d] + 1] - h->indptr[(size_t)distinct[d]]);
+    if (most > 0) {
+        const unsigned gx = bm25s_df_plan(most);
+        for (long long d0 = 0; d0 < D; d0 += 32768)   // grid.y holds fewer than 65 536
+            hipLaunchKernelGGL(k_bm25_sub_df, dim3(gx, (unsigned)std::min<long long>(32768, D - d0)), dim3(kBmThreads), 0, st, sa, (int)d0);
+    }
+    VFS_HIP(hipGetLastError());
+    VFS_HIP(hipMemcpyAsync(back.data(), h->d_sub, 8 + (size_t)D * 4, hipMemcpyDeviceToHost, st));
+    VFS_HIP(hipStreamSynchronize(st));
+    const int32_t* df = (const int32_t*)(back.data() + 1);
+    for (long long t = 0; t < T; ++t) sq->df[t] = df[pos2d[(size_t)t]];
+    sq->total_len = (int64_t)back[0]; sq->m = m; sq->generation = h->gen;
+    h->allow_staged = true;
+    return VF_OK;
+}
+
 // the scoring and the radix select of the group's queries (slots 0 .. g-1); sel / tblk / out set by the caller.  allow: the device
 // bitmap of a filtered call (the scatter skips the rows outside it), or null
-static int bm_score_select(vf_bm25* h, BmArgs& a, const int64_t* q_off, int g, const u32* allow) {
+static int bm_score_select(vf_bm25* h, BmArgs& a, const int64_t* q_off, int g, const u32* allow, const SubArgs* ss = nullptr) {
     hipStream_t st = h->stream;
     long long maxlen = 0;
     for (int s = 0; s < g; ++s) maxlen = std::max<long long>(maxlen, q_off[a.q0 + s + 1] - q_off[a.q0 + s]);
@@ -1016,7 +1174,8 @@ static int bm_score_select(vf_bm25* h, BmArgs& a, const int64_t* q_off, int g, c
             }
         }
         if (post == 0) continue;
-        if (allow) hipLaunchKernelGGL(k_bm25_accum_f, dim3(bm_grid(post, kBmThreads, 4096), g), dim3(kBmThreads), 0, st, a, (int)t, allow);
+        if (ss) hipLaunchKernelGGL(k_bm25_accum_s, dim3(bm_grid(post, kBmThreads, 4096), g), dim3(kBmThreads), 0, st, a, (int)t, *ss);
+        else if (allow) hipLaunchKernelGGL(k_bm25_accum_f, dim3(bm_grid(post, kBmThreads, 4096), g), dim3(kBmThreads), 0, st, a, (int)t, allow);
         else hipLaunchKernelGGL(k_bm25_accum, dim3(bm_grid(post, kBmThreads, 4096), g), dim3(kBmThreads), 0, st, a, (int)t);
         VFS_HIP(hipGetLastError());
     }
@@ -1056,16 +1215,23 @@ extern "C" int vf_bm25_search(vf_bm25* h, const int64_t* q_offsets, const int32_
     if (!h) return bm_fail(VF_EINVAL, "vf_bm25_search: null handle");
     if (nq < 0) return bm_fail(VF_EINVAL, "vf_bm25_search: negative nq");
     const vf_bm25_filter_query* fq = nullptr;   // VF_BM25_FILTER: one set of rows for every query of the call
+    vf_bm25_substats_query* sq = nullptr;       // ... | VF_BM25_SUBSTATS: scored by that set's own statistics, in two phases
     if (nq & VF_BM25_FILTER) {
         fq = (const vf_bm25_filter_query*)(const void*)q_offsets;
         if (!fq) return bm_fail(VF_EINVAL, "vf_bm25_search: VF_BM25_FILTER with a null vf_bm25_filter_query");
+        if (nq & VF_BM25_SUBSTATS) sq = (vf_bm25_substats_query*)(void*)q_offsets;   // its first three members are fq's
         q_offsets = fq->q_offsets;
-        nq &= ~VF_BM25_FILTER;
+        nq &= ~(VF_BM25_FILTER | VF_BM25_SUBSTATS);
+    } else if (nq & VF_BM25_SUBSTATS) {
+        return bm_fail(VF_EINVAL, "vf_bm25_search: VF_BM25_SUBSTATS goes with VF_BM25_FILTER (the statistics are those of the allowed rows)");
     }
+    const bool stage = sq && sq->phase == VF_BM25_SUBSTATS_STAGE;
+    if (sq && !stage && sq->phase != VF_BM25_SUBSTATS_SEARCH)
+        return bm_fail(VF_EINVAL, "vf_bm25_search: vf_bm25_substats_query.phase must be VF_BM25_SUBSTATS_STAGE or VF_BM25_SUBSTATS_SEARCH");
     if (nq == 0) return VF_OK;
-    if (!q_offsets || !out_ids || !out_scores) return bm_fail(VF_EINVAL, "vf_bm25_search: null buffer");
+    if (!q_offsets || (!stage && (!out_ids || !out_scores))) return bm_fail(VF_EINVAL, "vf_bm25_search: null buffer");
     std::lock_guard<std::mutex> lk(h->mu);   // before n_docs and the vocabulary are read: a live handle's update changes both
-    if (k < 1 || (long long)k > h->n) return bm_fail(VF_EINVAL, "vf_bm25_search: k must be in [1, n_docs]");
+    if (!stage && (k < 1 || (long long)k > h->n)) return bm_fail(VF_EINVAL, "vf_bm25_search: k must be in [1, n_docs]");
     if (q_offsets[0] != 0) return bm_fail(VF_EINVAL, "vf_bm25_search: q_offsets[0] must be 0");
     for (int q = 0; q < nq; ++q)
         if (q_offsets[q + 1] < q_offsets[q]) return bm_fail(VF_EINVAL, "vf_bm25_search: q_offsets must be non-decreasing");
@@ -1082,12 +1248,36 @@ extern "C" int vf_bm25_search(vf_bm25* h, const int64_t* q_offsets, const int32_
         const Bm25FilterCheck fc = bm25f_check(fq->allow, h->n);
         if (fc.bad_row >= 0)
             return bm_fail(VF_EINVAL, "vf_bm25_search: the filter allows row " + std::to_string(fc.bad_row) + ", at or past n_docs = " + std::to_string(h->n));
+        if (sq) {
+            if (!h->live || !h->born)
+                return bm_fail(VF_EUNSUPPORTED, "vf_bm25_search: VF_BM25_SUBSTATS needs a live handle (VF_BM25_LIVE): only it keeps the term frequencies and the document lengths");
+            if (stage) {
+                if (T > 0 && !sq->df) return bm_fail(VF_EINVAL, "vf_bm25_search: VF_BM25_SUBSTATS_STAGE with a null df");
+            } else {
+                if (sq->generation != h->gen)
+                    return bm_fail(VF_EINVAL, "vf_bm25_search: the statistics were staged at update generation " + std::to_string(sq->generation) + ", the handle is at " +
+                                                  std::to_string(h->gen) + " (the live index was updated between the stage and the search: stage again)");
+                if (T > 0 && !sq->idf) return bm_fail(VF_EINVAL, "vf_bm25_search: VF_BM25_SUBSTATS_SEARCH with a null idf");
+                for (long long t = 0; t < T; ++t)
+                    if (!(sq->idf[t] >= 0.0) || !(sq->idf[t] <= DBL_MAX))
+                        return bm_fail(VF_EINVAL, "vf_bm25_search: idf[" + std::to_string(t) + "] is negative or not finite");
+                if (!(sq->avgdl > 0.0) || !(sq->avgdl <= DBL_MAX) || !(sq->k1 >= 0.0) || !(sq->b >= 0.0 && sq->b <= 1.0))
+                    return bm_fail(VF_EINVAL, "vf_bm25_search: VF_BM25_SUBSTATS_SEARCH needs avgdl > 0, k1 >= 0 and b in [0, 1]");
+            }
+        }
         fp = bm25f_plan(h->words, fc.m, k);
         if (fc.m == 0) {   // nothing may be returned: all padding, no launch
-            std::fill(out_ids, out_ids + (size_t)nq * k, (int64_t)-1);
-            std::fill(out_scores, out_scores + (size_t)nq * k, -FLT_MAX);
+            if (out_ids && out_scores && k >= 1) {
+                std::fill(out_ids, out_ids + (size_t)nq * k, (int64_t)-1);
+                std::fill(out_scores, out_scores + (size_t)nq * k, -FLT_MAX);
+            }
+            if (stage) {
+                std::fill(sq->df, sq->df + T, (int64_t)0);
+                sq->total_len = 0; sq->m = 0; sq->generation = h->gen;
+            }
             return VF_OK;
         }
+        if (stage) return bm_substats_stage(h, sq, fq->allow, fc.m, q_terms, nq, T);
     }
     DeviceGuard guard;
     VFS_HIP(hipSetDevice(h->device));
@@ -1127,9 +1317,22 @@ extern "C" int vf_bm25_search(vf_bm25* h, const int64_t* q_offsets, const int32_
     if (fq) {   // the bitmap goes up with every filtered call (n / 8 bytes): no filter is kept on the device between calls
         const int rc = bm_ensure_filter(h);
         if (rc != VF_OK) return rc;
-        VFS_HIP(hipMemcpyAsync(h->d_allow, fq->allow, (size_t)bm25f_words(h->n) * 4, hipMemcpyHostToDevice, st));
+        // ... except from a VF_BM25_SUBSTATS stage to its search: the stage's copy serves when it holds these very words
+        const size_t aw = (size_t)bm25f_words(h->n);
+        const bool staged = sq && h->allow_staged && h->staged_allow.size() == aw && std::equal(h->staged_allow.begin(), h->staged_allow.end(), fq->allow);
+        h->allow_staged = false;
+        if (!staged) VFS_HIP(hipMemcpyAsync(h->d_allow, fq->allow, aw * 4, hipMemcpyHostToDevice, st));
         allow = h->d_allow;
     }
+    SubArgs sub{};
+    if (sq) {
+        const int rc = bm_ensure_sidf(h, T);
+        if (rc != VF_OK) return rc;
+        if (T > 0) VFS_HIP(hipMemcpyAsync(h->d_sidf, sq->idf, (size_t)T * 8, hipMemcpyHostToDevice, st));
+        sub.tf = h->d_tf; sub.doclen = h->d_doclen; sub.allow = allow; sub.n = h->n;
+        sub.idf = h->d_sidf; sub.avgdl = sq->avgdl; sub.k1 = sq->k1; sub.b = sq->b; sub.one_minus_b = 1.0 - sq->b;
+    }
+    const SubArgs* ss = sq ? &sub : nullptr;
     const unsigned pad_grid = bm_grid(k - fp.pad_from, kBmThreads, 64);   // a filtered call of fewer than k rows pads ranks pad_from .. k - 1
     a.scores = h->d_scores; a.score_stride = h->n;
     a.bits = h->d_bits; a.bits_stride = h->words;
@@ -1142,7 +1345,7 @@ extern "C" int vf_bm25_search(vf_bm25* h, const int64_t* q_offsets, const int32_
             a.tblk = h->d_tblk; a.tblk_stride = 1;
             if (fq) { a.tblk = h->d_ftblk; a.tblk_stride = fp.tblk_entries; }
             a.out_ids = h->d_ids; a.out_scores = h->d_out; a.out_stride = k;
-            int rc = bm_score_select(h, a, q_offsets, g, allow);
+            int rc = bm_score_select(h, a, q_offsets, g, allow, ss);
             if (rc != VF_OK) return rc;
             if (fq && fp.pad_from < k) hipLaunchKernelGGL(k_bm25_pad_out, dim3(pad_grid, g), dim3(kBmThreads), 0, st, a, fp.pad_from);
             const int Pk = (int)bm_pow2(k);
@@ -1155,7 +1358,7 @@ extern "C" int vf_bm25_search(vf_bm25* h, const int64_t* q_offsets, const int32_
             a.sel = h->d_big; a.sel_stride = 0; a.sel_cap = bm_pow2(h->n);
             a.tblk = h->d_big_tblk; a.tblk_stride = 0;
             a.out_ids = h->d_big_ids; a.out_scores = h->d_big_out; a.out_stride = 0;
-            int rc = bm_score_select(h, a, q_offsets, 1, allow);
+            int rc = bm_score_select(h, a, q_offsets, 1, allow, ss);
             if (rc != VF_OK) return rc;
             if (fq && fp.pad_from < k) hipLaunchKernelGGL(k_bm25_pad_out, dim3(pad_grid, 1), dim3(kBmThreads), 0, st, a, fp.pad_from);
             BmState bs;

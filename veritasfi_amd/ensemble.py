@@ -74,7 +74,7 @@ def _host_bm25(bm25_dir):
 class EnsembleRetriever:
     def __init__(self, bm25_dir, chroma, ts_chroma, k: int, embeddings, faiss_k: int = None, bm25_k: int = None,
                  faiss_ts_k: int = None, enable_expand: bool = False, bm25_retriever=None, retriever_cls=FaissRetriever,
-                 prefetch_documents: bool = False, similarity_from_rows: bool = None):
+                 prefetch_documents: bool = False, similarity_from_rows: bool = None, where_statistics: str = "corpus"):
         """Positional arguments as upstream (``ragManager.py:112`` passes bm25_dir, chroma, ts_chroma, k, embeddings).
         ``bm25_dir`` goes to the host application's ``BM25Retriever`` exactly as upstream (``:37``) unless
         ``bm25_retriever`` is given.
@@ -86,7 +86,14 @@ class EnsembleRetriever:
         embeds only texts it does not know, instead of embedding all n again (ensembleRetriever.py:275).  None (default) = on when
         that is the same matrix: the rows are held as given (not rounded to a narrower ``corpus_dtype``) and the embedder has no
         query instruction (upstream stores ``embed_documents(text)`` and compares ``embed_query(text)``: the same vector unless
-        the embedder prefixes queries).  False = always re-embed; True = rows even where auto would decline."""
+        the embedder prefixes queries).  False = always re-embed; True = rows even where auto would decline.
+        ``where_statistics``: what the BM25 leg of a filtered request (``invoke(..., where=)``) scores by.  "corpus" (default): the
+        whole corpus's N, df and mean length, today's calls.  "subset": the passing chunks' own, so that the BM25 leg too returns what
+        an ensemble over the passing chunks alone would; it needs a BM25 retriever that declares ``subset_statistics`` (this package's
+        ``BM25Retriever(bm25_dir, live=True)``), whose ``invoke`` is then called with ``stats="subset"``."""
+        if where_statistics not in ("corpus", "subset"):
+            raise ValueError(f"where_statistics={where_statistics!r}: 'corpus' or 'subset'")
+        self.where_statistics = where_statistics
         self.embeddings = embeddings
         self.faiss_k = faiss_k if faiss_k is not None else k
         self.bm25_k = bm25_k if bm25_k is not None else k
@@ -97,6 +104,11 @@ class EnsembleRetriever:
         self.bm25_retriever = bm25_retriever
         if self.bm25_retriever is None and self.bm25_k > 0:
             self.bm25_retriever = _host_bm25(bm25_dir)
+        if where_statistics == "subset" and self.bm25_k > 0:
+            bm = self.bm25_retriever
+            if not getattr(bm, "subset_statistics", False) or getattr(bm, "live", True) is False:
+                raise ValueError("where_statistics='subset' needs a BM25 retriever that declares subset_statistics, i.e. takes "
+                                 "invoke(query, k, subset=rows, stats='subset') -- e.g. veritasfi_amd.BM25Retriever(bm25_dir, live=True)")
 
         include = ["metadatas", "embeddings"] + (["documents"] if prefetch_documents else [])
         docs = chroma.get(include=include)
@@ -333,9 +345,11 @@ class EnsembleRetriever:
         where (``rows_where``'s argument; None = no filter, today's call): only chunks whose metadata passes are returned.  The rule:
         the result is what ``invoke`` would return over a store that held the passing chunks alone -- the dense leg searches those
         rows only (``FaissRetriever.invoke(subset=...)``: the retriever must take ``subset``), bundles and the neighbour expansion see
-        passing rows only, the title-summary leg's rows are filtered here.  ONE stated exception, the BM25 leg: it keeps the
+        passing rows only, the title-summary leg's rows are filtered here.  ONE stated exception, under ``where_statistics="corpus"``
+        (the default) only, the BM25 leg: it keeps the
         whole corpus's statistics (idf, average length), as upstream's own sketch does (bm25Retriever.py:91-132) -- its result is
-        the first ``bm25_k`` passing rows of the full ranking.  A retriever that declares ``filtered_prefix`` (this package's
+        the first ``bm25_k`` passing rows of the full ranking.  Under ``where_statistics="subset"`` there is no exception: the leg is
+        asked with ``stats="subset"`` and scores by the passing chunks' own statistics.  A retriever that declares ``filtered_prefix`` (this package's
         ``BM25Retriever``) is asked for exactly those, ``invoke(input, min(bm25_k, passing rows), subset=passing)``, and filters
         inside its kernels, so the exception costs nothing; any other retriever is asked for the full ranking, which is
         filtered here.  A filter nothing passes returns []."""
@@ -404,7 +418,10 @@ class EnsembleRetriever:
         if allow is not None:
             # filtered: the first bm25_k passing rows of the full ranking (whole-corpus statistics: the stated exception) -- from a
             # retriever that filters on its own (filtered_prefix), else from the full ranking, filtered here
-            if passing is not None and getattr(self.bm25_retriever, "filtered_prefix", False) is True:
+            if passing is not None and self.where_statistics == "subset":   # no exception: the passing chunks' own statistics
+                b_ids, b_scores = self.bm25_retriever.invoke(input, max(1, min(int(self.bm25_k), len(passing))), subset=passing, stats="subset")
+                kept = [(int(r), s) for r, s in zip(b_ids, b_scores)]
+            elif passing is not None and getattr(self.bm25_retriever, "filtered_prefix", False) is True:
                 b_ids, b_scores = self.bm25_retriever.invoke(input, max(1, min(int(self.bm25_k), len(passing))), subset=passing)
                 kept = [(int(r), s) for r, s in zip(b_ids, b_scores)]
             else:
