@@ -546,7 +546,8 @@ int vf_bm25_search(vf_bm25* h, const int64_t* q_offsets, const int32_t* q_terms,
  * allowed rows only, and the zero-score tail takes allowed untouched rows from every block of the bitmap.  The bitmap, n_docs / 8
  * bytes, is uploaded with every filtered call (no filter is kept on the device between calls); the handle allocates its device copy
  * and 4 B per 32 768 rows and query slot of tail scratch on the first filtered call.  Without the flag nothing about the call changes.
- * Not in scope: a filter per query, a filter that stays on the device across calls.  (Statistics over the set: VF_BM25_SUBSTATS below.) */
+ * Not in scope: a filter per query.  (Statistics over the set: VF_BM25_SUBSTATS below; a filter that stays on the device across
+ * calls: VF_BM25_PREPARED below.) */
 #define VF_BM25_FILTER 0x40000000      /* or'ed into `nq` of vf_bm25_search: `q_offsets` is a vf_bm25_filter_query */
 typedef struct vf_bm25_filter_query {
     const int64_t*  q_offsets;   /* what q_offsets was */
@@ -581,7 +582,8 @@ typedef struct vf_bm25_filter_query {
  * The bitmap goes up once per request: the stage leaves its device copy for the search that follows, which uploads it again only if
  * its `allow` differs from the staged words or another filtered call came between.  The handle allocates 8 B per q_terms position and
  * 8 B per distinct column on the first such call; a handle that never uses the mode allocates nothing.  Without the flag nothing
- * about vf_bm25_search changes.  Not in scope: a filter per query, statistics kept on the device across requests. */
+ * about vf_bm25_search changes.  Not in scope: a filter per query.  (Statistics kept on the device across requests: VF_BM25_PREPARED
+ * below.) */
 #define VF_BM25_SUBSTATS 0x20000000    /* or'ed into `nq` beside VF_BM25_FILTER: `q_offsets` is a vf_bm25_substats_query */
 #define VF_BM25_SUBSTATS_STAGE 1
 #define VF_BM25_SUBSTATS_SEARCH 2
@@ -597,6 +599,65 @@ typedef struct vf_bm25_substats_query {
     const double*   idf;         /* search: [q_offsets[nq]] */
     double          avgdl, k1, b;   /* search: the subset's mean length and the index's parameters */
 } vf_bm25_substats_query;
+
+/* ---- a PREPARED row filter: the bitmap and the subset's statistics kept on the device across calls (no new entry point) --------------
+ * The same filter on thousands of consecutive requests (one index per tenant) need not be packed, checked, uploaded and counted per
+ * request: the bitmap, m, the length sum and the subset's df -- hence its idf -- for every column of the vocabulary are properties of
+ * (index generation, filter).  A prepared filter computes them once; after that a filtered request is ONE call that uploads nothing but
+ * the query, in both statistics modes, and returns bit for bit what the unprepared call with the same rows and mode returns.
+ *   vf_bm25_prepared_query pq = {q_offsets, allow, n_docs, PHASE, ...};
+ *   vf_bm25_search(h, (const int64_t*)&pq, q_terms, nq | VF_BM25_PREPARED, k, out_ids, out_scores);
+ * The handle owns any number of prepared filters, each named by a token the library hands out (never 0, never reused); memory is the
+ * only bound.  A filter holds on the device its OWN bitmap (n_docs / 8 bytes, zero past n_docs, padded as the handle's own copy is; it
+ * never aliases that copy, and unprepared filtered calls may run between prepared ones), and in subset mode idf [vocab] in float64.
+ *   VF_BM25_PREPARED_PREPARE  reads allow, n_docs, mode (VF_BM25_PREPARED_CORPUS or VF_BM25_PREPARED_SUBSET) and chunk, under all of the
+ *                             filtered search's checks; uploads the bitmap once; fills token, m, generation and bytes (device bytes the
+ *                             filter holds).  Corpus mode computes nothing else.  Subset mode needs a live handle (else
+ *                             VF_EUNSUPPORTED) and df [vocab] with vocab = the handle's vocabulary (else VF_EINVAL): it sums the
+ *                             allowed rows' lengths and counts df for EVERY column in one pass over the flat posting array
+ *                             (k_bm25_sub_df_all), and fills total_len and df.  m == 0 is allowed: such a filter searches to all
+ *                             padding without a launch.  `chunk` (0 = 2048, else 1 .. 2048) is the number of postings one workgroup
+ *                             of the count takes: tests lower it.  q_terms, nq's count, k and the outputs are not read.
+ *   the caller                subset mode: idf[c] = log(1.0 + (m - df[c] + 0.5) / (df[c] + 0.5)) in float64 for every column, the
+ *                             expression that built the index; avgdl = (double)total_len / m, or 1.0 when total_len == 0.
+ *   VF_BM25_PREPARED_ARM      subset mode only: reads token, idf [vocab] (finite and >= 0, else VF_EINVAL naming the column), avgdl, k1
+ *                             and b under VF_BM25_SUBSTATS_SEARCH's checks, and uploads idf to the filter's table.  A filter whose
+ *                             generation is no longer the handle's is VF_EINVAL.  A subset-mode filter that was never armed refuses to
+ *                             search.
+ *   VF_BM25_PREPARED_SEARCH   reads token and q_offsets; q_terms, nq, k and the outputs are the search's own.  Corpus mode runs the
+ *                             filtered scatter on the filter's bitmap; subset mode scores each allowed posting from its term frequency
+ *                             with idf read per COLUMN from the filter's table.  Everything behind the scatter is the filtered
+ *                             search's.  An unknown or released token is VF_EINVAL; so is a filter made before the handle's last
+ *                             update (the message says to prepare again).
+ *   VF_BM25_PREPARED_RELEASE  frees the filter `token` names.  Releasing the handle frees them all.
+ * A committed live update invalidates every prepared filter of the handle and frees its device memory (rows have moved: no filter can
+ * search with stale bits); the token stays known, so that a search or an arm with it is refused by its generation, until it is released.
+ * An allocation failure is VF_ENOMEM and leaves the handle and every other filter as they were; a refused call changes nothing.
+ * Without the flag nothing about vf_bm25_search changes.  Not in scope: a filter per query, filters remapped across an update. */
+#define VF_BM25_PREPARED 0x10000000    /* or'ed into `nq` of vf_bm25_search: `q_offsets` is a vf_bm25_prepared_query */
+#define VF_BM25_PREPARED_PREPARE 1
+#define VF_BM25_PREPARED_ARM 2
+#define VF_BM25_PREPARED_SEARCH 3
+#define VF_BM25_PREPARED_RELEASE 4
+#define VF_BM25_PREPARED_CORPUS 0
+#define VF_BM25_PREPARED_SUBSET 1
+typedef struct vf_bm25_prepared_query {
+    const int64_t*  q_offsets;   /* search: what q_offsets was */
+    const uint32_t* allow;       /* prepare: host, (n_docs + 31) / 32 words, as vf_bm25_filter_query's */
+    int64_t         n_docs;      /* prepare: the document count the bitmap was made for */
+    int32_t         phase;       /* one of the four VF_BM25_PREPARED_* phases */
+    int32_t         mode;        /* prepare: VF_BM25_PREPARED_CORPUS or VF_BM25_PREPARED_SUBSET */
+    uint64_t        token;       /* out of prepare, into arm, search and release */
+    int64_t         vocab;       /* prepare (subset mode) and arm: entries of df / idf, the handle's vocabulary */
+    int64_t*        df;          /* out of prepare (subset mode): [vocab] allowed postings of every column */
+    int64_t         total_len;   /* out of prepare (subset mode): tokens of the allowed rows */
+    int64_t         m;           /* out of prepare: rows allowed */
+    uint64_t        generation;  /* out of prepare: the handle's update generation */
+    int64_t         bytes;       /* out of prepare: device bytes the filter holds */
+    const double*   idf;         /* arm: [vocab] */
+    double          avgdl, k1, b;   /* arm: the subset's mean length and the index's parameters */
+    int32_t         chunk;       /* prepare (subset mode): 0 = 2048, else 1 .. 2048 postings per workgroup of the count */
+} vf_bm25_prepared_query;
 
 #ifdef __cplusplus
 }

@@ -75,8 +75,8 @@ from .encoder import (HipDecoder, HipDecoderEmbeddings, HipDecoderModel, HipEmbe
 from .rank import rank_chunk  # noqa: F401
 from .vision import (HipClipTextEmbeddings, HipClipTextEncoder, HipImageEmbeddings, HipVisionEncoder, pack_hf_clip_text,  # noqa: F401
                      pack_hf_clip_vision)
-from .ensemble import EnsembleRetriever  # noqa: F401
-from .bm25 import (BM25Retriever, build_bm25_index, build_bm25_index_from_ids, load_bm25_index,  # noqa: F401
+from .ensemble import EnsembleRetriever, PreparedWhere  # noqa: F401
+from .bm25 import (BM25Retriever, BM25Subset, build_bm25_index, build_bm25_index_from_ids, load_bm25_index,  # noqa: F401
                    load_from_chroma_and_save)
 from .stages import StageTimer, get_profiler, set_profiler  # noqa: F401
 from .pretrained import (FlagLLMReranker, FlagReranker, HuggingFaceEmbeddings, ReplicaSet, from_config, load_embeddings,  # noqa: F401

@@ -32,6 +32,7 @@ import os
 import re
 import threading
 import time
+import weakref
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -247,6 +248,52 @@ def filter_words(subset, n: int):
     return words, int(np.count_nonzero(mask))
 
 
+_STATS_UNSET = object()   # ``stats=`` was not passed: "corpus" beside rows, the object's own mode beside a ``BM25Subset``
+
+
+class BM25Subset:
+    """A set of rows PREPARED on a ``BM25Retriever``'s device (``prepare_subset``): the filter's bitmap and, with ``stats="subset"``,
+    the subset's idf for every column of the vocabulary stay in HBM, so a search with ``subset=<this object>`` uploads nothing but its
+    query and is ONE device call in both modes.  ``m`` rows allowed, ``total_len`` their tokens and ``df`` (int64 [V], their postings
+    per column; both ``stats="subset"`` only, else 0 / None), ``stats`` the mode, ``generation`` the index's update generation it was
+    made at, ``nbytes`` the device memory it holds (0 once closed).  It holds rows, not meaning: after the retriever's next update
+    (``add_texts``, ``remove``, ...) it is stale and every search with it is refused -- call ``prepare_subset`` again.  ``close()``
+    (or ``with``) frees it; ``BM25Retriever.close()`` frees all of a retriever's."""
+
+    def __init__(self, retriever, token: int, stats: str, m: int, total_len: int, generation: int, df, nbytes: int):
+        self._retriever, self._token, self._closed, self._stale = retriever, int(token), False, False
+        self.stats, self.m, self.total_len, self.generation, self.df, self.nbytes = stats, int(m), int(total_len), int(generation), df, int(nbytes)
+
+    @property
+    def closed(self) -> bool:
+        return self._closed
+
+    @property
+    def stale(self) -> bool:
+        return self._stale
+
+    def close(self) -> None:
+        """Free the device copy; harmless twice, and after the retriever itself has closed (which has freed it)."""
+        if not self._closed:
+            self._retriever._release_subset(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        # never the library from a finaliser (it may run inside any call that holds the retriever's lock): the token is left for the
+        # retriever's next locked call to release; a retriever that has closed marked this object closed and has nothing left to free
+        try:
+            if not self._closed and not self._stale:
+                self._closed = True
+                self._retriever._orphans.append(self._token)
+        except Exception:
+            pass
+
+
 # ---- the retriever ---------------------------------------------------------------------------------------------------------
 class BM25Retriever:
     """The reference's constructor and ``invoke(query, k) -> (ids, scores)``; scoring and ranking run on the GPU.
@@ -274,7 +321,11 @@ class BM25Retriever:
     for bit, what ``bm25_index_arrays`` gives for the surviving documents followed by the new ones (every posting is re-scored:
     N, df and avgdl change with one document).  It needs the directory's term frequencies (``tf.csc.index.npy``) and the Lucene
     method; the posting scores are then computed on the device from tf, and the directory's own are not used.  During an update
-    the device holds the postings twice."""
+    the device holds the postings twice.
+
+    ``prepare_subset(subset, stats)`` -> ``BM25Subset``: the same filter on many requests (one index per tenant) is packed, checked,
+    uploaded and -- with stats="subset" -- counted ONCE; passed as ``subset=`` it makes every request one device call that uploads only
+    the query, with the result of the unprepared call bit for bit (VF_BM25_PREPARED)."""
 
     exact_prefix = True
     filtered_prefix = True
@@ -291,6 +342,8 @@ class BM25Retriever:
         self._h, slots = _ffi.vp(), _ffi.c_i32()
         self._mu = threading.Lock()
         self._update_mu = threading.RLock()   # one update at a time, tokenising included (a new token's column is decided there)
+        self._subsets = weakref.WeakValueDictionary()   # token -> BM25Subset: the prepared filters that can still search
+        self._orphans: list = []                        # tokens of collected BM25Subsets, released by the next locked call
         self._info = {"n_docs": int(ix.num_docs), "vocab": int(ix.indptr.size - 1), "nnz": int(ix.data.size), "slots": 0}
         if self.live:
             if ix.tf is None:
@@ -362,6 +415,7 @@ class BM25Retriever:
             self._live_call(delta, _ffi.VF_BM25_COMMIT, slots)
             # where the call's time went (tools/bench_bm25_live.py): stage = upload, row map, count, scan, counts back; host = idf and avgdl
             self.last_update_ms = {"stage": 1e3 * (t1 - t0), "host": 1e3 * (t2 - t1), "commit": 1e3 * (time.perf_counter() - t2)}
+            self._retire_subsets()   # the commit invalidated every prepared filter on the device: rows have moved
             self._dl, self._df, self._total = dl, counts, total
             self.num_docs = self.doc_len = N
             self._info = {"n_docs": N, "vocab": Vn, "nnz": int(counts.sum()), "slots": slots.value}
@@ -519,16 +573,119 @@ class BM25Retriever:
             df = self._substats_stage(sq, terms, len(cols))
         return int(sq.m), int(sq.total_len), [df[offsets[i]:offsets[i + 1]].copy() for i in range(len(columns))]
 
-    def search_columns(self, columns: Sequence[np.ndarray], k: int, subset=None, stats: str = "corpus"):
+    # -- prepared filters ------------------------------------------------------------------------------------------------------
+    def _prepared_call(self, pq, phase: int) -> int:
+        """A prepare, arm or release call (``self._mu`` held); returns the code."""
+        pq.phase = phase
+        return _ffi.lib().vf_bm25_search(self._h, _ffi.ctypes.cast(_ffi.ctypes.byref(pq), _ffi.p_i64), None, _ffi.VF_BM25_PREPARED, 1, None, None)
+
+    def _release_token(self, token: int) -> None:
+        if self._h.value:
+            pq = _ffi.Bm25PreparedQuery()
+            pq.token = int(token)
+            self._prepared_call(pq, _ffi.VF_BM25_PREPARED_RELEASE)   # a token the device no longer knows is no failure here
+
+    def _drop_orphans(self) -> None:
+        """Release what collected ``BM25Subset``s left behind (``self._mu`` held)."""
+        while self._orphans:
+            self._release_token(self._orphans.pop())
+
+    def _retire_subsets(self) -> None:
+        """After a committed update (``self._mu`` held): every prepared filter is stale -- the device has freed it -- and is forgotten."""
+        for s in list(self._subsets.values()):
+            s._stale, s.nbytes = True, 0
+            self._release_token(s._token)
+        self._subsets.clear()
+        self._drop_orphans()
+
+    def _release_subset(self, s: "BM25Subset") -> None:
+        with self._mu:
+            if s._closed:
+                return
+            s._closed, s.nbytes = True, 0
+            if not s._stale:
+                self._subsets.pop(s._token, None)
+                self._release_token(s._token)
+
+    def prepare_subset(self, subset, stats: str = "corpus") -> BM25Subset:
+        """Keep a filter on the device: ``subset`` (``filter_words``' argument) is packed, checked and uploaded ONCE, and the returned
+        ``BM25Subset`` is passed as ``subset=`` to ``search_columns`` / ``invoke`` / ``invoke_batch`` any number of times; each such
+        search is one device call that uploads only its query and returns, bit for bit, what the same call with the rows and this
+        ``stats`` returns.  stats="subset" (a live retriever): the device also sums the allowed rows' lengths and counts their postings
+        for EVERY column of the vocabulary in one pass over the index (``.df``), numpy takes the logarithm over the vocabulary (the
+        builder's own line) and the idf table goes back to the device (prepare, log, arm -- under the update lock, so that no update
+        lands in between).  A live retriever's ``live_chunk`` is also the number of postings one workgroup of that count takes.
+        The object is stale after this retriever's next update; ``close()`` it (or use ``with``) when the filter is no longer needed."""
+        if isinstance(subset, BM25Subset):
+            raise TypeError("prepare_subset takes rows (ids, a boolean mask or a RowSubset), not a BM25Subset")
+        if subset is None:
+            raise ValueError("prepare_subset needs the rows that may be returned")
+        by_subset = self._need_subset_stats(subset, stats)
+        with self._update_mu, self._mu:
+            if not self._h.value:
+                raise RuntimeError("BM25Retriever is closed")
+            self._drop_orphans()
+            t0 = time.perf_counter()
+            words, _ = filter_words(subset, self.num_docs)
+            V = self._info["vocab"]
+            pq = _ffi.Bm25PreparedQuery()
+            pq.allow, pq.n_docs = words.ctypes.data_as(_ffi.ctypes.POINTER(_ffi.ctypes.c_uint32)), self.num_docs
+            pq.mode = _ffi.VF_BM25_PREPARED_SUBSET if by_subset else _ffi.VF_BM25_PREPARED_CORPUS
+            df = None
+            if by_subset:
+                df = np.zeros(max(V, 1), np.int64)
+                pq.vocab, pq.df, pq.chunk = V, df.ctypes.data_as(_ffi.p_i64), self._chunk
+            t1 = time.perf_counter()
+            _ffi.check(self._prepared_call(pq, _ffi.VF_BM25_PREPARED_PREPARE), "vf_bm25_search")
+            t2 = t3 = time.perf_counter()
+            if by_subset:
+                df = df[:V]
+                m, dff = int(pq.m), df.astype(np.float64)
+                idf = np.ascontiguousarray(np.log(1.0 + (m - dff + 0.5) / (dff + 0.5)))      # as bm25_index_arrays, N = m
+                pq.idf = idf.ctypes.data_as(_ffi.ctypes.POINTER(_ffi.ctypes.c_double))
+                pq.avgdl = float(int(pq.total_len)) / m if m and pq.total_len else 1.0
+                pq.k1, pq.b = self._k1, self._b
+                t3 = time.perf_counter()
+                rc = self._prepared_call(pq, _ffi.VF_BM25_PREPARED_ARM)
+                if rc != _ffi.VF_OK:
+                    msg = _ffi.last_error()
+                    self._release_token(pq.token)
+                    raise RuntimeError(f"vf_bm25_search failed (rc={rc}): {msg}")
+            # where the time went (tools/bench_bm25_prepared.py): pack = the bitmap; prepare = its upload and, in subset mode, the two
+            # counts and their way back; host = the logarithm over the vocabulary; arm = the idf table's upload
+            self.last_prepare_ms = {"pack": 1e3 * (t1 - t0), "prepare": 1e3 * (t2 - t1), "host": 1e3 * (t3 - t2), "arm": 1e3 * (time.perf_counter() - t3)}
+            s = BM25Subset(self, pq.token, stats, pq.m, pq.total_len if by_subset else 0, pq.generation, df, pq.bytes)
+            self._subsets[s._token] = s
+            return s
+
+    def _prepared_mode(self, subset: BM25Subset, stats) -> None:
+        if subset._retriever is not self:
+            raise ValueError("subset: this BM25Subset was prepared on another BM25Retriever; prepare it on this one (prepare_subset)")
+        if stats is not _STATS_UNSET and stats != subset.stats:
+            raise ValueError(f"stats={stats!r} beside a BM25Subset prepared with stats={subset.stats!r}: the mode is the object's own; "
+                             "leave stats= out, or prepare another one")
+
+    def search_columns(self, columns: Sequence[np.ndarray], k: int, subset=None, stats=_STATS_UNSET):
         """Token-column lists -> (ids int64 [nq, k], scores float32 [nq, k]) in one device call.  subset (``filter_words``' argument):
         one set of rows for all the queries; with m rows allowed and k > m the ranks m .. k - 1 are padding, id -1 and score -FLT_MAX.
-        stats="subset" (a live retriever, with ``subset``): scored by the allowed rows' own N, df and mean length -- bit for bit what a
-        retriever over ``bm25_index_arrays`` of those documents alone returns, its rows mapped back.  Two device calls (the counts, then
-        the search) with numpy's log between them, as an update, and under the update lock, so that no update lands between them."""
-        by_subset = self._need_subset_stats(subset, stats)
+        stats="subset" (a live retriever, with ``subset``; default "corpus"): scored by the allowed rows' own N, df and mean length -- bit
+        for bit what a retriever over ``bm25_index_arrays`` of those documents alone returns, its rows mapped back.  Two device calls (the
+        counts, then the search) with numpy's log between them, as an update, and under the update lock, so that no update lands between
+        them.  subset=<a ``BM25Subset``> (``prepare_subset``): the same results from ONE call that uploads only the query; the mode is
+        the object's own (``stats=`` beside it must be absent or equal), a stale or closed one is a ValueError."""
+        prepared = isinstance(subset, BM25Subset)
+        if prepared:
+            self._prepared_mode(subset, stats)
+            by_subset = False
+        else:
+            stats = "corpus" if stats is _STATS_UNSET else stats
+            by_subset = self._need_subset_stats(subset, stats)
         cols, offsets, terms = self._columns_args(columns)
         nq, k = len(cols), int(k)
         with (self._update_mu if by_subset else _NO_LOCK), self._mu:   # the check of k included: a live retriever's update changes the count
+            if prepared and (subset._closed or subset._stale):   # before k: the object may have been made for another document count
+                raise ValueError("subset: this BM25Subset " + ("is closed" if subset._closed else "is stale (the retriever was updated "
+                                 f"after it was prepared at generation {subset.generation})") + ": call prepare_subset again")
             if not 1 <= k <= self.num_docs:
                 raise ValueError(f"k={k}: must be in [1, {self.num_docs}] (the number of documents)")
             ids = np.empty((nq, k), dtype=np.int64)
@@ -538,6 +695,13 @@ class BM25Retriever:
             if not self._h.value:
                 raise RuntimeError("BM25Retriever is closed")
             q_arg = offsets.ctypes.data_as(_ffi.p_i64)
+            if prepared:
+                pq = _ffi.Bm25PreparedQuery()
+                pq.q_offsets, pq.token, pq.phase = q_arg, subset._token, _ffi.VF_BM25_PREPARED_SEARCH
+                _ffi.check(_ffi.lib().vf_bm25_search(self._h, _ffi.ctypes.cast(_ffi.ctypes.byref(pq), _ffi.p_i64), terms.ctypes.data_as(_ffi.p_i32),
+                                                     nq | _ffi.VF_BM25_PREPARED, k, ids.ctypes.data_as(_ffi.p_i64),
+                                                     scores.ctypes.data_as(_ffi.p_f32)), "vf_bm25_search")
+                return ids, scores
             if by_subset:
                 t0 = time.perf_counter()
                 words, _ = filter_words(subset, self.num_docs)
@@ -575,7 +739,7 @@ class BM25Retriever:
             ids = [i for i, s in zip(ids, scores_row) if s >= self.min_score]
         return ids, scores_row
 
-    def invoke(self, query: str, k: int, metadata_filters=None, subset=None, stats: str = "corpus"):
+    def invoke(self, query: str, k: int, metadata_filters=None, subset=None, stats=_STATS_UNSET):
         """(ids, scores) of the k best rows (bm25Retriever.py:50-87); with ``subset`` the k best of those rows, min(k, rows allowed)
         of them, scored by the whole corpus's statistics or, with stats="subset", by those rows' own (``search_columns``).  The retriever holds no metadata: ``metadata_filters`` raises as upstream, ``EnsembleRetriever.rows_where`` turns
         a metadata filter into the rows ``subset`` takes."""
@@ -584,20 +748,26 @@ class BM25Retriever:
         ids, scores = self.search_columns([self.query_columns(query)], k, subset=subset, stats=stats)
         return self._result(ids[0], scores[0])
 
-    def invoke_batch(self, queries: Sequence[str], k: int, subset=None, stats: str = "corpus"):
+    def invoke_batch(self, queries: Sequence[str], k: int, subset=None, stats=_STATS_UNSET):
         """[(ids, scores)] per query, all in one device call; ``subset``: one set of rows for all of them, ``stats`` as ``search_columns``."""
         ids, scores = self.search_columns([self.query_columns(q) for q in queries], k, subset=subset, stats=stats)
         return [self._result(ids[i], scores[i]) for i in range(len(ids))]
 
     def info(self) -> dict:
-        """n_docs, vocab, nnz, and slots: queries one device pass serves."""
-        return dict(self._info)
+        """n_docs, vocab, nnz, slots: queries one device pass serves, prepared: the ``BM25Subset``s that can search, and
+        prepared_bytes: the device memory they hold."""
+        alive = [s for s in list(self._subsets.values()) if not s._closed and not s._stale]
+        return dict(self._info, prepared=len(alive), prepared_bytes=sum(s.nbytes for s in alive))
 
     def close(self) -> None:
         mu = getattr(self, "_mu", None)
         if mu is None:
             return
         with mu:
+            for s in list(self._subsets.values()):   # the release below frees them on the device: they never touch the library again
+                s._closed, s.nbytes = True, 0
+            self._subsets.clear()
+            del self._orphans[:]
             if self._h.value:
                 h = _ffi.vp(self._h.value)
                 _ffi.lib().vf_bm25_create(None, 0, None, None, 0, 0, 0, _ffi.ctypes.byref(h), None)   # release

@@ -22,12 +22,16 @@
 //   k_bm25_sub_len, k_bm25_sub_df, k_bm25_accum_s   a filtered search scored by the subset's own statistics (VF_BM25_SUBSTATS; the index
 //                      arithmetic is vf_bm25_substats.h): the allowed rows' lengths summed and the allowed postings of each distinct query
 //                      column counted (the stage), then a scatter that scores each posting from its tf by the caller's idf and avgdl
+//   k_bm25_sub_df_all, k_bm25_accum_sc   a PREPARED row filter (VF_BM25_PREPARED; the index arithmetic is vf_bm25_prepared.h): its bitmap stays
+//                      on the device, and in subset mode df is counted once for EVERY column in one pass over the flat posting array,
+//                      so that the scatter reads idf per column from the filter's own table and a request uploads only its query
 //   k_bm25_live_*      a live handle's update: documents leave and arrive, every posting is re-scored into a second set of
 //                      arrays (described where they stand; the index arithmetic is vf_bm25_live.h)
 #include "vf_internal.h"
 #include "vf_bm25_live.h"
 #include "vf_bm25_filter.h"
 #include "vf_bm25_substats.h"
+#include "vf_bm25_prepared.h"
 
 #include <float.h>
 #include <algorithm>
@@ -47,6 +51,7 @@ constexpr long long kBmScratchBudget = 3ll << 30;                   // bytes of 
 constexpr int kBmSortChunk = 4096;                                  // keys per LDS chunk of the global bitonic sort
 static_assert(kBmWordsPerBlock == kBm25FilterBlockWords, "vf_bm25_filter.h plans the tail over blocks of kBmWordsPerBlock words");
 static_assert(kBmThreads == kBm25SubThreads && kBmWordsPerThread == kBm25SubWordsPerThread, "vf_bm25_substats.h plans the counting kernels");
+static_assert(kBmThreads == kBm25PrepThreads, "vf_bm25_prepared.h plans the all-columns count");
 
 struct BmState {          // per slot, rewritten by pass 0 of every query
     u64 prefix;           // selected keys are those >= prefix
@@ -152,12 +157,14 @@ __global__ __launch_bounds__(kBmThreads) void k_bm25_sub_df(SubArgs a, int d0) {
 
 // k_bm25_accum_f with the posting's score computed from its tf by the subset's statistics in place of the stored one; idf is indexed
 // by the token's position in q_terms.  The same plain read-add-write, one launch per position: the fp32 order is fixed.
-__global__ __launch_bounds__(kBmThreads) void k_bm25_accum_s(BmArgs a, int t, SubArgs sa) {
+// kByCol: idf is a prepared filter's table over the whole vocabulary, indexed by the token's column (k_bm25_accum_sc)
+template <bool kByCol>
+__device__ __forceinline__ void bm_accum_s(const BmArgs& a, int t, const SubArgs& sa) {
     const int s = blockIdx.y, q = a.q0 + s;
     const long long b = a.q_off[q], e = a.q_off[q + 1];
     if (b + t >= e) return;
     const int col = a.q_terms[b + t];
-    const double idf = sa.idf[b + t];
+    const double idf = kByCol ? sa.idf[col] : sa.idf[b + t];
     const long long p0 = a.indptr[col], p1 = a.indptr[col + 1];
     float* sc = a.scores + s * a.score_stride;
     u32* bits = a.bits + s * a.bits_stride;
@@ -168,6 +175,9 @@ __global__ __launch_bounds__(kBmThreads) void k_bm25_accum_s(BmArgs a, int t, Su
         atomicOr(&bits[row >> 5], 1u << (row & 31u));
     }
 }
+
+__global__ __launch_bounds__(kBmThreads) void k_bm25_accum_s(BmArgs a, int t, SubArgs sa) { bm_accum_s<false>(a, t, sa); }
+__global__ __launch_bounds__(kBmThreads) void k_bm25_accum_sc(BmArgs a, int t, SubArgs sa) { bm_accum_s<true>(a, t, sa); }
 
 // histogram of digit (key >> shift) & 255 over the touched keys whose upper digits equal the prefix
 __global__ __launch_bounds__(kBmThreads) void k_bm25_hist(BmArgs a, int pass) {
@@ -489,14 +499,10 @@ __device__ __forceinline__ T live_block_scan(T v, T id, T* part, T* total) {
     return excl;
 }
 
-// rows[i] = the new row of the chunk's posting i (or -1); rank[i] = survivors among the postings below i, rank[cnt] = all of them
-__device__ __forceinline__ void live_chunk_ranks(const LiveArgs& a, long long lo, int cnt, int* rows, int* rank, int* part) {
+// the flags rank[0 .. cnt) of a chunk (0 or 1, all written, not yet fenced) to their exclusive prefix: rank[i] = flags set below i,
+// rank[cnt] = all of them
+__device__ __forceinline__ void live_flags_to_ranks(int cnt, int* rank, int* part) {
     const int t = threadIdx.x;
-    for (int i = t; i < cnt; i += kBmThreads) {
-        const int r = a.map[a.indices[lo + i]];
-        if (rows) rows[i] = r;
-        rank[i] = r >= 0;
-    }
     __syncthreads();
     const int L = (cnt + kBmThreads - 1) / kBmThreads;
     const int b0 = min(t * L, cnt), b1 = min(b0 + L, cnt);
@@ -511,6 +517,47 @@ __device__ __forceinline__ void live_chunk_ranks(const LiveArgs& a, long long lo
     }
     if (t == 0) rank[cnt] = total;
     __syncthreads();
+}
+
+// rows[i] = the new row of the chunk's posting i (or -1); rank[i] = survivors among the postings below i, rank[cnt] = all of them
+__device__ __forceinline__ void live_chunk_ranks(const LiveArgs& a, long long lo, int cnt, int* rows, int* rank, int* part) {
+    const int t = threadIdx.x;
+    for (int i = t; i < cnt; i += kBmThreads) {
+        const int r = a.map[a.indices[lo + i]];
+        if (rows) rows[i] = r;
+        rank[i] = r >= 0;
+    }
+    live_flags_to_ranks(cnt, rank, part);
+}
+
+// ---- a prepared filter's df for EVERY column (vf_bm25_prepared.h): one workgroup per chunk of C flat postings ---------------------------
+struct PrepArgs {
+    const long long* indptr; const int* indices; long long V, nnz; int C;   // the handle's index
+    const u32* allow;                                                       // the prepared filter's own bitmap
+    int* df;                                                                // [V], zeroed before the launch
+};
+
+// The chunk's postings are flagged by the bitmap and the flags' exclusive prefix is left in LDS; every column that intersects the chunk
+// then takes the difference of two prefix entries.  A column wholly inside the chunk has this workgroup as its only writer (a plain
+// store); one that crosses a chunk boundary is added to, one integer atomic per (column, chunk).  Empty columns keep the memset's zero.
+__global__ __launch_bounds__(kBmThreads) void k_bm25_sub_df_all(PrepArgs a) {
+    __shared__ int rank[kLiveMaxChunk + 1];
+    __shared__ int part[kBmThreads];
+    const LiveChunk ch = live_chunk(a.nnz, a.C, blockIdx.x);
+    const int cnt = (int)(ch.hi - ch.lo), t = threadIdx.x;
+    if (cnt == 0) return;
+    for (int i = t; i < cnt; i += kBmThreads) rank[i] = bm25f_row_allowed(a.allow, (u32)a.indices[ch.lo + i]);
+    live_flags_to_ranks(cnt, rank, part);
+    const long long c0 = bm25p_first_col(a.indptr, a.V, a.nnz, ch), c1 = bm25p_end_col(a.indptr, a.V, a.nnz, ch);
+    for (long long c = c0 + t; c < c1; c += kBmThreads) {   // c < c1 <= V: indptr[c + 1] and df[c] exist
+        const Bm25pSpan s = bm25p_span(a.indptr[c], a.indptr[c + 1], ch);
+        const int d = rank[s.hi] - rank[s.lo];
+        if (s.owned) {
+            if (s.hi > s.lo) a.df[c] = d;
+        } else if (d) {
+            atomicAdd(&a.df[c], d);
+        }
+    }
 }
 
 __global__ __launch_bounds__(kBmThreads) void k_bm25_live_rowmap(LiveArgs a) {
@@ -679,7 +726,21 @@ struct vf_bm25 {
     long long sidf_cap = 0;
     std::vector<u32> staged_allow;          // the bitmap the last stage left in d_allow, while allow_staged: its search does not upload it again
     bool allow_staged = false;
+    // prepared filters (VF_BM25_PREPARED): each owns its device memory; none aliases d_allow
+    std::vector<struct BmPrepared*> prepared;
+    unsigned long long next_token = 1;
     std::mutex mu;
+};
+
+// One prepared filter.  A committed update frees its device memory and leaves the entry (stale) so that its token is refused by
+// generation; a release or the handle's end removes it.
+struct BmPrepared {
+    unsigned long long token = 0, gen = 0;
+    bool subset = false, armed = false, stale = false;
+    long long m = 0, total_len = 0, V = 0, bytes = 0;
+    u32* d_allow = nullptr;                 // [words] the filter's own bitmap, zero past n
+    double* d_idf = nullptr;                // subset mode: [V] the subset's idf per column
+    double avgdl = 1.0, k1 = 0.0, b = 0.0;  // subset mode, from the arm
 };
 
 // What a stage leaves for its commit.  Everything an update allocates is allocated here, before the first kernel.
@@ -790,6 +851,28 @@ static void bm_drop_stage(vf_bm25* h) {
     h->stage = nullptr;
 }
 
+static void bm_prepared_free_device(BmPrepared* f) {
+    if (f->d_allow) (void)hipFree(f->d_allow);
+    if (f->d_idf) (void)hipFree(f->d_idf);
+    f->d_allow = nullptr; f->d_idf = nullptr; f->bytes = 0;
+}
+
+// a committed update: no prepared filter may search again (rows have moved); the tokens stay known until they are released
+static void bm_prepared_invalidate(vf_bm25* h) {
+    for (BmPrepared* f : h->prepared) {
+        bm_prepared_free_device(f);
+        f->stale = true; f->armed = false;
+    }
+}
+
+static void bm_prepared_free_all(vf_bm25* h) {
+    for (BmPrepared* f : h->prepared) {
+        bm_prepared_free_device(f);
+        delete f;
+    }
+    h->prepared.clear();
+}
+
 static LiveArgs bm_live_args(const vf_bm25* h, const BmStage* s) {
     LiveArgs a{};
     a.indptr = h->d_indptr; a.indices = h->d_indices; a.tf = h->d_tf;
@@ -809,6 +892,7 @@ static int bm_destroy(vf_bm25* h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     bm_free_slots(h);
     bm_drop_stage(h);
+    bm_prepared_free_all(h);
     void* ps[] = {h->d_indptr, h->d_indices, h->d_data, h->d_big, h->d_big_tblk, h->d_big_ids, h->d_big_out, h->d_qoff, h->d_qterms,
                   h->d_tf, h->d_doclen, h->d_sub, h->d_sidf};
     for (void* p : ps)
@@ -959,6 +1043,7 @@ static int bm_live_commit(vf_bm25* h, const vf_bm25_delta* d) {
     h->born = true;
     ++h->gen;                  // what a VF_BM25_SUBSTATS stage counted is no longer this index's
     h->allow_staged = false;
+    bm_prepared_invalidate(h); // ... and no prepared filter's bits are this index's rows
     bm_drop_stage(h);
     return VF_OK;
 }
@@ -1158,9 +1243,136 @@ static int bm_substats_stage(vf_bm25* h, vf_bm25_substats_query* sq, const uint3
     return VF_OK;
 }
 
+// ---- prepared filters (include/veritasfi_hip.h: VF_BM25_PREPARED) -----------------------------------------------------------------
+static BmPrepared* bm_prepared_find(vf_bm25* h, unsigned long long token) {
+    for (BmPrepared* f : h->prepared)
+        if (f->token == token) return f;
+    return nullptr;
+}
+
+static int bm_prepared_stale(const vf_bm25* h, const BmPrepared* f, const char* what) {
+    return bm_fail(VF_EINVAL, std::string("vf_bm25_search: ") + what + ": the filter was prepared at update generation " + std::to_string(f->gen) +
+                                  ", the handle is at " + std::to_string(h->gen) + " (the live index was updated since: prepare the filter again)");
+}
+
+// PREPARE.  Everything is checked and allocated before the first device write; the filter joins the handle and the struct's out members
+// are written last, so a failure leaves the handle and every other filter as they were.
+static int bm_prepared_prepare(vf_bm25* h, vf_bm25_prepared_query* pq) {
+    if (pq->mode != VF_BM25_PREPARED_CORPUS && pq->mode != VF_BM25_PREPARED_SUBSET)
+        return bm_fail(VF_EINVAL, "vf_bm25_search: vf_bm25_prepared_query.mode must be VF_BM25_PREPARED_CORPUS or VF_BM25_PREPARED_SUBSET");
+    const bool subset = pq->mode == VF_BM25_PREPARED_SUBSET;
+    if (!pq->allow) return bm_fail(VF_EINVAL, "vf_bm25_search: VF_BM25_PREPARED_PREPARE with a null allow bitmap");
+    if (pq->n_docs != h->n)
+        return bm_fail(VF_EINVAL, "vf_bm25_search: the filter was made for " + std::to_string(pq->n_docs) + " documents, the handle holds " +
+                                      std::to_string(h->n) + " (a live handle may have changed since the bitmap was made: make it again)");
+    const Bm25FilterCheck fc = bm25f_check(pq->allow, h->n);
+    if (fc.bad_row >= 0)
+        return bm_fail(VF_EINVAL, "vf_bm25_search: the filter allows row " + std::to_string(fc.bad_row) + ", at or past n_docs = " + std::to_string(h->n));
+    const int C = pq->chunk == 0 ? kLiveMaxChunk : pq->chunk;
+    if (subset) {
+        if (!h->live || !h->born)
+            return bm_fail(VF_EUNSUPPORTED, "vf_bm25_search: a prepared filter in subset mode needs a live handle (VF_BM25_LIVE): only it keeps the term frequencies and the document lengths");
+        if (pq->vocab != h->V || (h->V > 0 && !pq->df))
+            return bm_fail(VF_EINVAL, "vf_bm25_search: VF_BM25_PREPARED_PREPARE in subset mode needs df[vocab] with vocab = the handle's " + std::to_string(h->V) + " columns");
+        if (C < 1 || C > kLiveMaxChunk) return bm_fail(VF_EINVAL, "vf_bm25_search: vf_bm25_prepared_query.chunk must be 0 or in [1, " + std::to_string(kLiveMaxChunk) + "]");
+    }
+    BmPrepared* f = new (std::nothrow) BmPrepared();
+    if (!f) return bm_fail(VF_ENOMEM, "host allocation failed");
+    const long long V = h->V;
+    std::vector<unsigned long long> back;   // the length sum, then the counts (two int32 per word)
+    try {
+        h->prepared.reserve(h->prepared.size() + 1);
+        if (subset) back.assign((size_t)(1 + (V + 1) / 2), 0ull);
+    } catch (const std::bad_alloc&) {
+        delete f;
+        return bm_fail(VF_ENOMEM, "host allocation failed");
+    }
+    DeviceGuard guard;
+    hipError_t e = hipSetDevice(h->device);
+    hipStream_t st = h->stream;
+    const size_t aw = (size_t)bm25f_words(h->n), wbytes = (size_t)h->words * 4, cbytes = 8 + (size_t)std::max<long long>(V, 1) * 4;
+    unsigned long long* d_cnt = nullptr;    // subset mode, for this call only: the length sum (8 B), then df [V] as int32
+    if (e == hipSuccess) e = hipMalloc((void**)&f->d_allow, wbytes);
+    if (e == hipSuccess && subset) e = hipMalloc((void**)&f->d_idf, (size_t)std::max<long long>(V, 1) * 8);
+    if (e == hipSuccess && subset) e = hipMalloc((void**)&d_cnt, cbytes);
+    if (e == hipSuccess) e = hipMemsetAsync(f->d_allow, 0, wbytes, st);   // the words past n stay zero
+    if (e == hipSuccess) e = hipMemcpyAsync(f->d_allow, pq->allow, aw * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && subset && fc.m > 0) {
+        e = hipMemsetAsync(d_cnt, 0, cbytes, st);
+        if (e == hipSuccess) {
+            SubArgs sa{};
+            sa.doclen = h->d_doclen; sa.allow = f->d_allow; sa.n = h->n; sa.total = d_cnt;
+            hipLaunchKernelGGL(k_bm25_sub_len, dim3((unsigned)(h->words / kBmWordsPerBlock)), dim3(kBmThreads), 0, st, sa);
+            if (h->nnz > 0) {
+                PrepArgs pa{};
+                pa.indptr = h->d_indptr; pa.indices = h->d_indices; pa.V = V; pa.nnz = h->nnz; pa.C = C;
+                pa.allow = f->d_allow; pa.df = (int*)(d_cnt + 1);
+                hipLaunchKernelGGL(k_bm25_sub_df_all, dim3((unsigned)live_chunks(h->nnz, C)), dim3(kBmThreads), 0, st, pa);
+            }
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(back.data(), d_cnt, 8 + (size_t)V * 4, hipMemcpyDeviceToHost, st);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (d_cnt) (void)hipFree(d_cnt);
+    if (e != hipSuccess) {
+        const std::string msg = std::string("vf_bm25_search (prepare): ") + hipGetErrorString(e);
+        bm_prepared_free_device(f);
+        delete f;
+        return bm_fail(e == hipErrorOutOfMemory ? VF_ENOMEM : VF_EHIP, msg);
+    }
+    f->token = h->next_token++; f->gen = h->gen; f->subset = subset; f->m = fc.m; f->V = V;
+    f->total_len = subset ? (long long)back[0] : 0;
+    f->bytes = (long long)wbytes + (subset ? std::max<long long>(V, 1) * 8 : 0);
+    h->prepared.push_back(f);   // reserved above: does not allocate
+    if (subset) {
+        const int32_t* df = (const int32_t*)(back.data() + 1);
+        for (long long c = 0; c < V; ++c) pq->df[c] = df[c];
+        pq->total_len = f->total_len;
+    }
+    pq->token = f->token; pq->m = f->m; pq->generation = f->gen; pq->bytes = f->bytes;
+    return VF_OK;
+}
+
+static int bm_prepared_arm(vf_bm25* h, const vf_bm25_prepared_query* pq) {
+    BmPrepared* f = bm_prepared_find(h, pq->token);
+    if (!f) return bm_fail(VF_EINVAL, "vf_bm25_search: VF_BM25_PREPARED_ARM: token " + std::to_string(pq->token) + " names no prepared filter of this handle (unknown or released)");
+    if (!f->subset) return bm_fail(VF_EINVAL, "vf_bm25_search: VF_BM25_PREPARED_ARM: the filter was prepared in corpus mode (it has no idf table)");
+    if (f->stale || f->gen != h->gen) return bm_prepared_stale(h, f, "VF_BM25_PREPARED_ARM");
+    if (pq->vocab != f->V || (f->V > 0 && !pq->idf))
+        return bm_fail(VF_EINVAL, "vf_bm25_search: VF_BM25_PREPARED_ARM needs idf[vocab] with vocab = the filter's " + std::to_string(f->V) + " columns");
+    for (long long c = 0; c < f->V; ++c)
+        if (!(pq->idf[c] >= 0.0) || !(pq->idf[c] <= DBL_MAX))
+            return bm_fail(VF_EINVAL, "vf_bm25_search: idf[" + std::to_string(c) + "] is negative or not finite");
+    if (!(pq->avgdl > 0.0) || !(pq->avgdl <= DBL_MAX) || !(pq->k1 >= 0.0) || !(pq->b >= 0.0 && pq->b <= 1.0))
+        return bm_fail(VF_EINVAL, "vf_bm25_search: VF_BM25_PREPARED_ARM needs avgdl > 0, k1 >= 0 and b in [0, 1]");
+    DeviceGuard guard;
+    VFS_HIP(hipSetDevice(h->device));
+    if (f->V > 0) VFS_HIP(hipMemcpyAsync(f->d_idf, pq->idf, (size_t)f->V * 8, hipMemcpyHostToDevice, h->stream));
+    VFS_HIP(hipStreamSynchronize(h->stream));
+    f->avgdl = pq->avgdl; f->k1 = pq->k1; f->b = pq->b; f->armed = true;
+    return VF_OK;
+}
+
+static int bm_prepared_release(vf_bm25* h, const vf_bm25_prepared_query* pq) {
+    for (size_t i = 0; i < h->prepared.size(); ++i) {
+        BmPrepared* f = h->prepared[i];
+        if (f->token != pq->token) continue;
+        DeviceGuard guard;
+        (void)hipSetDevice(h->device);
+        (void)hipStreamSynchronize(h->stream);
+        bm_prepared_free_device(f);
+        delete f;
+        h->prepared.erase(h->prepared.begin() + (long)i);
+        return VF_OK;
+    }
+    return bm_fail(VF_EINVAL, "vf_bm25_search: VF_BM25_PREPARED_RELEASE: token " + std::to_string(pq->token) + " names no prepared filter of this handle (unknown or released)");
+}
+
 // the scoring and the radix select of the group's queries (slots 0 .. g-1); sel / tblk / out set by the caller.  allow: the device
 // bitmap of a filtered call (the scatter skips the rows outside it), or null
-static int bm_score_select(vf_bm25* h, BmArgs& a, const int64_t* q_off, int g, const u32* allow, const SubArgs* ss = nullptr) {
+// ss: a search by the subset's statistics; by_col: its idf is a prepared filter's table over the vocabulary, not one entry per position
+static int bm_score_select(vf_bm25* h, BmArgs& a, const int64_t* q_off, int g, const u32* allow, const SubArgs* ss = nullptr, bool by_col = false) {
     hipStream_t st = h->stream;
     long long maxlen = 0;
     for (int s = 0; s < g; ++s) maxlen = std::max<long long>(maxlen, q_off[a.q0 + s + 1] - q_off[a.q0 + s]);
@@ -1174,7 +1386,8 @@ static int bm_score_select(vf_bm25* h, BmArgs& a, const int64_t* q_off, int g, c
             }
         }
         if (post == 0) continue;
-        if (ss) hipLaunchKernelGGL(k_bm25_accum_s, dim3(bm_grid(post, kBmThreads, 4096), g), dim3(kBmThreads), 0, st, a, (int)t, *ss);
+        if (ss && by_col) hipLaunchKernelGGL(k_bm25_accum_sc, dim3(bm_grid(post, kBmThreads, 4096), g), dim3(kBmThreads), 0, st, a, (int)t, *ss);
+        else if (ss) hipLaunchKernelGGL(k_bm25_accum_s, dim3(bm_grid(post, kBmThreads, 4096), g), dim3(kBmThreads), 0, st, a, (int)t, *ss);
         else if (allow) hipLaunchKernelGGL(k_bm25_accum_f, dim3(bm_grid(post, kBmThreads, 4096), g), dim3(kBmThreads), 0, st, a, (int)t, allow);
         else hipLaunchKernelGGL(k_bm25_accum, dim3(bm_grid(post, kBmThreads, 4096), g), dim3(kBmThreads), 0, st, a, (int)t);
         VFS_HIP(hipGetLastError());
@@ -1216,7 +1429,22 @@ extern "C" int vf_bm25_search(vf_bm25* h, const int64_t* q_offsets, const int32_
     if (nq < 0) return bm_fail(VF_EINVAL, "vf_bm25_search: negative nq");
     const vf_bm25_filter_query* fq = nullptr;   // VF_BM25_FILTER: one set of rows for every query of the call
     vf_bm25_substats_query* sq = nullptr;       // ... | VF_BM25_SUBSTATS: scored by that set's own statistics, in two phases
-    if (nq & VF_BM25_FILTER) {
+    vf_bm25_prepared_query* pq = nullptr;       // VF_BM25_PREPARED: the set and its statistics are a prepared filter's, on the device
+    if (nq & VF_BM25_PREPARED) {
+        if (nq & (VF_BM25_FILTER | VF_BM25_SUBSTATS))
+            return bm_fail(VF_EINVAL, "vf_bm25_search: VF_BM25_PREPARED goes alone (the prepared filter carries its rows and its mode)");
+        pq = (vf_bm25_prepared_query*)(void*)q_offsets;
+        if (!pq) return bm_fail(VF_EINVAL, "vf_bm25_search: VF_BM25_PREPARED with a null vf_bm25_prepared_query");
+        nq &= ~VF_BM25_PREPARED;
+        if (pq->phase != VF_BM25_PREPARED_SEARCH) {
+            std::lock_guard<std::mutex> lk(h->mu);
+            if (pq->phase == VF_BM25_PREPARED_PREPARE) return bm_prepared_prepare(h, pq);
+            if (pq->phase == VF_BM25_PREPARED_ARM) return bm_prepared_arm(h, pq);
+            if (pq->phase == VF_BM25_PREPARED_RELEASE) return bm_prepared_release(h, pq);
+            return bm_fail(VF_EINVAL, "vf_bm25_search: vf_bm25_prepared_query.phase must be one of the four VF_BM25_PREPARED_* phases");
+        }
+        q_offsets = pq->q_offsets;
+    } else if (nq & VF_BM25_FILTER) {
         fq = (const vf_bm25_filter_query*)(const void*)q_offsets;
         if (!fq) return bm_fail(VF_EINVAL, "vf_bm25_search: VF_BM25_FILTER with a null vf_bm25_filter_query");
         if (nq & VF_BM25_SUBSTATS) sq = (vf_bm25_substats_query*)(void*)q_offsets;   // its first three members are fq's
@@ -1279,6 +1507,21 @@ extern "C" int vf_bm25_search(vf_bm25* h, const int64_t* q_offsets, const int32_
         }
         if (stage) return bm_substats_stage(h, sq, fq->allow, fc.m, q_terms, nq, T);
     }
+    const BmPrepared* pf = nullptr;
+    if (pq) {   // the filter's own checks were made when it was prepared: only that it is still this index's is looked at here
+        pf = bm_prepared_find(h, pq->token);
+        if (!pf) return bm_fail(VF_EINVAL, "vf_bm25_search: token " + std::to_string(pq->token) + " names no prepared filter of this handle (unknown or released)");
+        if (pf->stale || pf->gen != h->gen) return bm_prepared_stale(h, pf, "VF_BM25_PREPARED_SEARCH");
+        if (pf->subset && !pf->armed)
+            return bm_fail(VF_EINVAL, "vf_bm25_search: the prepared filter is in subset mode and was never armed (VF_BM25_PREPARED_ARM gives it its idf)");
+        fp = bm25f_plan(h->words, pf->m, k);
+        if (pf->m == 0) {   // nothing may be returned: all padding, no launch
+            std::fill(out_ids, out_ids + (size_t)nq * k, (int64_t)-1);
+            std::fill(out_scores, out_scores + (size_t)nq * k, -FLT_MAX);
+            return VF_OK;
+        }
+    }
+    const bool filtered = fq || pf;
     DeviceGuard guard;
     VFS_HIP(hipSetDevice(h->device));
     hipStream_t st = h->stream;
@@ -1324,6 +1567,11 @@ extern "C" int vf_bm25_search(vf_bm25* h, const int64_t* q_offsets, const int32_
         if (!staged) VFS_HIP(hipMemcpyAsync(h->d_allow, fq->allow, aw * 4, hipMemcpyHostToDevice, st));
         allow = h->d_allow;
     }
+    if (pf) {   // nothing goes up: the bitmap is the filter's own (d_allow and what a stage left in it are not touched)
+        const int rc = bm_ensure_filter(h);   // the tail's scratch over every bitmap block
+        if (rc != VF_OK) return rc;
+        allow = pf->d_allow;
+    }
     SubArgs sub{};
     if (sq) {
         const int rc = bm_ensure_sidf(h, T);
@@ -1332,7 +1580,12 @@ extern "C" int vf_bm25_search(vf_bm25* h, const int64_t* q_offsets, const int32_
         sub.tf = h->d_tf; sub.doclen = h->d_doclen; sub.allow = allow; sub.n = h->n;
         sub.idf = h->d_sidf; sub.avgdl = sq->avgdl; sub.k1 = sq->k1; sub.b = sq->b; sub.one_minus_b = 1.0 - sq->b;
     }
-    const SubArgs* ss = sq ? &sub : nullptr;
+    const bool by_col = pf && pf->subset;
+    if (by_col) {
+        sub.tf = h->d_tf; sub.doclen = h->d_doclen; sub.allow = allow; sub.n = h->n;
+        sub.idf = pf->d_idf; sub.avgdl = pf->avgdl; sub.k1 = pf->k1; sub.b = pf->b; sub.one_minus_b = 1.0 - pf->b;
+    }
+    const SubArgs* ss = (sq || by_col) ? &sub : nullptr;
     const unsigned pad_grid = bm_grid(k - fp.pad_from, kBmThreads, 64);   // a filtered call of fewer than k rows pads ranks pad_from .. k - 1
     a.scores = h->d_scores; a.score_stride = h->n;
     a.bits = h->d_bits; a.bits_stride = h->words;
@@ -1343,24 +1596,24 @@ extern "C" int vf_bm25_search(vf_bm25* h, const int64_t* q_offsets, const int32_
         if (small) {
             a.sel = h->d_sel; a.sel_stride = kBmSmallK; a.sel_cap = kBmSmallK;
             a.tblk = h->d_tblk; a.tblk_stride = 1;
-            if (fq) { a.tblk = h->d_ftblk; a.tblk_stride = fp.tblk_entries; }
+            if (filtered) { a.tblk = h->d_ftblk; a.tblk_stride = fp.tblk_entries; }
             a.out_ids = h->d_ids; a.out_scores = h->d_out; a.out_stride = k;
-            int rc = bm_score_select(h, a, q_offsets, g, allow, ss);
+            int rc = bm_score_select(h, a, q_offsets, g, allow, ss, by_col);
             if (rc != VF_OK) return rc;
-            if (fq && fp.pad_from < k) hipLaunchKernelGGL(k_bm25_pad_out, dim3(pad_grid, g), dim3(kBmThreads), 0, st, a, fp.pad_from);
+            if (filtered && fp.pad_from < k) hipLaunchKernelGGL(k_bm25_pad_out, dim3(pad_grid, g), dim3(kBmThreads), 0, st, a, fp.pad_from);
             const int Pk = (int)bm_pow2(k);
             hipLaunchKernelGGL(k_bm25_sort_small, dim3(1, g), dim3(512), (size_t)Pk * 8, st, a, Pk);
             // fewer than k touched rows means fewer than kBmSmallK: the tail lies in the first 2 * kBmSmallK rows, one bitmap block --
             // unless a filter strikes rows out: then the allowed untouched rows can lie in any block, and every block is counted
-            rc = bm_tail_and_reset(h, a, q_offsets, g, fq ? fp.tail_blocks : 1, allow);
+            rc = bm_tail_and_reset(h, a, q_offsets, g, filtered ? fp.tail_blocks : 1, allow);
             if (rc != VF_OK) return rc;
         } else {
             a.sel = h->d_big; a.sel_stride = 0; a.sel_cap = bm_pow2(h->n);
             a.tblk = h->d_big_tblk; a.tblk_stride = 0;
             a.out_ids = h->d_big_ids; a.out_scores = h->d_big_out; a.out_stride = 0;
-            int rc = bm_score_select(h, a, q_offsets, 1, allow, ss);
+            int rc = bm_score_select(h, a, q_offsets, 1, allow, ss, by_col);
             if (rc != VF_OK) return rc;
-            if (fq && fp.pad_from < k) hipLaunchKernelGGL(k_bm25_pad_out, dim3(pad_grid, 1), dim3(kBmThreads), 0, st, a, fp.pad_from);
+            if (filtered && fp.pad_from < k) hipLaunchKernelGGL(k_bm25_pad_out, dim3(pad_grid, 1), dim3(kBmThreads), 0, st, a, fp.pad_from);
             BmState bs;
             VFS_HIP(hipMemcpyAsync(&bs, h->d_st, sizeof(bs), hipMemcpyDeviceToHost, st));
             VFS_HIP(hipStreamSynchronize(st));

@@ -71,6 +71,72 @@ def _host_bm25(bm25_dir):
                       "switch the branch off explicitly")
 
 
+class PreparedWhere:
+    """A metadata filter prepared ONCE for many ``EnsembleRetriever.invoke(..., where=<this object>)`` calls (``prepare_where``): the
+    same ``where`` on thousands of consecutive requests (one tenant) need not be looked up, turned into a set and shipped to both legs
+    per request.  It holds ``where`` itself, the passing rows (``passing``, ``rows_where``'s answer), their set (``allow``), for the dense
+    leg a device-resident ``RowSubset`` when the retriever's index is a single-device handle that offers ``row_subset`` (else the ids),
+    and for the BM25 leg a ``BM25Subset`` (``prepare_subset(passing, stats=where_statistics)``) when the retriever offers
+    ``prepare_subset`` (else the ids).
+    It holds MEANING, not rows: after ``add_documents`` / ``remove_documents`` rows have shifted and metadata has changed, but the dict
+    still means what it meant, so the next use re-prepares it from ``where`` (releasing the old device objects).  The lower-level
+    ``BM25Subset`` and ``RowSubset`` hold rows and keep refusing when stale.  ``close()`` (or ``with``) releases both legs."""
+
+    def __init__(self, retriever, where):
+        if not isinstance(where, dict):
+            raise TypeError("prepare_where: `where` is a dict field -> value, or field -> a collection of values")
+        self._retriever, self.where = retriever, dict(where)
+        self._mu = threading.Lock()
+        self._closed, self._epoch = False, None
+        self.passing = self.allow = self.dense = self.bm25 = None
+        with self._mu:
+            self._prepare()
+
+    def _release(self) -> None:
+        bm, self.bm25, self.dense = self.bm25, None, None   # a RowSubset's device ids go with its last reference
+        if hasattr(bm, "close"):
+            bm.close()
+
+    def _prepare(self) -> None:
+        r = self._retriever
+        self._release()
+        self.passing = r.rows_where(self.where)
+        self.allow = set(self.passing.tolist())
+        self.dense = self.bm25 = self.passing
+        self._epoch = r._epoch
+        if self.passing.size == 0:      # invoke returns [] before any leg is asked
+            return
+        ix = getattr(r.faiss_retriever, "index", None)
+        if r.faiss_k > 0 and hasattr(ix, "row_subset") and getattr(ix, "device_ids", None) is None:
+            self.dense = ix.row_subset(self.passing)
+        bm = r.bm25_retriever
+        if r.bm25_k > 0 and hasattr(bm, "prepare_subset"):
+            self.bm25 = bm.prepare_subset(self.passing, stats=r.where_statistics)
+
+    def _current(self, retriever):
+        """(passing, allow, dense subset, BM25 subset) for a request of ``retriever``, prepared again if the corpus has changed."""
+        if retriever is not self._retriever:
+            raise ValueError("where: this PreparedWhere was prepared on another EnsembleRetriever; use that retriever's prepare_where")
+        with self._mu:
+            if self._closed:
+                raise ValueError("where: this PreparedWhere is closed; call prepare_where again")
+            if self._epoch != retriever._epoch:
+                self._prepare()
+            return self.passing, self.allow, self.dense, self.bm25
+
+    def close(self) -> None:
+        with self._mu:
+            if not self._closed:
+                self._closed = True
+                self._release()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class EnsembleRetriever:
     def __init__(self, bm25_dir, chroma, ts_chroma, k: int, embeddings, faiss_k: int = None, bm25_k: int = None,
                  faiss_ts_k: int = None, enable_expand: bool = False, bm25_retriever=None, retriever_cls=FaissRetriever,
@@ -94,6 +160,7 @@ class EnsembleRetriever:
         if where_statistics not in ("corpus", "subset"):
             raise ValueError(f"where_statistics={where_statistics!r}: 'corpus' or 'subset'")
         self.where_statistics = where_statistics
+        self._epoch = 0   # advanced by add_documents / remove_documents: a PreparedWhere of an older epoch prepares itself again
         self.embeddings = embeddings
         self.faiss_k = faiss_k if faiss_k is not None else k
         self.bm25_k = bm25_k if bm25_k is not None else k
@@ -228,6 +295,7 @@ class EnsembleRetriever:
             if b is not None:
                 self._bundle_rows.setdefault(b, []).append(row)
             self._title_rows.setdefault(md.get("title_summary", ""), []).append(row)
+        self._epoch += 1
         return list(range(first, self.num_chunk))
 
     def remove_documents(self, doc_ids) -> int:
@@ -263,6 +331,7 @@ class EnsembleRetriever:
             self._documents = [t for r, t in enumerate(self._documents) if r not in gone]
         self._build_maps()
         self._text_rows = _TextRows()
+        self._epoch += 1
         return len(rows)
 
     # -- metadata filters -----------------------------------------------------------------------------
@@ -289,6 +358,13 @@ class EnsembleRetriever:
             hit = np.asarray(hit, dtype=np.int64)
             rows = hit if rows is None else np.intersect1d(rows, hit, assume_unique=True)
         return np.arange(self.num_chunk, dtype=np.int64) if rows is None else rows
+
+    def prepare_where(self, where) -> PreparedWhere:
+        """``where`` (``rows_where``'s argument) prepared once for many ``invoke(..., where=<the returned object>)`` calls: the passing
+        rows, their set, the dense leg's device-resident ``RowSubset`` and the BM25 leg's ``BM25Subset`` (under this retriever's
+        ``where_statistics``) are computed here and not per request.  The output of ``invoke`` is that of the dict form.  After
+        ``add_documents`` / ``remove_documents`` the object prepares itself again on its next use; ``close()`` it when done."""
+        return PreparedWhere(self, where)
 
     # -- pieces -------------------------------------------------------------------------------------
     def _bundle_of(self, row: int, seen: set, allow=None) -> List[int]:
@@ -352,7 +428,8 @@ class EnsembleRetriever:
         asked with ``stats="subset"`` and scores by the passing chunks' own statistics.  A retriever that declares ``filtered_prefix`` (this package's
         ``BM25Retriever``) is asked for exactly those, ``invoke(input, min(bm25_k, passing rows), subset=passing)``, and filters
         inside its kernels, so the exception costs nothing; any other retriever is asked for the full ranking, which is
-        filtered here.  A filter nothing passes returns []."""
+        filtered here.  A filter nothing passes returns [].  A ``PreparedWhere`` (``prepare_where``) in place of the dict gives the same
+        output without the per-request host work: the rows, their set and both legs' device-resident filters are its own."""
         with stages.stage("retrieve"):
             out = self._invoke(input, hyde_chunks, where)
         stages.metric("retrieved_chunks", len(out))
@@ -362,22 +439,27 @@ class EnsembleRetriever:
         seen: set = set()
         out: list = []
         bundle_cnt = 0
-        passing = None if where is None else self.rows_where(where)
-        allow = None if passing is None else set(passing.tolist())
+        dense_rows = bm25_rows = None   # what the two legs take as subset=: the passing rows, or a PreparedWhere's device-resident filters
+        if isinstance(where, PreparedWhere):
+            passing, allow, dense_rows, bm25_rows = where._current(self)
+        else:
+            passing = None if where is None else self.rows_where(where)
+            allow = None if passing is None else set(passing.tolist())
+            dense_rows = bm25_rows = passing
         if passing is not None and passing.size == 0:
             return out
         if self.faiss_k > 0:
             with stages.stage("retrieve_faiss"):
-                bundle_cnt = self._faiss_branch(input, hyde_chunks, seen, out, bundle_cnt, passing, allow)
+                bundle_cnt = self._faiss_branch(input, hyde_chunks, seen, out, bundle_cnt, passing, allow, dense_rows)
         if self.faiss_ts_k > 0:
             with stages.stage("retrieve_faiss_ts"):
                 bundle_cnt = self._title_branch(input, seen, out, bundle_cnt, allow)
         if self.bm25_k > 0:
             with stages.stage("retrieve_bm25"):
-                bundle_cnt = self._bm25_branch(input, seen, out, bundle_cnt, allow, passing)
+                bundle_cnt = self._bm25_branch(input, seen, out, bundle_cnt, allow, passing, bm25_rows)
         return out
 
-    def _faiss_branch(self, input, hyde_chunks, seen, out, bundle_cnt, passing=None, allow=None):
+    def _faiss_branch(self, input, hyde_chunks, seen, out, bundle_cnt, passing=None, allow=None, dense_rows=None):
         inputs = [input] + list(hyde_chunks)
         # upstream always searches 2048 deep (:64-66) and reads the tail only as the neighbour expansion's score map (:85-107): without
         # enable_expand the first faiss_k entries are all that is looked at, and an exact search's top-k is a prefix of its top-2048
@@ -385,7 +467,7 @@ class EnsembleRetriever:
         if passing is None:
             ids_list, scores_list = self.faiss_retriever.invoke(inputs, depth)
         else:   # rows are ids here (the retriever's index starts at 0, as upstream's does)
-            ids_list, scores_list = self.faiss_retriever.invoke(inputs, depth, subset=passing)
+            ids_list, scores_list = self.faiss_retriever.invoke(inputs, depth, subset=passing if dense_rows is None else dense_rows)
         for ids, scores in zip(ids_list, scores_list):
             ids = [int(i) for i in ids]
             score_map = dict(zip(ids, scores))
@@ -414,11 +496,14 @@ class EnsembleRetriever:
                 bundle_cnt += 1
         return bundle_cnt
 
-    def _bm25_branch(self, input, seen, out, bundle_cnt, allow=None, passing=None):
+    def _bm25_branch(self, input, seen, out, bundle_cnt, allow=None, passing=None, bm25_rows=None):
         if allow is not None:
             # filtered: the first bm25_k passing rows of the full ranking (whole-corpus statistics: the stated exception) -- from a
             # retriever that filters on its own (filtered_prefix), else from the full ranking, filtered here
-            if passing is not None and self.where_statistics == "subset":   # no exception: the passing chunks' own statistics
+            if passing is not None and bm25_rows is not None and bm25_rows is not passing:   # a prepared filter: its mode is its own
+                b_ids, b_scores = self.bm25_retriever.invoke(input, max(1, min(int(self.bm25_k), len(passing))), subset=bm25_rows)
+                kept = [(int(r), s) for r, s in zip(b_ids, b_scores)]
+            elif passing is not None and self.where_statistics == "subset":   # no exception: the passing chunks' own statistics
                 b_ids, b_scores = self.bm25_retriever.invoke(input, max(1, min(int(self.bm25_k), len(passing))), subset=passing, stats="subset")
                 kept = [(int(r), s) for r, s in zip(b_ids, b_scores)]
             elif passing is not None and getattr(self.bm25_retriever, "filtered_prefix", False) is True:
