@@ -549,13 +549,26 @@ class BM25Retriever:
         terms = np.ascontiguousarray(np.concatenate(cols) if cols else np.zeros(0, np.int32), dtype=np.int32)
         return cols, offsets, terms
 
+    def _search(self, q, terms, nq: int, k: int, ids=None, scores=None) -> int:
+        """``vf_bm25_search`` (``self._mu`` held) -> its code.  ``q``: the query offsets' pointer, or the struct ``nq``'s flags announce."""
+        if isinstance(q, _ffi.ctypes.Structure):
+            q = _ffi.ctypes.cast(_ffi.ctypes.byref(q), _ffi.p_i64)
+        return _ffi.lib().vf_bm25_search(self._h, q, None if terms is None else terms.ctypes.data_as(_ffi.p_i32), nq, k,
+                                         None if ids is None else ids.ctypes.data_as(_ffi.p_i64), None if scores is None else scores.ctypes.data_as(_ffi.p_f32))
+
     def _substats_stage(self, sq, terms, nq: int) -> np.ndarray:
         """The stage call (``self._mu`` held): fills sq.m, sq.total_len and sq.generation, returns df per q_terms position."""
         df = np.zeros(max(int(terms.size), 1), np.int64)
         sq.phase, sq.df = _ffi.VF_BM25_SUBSTATS_STAGE, df.ctypes.data_as(_ffi.p_i64)
-        _ffi.check(_ffi.lib().vf_bm25_search(self._h, _ffi.ctypes.cast(_ffi.ctypes.byref(sq), _ffi.p_i64), terms.ctypes.data_as(_ffi.p_i32),
-                                             nq | _ffi.VF_BM25_FILTER | _ffi.VF_BM25_SUBSTATS, 1, None, None), "vf_bm25_search")
+        _ffi.check(self._search(sq, terms, nq | _ffi.VF_BM25_FILTER | _ffi.VF_BM25_SUBSTATS, 1), "vf_bm25_search")
         return df[:terms.size]
+
+    @staticmethod
+    def _subset_idf_avgdl(m: int, df, total_len: int):
+        """(idf per entry of ``df``, avgdl) of ``m`` rows holding ``total_len`` tokens: ``bm25_index_arrays``' expression with N = m; 1.0 for no token."""
+        df = df.astype(np.float64)
+        idf = np.ascontiguousarray(np.log(1.0 + (m - df + 0.5) / (df + 0.5)))
+        return idf, (float(int(total_len)) / m if m and total_len else 1.0)
 
     # The attribute ``subset_statistics`` declares that ``invoke`` takes stats="subset" (EnsembleRetriever(where_statistics="subset") asks
     # for a truthy one; a retriever of another make sets ``subset_statistics = True``).  Here it is the method that exposes the counts.
@@ -577,7 +590,7 @@ class BM25Retriever:
     def _prepared_call(self, pq, phase: int) -> int:
         """A prepare, arm or release call (``self._mu`` held); returns the code."""
         pq.phase = phase
-        return _ffi.lib().vf_bm25_search(self._h, _ffi.ctypes.cast(_ffi.ctypes.byref(pq), _ffi.p_i64), None, _ffi.VF_BM25_PREPARED, 1, None, None)
+        return self._search(pq, None, _ffi.VF_BM25_PREPARED, 1)
 
     def _release_token(self, token: int) -> None:
         if self._h.value:
@@ -640,10 +653,8 @@ class BM25Retriever:
             t2 = t3 = time.perf_counter()
             if by_subset:
                 df = df[:V]
-                m, dff = int(pq.m), df.astype(np.float64)
-                idf = np.ascontiguousarray(np.log(1.0 + (m - dff + 0.5) / (dff + 0.5)))      # as bm25_index_arrays, N = m
+                idf, pq.avgdl = self._subset_idf_avgdl(int(pq.m), df, pq.total_len)
                 pq.idf = idf.ctypes.data_as(_ffi.ctypes.POINTER(_ffi.ctypes.c_double))
-                pq.avgdl = float(int(pq.total_len)) / m if m and pq.total_len else 1.0
                 pq.k1, pq.b = self._k1, self._b
                 t3 = time.perf_counter()
                 rc = self._prepared_call(pq, _ffi.VF_BM25_PREPARED_ARM)
@@ -698,36 +709,27 @@ class BM25Retriever:
             if prepared:
                 pq = _ffi.Bm25PreparedQuery()
                 pq.q_offsets, pq.token, pq.phase = q_arg, subset._token, _ffi.VF_BM25_PREPARED_SEARCH
-                _ffi.check(_ffi.lib().vf_bm25_search(self._h, _ffi.ctypes.cast(_ffi.ctypes.byref(pq), _ffi.p_i64), terms.ctypes.data_as(_ffi.p_i32),
-                                                     nq | _ffi.VF_BM25_PREPARED, k, ids.ctypes.data_as(_ffi.p_i64),
-                                                     scores.ctypes.data_as(_ffi.p_f32)), "vf_bm25_search")
+                _ffi.check(self._search(pq, terms, nq | _ffi.VF_BM25_PREPARED, k, ids, scores), "vf_bm25_search")
                 return ids, scores
             if by_subset:
                 t0 = time.perf_counter()
                 words, _ = filter_words(subset, self.num_docs)
                 sq = _ffi.Bm25SubstatsQuery(q_arg, words.ctypes.data_as(_ffi.ctypes.POINTER(_ffi.ctypes.c_uint32)), self.num_docs)
                 t1 = time.perf_counter()
-                df = self._substats_stage(sq, terms, nq).astype(np.float64)
+                df = self._substats_stage(sq, terms, nq)
                 t2 = time.perf_counter()
-                m = int(sq.m)
-                idf = np.ascontiguousarray(np.log(1.0 + (m - df + 0.5) / (df + 0.5)))      # as bm25_index_arrays, N = m
+                idf, sq.avgdl = self._subset_idf_avgdl(int(sq.m), df, sq.total_len)
                 sq.idf = idf.ctypes.data_as(_ffi.ctypes.POINTER(_ffi.ctypes.c_double))
-                sq.avgdl = float(int(sq.total_len)) / m if m and sq.total_len else 1.0
                 sq.k1, sq.b, sq.phase = self._k1, self._b, _ffi.VF_BM25_SUBSTATS_SEARCH
                 t3 = time.perf_counter()
-                _ffi.check(_ffi.lib().vf_bm25_search(self._h, _ffi.ctypes.cast(_ffi.ctypes.byref(sq), _ffi.p_i64), terms.ctypes.data_as(_ffi.p_i32),
-                                                     nq | _ffi.VF_BM25_FILTER | _ffi.VF_BM25_SUBSTATS, k, ids.ctypes.data_as(_ffi.p_i64),
-                                                     scores.ctypes.data_as(_ffi.p_f32)), "vf_bm25_search")
+                _ffi.check(self._search(sq, terms, nq | _ffi.VF_BM25_FILTER | _ffi.VF_BM25_SUBSTATS, k, ids, scores), "vf_bm25_search")
                 # where the request's time went (tools/bench_bm25_substats.py): pack = the bitmap; host = idf and avgdl
                 self.last_subset_ms = {"pack": 1e3 * (t1 - t0), "stage": 1e3 * (t2 - t1), "host": 1e3 * (t3 - t2), "search": 1e3 * (time.perf_counter() - t3)}
                 return ids, scores
             if subset is not None:   # packed under the lock: the mask's length is held to the count the device has now
                 words, _ = filter_words(subset, self.num_docs)
-                fq = _ffi.Bm25FilterQuery(q_arg, words.ctypes.data_as(_ffi.ctypes.POINTER(_ffi.ctypes.c_uint32)), self.num_docs)
-                q_arg, nq = _ffi.ctypes.cast(_ffi.ctypes.byref(fq), _ffi.p_i64), nq | _ffi.VF_BM25_FILTER
-            _ffi.check(_ffi.lib().vf_bm25_search(self._h, q_arg, terms.ctypes.data_as(_ffi.p_i32),
-                                                 nq, k, ids.ctypes.data_as(_ffi.p_i64), scores.ctypes.data_as(_ffi.p_f32)),
-                       "vf_bm25_search")
+                q_arg, nq = _ffi.Bm25FilterQuery(q_arg, words.ctypes.data_as(_ffi.ctypes.POINTER(_ffi.ctypes.c_uint32)), self.num_docs), nq | _ffi.VF_BM25_FILTER
+            _ffi.check(self._search(q_arg, terms, nq, k, ids, scores), "vf_bm25_search")
         return ids, scores
 
     def _result(self, ids_row: np.ndarray, scores_row: np.ndarray):

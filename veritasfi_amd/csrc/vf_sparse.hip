@@ -671,9 +671,32 @@ __global__ __launch_bounds__(kBmThreads) void k_bm25_live_append(LiveArgs a) {
 
 }  // namespace vf
 
+// ---- the host path ---------------------------------------------------------------------------------------------------------------
+// Everything above is device code; from here on the host decides what runs.
+//   the mode of a call     vf_bm25_call.h: bm25c_decode turns `nq`'s flag bits and the struct's phase into one of eight kinds or a
+//                          refusal, bm25c_plan turns (kind, k, nq, slots, words, m) into the kernels of the group loop.  vf_bm25_search
+//                          is decode, the checks every kind shares, the filter resolved into a BmFilter (bm_filter_check, then
+//                          bm_filter_bind once the slots exist), one group loop.
+//   the checks             each written once: bm_check_allow (a caller's bitmap), bm_check_scoring (idf, avgdl, k1, b), bm_all_padding,
+//                          bm_sub_args (the SubArgs of the stage, the prepare and both scored searches).
+//   device memory          bm_free frees and nulls, bm_alloc makes a list of buffers or none of them, bm_grow serves the buffers that
+//                          follow a call's size.  The handle owns the index arrays, the query buffers, d_sub and d_sidf for its whole
+//                          life; the slots' scratch with d_allow and d_ftblk (bm_free_slots) and the deep-k scratch (bm_free_big) until
+//                          an update changes n; a BmStage owns an update's second set of arrays until the commit swaps them in; a
+//                          BmPrepared owns its bitmap and idf table until it is released or an update makes it stale.
+#include "vf_bm25_call.h"
+
+#include <initializer_list>
+
 using namespace vf;
 
+static_assert(kBm25cFilter == VF_BM25_FILTER && kBm25cSubstats == VF_BM25_SUBSTATS && kBm25cPrepared == VF_BM25_PREPARED, "vf_bm25_call.h decodes the ABI's flag bits");
+static_assert(kBm25cSmallK == kBmSmallK, "vf_bm25_call.h plans the small-k arm");
+static_assert(VF_BM25_SUBSTATS_STAGE == 1 && VF_BM25_SUBSTATS_SEARCH == 2 && VF_BM25_PREPARED_PREPARE == 1 && VF_BM25_PREPARED_ARM == 2 &&
+              VF_BM25_PREPARED_SEARCH == 3 && VF_BM25_PREPARED_RELEASE == 4, "vf_bm25_call.h decodes the ABI's phases");
+
 static int bm_fail(int code, const std::string& msg) { return vf::set_error(code, msg); }
+static int bm_hip_fail(const char* what, hipError_t e) { return bm_fail(e == hipErrorOutOfMemory ? VF_ENOMEM : VF_EHIP, std::string(what) + ": " + hipGetErrorString(e)); }
 
 #define VFS_HIP(expr)                                                                                                   \
     do {                                                                                                                \
@@ -765,31 +788,59 @@ static long long bm_slot_bytes(const vf_bm25* h) {
     return h->n * 4 + (long long)h->words * 4 + 256 * 4 + (long long)sizeof(BmState) + 4 + (long long)kBmSmallK * (8 + 8 + 4);
 }
 
+// ---- device buffers: every hipMalloc and hipFree of the BM25 leg goes through these three ---------------------------------------------
+template <class... T>
+static void bm_free(T*&... p) {   // free and null
+    ((p ? (void)hipFree((void*)p) : (void)0, p = nullptr), ...);
+}
+
+struct BmBuf { void** p; size_t bytes; };
+template <class T>
+static BmBuf bm_buf(T*& p, size_t bytes) { return BmBuf{(void**)&p, bytes}; }
+
+// Makes every buffer of the list (all null on entry; an entry of 0 bytes is not wanted and stays null) or, on a failure, none of them: what
+// it made is freed and null again.  `what` opens the message.
+static int bm_alloc(const char* what, std::initializer_list<BmBuf> bufs) {
+    for (const BmBuf& b : bufs) {
+        const hipError_t e = b.bytes ? hipMalloc(b.p, b.bytes) : hipSuccess;
+        if (e == hipSuccess) continue;
+        *b.p = nullptr;
+        for (const BmBuf& made : bufs) bm_free(*made.p);   // the entries past the failure are null still
+        return bm_hip_fail(what, e);
+    }
+    return VF_OK;
+}
+
+// a buffer that follows a call's size: made again (its contents are the call's own) when `want` entries exceed what it holds
+template <class T>
+static int bm_grow(const char* what, T*& p, long long& cap, long long want, size_t bytes) {
+    if (want <= cap) return VF_OK;
+    bm_free(p);
+    cap = 0;
+    const int rc = bm_alloc(what, {bm_buf(p, bytes)});
+    if (rc == VF_OK) cap = want;
+    return rc;
+}
+
 static void bm_free_slots(vf_bm25* h) {
-    void* ps[] = {h->d_scores, h->d_bits, h->d_hist, h->d_st, h->d_sel, h->d_tblk, h->d_ids, h->d_out, h->d_allow, h->d_ftblk};
-    for (void* p : ps)
-        if (p) (void)hipFree(p);
-    h->d_scores = nullptr; h->d_bits = nullptr; h->d_hist = nullptr; h->d_st = nullptr; h->d_sel = nullptr;
-    h->d_tblk = nullptr; h->d_ids = nullptr; h->d_out = nullptr;
-    h->d_allow = nullptr; h->d_ftblk = nullptr;   // sized by the slots and the words that go here: the next filtered call makes them again
+    // d_allow and d_ftblk are sized by the slots and the words that go here: the next filtered call makes them again
+    bm_free(h->d_scores, h->d_bits, h->d_hist, h->d_st, h->d_sel, h->d_tblk, h->d_ids, h->d_out, h->d_allow, h->d_ftblk);
     h->allow_staged = false;
     h->slots = 0;
 }
 
+static void bm_free_big(vf_bm25* h) { bm_free(h->d_big, h->d_big_tblk, h->d_big_ids, h->d_big_out); }
+
 // what a filtered call holds beyond the slots (after bm_ensure_slots: h->slots and h->words are the call's)
 static int bm_ensure_filter(vf_bm25* h) {
-    hipError_t e = hipSuccess;
-    if (!h->d_allow) {
-        e = hipMalloc((void**)&h->d_allow, (size_t)h->words * 4);
-        if (e == hipSuccess) e = hipMemsetAsync(h->d_allow, 0, (size_t)h->words * 4, h->stream);   // the words past n stay zero
-    }
-    if (e == hipSuccess && !h->d_ftblk) e = hipMalloc((void**)&h->d_ftblk, (size_t)h->slots * (size_t)(h->words / kBmWordsPerBlock) * 4);
-    if (e != hipSuccess) {
-        if (h->d_allow) (void)hipFree(h->d_allow);
-        h->d_allow = nullptr; h->d_ftblk = nullptr;   // d_ftblk was the allocation that failed, or was never reached
-        return bm_fail(e == hipErrorOutOfMemory ? VF_ENOMEM : VF_EHIP, std::string("vf_bm25: filter scratch: ") + hipGetErrorString(e));
-    }
-    return VF_OK;
+    if (h->d_allow) return VF_OK;   // made and dropped together: d_allow stands for both
+    const size_t wbytes = (size_t)h->words * 4;
+    const int rc = bm_alloc("vf_bm25: filter scratch", {bm_buf(h->d_allow, wbytes), bm_buf(h->d_ftblk, (size_t)h->slots * (size_t)(h->words / kBmWordsPerBlock) * 4)});
+    if (rc != VF_OK) return rc;
+    const hipError_t e = hipMemsetAsync(h->d_allow, 0, wbytes, h->stream);   // the words past n stay zero
+    if (e == hipSuccess) return VF_OK;
+    bm_free(h->d_allow, h->d_ftblk);
+    return bm_hip_fail("vf_bm25: filter scratch", e);
 }
 
 // the per-query scratch of `want` slots, zeroed (the reset keeps it zero between queries)
@@ -798,41 +849,22 @@ static int bm_ensure_slots(vf_bm25* h, int want) {
     VFS_HIP(hipStreamSynchronize(h->stream));
     bm_free_slots(h);
     const size_t S = (size_t)want;
-    hipError_t e = hipMalloc((void**)&h->d_scores, S * h->n * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_bits, S * h->words * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_hist, S * 256 * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_st, S * sizeof(BmState));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_sel, S * kBmSmallK * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_tblk, S * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_ids, S * kBmSmallK * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_out, S * kBmSmallK * 4);
-    if (e == hipSuccess) e = hipMemsetAsync(h->d_scores, 0, S * h->n * 4, h->stream);
+    const int rc = bm_alloc("vf_bm25: query scratch", {bm_buf(h->d_scores, S * h->n * 4), bm_buf(h->d_bits, S * h->words * 4), bm_buf(h->d_hist, S * 256 * 4),
+                                                        bm_buf(h->d_st, S * sizeof(BmState)), bm_buf(h->d_sel, S * kBmSmallK * 8), bm_buf(h->d_tblk, S * 4),
+                                                        bm_buf(h->d_ids, S * kBmSmallK * 8), bm_buf(h->d_out, S * kBmSmallK * 4)});
+    if (rc != VF_OK) return rc;
+    hipError_t e = hipMemsetAsync(h->d_scores, 0, S * h->n * 4, h->stream);
     if (e == hipSuccess) e = hipMemsetAsync(h->d_bits, 0, S * h->words * 4, h->stream);
     if (e == hipSuccess) e = hipMemsetAsync(h->d_hist, 0, S * 256 * 4, h->stream);
     if (e == hipSuccess) e = hipMemsetAsync(h->d_st, 0, S * sizeof(BmState), h->stream);
-    if (e != hipSuccess) {
-        bm_free_slots(h);
-        return bm_fail(e == hipErrorOutOfMemory ? VF_ENOMEM : VF_EHIP, std::string("vf_bm25: query scratch: ") + hipGetErrorString(e));
-    }
+    if (e != hipSuccess) { bm_free_slots(h); return bm_hip_fail("vf_bm25: query scratch", e); }
     h->slots = want;
     return VF_OK;
 }
 
-static int bm_ensure_big(vf_bm25* h) {
-    if (h->d_big) return VF_OK;
-    const long long P = bm_pow2(h->n);
-    hipError_t e = hipMalloc((void**)&h->d_big, (size_t)P * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_big_tblk, (size_t)(h->words / kBmWordsPerBlock) * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_big_ids, (size_t)h->n * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_big_out, (size_t)h->n * 4);
-    if (e != hipSuccess) {
-        void* ps[] = {h->d_big, h->d_big_tblk, h->d_big_ids, h->d_big_out};
-        for (void* p : ps)
-            if (p) (void)hipFree(p);
-        h->d_big = nullptr; h->d_big_tblk = nullptr; h->d_big_ids = nullptr; h->d_big_out = nullptr;
-        return bm_fail(e == hipErrorOutOfMemory ? VF_ENOMEM : VF_EHIP, std::string("vf_bm25: deep-k scratch: ") + hipGetErrorString(e));
-    }
-    return VF_OK;
+static int bm_ensure_big(vf_bm25* h) {   // all four or none: d_big stands for them
+    return h->d_big ? VF_OK : bm_alloc("vf_bm25: deep-k scratch", {bm_buf(h->d_big, (size_t)bm_pow2(h->n) * 8), bm_buf(h->d_big_tblk, (size_t)(h->words / kBmWordsPerBlock) * 4),
+                                                bm_buf(h->d_big_ids, (size_t)h->n * 8), bm_buf(h->d_big_out, (size_t)h->n * 4)});
 }
 
 static unsigned bm_grid(long long work, long long per_block, long long cap) {
@@ -843,18 +875,15 @@ static unsigned bm_grid(long long work, long long per_block, long long cap) {
 static void bm_drop_stage(vf_bm25* h) {
     BmStage* s = h->stage;
     if (!s) return;
-    void* ps[] = {s->d_rem, s->d_map, s->d_doclen1, s->d_delta_dl, s->d_csum, s->d_dptr, s->d_drows, s->d_dtf, s->d_newptr, s->d_indices1,
-                  s->d_tf1, s->d_data1, s->d_idf};
-    for (void* p : ps)
-        if (p) (void)hipFree(p);
+    bm_free(s->d_rem, s->d_map, s->d_doclen1, s->d_delta_dl, s->d_csum, s->d_dptr, s->d_drows, s->d_dtf, s->d_newptr, s->d_indices1, s->d_tf1,
+            s->d_data1, s->d_idf);
     delete s;
     h->stage = nullptr;
 }
 
 static void bm_prepared_free_device(BmPrepared* f) {
-    if (f->d_allow) (void)hipFree(f->d_allow);
-    if (f->d_idf) (void)hipFree(f->d_idf);
-    f->d_allow = nullptr; f->d_idf = nullptr; f->bytes = 0;
+    bm_free(f->d_allow, f->d_idf);
+    f->bytes = 0;
 }
 
 // a committed update: no prepared filter may search again (rows have moved); the tokens stay known until they are released
@@ -891,28 +920,34 @@ static int bm_destroy(vf_bm25* h) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     bm_free_slots(h);
+    bm_free_big(h);
     bm_drop_stage(h);
     bm_prepared_free_all(h);
-    void* ps[] = {h->d_indptr, h->d_indices, h->d_data, h->d_big, h->d_big_tblk, h->d_big_ids, h->d_big_out, h->d_qoff, h->d_qterms,
-                  h->d_tf, h->d_doclen, h->d_sub, h->d_sidf};
-    for (void* p : ps)
-        if (p) (void)hipFree(p);
+    bm_free(h->d_indptr, h->d_indices, h->d_data, h->d_qoff, h->d_qterms, h->d_tf, h->d_doclen, h->d_sub, h->d_sidf);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return VF_OK;
-}
-
-static void bm_free_big(vf_bm25* h) {
-    void* ps[] = {h->d_big, h->d_big_tblk, h->d_big_ids, h->d_big_out};
-    for (void* p : ps)
-        if (p) (void)hipFree(p);
-    h->d_big = nullptr; h->d_big_tblk = nullptr; h->d_big_ids = nullptr; h->d_big_out = nullptr;
 }
 
 static void bm_set_docs(vf_bm25* h, long long n) {   // what depends on the document count
     h->n = n;
     h->words = (int)(((n + 31) / 32 + kBmWordsPerBlock - 1) / kBmWordsPerBlock * kBmWordsPerBlock);
     h->slot_cap = (int)std::max(1ll, std::min((long long)kBmMaxSlots, kBmScratchBudget / bm_slot_bytes(h)));
+}
+
+// A handle on device `dev` with its stream and nothing else; the caller's DeviceGuard puts the thread's device back.
+static int bm_new_handle(int dev, vf_bm25** out) {
+    int ndev = 0;
+    VFS_HIP(hipGetDeviceCount(&ndev));
+    if (dev < 0 || dev >= ndev) return bm_fail(VF_EINVAL, "vf_bm25_create: bad device_id");
+    VFS_HIP(hipSetDevice(dev));
+    vf_bm25* h = new (std::nothrow) vf_bm25();
+    if (!h) return bm_fail(VF_ENOMEM, "host allocation failed");
+    h->device = dev;
+    const hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+    if (e != hipSuccess) { bm_destroy(h); return bm_hip_fail("vf_bm25_create", e); }
+    *out = h;
+    return VF_OK;
 }
 
 // ---- live updates (include/veritasfi_hip.h: VF_BM25_LIVE) ---------------------------------------------------------------------
@@ -962,22 +997,16 @@ static int bm_live_stage(vf_bm25* h, vf_bm25_delta* d) {
     s->cap = h->nnz + dnnz;                       // survivors <= nnz: known exactly only after the count, and allocations come first
     s->chunks = live_chunks(h->nnz, C);
     try { s->newptr.resize((size_t)Vn + 1); } catch (const std::bad_alloc&) { bm_drop_stage(h); return bm_fail(VF_ENOMEM, "host allocation failed"); }
-    const size_t one = 1;
-    hipError_t e = hipMalloc((void**)&s->d_rem, std::max(one, (size_t)m) * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&s->d_map, std::max(one, (size_t)n0) * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&s->d_doclen1, (size_t)(n1 + n_new) * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&s->d_delta_dl, std::max(one, (size_t)n_new) * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&s->d_csum, (size_t)(s->chunks + 1) * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&s->d_dptr, (size_t)(Vn + 1) * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&s->d_drows, std::max(one, (size_t)dnnz) * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&s->d_dtf, std::max(one, (size_t)dnnz) * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&s->d_newptr, (size_t)(Vn + 1) * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&s->d_indices1, std::max(one, (size_t)s->cap) * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&s->d_tf1, std::max(one, (size_t)s->cap) * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&s->d_data1, std::max(one, (size_t)s->cap) * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&s->d_idf, std::max(one, (size_t)Vn) * 8);
+    const auto some = [](long long count) { return (size_t)std::max(1ll, count); };
+    const int rc = bm_alloc("vf_bm25_create (stage)", {bm_buf(s->d_rem, some(m) * 4), bm_buf(s->d_map, some(n0) * 4), bm_buf(s->d_doclen1, (size_t)(n1 + n_new) * 4),
+                                                       bm_buf(s->d_delta_dl, some(n_new) * 4), bm_buf(s->d_csum, (size_t)(s->chunks + 1) * 8),
+                                                       bm_buf(s->d_dptr, (size_t)(Vn + 1) * 8), bm_buf(s->d_drows, some(dnnz) * 4), bm_buf(s->d_dtf, some(dnnz) * 4),
+                                                       bm_buf(s->d_newptr, (size_t)(Vn + 1) * 8), bm_buf(s->d_indices1, some(s->cap) * 4),
+                                                       bm_buf(s->d_tf1, some(s->cap) * 4), bm_buf(s->d_data1, some(s->cap) * 4), bm_buf(s->d_idf, some(Vn) * 8)});
+    if (rc != VF_OK) { bm_drop_stage(h); return rc; }
     hipStream_t st = h->stream;
-    if (e == hipSuccess && m) e = hipMemcpyAsync(s->d_rem, rem.data(), (size_t)m * 4, hipMemcpyHostToDevice, st);
+    hipError_t e = hipSuccess;
+    if (m) e = hipMemcpyAsync(s->d_rem, rem.data(), (size_t)m * 4, hipMemcpyHostToDevice, st);
     if (e == hipSuccess && n_new) e = hipMemcpyAsync(s->d_delta_dl, delta_dl.data(), (size_t)n_new * 4, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(s->d_dptr, d->indptr, (size_t)(Vn + 1) * 8, hipMemcpyHostToDevice, st);
     if (e == hipSuccess && dnnz) e = hipMemcpyAsync(s->d_drows, d->rows, (size_t)dnnz * 4, hipMemcpyHostToDevice, st);
@@ -992,11 +1021,7 @@ static int bm_live_stage(vf_bm25* h, vf_bm25_delta* d) {
     }
     if (e == hipSuccess) e = hipMemcpyAsync(s->newptr.data(), s->d_newptr, (size_t)(Vn + 1) * 8, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        const std::string msg = std::string("vf_bm25_create (stage): ") + hipGetErrorString(e);
-        bm_drop_stage(h);
-        return bm_fail(e == hipErrorOutOfMemory ? VF_ENOMEM : VF_EHIP, msg);
-    }
+    if (e != hipSuccess) { bm_drop_stage(h); return bm_hip_fail("vf_bm25_create (stage)", e); }
     for (long long c = 0; c < Vn; ++c) d->counts[c] = s->newptr[c + 1] - s->newptr[c];
     d->n_removed = m;
     return VF_OK;
@@ -1021,15 +1046,9 @@ static int bm_live_commit(vf_bm25* h, const vf_bm25_delta* d) {
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        const std::string msg = std::string("vf_bm25_create (commit): ") + hipGetErrorString(e);
-        bm_drop_stage(h);
-        return bm_fail(VF_EHIP, msg);
-    }
+    if (e != hipSuccess) { bm_drop_stage(h); return bm_fail(VF_EHIP, std::string("vf_bm25_create (commit): ") + hipGetErrorString(e)); }
     // the swap: from here nothing can fail
-    void* old[] = {h->d_indptr, h->d_indices, h->d_data, h->d_tf, h->d_doclen};
-    for (void* p : old)
-        if (p) (void)hipFree(p);
+    bm_free(h->d_indptr, h->d_indices, h->d_data, h->d_tf, h->d_doclen);
     h->d_indptr = s->d_newptr; h->d_indices = s->d_indices1; h->d_data = s->d_data1; h->d_tf = s->d_tf1; h->d_doclen = s->d_doclen1;
     s->d_newptr = nullptr; s->d_indices1 = nullptr; s->d_data1 = nullptr; s->d_tf1 = nullptr; s->d_doclen1 = nullptr;
     h->indptr.swap(s->newptr);
@@ -1068,23 +1087,16 @@ static int bm_live_call(vf_bm25_delta* d, int32_t device_id, vf_bm25** out, int3
     vf_bm25* h = *out;
     if (!h) {   // a stage on no handle starts one: it is born by its commit
         if (phase != VF_BM25_LIVE) return bm_fail(VF_EINVAL, "vf_bm25_create: null handle");
-        int ndev = 0;
-        VFS_HIP(hipGetDeviceCount(&ndev));
-        if (dev >= ndev) return bm_fail(VF_EINVAL, "vf_bm25_create: bad device_id");
         DeviceGuard guard;
-        VFS_HIP(hipSetDevice(dev));
-        h = new (std::nothrow) vf_bm25();
-        if (!h) return bm_fail(VF_ENOMEM, "host allocation failed");
-        h->device = dev; h->live = true; h->born = false;
-        hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_indptr, 8);
-        if (e == hipSuccess) e = hipMemset(h->d_indptr, 0, 8);
-        if (e != hipSuccess) {
-            const std::string msg = std::string("vf_bm25_create: ") + hipGetErrorString(e);
-            bm_destroy(h);
-            return bm_fail(e == hipErrorOutOfMemory ? VF_ENOMEM : VF_EHIP, msg);
+        int rc = bm_new_handle(dev, &h);
+        if (rc != VF_OK) return rc;
+        h->live = true; h->born = false;
+        rc = bm_alloc("vf_bm25_create", {bm_buf(h->d_indptr, 8)});
+        if (rc == VF_OK) {
+            const hipError_t e = hipMemset(h->d_indptr, 0, 8);
+            if (e != hipSuccess) rc = bm_hip_fail("vf_bm25_create", e);
         }
-        int rc;
+        if (rc != VF_OK) { bm_destroy(h); return rc; }
         try {   // the host vectors of a stage allocate: no exception leaves the C ABI
             h->indptr.assign(1, 0);
             rc = bm_live_stage(h, d);
@@ -1144,50 +1156,71 @@ extern "C" int vf_bm25_create(const int64_t* indptr, int64_t V, const int32_t* i
             if (!(data[p] > 0.0f) || !(data[p] <= FLT_MAX)) return bm_fail(VF_EINVAL, "vf_bm25_create: posting scores must be finite and > 0");
         }
     }
-    int ndev = 0;
-    VFS_HIP(hipGetDeviceCount(&ndev));
-    if (device_id < 0 || device_id >= ndev) return bm_fail(VF_EINVAL, "vf_bm25_create: bad device_id");
     DeviceGuard guard;
-    VFS_HIP(hipSetDevice(device_id));
-    vf_bm25* h = new (std::nothrow) vf_bm25();
-    if (!h) return bm_fail(VF_ENOMEM, "host allocation failed");
-    h->device = device_id; h->n = n_docs; h->V = V; h->nnz = nnz;
-    h->words = (int)(((n_docs + 31) / 32 + kBmWordsPerBlock - 1) / kBmWordsPerBlock * kBmWordsPerBlock);
+    vf_bm25* h = nullptr;
+    int rc = bm_new_handle(device_id, &h);
+    if (rc != VF_OK) return rc;
+    h->V = V; h->nnz = nnz;
+    bm_set_docs(h, n_docs);
     h->indptr.assign(indptr, indptr + V + 1);
-    const long long per_slot = bm_slot_bytes(h);
-    h->slot_cap = (int)std::max(1ll, std::min((long long)kBmMaxSlots, kBmScratchBudget / per_slot));
-    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_indptr, (size_t)(V + 1) * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_indices, (size_t)std::max<int64_t>(nnz, 1) * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_data, (size_t)std::max<int64_t>(nnz, 1) * 4);
-    if (e == hipSuccess) e = hipMemcpy(h->d_indptr, indptr, (size_t)(V + 1) * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess && nnz) e = hipMemcpy(h->d_indices, indices, (size_t)nnz * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess && nnz) e = hipMemcpy(h->d_data, data, (size_t)nnz * 4, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        const std::string msg = std::string("vf_bm25_create: ") + hipGetErrorString(e);
-        bm_destroy(h);
-        return bm_fail(e == hipErrorOutOfMemory ? VF_ENOMEM : VF_EHIP, msg);
+    const size_t pbytes = (size_t)std::max<int64_t>(nnz, 1) * 4;
+    rc = bm_alloc("vf_bm25_create", {bm_buf(h->d_indptr, (size_t)(V + 1) * 8), bm_buf(h->d_indices, pbytes), bm_buf(h->d_data, pbytes)});
+    if (rc == VF_OK) {
+        hipError_t e = hipMemcpy(h->d_indptr, indptr, (size_t)(V + 1) * 8, hipMemcpyHostToDevice);
+        if (e == hipSuccess && nnz) e = hipMemcpy(h->d_indices, indices, (size_t)nnz * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess && nnz) e = hipMemcpy(h->d_data, data, (size_t)nnz * 4, hipMemcpyHostToDevice);
+        if (e != hipSuccess) rc = bm_hip_fail("vf_bm25_create", e);
     }
+    if (rc != VF_OK) { bm_destroy(h); return rc; }
     if (slots) *slots = h->slot_cap;
     *out = h;
     return VF_OK;
 }
 
 // ---- a search by the subset's own statistics (include/veritasfi_hip.h: VF_BM25_SUBSTATS) --------------------------------------------
-static int bm_ensure_sidf(vf_bm25* h, long long T) {
-    const long long want = std::max<long long>(T, 1);
-    if (want <= h->sidf_cap) return VF_OK;
-    if (h->d_sidf) (void)hipFree(h->d_sidf);
-    h->d_sidf = nullptr; h->sidf_cap = 0;
-    const hipError_t e = hipMalloc((void**)&h->d_sidf, (size_t)want * 8);
-    if (e != hipSuccess) return bm_fail(e == hipErrorOutOfMemory ? VF_ENOMEM : VF_EHIP, std::string("vf_bm25: idf of the query positions: ") + hipGetErrorString(e));
-    h->sidf_cap = want;
+// ---- the checks the modes share, each written once ---------------------------------------------------------------------------------
+// a caller's bitmap (`who`: the flag or phase it came with): not null, made for this document count, no bit at or past it; fc->m: rows allowed
+static int bm_check_allow(const vf_bm25* h, const uint32_t* allow, long long n_docs, Bm25FilterCheck* fc, const char* who) {
+    if (!allow) return bm_fail(VF_EINVAL, std::string("vf_bm25_search: ") + who + " with a null allow bitmap");
+    if (n_docs != h->n)
+        return bm_fail(VF_EINVAL, "vf_bm25_search: the filter was made for " + std::to_string(n_docs) + " documents, the handle holds " +
+                                      std::to_string(h->n) + " (a live handle may have changed since the bitmap was made: make it again)");
+    *fc = bm25f_check(allow, h->n);
+    if (fc->bad_row >= 0)
+        return bm_fail(VF_EINVAL, "vf_bm25_search: the filter allows row " + std::to_string(fc->bad_row) + ", at or past n_docs = " + std::to_string(h->n));
     return VF_OK;
 }
 
+// what a scored search takes from its caller (`who`: the phase that brought it): idf[count] finite and >= 0, avgdl > 0, k1 >= 0, b in [0, 1]
+static int bm_check_scoring(const double* idf, long long count, double avgdl, double k1, double b, const char* who) {
+    for (long long i = 0; i < count; ++i)
+        if (!(idf[i] >= 0.0) || !(idf[i] <= DBL_MAX)) return bm_fail(VF_EINVAL, "vf_bm25_search: idf[" + std::to_string(i) + "] is negative or not finite");
+    if (!(avgdl > 0.0) || !(avgdl <= DBL_MAX) || !(k1 >= 0.0) || !(b >= 0.0 && b <= 1.0))
+        return bm_fail(VF_EINVAL, std::string("vf_bm25_search: ") + who + " needs avgdl > 0, k1 >= 0 and b in [0, 1]");
+    return VF_OK;
+}
+
+// nothing may be returned: every rank of every query is padding (a stage's outputs may be absent)
+static void bm_all_padding(int64_t* out_ids, float* out_scores, int nq, int k) {
+    if (!out_ids || !out_scores || k < 1) return;
+    std::fill(out_ids, out_ids + (size_t)nq * k, (int64_t)-1);
+    std::fill(out_scores, out_scores + (size_t)nq * k, -FLT_MAX);
+}
+
+// the SubArgs of the counting kernels (counts: the length sum, then df as int32) and of the scoring scatters (idf and what follows it)
+static SubArgs bm_sub_args(const vf_bm25* h, const u32* allow, unsigned long long* counts, const double* idf = nullptr, double avgdl = 1.0, double k1 = 0.0, double b = 0.0) {
+    SubArgs sa{};
+    sa.indptr = h->d_indptr; sa.indices = h->d_indices; sa.tf = h->d_tf; sa.doclen = h->d_doclen;
+    sa.allow = allow; sa.n = h->n;
+    sa.total = counts; sa.df = counts ? (int*)(counts + 1) : nullptr;
+    sa.idf = idf; sa.avgdl = avgdl; sa.k1 = k1; sa.b = b; sa.one_minus_b = 1.0 - b;
+    return sa;
+}
+
 // The stage.  Every check has passed and m > 0.  Uploads the bitmap (it stays for the search that follows), sums the allowed rows'
-// lengths, counts the allowed postings of the batch's distinct columns, and writes the struct's out members last.
-static int bm_substats_stage(vf_bm25* h, vf_bm25_substats_query* sq, const uint32_t* allow_host, long long m, const int32_t* q_terms, int nq, long long T) {
+// lengths, counts the allowed postings of the batch's distinct columns, and writes the struct's out members last.  S: that search's slots
+static int bm_substats_stage(vf_bm25* h, vf_bm25_substats_query* sq, long long m, const int32_t* q_terms, int S, long long T) {
+    const uint32_t* allow_host = sq->allow;
     std::vector<int32_t> distinct, pos2d;
     std::vector<unsigned long long> back;   // the length sum, then the counts (two int32 per word)
     long long D = 0;
@@ -1204,24 +1237,13 @@ static int bm_substats_stage(vf_bm25* h, vf_bm25_substats_query* sq, const uint3
     DeviceGuard guard;
     VFS_HIP(hipSetDevice(h->device));
     hipStream_t st = h->stream;
-    {   // the slots of the search that follows, so that it does not make d_allow again
-        const int rc = bm_ensure_slots(h, std::max(std::min<int>(nq, h->slot_cap), h->slots));
-        if (rc != VF_OK) return rc;
-        const int rc2 = bm_ensure_filter(h);
-        if (rc2 != VF_OK) return rc2;
-    }
-    if (std::max<long long>(D, 1) > h->sub_cap) {
-        if (h->d_sub) (void)hipFree(h->d_sub);
-        h->d_sub = nullptr; h->sub_cap = 0;
-        const long long cap = std::max<long long>(D, 1) + (std::max<long long>(D, 1) & 1);   // even: the columns start on 8 bytes as well
-        const hipError_t e = hipMalloc((void**)&h->d_sub, 8 + (size_t)cap * 8);
-        if (e != hipSuccess) return bm_fail(e == hipErrorOutOfMemory ? VF_ENOMEM : VF_EHIP, std::string("vf_bm25: subset counts: ") + hipGetErrorString(e));
-        h->sub_cap = cap;
-    }
-    SubArgs sa{};
-    sa.indptr = h->d_indptr; sa.indices = h->d_indices; sa.tf = h->d_tf; sa.doclen = h->d_doclen;
-    sa.allow = h->d_allow; sa.n = h->n;
-    sa.total = h->d_sub; sa.df = (int*)(h->d_sub + 1); sa.dcols = sa.df + h->sub_cap;
+    int rc = bm_ensure_slots(h, std::max(S, h->slots));   // the slots of the search that follows, so that it does not make d_allow again
+    if (rc == VF_OK) rc = bm_ensure_filter(h);
+    const long long cap = std::max<long long>(D, 1) + (std::max<long long>(D, 1) & 1);   // even: the columns start on 8 bytes as well
+    if (rc == VF_OK) rc = bm_grow("vf_bm25: subset counts", h->d_sub, h->sub_cap, cap, 8 + (size_t)cap * 8);
+    if (rc != VF_OK) return rc;
+    SubArgs sa = bm_sub_args(h, h->d_allow, h->d_sub);
+    sa.dcols = sa.df + h->sub_cap;
     VFS_HIP(hipMemcpyAsync(h->d_allow, allow_host, aw * 4, hipMemcpyHostToDevice, st));
     VFS_HIP(hipMemsetAsync(h->d_sub, 0, 8 + (size_t)h->sub_cap * 4, st));
     if (D > 0) VFS_HIP(hipMemcpyAsync((void*)sa.dcols, distinct.data(), (size_t)D * 4, hipMemcpyHostToDevice, st));
@@ -1261,13 +1283,9 @@ static int bm_prepared_prepare(vf_bm25* h, vf_bm25_prepared_query* pq) {
     if (pq->mode != VF_BM25_PREPARED_CORPUS && pq->mode != VF_BM25_PREPARED_SUBSET)
         return bm_fail(VF_EINVAL, "vf_bm25_search: vf_bm25_prepared_query.mode must be VF_BM25_PREPARED_CORPUS or VF_BM25_PREPARED_SUBSET");
     const bool subset = pq->mode == VF_BM25_PREPARED_SUBSET;
-    if (!pq->allow) return bm_fail(VF_EINVAL, "vf_bm25_search: VF_BM25_PREPARED_PREPARE with a null allow bitmap");
-    if (pq->n_docs != h->n)
-        return bm_fail(VF_EINVAL, "vf_bm25_search: the filter was made for " + std::to_string(pq->n_docs) + " documents, the handle holds " +
-                                      std::to_string(h->n) + " (a live handle may have changed since the bitmap was made: make it again)");
-    const Bm25FilterCheck fc = bm25f_check(pq->allow, h->n);
-    if (fc.bad_row >= 0)
-        return bm_fail(VF_EINVAL, "vf_bm25_search: the filter allows row " + std::to_string(fc.bad_row) + ", at or past n_docs = " + std::to_string(h->n));
+    Bm25FilterCheck fc{};
+    int rc = bm_check_allow(h, pq->allow, pq->n_docs, &fc, "VF_BM25_PREPARED_PREPARE");
+    if (rc != VF_OK) return rc;
     const int C = pq->chunk == 0 ? kLiveMaxChunk : pq->chunk;
     if (subset) {
         if (!h->live || !h->born)
@@ -1290,18 +1308,17 @@ static int bm_prepared_prepare(vf_bm25* h, vf_bm25_prepared_query* pq) {
     DeviceGuard guard;
     hipError_t e = hipSetDevice(h->device);
     hipStream_t st = h->stream;
-    const size_t aw = (size_t)bm25f_words(h->n), wbytes = (size_t)h->words * 4, cbytes = 8 + (size_t)std::max<long long>(V, 1) * 4;
+    const size_t aw = (size_t)bm25f_words(h->n), wbytes = (size_t)h->words * 4, ventries = (size_t)std::max<long long>(V, 1), cbytes = 8 + ventries * 4;
     unsigned long long* d_cnt = nullptr;    // subset mode, for this call only: the length sum (8 B), then df [V] as int32
-    if (e == hipSuccess) e = hipMalloc((void**)&f->d_allow, wbytes);
-    if (e == hipSuccess && subset) e = hipMalloc((void**)&f->d_idf, (size_t)std::max<long long>(V, 1) * 8);
-    if (e == hipSuccess && subset) e = hipMalloc((void**)&d_cnt, cbytes);
-    if (e == hipSuccess) e = hipMemsetAsync(f->d_allow, 0, wbytes, st);   // the words past n stay zero
+    rc = e != hipSuccess ? bm_hip_fail("vf_bm25_search (prepare)", e)
+                         : bm_alloc("vf_bm25_search (prepare)", {bm_buf(f->d_allow, wbytes), bm_buf(f->d_idf, subset ? ventries * 8 : 0), bm_buf(d_cnt, subset ? cbytes : 0)});
+    if (rc != VF_OK) { delete f; return rc; }
+    e = hipMemsetAsync(f->d_allow, 0, wbytes, st);   // the words past n stay zero
     if (e == hipSuccess) e = hipMemcpyAsync(f->d_allow, pq->allow, aw * 4, hipMemcpyHostToDevice, st);
     if (e == hipSuccess && subset && fc.m > 0) {
         e = hipMemsetAsync(d_cnt, 0, cbytes, st);
         if (e == hipSuccess) {
-            SubArgs sa{};
-            sa.doclen = h->d_doclen; sa.allow = f->d_allow; sa.n = h->n; sa.total = d_cnt;
+            const SubArgs sa = bm_sub_args(h, f->d_allow, d_cnt);
             hipLaunchKernelGGL(k_bm25_sub_len, dim3((unsigned)(h->words / kBmWordsPerBlock)), dim3(kBmThreads), 0, st, sa);
             if (h->nnz > 0) {
                 PrepArgs pa{};
@@ -1314,13 +1331,8 @@ static int bm_prepared_prepare(vf_bm25* h, vf_bm25_prepared_query* pq) {
         if (e == hipSuccess) e = hipMemcpyAsync(back.data(), d_cnt, 8 + (size_t)V * 4, hipMemcpyDeviceToHost, st);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (d_cnt) (void)hipFree(d_cnt);
-    if (e != hipSuccess) {
-        const std::string msg = std::string("vf_bm25_search (prepare): ") + hipGetErrorString(e);
-        bm_prepared_free_device(f);
-        delete f;
-        return bm_fail(e == hipErrorOutOfMemory ? VF_ENOMEM : VF_EHIP, msg);
-    }
+    bm_free(d_cnt);
+    if (e != hipSuccess) { bm_prepared_free_device(f); delete f; return bm_hip_fail("vf_bm25_search (prepare)", e); }
     f->token = h->next_token++; f->gen = h->gen; f->subset = subset; f->m = fc.m; f->V = V;
     f->total_len = subset ? (long long)back[0] : 0;
     f->bytes = (long long)wbytes + (subset ? std::max<long long>(V, 1) * 8 : 0);
@@ -1341,11 +1353,8 @@ static int bm_prepared_arm(vf_bm25* h, const vf_bm25_prepared_query* pq) {
     if (f->stale || f->gen != h->gen) return bm_prepared_stale(h, f, "VF_BM25_PREPARED_ARM");
     if (pq->vocab != f->V || (f->V > 0 && !pq->idf))
         return bm_fail(VF_EINVAL, "vf_bm25_search: VF_BM25_PREPARED_ARM needs idf[vocab] with vocab = the filter's " + std::to_string(f->V) + " columns");
-    for (long long c = 0; c < f->V; ++c)
-        if (!(pq->idf[c] >= 0.0) || !(pq->idf[c] <= DBL_MAX))
-            return bm_fail(VF_EINVAL, "vf_bm25_search: idf[" + std::to_string(c) + "] is negative or not finite");
-    if (!(pq->avgdl > 0.0) || !(pq->avgdl <= DBL_MAX) || !(pq->k1 >= 0.0) || !(pq->b >= 0.0 && pq->b <= 1.0))
-        return bm_fail(VF_EINVAL, "vf_bm25_search: VF_BM25_PREPARED_ARM needs avgdl > 0, k1 >= 0 and b in [0, 1]");
+    const int rc = bm_check_scoring(pq->idf, f->V, pq->avgdl, pq->k1, pq->b, "VF_BM25_PREPARED_ARM");
+    if (rc != VF_OK) return rc;
     DeviceGuard guard;
     VFS_HIP(hipSetDevice(h->device));
     if (f->V > 0) VFS_HIP(hipMemcpyAsync(f->d_idf, pq->idf, (size_t)f->V * 8, hipMemcpyHostToDevice, h->stream));
@@ -1355,24 +1364,109 @@ static int bm_prepared_arm(vf_bm25* h, const vf_bm25_prepared_query* pq) {
 }
 
 static int bm_prepared_release(vf_bm25* h, const vf_bm25_prepared_query* pq) {
-    for (size_t i = 0; i < h->prepared.size(); ++i) {
-        BmPrepared* f = h->prepared[i];
-        if (f->token != pq->token) continue;
-        DeviceGuard guard;
-        (void)hipSetDevice(h->device);
-        (void)hipStreamSynchronize(h->stream);
-        bm_prepared_free_device(f);
-        delete f;
-        h->prepared.erase(h->prepared.begin() + (long)i);
-        return VF_OK;
-    }
-    return bm_fail(VF_EINVAL, "vf_bm25_search: VF_BM25_PREPARED_RELEASE: token " + std::to_string(pq->token) + " names no prepared filter of this handle (unknown or released)");
+    BmPrepared* f = bm_prepared_find(h, pq->token);
+    if (!f) return bm_fail(VF_EINVAL, "vf_bm25_search: VF_BM25_PREPARED_RELEASE: token " + std::to_string(pq->token) + " names no prepared filter of this handle (unknown or released)");
+    DeviceGuard guard;
+    (void)hipSetDevice(h->device);
+    (void)hipStreamSynchronize(h->stream);
+    h->prepared.erase(std::find(h->prepared.begin(), h->prepared.end(), f));
+    bm_prepared_free_device(f);
+    delete f;
+    return VF_OK;
 }
 
-// the scoring and the radix select of the group's queries (slots 0 .. g-1); sel / tblk / out set by the caller.  allow: the device
-// bitmap of a filtered call (the scatter skips the rows outside it), or null
-// ss: a search by the subset's statistics; by_col: its idf is a prepared filter's table over the vocabulary, not one entry per position
-static int bm_score_select(vf_bm25* h, BmArgs& a, const int64_t* q_off, int g, const u32* allow, const SubArgs* ss = nullptr, bool by_col = false) {
+// ---- the search --------------------------------------------------------------------------------------------------------------------
+static const char* const kBmRefusalText[kBm25Refusals] = {
+    "",
+    "vf_bm25_search: VF_BM25_PREPARED goes alone (the prepared filter carries its rows and its mode)",
+    "vf_bm25_search: VF_BM25_PREPARED with a null vf_bm25_prepared_query",
+    "vf_bm25_search: vf_bm25_prepared_query.phase must be one of the four VF_BM25_PREPARED_* phases",
+    "vf_bm25_search: VF_BM25_FILTER with a null vf_bm25_filter_query",
+    "vf_bm25_search: vf_bm25_substats_query.phase must be VF_BM25_SUBSTATS_STAGE or VF_BM25_SUBSTATS_SEARCH",
+    "vf_bm25_search: VF_BM25_SUBSTATS goes with VF_BM25_FILTER (the statistics are those of the allowed rows)",
+};
+
+// What `q_offsets` points to in a flagged call, as the one struct type its flags say it is; the two others stay null.
+struct BmCallArg {
+    const vf_bm25_filter_query* fq = nullptr;   // VF_BM25_FILTER alone
+    vf_bm25_substats_query* sq = nullptr;       // VF_BM25_FILTER | VF_BM25_SUBSTATS
+    vf_bm25_prepared_query* pq = nullptr;       // VF_BM25_PREPARED
+    BmCallArg(const void* p, int nq_raw) {
+        if (nq_raw & VF_BM25_PREPARED) pq = (vf_bm25_prepared_query*)p;
+        else if (nq_raw & VF_BM25_SUBSTATS) sq = (vf_bm25_substats_query*)p;
+        else fq = (const vf_bm25_filter_query*)p;
+    }
+    const int64_t* q_offsets() const { return pq ? pq->q_offsets : sq ? sq->q_offsets : fq->q_offsets; }
+    const uint32_t* allow() const { return sq ? sq->allow : fq->allow; }
+    long long n_docs() const { return sq ? sq->n_docs : fq->n_docs; }
+};
+
+// The filter of a call, resolved: what the scatter and the tail read.  bm_filter_check fills m from the host's side, before any device
+// work; bm_filter_bind, once the slots exist, sets the device bitmap and the scoring scatters' arguments.
+struct BmFilter {
+    const u32* allow = nullptr;       // device bitmap; null: every row may be returned
+    long long m = 0;                  // rows allowed
+    const BmPrepared* pf = nullptr;   // kBm25PrepSearch: the filter its token names
+    SubArgs sub{};                    // read by the scatters that score from tf (the plan's kBm25ScatterSubPos and kBm25ScatterSubCol)
+};
+
+// Every check of the call's filter, in the order of include/veritasfi_hip.h.  A prepared search's filter is found here, under the lock, and with it
+// its mode: c.subset is set for the plan (the decoder cannot know it).
+static int bm_filter_check(vf_bm25* h, Bm25Call& c, const BmCallArg& arg, long long T, BmFilter* f) {
+    if (c.kind == kBm25Plain) return VF_OK;
+    if (c.kind == kBm25PrepSearch) {   // the filter's own checks were made when it was prepared: only that it is still this index's is looked at here
+        const unsigned long long token = arg.pq->token;
+        const BmPrepared* pf = bm_prepared_find(h, token);
+        if (!pf) return bm_fail(VF_EINVAL, "vf_bm25_search: token " + std::to_string(token) + " names no prepared filter of this handle (unknown or released)");
+        if (pf->stale || pf->gen != h->gen) return bm_prepared_stale(h, pf, "VF_BM25_PREPARED_SEARCH");
+        if (pf->subset && !pf->armed)
+            return bm_fail(VF_EINVAL, "vf_bm25_search: the prepared filter is in subset mode and was never armed (VF_BM25_PREPARED_ARM gives it its idf)");
+        f->pf = pf; f->m = pf->m; c.subset = pf->subset;
+        return VF_OK;
+    }
+    Bm25FilterCheck fc{};
+    const int rc = bm_check_allow(h, arg.allow(), arg.n_docs(), &fc, "VF_BM25_FILTER");
+    if (rc != VF_OK) return rc;
+    f->m = fc.m;
+    if (c.kind == kBm25Filtered) return VF_OK;
+    const vf_bm25_substats_query* sq = arg.sq;
+    if (!h->live || !h->born)
+        return bm_fail(VF_EUNSUPPORTED, "vf_bm25_search: VF_BM25_SUBSTATS needs a live handle (VF_BM25_LIVE): only it keeps the term frequencies and the document lengths");
+    if (c.kind == kBm25SubStage) return T > 0 && !sq->df ? bm_fail(VF_EINVAL, "vf_bm25_search: VF_BM25_SUBSTATS_STAGE with a null df") : VF_OK;
+    if (sq->generation != h->gen)
+        return bm_fail(VF_EINVAL, "vf_bm25_search: the statistics were staged at update generation " + std::to_string(sq->generation) + ", the handle is at " +
+                                      std::to_string(h->gen) + " (the live index was updated between the stage and the search: stage again)");
+    if (T > 0 && !sq->idf) return bm_fail(VF_EINVAL, "vf_bm25_search: VF_BM25_SUBSTATS_SEARCH with a null idf");
+    return bm_check_scoring(sq->idf, T, sq->avgdl, sq->k1, sq->b, "VF_BM25_SUBSTATS_SEARCH");
+}
+
+static int bm_filter_bind(vf_bm25* h, const Bm25Call& c, const BmCallArg& arg, long long T, BmFilter* f) {
+    if (c.kind == kBm25Plain) return VF_OK;
+    int rc = bm_ensure_filter(h);   // d_allow, and the tail's scratch over every bitmap block
+    if (rc != VF_OK) return rc;
+    if (f->pf) {   // nothing goes up: the bitmap is the filter's own (d_allow and what a stage left in it are not touched)
+        f->allow = f->pf->d_allow;
+        if (c.subset) f->sub = bm_sub_args(h, f->allow, nullptr, f->pf->d_idf, f->pf->avgdl, f->pf->k1, f->pf->b);
+        return VF_OK;
+    }
+    // the bitmap goes up with every filtered call (n / 8 bytes): no filter is kept on the device between calls ...
+    // ... except from a VF_BM25_SUBSTATS stage to its search: the stage's copy serves when it holds these very words
+    const bool scored = c.kind == kBm25SubSearch;
+    const size_t aw = (size_t)bm25f_words(h->n);
+    const bool staged = scored && h->allow_staged && h->staged_allow.size() == aw && std::equal(h->staged_allow.begin(), h->staged_allow.end(), arg.allow());
+    h->allow_staged = false;
+    if (!staged) VFS_HIP(hipMemcpyAsync(h->d_allow, arg.allow(), aw * 4, hipMemcpyHostToDevice, h->stream));
+    f->allow = h->d_allow;
+    if (!scored) return VF_OK;
+    rc = bm_grow("vf_bm25: idf of the query positions", h->d_sidf, h->sidf_cap, std::max<long long>(T, 1), (size_t)std::max<long long>(T, 1) * 8);
+    if (rc != VF_OK) return rc;
+    if (T > 0) VFS_HIP(hipMemcpyAsync(h->d_sidf, arg.sq->idf, (size_t)T * 8, hipMemcpyHostToDevice, h->stream));
+    f->sub = bm_sub_args(h, f->allow, nullptr, h->d_sidf, arg.sq->avgdl, arg.sq->k1, arg.sq->b);
+    return VF_OK;
+}
+
+// the scoring and the radix select of the group's queries (slots 0 .. g-1); sel / tblk / out set by the caller
+static int bm_score_select(vf_bm25* h, BmArgs& a, const int64_t* q_off, int g, const Bm25LaunchPlan& p, const BmFilter& f) {
     hipStream_t st = h->stream;
     long long maxlen = 0;
     for (int s = 0; s < g; ++s) maxlen = std::max<long long>(maxlen, q_off[a.q0 + s + 1] - q_off[a.q0 + s]);
@@ -1386,10 +1480,13 @@ static int bm_score_select(vf_bm25* h, BmArgs& a, const int64_t* q_off, int g, c
             }
         }
         if (post == 0) continue;
-        if (ss && by_col) hipLaunchKernelGGL(k_bm25_accum_sc, dim3(bm_grid(post, kBmThreads, 4096), g), dim3(kBmThreads), 0, st, a, (int)t, *ss);
-        else if (ss) hipLaunchKernelGGL(k_bm25_accum_s, dim3(bm_grid(post, kBmThreads, 4096), g), dim3(kBmThreads), 0, st, a, (int)t, *ss);
-        else if (allow) hipLaunchKernelGGL(k_bm25_accum_f, dim3(bm_grid(post, kBmThreads, 4096), g), dim3(kBmThreads), 0, st, a, (int)t, allow);
-        else hipLaunchKernelGGL(k_bm25_accum, dim3(bm_grid(post, kBmThreads, 4096), g), dim3(kBmThreads), 0, st, a, (int)t);
+        const dim3 grid(bm_grid(post, kBmThreads, 4096), g), block(kBmThreads);
+        switch (p.scatter) {   // the filtered forms skip the rows outside the set; the two last score each posting from its tf
+            case kBm25ScatterPlain: hipLaunchKernelGGL(k_bm25_accum, grid, block, 0, st, a, (int)t); break;
+            case kBm25ScatterFiltered: hipLaunchKernelGGL(k_bm25_accum_f, grid, block, 0, st, a, (int)t, f.allow); break;
+            case kBm25ScatterSubPos: hipLaunchKernelGGL(k_bm25_accum_s, grid, block, 0, st, a, (int)t, f.sub); break;       // idf per q_terms position
+            case kBm25ScatterSubCol: hipLaunchKernelGGL(k_bm25_accum_sc, grid, block, 0, st, a, (int)t, f.sub); break;      // idf per column
+        }
         VFS_HIP(hipGetLastError());
     }
     const unsigned wblk = (unsigned)(h->words / kBmWordsPerBlock);
@@ -1402,23 +1499,41 @@ static int bm_score_select(vf_bm25* h, BmArgs& a, const int64_t* q_off, int g, c
     return VF_OK;
 }
 
-static int bm_tail_and_reset(vf_bm25* h, BmArgs& a, const int64_t* q_off, int g, int tail_blocks, const u32* allow) {
+// k > kBmSmallK, one query: the search's one read-back (how many keys the select gathered), then the global bitonic sort of that many
+static int bm_sort_deep(vf_bm25* h, BmArgs& a) {
     hipStream_t st = h->stream;
-    if (allow) hipLaunchKernelGGL(k_bm25_tail_count_f, dim3(tail_blocks, g), dim3(kBmThreads), 0, st, a, allow);
-    else hipLaunchKernelGGL(k_bm25_tail_count, dim3(tail_blocks, g), dim3(kBmThreads), 0, st, a);
-    hipLaunchKernelGGL(k_bm25_tail_scan, dim3(1, g), dim3(kBmThreads), 0, st, a, tail_blocks);
-    if (allow) hipLaunchKernelGGL(k_bm25_tail_write_f, dim3(tail_blocks, g), dim3(kBmThreads), 0, st, a, allow);
-    else hipLaunchKernelGGL(k_bm25_tail_write, dim3(tail_blocks, g), dim3(kBmThreads), 0, st, a);
+    BmState bs;
+    VFS_HIP(hipMemcpyAsync(&bs, h->d_st, sizeof(bs), hipMemcpyDeviceToHost, st));
+    VFS_HIP(hipStreamSynchronize(st));
+    const long long P = bm_pow2(std::max<long long>(bs.nsel, 1));
+    if (P > bs.nsel) hipLaunchKernelGGL(k_bm25_pad, dim3(bm_grid(P - bs.nsel, kBmThreads, 4096)), dim3(kBmThreads), 0, st, h->d_big, (long long)bs.nsel, P);
+    const int L = (int)std::min<long long>(P, kBmSortChunk);
+    const unsigned chunks = (unsigned)(P / L), pairs = bm_grid(P / 2, kBmThreads, 8192);
+    hipLaunchKernelGGL(k_bitonic_lds, dim3(chunks), dim3(1024), 0, st, h->d_big, L, 2ll, (long long)L, 1ll);
+    for (long long kk = 2ll * L; kk <= P; kk <<= 1) {
+        for (long long j = kk >> 1; j >= L; j >>= 1) hipLaunchKernelGGL(k_bitonic_global, dim3(pairs), dim3(kBmThreads), 0, st, h->d_big, P, kk, j);
+        hipLaunchKernelGGL(k_bitonic_lds, dim3(chunks), dim3(1024), 0, st, h->d_big, L, kk, kk, (long long)(L / 2));
+    }
+    if (bs.nsel > 0) hipLaunchKernelGGL(k_bm25_emit, dim3(bm_grid(bs.nsel, kBmThreads, 8192)), dim3(kBmThreads), 0, st, a);
+    VFS_HIP(hipGetLastError());
+    return VF_OK;
+}
+
+static int bm_tail_and_reset(vf_bm25* h, BmArgs& a, const int64_t* q_off, int g, const Bm25LaunchPlan& p, const BmFilter& f) {
+    hipStream_t st = h->stream;
+    const dim3 grid(p.tail_blocks, g), block(kBmThreads);
+    if (p.tail_f) hipLaunchKernelGGL(k_bm25_tail_count_f, grid, block, 0, st, a, f.allow);
+    else hipLaunchKernelGGL(k_bm25_tail_count, grid, block, 0, st, a);
+    hipLaunchKernelGGL(k_bm25_tail_scan, dim3(1, g), block, 0, st, a, p.tail_blocks);
+    if (p.tail_f) hipLaunchKernelGGL(k_bm25_tail_write_f, grid, block, 0, st, a, f.allow);
+    else hipLaunchKernelGGL(k_bm25_tail_write, grid, block, 0, st, a);
     long long post = 0;
-    for (int s = 0; s < g; ++s) {
-        long long p = 0;
+    for (int s = 0; s < g; ++s)
         for (long long t = q_off[a.q0 + s]; t < q_off[a.q0 + s + 1]; ++t) {
             const long long c = h->qterms_host[t];
-            p = std::max(p, h->indptr[c + 1] - h->indptr[c]);
+            post = std::max(post, h->indptr[c + 1] - h->indptr[c]);
         }
-        post = std::max(post, p);
-    }
-    if (post > 0) hipLaunchKernelGGL(k_bm25_reset, dim3(bm_grid(post, kBmThreads, 4096), g), dim3(kBmThreads), 0, st, a);
+    if (post > 0) hipLaunchKernelGGL(k_bm25_reset, dim3(bm_grid(post, kBmThreads, 4096), g), block, 0, st, a);
     VFS_HIP(hipGetLastError());
     return VF_OK;
 }
@@ -1427,35 +1542,18 @@ extern "C" int vf_bm25_search(vf_bm25* h, const int64_t* q_offsets, const int32_
                               int64_t* out_ids, float* out_scores) {
     if (!h) return bm_fail(VF_EINVAL, "vf_bm25_search: null handle");
     if (nq < 0) return bm_fail(VF_EINVAL, "vf_bm25_search: negative nq");
-    const vf_bm25_filter_query* fq = nullptr;   // VF_BM25_FILTER: one set of rows for every query of the call
-    vf_bm25_substats_query* sq = nullptr;       // ... | VF_BM25_SUBSTATS: scored by that set's own statistics, in two phases
-    vf_bm25_prepared_query* pq = nullptr;       // VF_BM25_PREPARED: the set and its statistics are a prepared filter's, on the device
-    if (nq & VF_BM25_PREPARED) {
-        if (nq & (VF_BM25_FILTER | VF_BM25_SUBSTATS))
-            return bm_fail(VF_EINVAL, "vf_bm25_search: VF_BM25_PREPARED goes alone (the prepared filter carries its rows and its mode)");
-        pq = (vf_bm25_prepared_query*)(void*)q_offsets;
-        if (!pq) return bm_fail(VF_EINVAL, "vf_bm25_search: VF_BM25_PREPARED with a null vf_bm25_prepared_query");
-        nq &= ~VF_BM25_PREPARED;
-        if (pq->phase != VF_BM25_PREPARED_SEARCH) {
-            std::lock_guard<std::mutex> lk(h->mu);
-            if (pq->phase == VF_BM25_PREPARED_PREPARE) return bm_prepared_prepare(h, pq);
-            if (pq->phase == VF_BM25_PREPARED_ARM) return bm_prepared_arm(h, pq);
-            if (pq->phase == VF_BM25_PREPARED_RELEASE) return bm_prepared_release(h, pq);
-            return bm_fail(VF_EINVAL, "vf_bm25_search: vf_bm25_prepared_query.phase must be one of the four VF_BM25_PREPARED_* phases");
-        }
-        q_offsets = pq->q_offsets;
-    } else if (nq & VF_BM25_FILTER) {
-        fq = (const vf_bm25_filter_query*)(const void*)q_offsets;
-        if (!fq) return bm_fail(VF_EINVAL, "vf_bm25_search: VF_BM25_FILTER with a null vf_bm25_filter_query");
-        if (nq & VF_BM25_SUBSTATS) sq = (vf_bm25_substats_query*)(void*)q_offsets;   // its first three members are fq's
-        q_offsets = fq->q_offsets;
-        nq &= ~(VF_BM25_FILTER | VF_BM25_SUBSTATS);
-    } else if (nq & VF_BM25_SUBSTATS) {
-        return bm_fail(VF_EINVAL, "vf_bm25_search: VF_BM25_SUBSTATS goes with VF_BM25_FILTER (the statistics are those of the allowed rows)");
+    // 1. the kind of call: `arg` is a flagged call's struct
+    const BmCallArg arg(q_offsets, nq);
+    Bm25Call c = bm25c_decode(nq, !q_offsets, q_offsets && bm25c_has_phase(nq) ? (arg.pq ? arg.pq->phase : arg.sq->phase) : 0);
+    if (c.refusal) return bm_fail(VF_EINVAL, kBmRefusalText[c.refusal]);
+    if (c.kind == kBm25PrepPrepare || c.kind == kBm25PrepArm || c.kind == kBm25PrepRelease) {
+        std::lock_guard<std::mutex> lk(h->mu);
+        return c.kind == kBm25PrepPrepare ? bm_prepared_prepare(h, arg.pq) : c.kind == kBm25PrepArm ? bm_prepared_arm(h, arg.pq) : bm_prepared_release(h, arg.pq);
     }
-    const bool stage = sq && sq->phase == VF_BM25_SUBSTATS_STAGE;
-    if (sq && !stage && sq->phase != VF_BM25_SUBSTATS_SEARCH)
-        return bm_fail(VF_EINVAL, "vf_bm25_search: vf_bm25_substats_query.phase must be VF_BM25_SUBSTATS_STAGE or VF_BM25_SUBSTATS_SEARCH");
+    if (c.kind != kBm25Plain) q_offsets = arg.q_offsets();
+    nq = c.nq;
+    const bool stage = c.kind == kBm25SubStage;   // it reads neither k nor the outputs
+    // 2. the checks every kind shares
     if (nq == 0) return VF_OK;
     if (!q_offsets || (!stage && (!out_ids || !out_scores))) return bm_fail(VF_EINVAL, "vf_bm25_search: null buffer");
     std::lock_guard<std::mutex> lk(h->mu);   // before n_docs and the vocabulary are read: a live handle's update changes both
@@ -1467,170 +1565,56 @@ extern "C" int vf_bm25_search(vf_bm25* h, const int64_t* q_offsets, const int32_
     if (T > 0 && !q_terms) return bm_fail(VF_EINVAL, "vf_bm25_search: null q_terms");
     for (long long t = 0; t < T; ++t)
         if (q_terms[t] < 0 || q_terms[t] >= h->V) return bm_fail(VF_EINVAL, "vf_bm25_search: a token column is out of range");
-    Bm25FilterPlan fp{};
-    if (fq) {
-        if (!fq->allow) return bm_fail(VF_EINVAL, "vf_bm25_search: VF_BM25_FILTER with a null allow bitmap");
-        if (fq->n_docs != h->n)
-            return bm_fail(VF_EINVAL, "vf_bm25_search: the filter was made for " + std::to_string(fq->n_docs) + " documents, the handle holds " +
-                                          std::to_string(h->n) + " (a live handle may have changed since the bitmap was made: make it again)");
-        const Bm25FilterCheck fc = bm25f_check(fq->allow, h->n);
-        if (fc.bad_row >= 0)
-            return bm_fail(VF_EINVAL, "vf_bm25_search: the filter allows row " + std::to_string(fc.bad_row) + ", at or past n_docs = " + std::to_string(h->n));
-        if (sq) {
-            if (!h->live || !h->born)
-                return bm_fail(VF_EUNSUPPORTED, "vf_bm25_search: VF_BM25_SUBSTATS needs a live handle (VF_BM25_LIVE): only it keeps the term frequencies and the document lengths");
-            if (stage) {
-                if (T > 0 && !sq->df) return bm_fail(VF_EINVAL, "vf_bm25_search: VF_BM25_SUBSTATS_STAGE with a null df");
-            } else {
-                if (sq->generation != h->gen)
-                    return bm_fail(VF_EINVAL, "vf_bm25_search: the statistics were staged at update generation " + std::to_string(sq->generation) + ", the handle is at " +
-                                                  std::to_string(h->gen) + " (the live index was updated between the stage and the search: stage again)");
-                if (T > 0 && !sq->idf) return bm_fail(VF_EINVAL, "vf_bm25_search: VF_BM25_SUBSTATS_SEARCH with a null idf");
-                for (long long t = 0; t < T; ++t)
-                    if (!(sq->idf[t] >= 0.0) || !(sq->idf[t] <= DBL_MAX))
-                        return bm_fail(VF_EINVAL, "vf_bm25_search: idf[" + std::to_string(t) + "] is negative or not finite");
-                if (!(sq->avgdl > 0.0) || !(sq->avgdl <= DBL_MAX) || !(sq->k1 >= 0.0) || !(sq->b >= 0.0 && sq->b <= 1.0))
-                    return bm_fail(VF_EINVAL, "vf_bm25_search: VF_BM25_SUBSTATS_SEARCH needs avgdl > 0, k1 >= 0 and b in [0, 1]");
-            }
+    // 3. the filter, and with its m the plan
+    BmFilter f;
+    int rc = bm_filter_check(h, c, arg, T, &f);
+    if (rc != VF_OK) return rc;
+    const Bm25LaunchPlan p = bm25c_plan(c, k, nq, h->slot_cap, h->words, f.m);
+    if (p.no_launch) {   // no row is allowed
+        bm_all_padding(out_ids, out_scores, nq, k);
+        if (stage) {
+            std::fill(arg.sq->df, arg.sq->df + T, (int64_t)0);
+            arg.sq->total_len = 0; arg.sq->m = 0; arg.sq->generation = h->gen;
         }
-        fp = bm25f_plan(h->words, fc.m, k);
-        if (fc.m == 0) {   // nothing may be returned: all padding, no launch
-            if (out_ids && out_scores && k >= 1) {
-                std::fill(out_ids, out_ids + (size_t)nq * k, (int64_t)-1);
-                std::fill(out_scores, out_scores + (size_t)nq * k, -FLT_MAX);
-            }
-            if (stage) {
-                std::fill(sq->df, sq->df + T, (int64_t)0);
-                sq->total_len = 0; sq->m = 0; sq->generation = h->gen;
-            }
-            return VF_OK;
-        }
-        if (stage) return bm_substats_stage(h, sq, fq->allow, fc.m, q_terms, nq, T);
+        return VF_OK;
     }
-    const BmPrepared* pf = nullptr;
-    if (pq) {   // the filter's own checks were made when it was prepared: only that it is still this index's is looked at here
-        pf = bm_prepared_find(h, pq->token);
-        if (!pf) return bm_fail(VF_EINVAL, "vf_bm25_search: token " + std::to_string(pq->token) + " names no prepared filter of this handle (unknown or released)");
-        if (pf->stale || pf->gen != h->gen) return bm_prepared_stale(h, pf, "VF_BM25_PREPARED_SEARCH");
-        if (pf->subset && !pf->armed)
-            return bm_fail(VF_EINVAL, "vf_bm25_search: the prepared filter is in subset mode and was never armed (VF_BM25_PREPARED_ARM gives it its idf)");
-        fp = bm25f_plan(h->words, pf->m, k);
-        if (pf->m == 0) {   // nothing may be returned: all padding, no launch
-            std::fill(out_ids, out_ids + (size_t)nq * k, (int64_t)-1);
-            std::fill(out_scores, out_scores + (size_t)nq * k, -FLT_MAX);
-            return VF_OK;
-        }
-    }
-    const bool filtered = fq || pf;
+    if (stage) return bm_substats_stage(h, arg.sq, f.m, q_terms, p.S, T);
     DeviceGuard guard;
     VFS_HIP(hipSetDevice(h->device));
     hipStream_t st = h->stream;
-    if (nq + 1 > h->q_cap) {
-        if (h->d_qoff) (void)hipFree(h->d_qoff);
-        h->d_qoff = nullptr; h->q_cap = 0;
-        VFS_HIP(hipMalloc((void**)&h->d_qoff, (size_t)(nq + 1) * 8));
-        h->q_cap = nq + 1;
-    }
-    if (std::max<long long>(T, 1) > h->t_cap) {
-        if (h->d_qterms) (void)hipFree(h->d_qterms);
-        h->d_qterms = nullptr; h->t_cap = 0;
-        VFS_HIP(hipMalloc((void**)&h->d_qterms, (size_t)std::max<long long>(T, 1) * 4));
-        h->t_cap = std::max<long long>(T, 1);
-    }
+    rc = bm_grow("vf_bm25: query offsets", h->d_qoff, h->q_cap, nq + 1, (size_t)(nq + 1) * 8);
+    if (rc == VF_OK) rc = bm_grow("vf_bm25: query tokens", h->d_qterms, h->t_cap, std::max<long long>(T, 1), (size_t)std::max<long long>(T, 1) * 4);
+    if (rc != VF_OK) return rc;
     VFS_HIP(hipMemcpyAsync(h->d_qoff, q_offsets, (size_t)(nq + 1) * 8, hipMemcpyHostToDevice, st));
     if (T > 0) VFS_HIP(hipMemcpyAsync(h->d_qterms, q_terms, (size_t)T * 4, hipMemcpyHostToDevice, st));
     h->qterms_host = q_terms;
-
+    rc = bm_ensure_slots(h, std::max(p.S, h->slots));
+    if (rc == VF_OK && !p.small) rc = bm_ensure_big(h);
+    if (rc == VF_OK) rc = bm_filter_bind(h, c, arg, T, &f);
+    if (rc != VF_OK) return rc;
+    // 4. one loop over groups of S queries; the two arms differ in their buffers and their sort
     BmArgs a{};
     a.indptr = h->d_indptr; a.indices = h->d_indices; a.data = h->d_data;
     a.q_off = h->d_qoff; a.q_terms = h->d_qterms;
-    a.n = h->n; a.words = h->words;
-    a.k = k;
-    const bool small = k <= kBmSmallK;
-    const int S = small ? std::min<int>(nq, h->slot_cap) : 1;
-    {
-        const int rc = bm_ensure_slots(h, std::max(S, h->slots));
-        if (rc != VF_OK) return rc;
-    }
-    if (!small) {
-        const int rc = bm_ensure_big(h);
-        if (rc != VF_OK) return rc;
-    }
-    const u32* allow = nullptr;
-    if (fq) {   // the bitmap goes up with every filtered call (n / 8 bytes): no filter is kept on the device between calls
-        const int rc = bm_ensure_filter(h);
-        if (rc != VF_OK) return rc;
-        // ... except from a VF_BM25_SUBSTATS stage to its search: the stage's copy serves when it holds these very words
-        const size_t aw = (size_t)bm25f_words(h->n);
-        const bool staged = sq && h->allow_staged && h->staged_allow.size() == aw && std::equal(h->staged_allow.begin(), h->staged_allow.end(), fq->allow);
-        h->allow_staged = false;
-        if (!staged) VFS_HIP(hipMemcpyAsync(h->d_allow, fq->allow, aw * 4, hipMemcpyHostToDevice, st));
-        allow = h->d_allow;
-    }
-    if (pf) {   // nothing goes up: the bitmap is the filter's own (d_allow and what a stage left in it are not touched)
-        const int rc = bm_ensure_filter(h);   // the tail's scratch over every bitmap block
-        if (rc != VF_OK) return rc;
-        allow = pf->d_allow;
-    }
-    SubArgs sub{};
-    if (sq) {
-        const int rc = bm_ensure_sidf(h, T);
-        if (rc != VF_OK) return rc;
-        if (T > 0) VFS_HIP(hipMemcpyAsync(h->d_sidf, sq->idf, (size_t)T * 8, hipMemcpyHostToDevice, st));
-        sub.tf = h->d_tf; sub.doclen = h->d_doclen; sub.allow = allow; sub.n = h->n;
-        sub.idf = h->d_sidf; sub.avgdl = sq->avgdl; sub.k1 = sq->k1; sub.b = sq->b; sub.one_minus_b = 1.0 - sq->b;
-    }
-    const bool by_col = pf && pf->subset;
-    if (by_col) {
-        sub.tf = h->d_tf; sub.doclen = h->d_doclen; sub.allow = allow; sub.n = h->n;
-        sub.idf = pf->d_idf; sub.avgdl = pf->avgdl; sub.k1 = pf->k1; sub.b = pf->b; sub.one_minus_b = 1.0 - pf->b;
-    }
-    const SubArgs* ss = (sq || by_col) ? &sub : nullptr;
-    const unsigned pad_grid = bm_grid(k - fp.pad_from, kBmThreads, 64);   // a filtered call of fewer than k rows pads ranks pad_from .. k - 1
+    a.n = h->n; a.words = h->words; a.k = k;
     a.scores = h->d_scores; a.score_stride = h->n;
     a.bits = h->d_bits; a.bits_stride = h->words;
     a.hist = h->d_hist; a.st = h->d_st;
-    for (int q0 = 0; q0 < nq; q0 += S) {
-        const int g = std::min(S, nq - q0);
+    a.sel = p.small ? h->d_sel : h->d_big; a.sel_stride = p.small ? kBmSmallK : 0; a.sel_cap = p.small ? kBmSmallK : bm_pow2(h->n);
+    a.tblk = !p.small ? h->d_big_tblk : p.tail_f ? h->d_ftblk : h->d_tblk; a.tblk_stride = p.tblk_stride;
+    a.out_ids = p.small ? h->d_ids : h->d_big_ids; a.out_scores = p.small ? h->d_out : h->d_big_out; a.out_stride = p.small ? k : 0;
+    const unsigned pad_grid = bm_grid(k - p.pad_from, kBmThreads, 64);   // a filtered call of fewer than k rows pads ranks pad_from .. k - 1
+    const int Pk = (int)bm_pow2(k);
+    for (int q0 = 0; q0 < nq; q0 += p.S) {
+        const int g = std::min(p.S, nq - q0);
         a.q0 = q0;
-        if (small) {
-            a.sel = h->d_sel; a.sel_stride = kBmSmallK; a.sel_cap = kBmSmallK;
-            a.tblk = h->d_tblk; a.tblk_stride = 1;
-            if (filtered) { a.tblk = h->d_ftblk; a.tblk_stride = fp.tblk_entries; }
-            a.out_ids = h->d_ids; a.out_scores = h->d_out; a.out_stride = k;
-            int rc = bm_score_select(h, a, q_offsets, g, allow, ss, by_col);
-            if (rc != VF_OK) return rc;
-            if (filtered && fp.pad_from < k) hipLaunchKernelGGL(k_bm25_pad_out, dim3(pad_grid, g), dim3(kBmThreads), 0, st, a, fp.pad_from);
-            const int Pk = (int)bm_pow2(k);
-            hipLaunchKernelGGL(k_bm25_sort_small, dim3(1, g), dim3(512), (size_t)Pk * 8, st, a, Pk);
-            // fewer than k touched rows means fewer than kBmSmallK: the tail lies in the first 2 * kBmSmallK rows, one bitmap block --
-            // unless a filter strikes rows out: then the allowed untouched rows can lie in any block, and every block is counted
-            rc = bm_tail_and_reset(h, a, q_offsets, g, filtered ? fp.tail_blocks : 1, allow);
-            if (rc != VF_OK) return rc;
-        } else {
-            a.sel = h->d_big; a.sel_stride = 0; a.sel_cap = bm_pow2(h->n);
-            a.tblk = h->d_big_tblk; a.tblk_stride = 0;
-            a.out_ids = h->d_big_ids; a.out_scores = h->d_big_out; a.out_stride = 0;
-            int rc = bm_score_select(h, a, q_offsets, 1, allow, ss, by_col);
-            if (rc != VF_OK) return rc;
-            if (filtered && fp.pad_from < k) hipLaunchKernelGGL(k_bm25_pad_out, dim3(pad_grid, 1), dim3(kBmThreads), 0, st, a, fp.pad_from);
-            BmState bs;
-            VFS_HIP(hipMemcpyAsync(&bs, h->d_st, sizeof(bs), hipMemcpyDeviceToHost, st));
-            VFS_HIP(hipStreamSynchronize(st));
-            const long long P = bm_pow2(std::max<long long>(bs.nsel, 1));
-            if (P > bs.nsel) hipLaunchKernelGGL(k_bm25_pad, dim3(bm_grid(P - bs.nsel, kBmThreads, 4096)), dim3(kBmThreads), 0, st, h->d_big, (long long)bs.nsel, P);
-            const int L = (int)std::min<long long>(P, kBmSortChunk);
-            const unsigned chunks = (unsigned)(P / L), pairs = bm_grid(P / 2, kBmThreads, 8192);
-            hipLaunchKernelGGL(k_bitonic_lds, dim3(chunks), dim3(1024), 0, st, h->d_big, L, 2ll, (long long)L, 1ll);
-            for (long long kk = 2ll * L; kk <= P; kk <<= 1) {
-                for (long long j = kk >> 1; j >= L; j >>= 1) hipLaunchKernelGGL(k_bitonic_global, dim3(pairs), dim3(kBmThreads), 0, st, h->d_big, P, kk, j);
-                hipLaunchKernelGGL(k_bitonic_lds, dim3(chunks), dim3(1024), 0, st, h->d_big, L, kk, kk, (long long)(L / 2));
-            }
-            if (bs.nsel > 0) hipLaunchKernelGGL(k_bm25_emit, dim3(bm_grid(bs.nsel, kBmThreads, 8192)), dim3(kBmThreads), 0, st, a);
-            VFS_HIP(hipGetLastError());
-            rc = bm_tail_and_reset(h, a, q_offsets, 1, h->words / kBmWordsPerBlock, allow);
-            if (rc != VF_OK) return rc;
-        }
+        rc = bm_score_select(h, a, q_offsets, g, p, f);
+        if (rc != VF_OK) return rc;
+        if (p.pad_out) hipLaunchKernelGGL(k_bm25_pad_out, dim3(pad_grid, g), dim3(kBmThreads), 0, st, a, p.pad_from);
+        if (p.small) hipLaunchKernelGGL(k_bm25_sort_small, dim3(1, g), dim3(512), (size_t)Pk * 8, st, a, Pk);
+        else rc = bm_sort_deep(h, a);
+        if (rc == VF_OK) rc = bm_tail_and_reset(h, a, q_offsets, g, p, f);
+        if (rc != VF_OK) return rc;
         VFS_HIP(hipMemcpyAsync(out_ids + (size_t)q0 * k, a.out_ids, (size_t)g * k * 8, hipMemcpyDeviceToHost, st));
         VFS_HIP(hipMemcpyAsync(out_scores + (size_t)q0 * k, a.out_scores, (size_t)g * k * 4, hipMemcpyDeviceToHost, st));
     }
@@ -1638,3 +1622,4 @@ extern "C" int vf_bm25_search(vf_bm25* h, const int64_t* q_offsets, const int32_
     h->qterms_host = nullptr;
     return VF_OK;
 }
+
