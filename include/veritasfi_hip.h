@@ -546,8 +546,8 @@ int vf_bm25_search(vf_bm25* h, const int64_t* q_offsets, const int32_t* q_terms,
  * allowed rows only, and the zero-score tail takes allowed untouched rows from every block of the bitmap.  The bitmap, n_docs / 8
  * bytes, is uploaded with every filtered call (no filter is kept on the device between calls); the handle allocates its device copy
  * and 4 B per 32 768 rows and query slot of tail scratch on the first filtered call.  Without the flag nothing about the call changes.
- * Not in scope: a filter per query.  (Statistics over the set: VF_BM25_SUBSTATS below; a filter that stays on the device across
- * calls: VF_BM25_PREPARED below.) */
+ * (Statistics over the set: VF_BM25_SUBSTATS below; a filter that stays on the device across calls, and a filter per query of a
+ * batch: VF_BM25_PREPARED below.) */
 #define VF_BM25_FILTER 0x40000000      /* or'ed into `nq` of vf_bm25_search: `q_offsets` is a vf_bm25_filter_query */
 typedef struct vf_bm25_filter_query {
     const int64_t*  q_offsets;   /* what q_offsets was */
@@ -582,8 +582,7 @@ typedef struct vf_bm25_filter_query {
  * The bitmap goes up once per request: the stage leaves its device copy for the search that follows, which uploads it again only if
  * its `allow` differs from the staged words or another filtered call came between.  The handle allocates 8 B per q_terms position and
  * 8 B per distinct column on the first such call; a handle that never uses the mode allocates nothing.  Without the flag nothing
- * about vf_bm25_search changes.  Not in scope: a filter per query.  (Statistics kept on the device across requests: VF_BM25_PREPARED
- * below.) */
+ * about vf_bm25_search changes.  (Statistics kept on the device across requests, and a filter per query: VF_BM25_PREPARED below.) */
 #define VF_BM25_SUBSTATS 0x20000000    /* or'ed into `nq` beside VF_BM25_FILTER: `q_offsets` is a vf_bm25_substats_query */
 #define VF_BM25_SUBSTATS_STAGE 1
 #define VF_BM25_SUBSTATS_SEARCH 2
@@ -624,8 +623,8 @@ typedef struct vf_bm25_substats_query {
  *                             and b under VF_BM25_SUBSTATS_SEARCH's checks, and uploads idf to the filter's table.  A filter whose
  *                             generation is no longer the handle's is VF_EINVAL.  A subset-mode filter that was never armed refuses to
  *                             search.
- *   VF_BM25_PREPARED_SEARCH   reads token and q_offsets; q_terms, nq, k and the outputs are the search's own.  Corpus mode runs the
- *                             filtered scatter on the filter's bitmap; subset mode scores each allowed posting from its term frequency
+ *   VF_BM25_PREPARED_SEARCH   reads token (or, per query, tokens: below) and q_offsets; q_terms, nq, k and the outputs are the search's
+ *                             own.  Corpus mode runs the filtered scatter on the filter's bitmap; subset mode scores each allowed posting from its term frequency
  *                             with idf read per COLUMN from the filter's table.  Everything behind the scatter is the filtered
  *                             search's.  An unknown or released token is VF_EINVAL; so is a filter made before the handle's last
  *                             update (the message says to prepare again).
@@ -633,7 +632,18 @@ typedef struct vf_bm25_substats_query {
  * A committed live update invalidates every prepared filter of the handle and frees its device memory (rows have moved: no filter can
  * search with stale bits); the token stays known, so that a search or an arm with it is refused by its generation, until it is released.
  * An allocation failure is VF_ENOMEM and leaves the handle and every other filter as they were; a refused call changes nothing.
- * Without the flag nothing about vf_bm25_search changes.  Not in scope: a filter per query, filters remapped across an update. */
+ * A filter PER QUERY of a batch (one index serves many tenants, and a server's batch holds requests of many): a search whose `mode` is
+ * VF_BM25_PREPARED_PER_QUERY reads `tokens` [nq] in place of `token`; tokens[i] names the prepared filter of query i, 0 (the library
+ * never hands it out) a query without one.  Row i of the result is, ids and score bits, what VF_BM25_PREPARED_SEARCH returns for query i
+ * alone with the token tokens[i] -- or, for 0, what the unflagged call returns for it: corpus-mode, subset-mode and unfiltered queries
+ * may stand side by side, at every k, with the padding of each query its own (ranks min(m_i, k) .. k - 1).  The call uploads 64 bytes
+ * per query beside the query itself and nothing of any filter.  `tokens` is read ONLY in this mode: a caller compiled against the
+ * struct without it passes mode 0 or 1 to a search, where `mode` was and is otherwise ignored.  Checked in query order under the
+ * handle's lock before any device work, VF_EINVAL each and naming the position and the token: a null `tokens`; a token that is unknown or released;
+ * a filter made before the handle's last update; a subset-mode filter that was never armed.  Corpus-mode tokens serve on any handle,
+ * subset-mode ones exist only on live handles.  The same token on every query is served as any other batch of this mode.
+ * Without the flag nothing about vf_bm25_search changes.  Not in scope: filters remapped across an update, a per-query filter that
+ * was not prepared. */
 #define VF_BM25_PREPARED 0x10000000    /* or'ed into `nq` of vf_bm25_search: `q_offsets` is a vf_bm25_prepared_query */
 #define VF_BM25_PREPARED_PREPARE 1
 #define VF_BM25_PREPARED_ARM 2
@@ -641,12 +651,13 @@ typedef struct vf_bm25_substats_query {
 #define VF_BM25_PREPARED_RELEASE 4
 #define VF_BM25_PREPARED_CORPUS 0
 #define VF_BM25_PREPARED_SUBSET 1
+#define VF_BM25_PREPARED_PER_QUERY 2   /* `mode` of a VF_BM25_PREPARED_SEARCH: `tokens` [nq] names a filter per query */
 typedef struct vf_bm25_prepared_query {
     const int64_t*  q_offsets;   /* search: what q_offsets was */
     const uint32_t* allow;       /* prepare: host, (n_docs + 31) / 32 words, as vf_bm25_filter_query's */
     int64_t         n_docs;      /* prepare: the document count the bitmap was made for */
     int32_t         phase;       /* one of the four VF_BM25_PREPARED_* phases */
-    int32_t         mode;        /* prepare: VF_BM25_PREPARED_CORPUS or VF_BM25_PREPARED_SUBSET */
+    int32_t         mode;        /* prepare: VF_BM25_PREPARED_CORPUS or VF_BM25_PREPARED_SUBSET; search: VF_BM25_PREPARED_PER_QUERY or anything else */
     uint64_t        token;       /* out of prepare, into arm, search and release */
     int64_t         vocab;       /* prepare (subset mode) and arm: entries of df / idf, the handle's vocabulary */
     int64_t*        df;          /* out of prepare (subset mode): [vocab] allowed postings of every column */
@@ -657,6 +668,7 @@ typedef struct vf_bm25_prepared_query {
     const double*   idf;         /* arm: [vocab] */
     double          avgdl, k1, b;   /* arm: the subset's mean length and the index's parameters */
     int32_t         chunk;       /* prepare (subset mode): 0 = 2048, else 1 .. 2048 postings per workgroup of the count */
+    const uint64_t* tokens;      /* search in mode VF_BM25_PREPARED_PER_QUERY only: [nq], the filter of each query, 0 = none */
 } vf_bm25_prepared_query;
 
 #ifdef __cplusplus

@@ -18,7 +18,7 @@ from veritasfi_amd import build as vf_build  # noqa: E402
 
 _FIELDS = {
     "Function Name": "name", "VGPRs": "vgprs", "AGPRs": "agprs", "ScratchSize [bytes/lane]": "scratch",
-    "VGPRs Spill": "vgpr_spill", "SGPRs Spill": "sgpr_spill", "SGPRs": "sgprs", "Occupancy [waves/SIMD]": "occupancy",
+    "VGPRs Spill": "vgpr_spill", "SGPRs Spill": "sgpr_spill", "SGPRs": "sgprs", "TotalSGPRs": "sgprs", "Occupancy [waves/SIMD]": "occupancy",
     "LDS Size [bytes/block]": "lds", "Dynamic Stack": "dynamic_stack",
 }
 _LINE = re.compile(r"remark: (?:[^:]+:\d+:\d+: )?\s*([A-Za-z][A-Za-z /\[\]]*?):\s*(\S+)\s*\[-Rpass-analysis")

@@ -65,17 +65,18 @@ class Bm25SubstatsQuery(ctypes.Structure):
 VF_BM25_PREPARED = 0x10000000
 VF_BM25_PREPARED_PREPARE, VF_BM25_PREPARED_ARM, VF_BM25_PREPARED_SEARCH, VF_BM25_PREPARED_RELEASE = 1, 2, 3, 4
 VF_BM25_PREPARED_CORPUS, VF_BM25_PREPARED_SUBSET = 0, 1
+VF_BM25_PREPARED_PER_QUERY = 2   # `mode` of a search: `tokens` [nq] names a prepared filter per query, 0 = none
 
 
 class Bm25PreparedQuery(ctypes.Structure):
     """vf_bm25_prepared_query of include/veritasfi_hip.h: a row filter kept on the device.  Prepare reads allow, n_docs, mode, chunk
     (and vocab, df in subset mode) and writes token, m, generation, bytes (and total_len, df); arm reads token, vocab, idf, avgdl, k1, b;
-    search reads token and q_offsets; release reads token."""
+    search reads token and q_offsets -- or, with mode VF_BM25_PREPARED_PER_QUERY, tokens [nq] in place of token; release reads token."""
     _fields_ = [("q_offsets", ctypes.POINTER(c_i64)), ("allow", ctypes.POINTER(ctypes.c_uint32)), ("n_docs", c_i64),
                 ("phase", c_i32), ("mode", c_i32), ("token", ctypes.c_uint64), ("vocab", c_i64), ("df", ctypes.POINTER(c_i64)),
                 ("total_len", c_i64), ("m", c_i64), ("generation", ctypes.c_uint64), ("bytes", c_i64),
                 ("idf", ctypes.POINTER(ctypes.c_double)), ("avgdl", ctypes.c_double), ("k1", ctypes.c_double), ("b", ctypes.c_double),
-                ("chunk", c_i32)]
+                ("chunk", c_i32), ("tokens", ctypes.POINTER(ctypes.c_uint64))]
 
 
 class SubsetQuery(ctypes.Structure):

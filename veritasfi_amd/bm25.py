@@ -325,7 +325,10 @@ class BM25Retriever:
 
     ``prepare_subset(subset, stats)`` -> ``BM25Subset``: the same filter on many requests (one index per tenant) is packed, checked,
     uploaded and -- with stats="subset" -- counted ONCE; passed as ``subset=`` it makes every request one device call that uploads only
-    the query, with the result of the unprepared call bit for bit (VF_BM25_PREPARED)."""
+    the query, with the result of the unprepared call bit for bit (VF_BM25_PREPARED).
+
+    ``subsets=[...]`` (``search_columns``, ``invoke_batch``): a ``BM25Subset`` or None PER QUERY -- a batch whose queries belong to
+    different tenants is still one device call, and query i returns what it returns alone with ``subset=subsets[i]``."""
 
     exact_prefix = True
     filtered_prefix = True
@@ -676,14 +679,59 @@ class BM25Retriever:
             raise ValueError(f"stats={stats!r} beside a BM25Subset prepared with stats={subset.stats!r}: the mode is the object's own; "
                              "leave stats= out, or prepare another one")
 
-    def search_columns(self, columns: Sequence[np.ndarray], k: int, subset=None, stats=_STATS_UNSET):
+    def _search_per_query(self, columns, k: int, subsets):
+        """``search_columns(columns, k, subsets=[...])``: the prepared filter of every query by its token, 0 for None (VF_BM25_PREPARED_PER_QUERY)."""
+        cols, offsets, terms = self._columns_args(columns)
+        nq, k = len(cols), int(k)
+        subsets = list(subsets)
+        if len(subsets) != nq:
+            raise ValueError(f"subsets: {len(subsets)} entries for {nq} queries; one BM25Subset or None per query")
+        for i, s in enumerate(subsets):
+            if s is None:
+                continue
+            if not isinstance(s, BM25Subset):
+                raise TypeError(f"subsets[{i}]: a BM25Subset (prepare_subset) or None, not {type(s).__name__}; rows that were not prepared go to subset=, one set per call")
+            if s._retriever is not self:
+                raise ValueError(f"subsets[{i}]: this BM25Subset was prepared on another BM25Retriever; prepare it on this one (prepare_subset)")
+        if all(s is None for s in subsets):
+            return self.search_columns(columns, k)
+        with self._mu:
+            for i, s in enumerate(subsets):   # before k: an object may have been made for another document count
+                if s is not None and (s._closed or s._stale):
+                    raise ValueError(f"subsets[{i}]: this BM25Subset " + ("is closed" if s._closed else "is stale (the retriever was updated "
+                                     f"after it was prepared at generation {s.generation})") + ": call prepare_subset again")
+            if not 1 <= k <= self.num_docs:
+                raise ValueError(f"k={k}: must be in [1, {self.num_docs}] (the number of documents)")
+            ids = np.empty((nq, k), dtype=np.int64)
+            scores = np.empty((nq, k), dtype=np.float32)
+            if not self._h.value:
+                raise RuntimeError("BM25Retriever is closed")
+            tokens = np.asarray([0 if s is None else s._token for s in subsets], dtype=np.uint64)
+            pq = _ffi.Bm25PreparedQuery()
+            pq.q_offsets, pq.phase, pq.mode = offsets.ctypes.data_as(_ffi.p_i64), _ffi.VF_BM25_PREPARED_SEARCH, _ffi.VF_BM25_PREPARED_PER_QUERY
+            pq.tokens = tokens.ctypes.data_as(_ffi.ctypes.POINTER(_ffi.ctypes.c_uint64))
+            _ffi.check(self._search(pq, terms, nq | _ffi.VF_BM25_PREPARED, k, ids, scores), "vf_bm25_search")
+        return ids, scores
+
+    def search_columns(self, columns: Sequence[np.ndarray], k: int, subset=None, stats=_STATS_UNSET, subsets=None):
         """Token-column lists -> (ids int64 [nq, k], scores float32 [nq, k]) in one device call.  subset (``filter_words``' argument):
         one set of rows for all the queries; with m rows allowed and k > m the ranks m .. k - 1 are padding, id -1 and score -FLT_MAX.
         stats="subset" (a live retriever, with ``subset``; default "corpus"): scored by the allowed rows' own N, df and mean length -- bit
         for bit what a retriever over ``bm25_index_arrays`` of those documents alone returns, its rows mapped back.  Two device calls (the
         counts, then the search) with numpy's log between them, as an update, and under the update lock, so that no update lands between
         them.  subset=<a ``BM25Subset``> (``prepare_subset``): the same results from ONE call that uploads only the query; the mode is
-        the object's own (``stats=`` beside it must be absent or equal), a stale or closed one is a ValueError."""
+        the object's own (``stats=`` beside it must be absent or equal), a stale or closed one is a ValueError.
+        subsets=[...] (in place of ``subset``): one entry per query, a ``BM25Subset`` of this retriever or None -- a batch whose queries
+        belong to different tenants, still ONE device call that uploads only the queries and a token each.  Row i is, ids and score bits,
+        what ``search_columns([columns[i]], k, subset=subsets[i])`` returns (the plain call for None); corpus-mode, subset-mode and
+        unfiltered queries may be mixed, the mode is each object's own.  ``subset=`` or ``stats=`` beside it, a wrong length, an entry of
+        another retriever and a closed or stale entry are ValueErrors that name the position; all None is the plain call."""
+        if subsets is not None:
+            if subset is not None:
+                raise ValueError("subset= and subsets= together: one set of rows for the whole batch, or one prepared filter per query")
+            if stats is not _STATS_UNSET:
+                raise ValueError(f"stats={stats!r} beside subsets=: the mode is each BM25Subset's own; leave stats= out")
+            return self._search_per_query(columns, k, subsets)
         prepared = isinstance(subset, BM25Subset)
         if prepared:
             self._prepared_mode(subset, stats)
@@ -750,9 +798,10 @@ class BM25Retriever:
         ids, scores = self.search_columns([self.query_columns(query)], k, subset=subset, stats=stats)
         return self._result(ids[0], scores[0])
 
-    def invoke_batch(self, queries: Sequence[str], k: int, subset=None, stats=_STATS_UNSET):
-        """[(ids, scores)] per query, all in one device call; ``subset``: one set of rows for all of them, ``stats`` as ``search_columns``."""
-        ids, scores = self.search_columns([self.query_columns(q) for q in queries], k, subset=subset, stats=stats)
+    def invoke_batch(self, queries: Sequence[str], k: int, subset=None, stats=_STATS_UNSET, subsets=None):
+        """[(ids, scores)] per query, all in one device call; ``subset``: one set of rows for all of them, ``stats`` as ``search_columns``;
+        ``subsets``: a ``BM25Subset`` or None per query (``search_columns``), query i then returns min(k, rows its filter allows) rows."""
+        ids, scores = self.search_columns([self.query_columns(q) for q in queries], k, subset=subset, stats=stats, subsets=subsets)
         return [self._result(ids[i], scores[i]) for i in range(len(ids))]
 
     def info(self) -> dict:

@@ -25,6 +25,9 @@
 //   k_bm25_sub_df_all, k_bm25_accum_sc   a PREPARED row filter (VF_BM25_PREPARED; the index arithmetic is vf_bm25_prepared.h): its bitmap stays
 //                      on the device, and in subset mode df is counted once for EVERY column in one pass over the flat posting array,
 //                      so that the scatter reads idf per column from the filter's own table and a request uploads only its query
+//   k_bm25_accum_m, k_bm25_tail_count_m, k_bm25_tail_write_m, k_bm25_pad_out_m   a prepared filter PER QUERY (VF_BM25_PREPARED_PER_QUERY; the
+//                      descriptors and the plan are vf_bm25_multi.h): each slot reads which bitmap, idf table and first padded rank are
+//                      its own from a table indexed by its query, and then runs the body of the form that filter means
 //   k_bm25_live_*      a live handle's update: documents leave and arrive, every posting is re-scored into a second set of
 //                      arrays (described where they stand; the index arithmetic is vf_bm25_live.h)
 #include "vf_internal.h"
@@ -32,6 +35,7 @@
 #include "vf_bm25_filter.h"
 #include "vf_bm25_substats.h"
 #include "vf_bm25_prepared.h"
+#include "vf_bm25_multi.h"
 
 #include <float.h>
 #include <algorithm>
@@ -52,6 +56,7 @@ constexpr int kBmSortChunk = 4096;                                  // keys per 
 static_assert(kBmWordsPerBlock == kBm25FilterBlockWords, "vf_bm25_filter.h plans the tail over blocks of kBmWordsPerBlock words");
 static_assert(kBmThreads == kBm25SubThreads && kBmWordsPerThread == kBm25SubWordsPerThread, "vf_bm25_substats.h plans the counting kernels");
 static_assert(kBmThreads == kBm25PrepThreads, "vf_bm25_prepared.h plans the all-columns count");
+static_assert(kBmSmallK == kBm25mSmallK, "vf_bm25_multi.h plans the group loop of a filter per query");
 
 struct BmState {          // per slot, rewritten by pass 0 of every query
     u64 prefix;           // selected keys are those >= prefix
@@ -179,6 +184,29 @@ __device__ __forceinline__ void bm_accum_s(const BmArgs& a, int t, const SubArgs
 __global__ __launch_bounds__(kBmThreads) void k_bm25_accum_s(BmArgs a, int t, SubArgs sa) { bm_accum_s<false>(a, t, sa); }
 __global__ __launch_bounds__(kBmThreads) void k_bm25_accum_sc(BmArgs a, int t, SubArgs sa) { bm_accum_s<true>(a, t, sa); }
 
+// ---- a prepared filter per query (vf_bm25_multi.h) ----------------------------------------------------------------------------------
+// The slot's descriptor: one address per workgroup, read before the kernel's first store, so the loads are scalar
+__device__ __forceinline__ Bm25Desc bm_desc(const BmArgs& a, const Bm25Desc* __restrict__ desc) { return desc[a.q0 + blockIdx.y]; }
+
+// bm_accum_s with its filter taken from the slot's descriptor: the bitmap, the idf table (per column) and the scoring parameters
+__device__ __forceinline__ void bm_accum_s(const BmArgs& a, int t, const Bm25Desc& d, const int* tf, const int* doclen) {
+    SubArgs sa{};
+    sa.tf = tf; sa.doclen = doclen; sa.allow = d.allow;
+    sa.idf = d.idf; sa.avgdl = d.avgdl; sa.k1 = d.k1; sa.b = d.b; sa.one_minus_b = d.one_minus_b;
+    bm_accum_s<true>(a, t, sa);
+}
+
+// The scatter of a group whose slots differ in their filter: per slot k_bm25_accum's, k_bm25_accum_f's or k_bm25_accum_sc's body, chosen by
+// a branch the whole workgroup takes alike.  tf, doclen: the live handle's (null on a frozen one, which holds no subset-mode filter)
+__global__ __launch_bounds__(kBmThreads) void k_bm25_accum_m(BmArgs a, int t, const Bm25Desc* __restrict__ desc, const int* tf, const int* doclen) {
+    const Bm25Desc d = bm_desc(a, desc);
+    switch (bm25m_form(d)) {
+        case kBm25mPlain: bm_accum<false>(a, t, nullptr); break;
+        case kBm25mCorpus: bm_accum<true>(a, t, d.allow); break;
+        case kBm25mSubset: bm_accum_s(a, t, d, tf, doclen); break;
+    }
+}
+
 // histogram of digit (key >> shift) & 255 over the touched keys whose upper digits equal the prefix
 __global__ __launch_bounds__(kBmThreads) void k_bm25_hist(BmArgs a, int pass) {
     const int s = blockIdx.y, tid = threadIdx.x;
@@ -303,14 +331,16 @@ __global__ __launch_bounds__(512) void k_bm25_sort_small(BmArgs a, int Pk) {
     for (int i = tid; i < (int)n; i += 512) bm_emit(a, s, i, keys[i]);
 }
 
-// zero bits (untouched rows < n) of the four words a thread owns in bitmap block b; kFilt: those of them `allow` [words] lets through
-template <bool kFilt>
+// zero bits (untouched rows < n) of the four words a thread owns in bitmap block b; kFilt: those of them `allow` [words] lets through;
+// kSlot: `allow` is the slot's own and may be null, which lets every row through (bm25m_tail_word, word by word)
+template <bool kFilt, bool kSlot = false>
 __device__ __forceinline__ void bm_zero_words(const BmArgs& a, int s, int b, int tid, const u32* allow, u32 z[4]) {
     const long long w0 = (long long)b * kBmWordsPerBlock + tid * 4;
     const uint4 w4 = *(const uint4*)(a.bits + s * a.bits_stride + w0);
     const u32 wv[4] = {w4.x, w4.y, w4.z, w4.w};
     uint4 f4 = make_uint4(~0u, ~0u, ~0u, ~0u);
-    if (kFilt) f4 = *(const uint4*)(allow + w0);
+    if (kFilt && !kSlot) f4 = *(const uint4*)(allow + w0);
+    if (kSlot) f4 = make_uint4(bm25m_tail_word(allow, w0), bm25m_tail_word(allow, w0 + 1), bm25m_tail_word(allow, w0 + 2), bm25m_tail_word(allow, w0 + 3));
     const u32 fv[4] = {f4.x, f4.y, f4.z, f4.w};
 #pragma unroll
     for (int j = 0; j < 4; ++j) z[j] = bm25f_allowed_untouched(wv[j], bm25f_valid_mask((w0 + j) * 32, a.n), fv[j]);
@@ -337,12 +367,12 @@ __device__ __forceinline__ u32 block_excl_scan(u32 v, u32* lds /* [kBmThreads / 
 }
 
 // the zero-score tail, only when fewer than k rows were touched: untouched rows per bitmap block ...
-template <bool kFilt>
+template <bool kFilt, bool kSlot = false>
 __device__ __forceinline__ void bm_tail_count(const BmArgs& a, const u32* allow) {
     const int s = blockIdx.y, tid = threadIdx.x;
     if (a.st[s].nsel >= (u32)a.k) return;
     u32 z[4];
-    bm_zero_words<kFilt>(a, s, blockIdx.x, tid, allow, z);
+    bm_zero_words<kFilt, kSlot>(a, s, blockIdx.x, tid, allow, z);
     __shared__ u32 lds[kBmThreads / 64];
     u32 total;
     block_excl_scan(__popc(z[0]) + __popc(z[1]) + __popc(z[2]) + __popc(z[3]), lds, &total);
@@ -351,6 +381,7 @@ __device__ __forceinline__ void bm_tail_count(const BmArgs& a, const u32* allow)
 
 __global__ __launch_bounds__(kBmThreads) void k_bm25_tail_count(BmArgs a) { bm_tail_count<false>(a, nullptr); }
 __global__ __launch_bounds__(kBmThreads) void k_bm25_tail_count_f(BmArgs a, const u32* allow) { bm_tail_count<true>(a, allow); }
+__global__ __launch_bounds__(kBmThreads) void k_bm25_tail_count_m(BmArgs a, const Bm25Desc* __restrict__ desc) { bm_tail_count<true, true>(a, bm_desc(a, desc).allow); }
 
 // ... their exclusive prefix over the blocks (one workgroup per slot) ...
 __global__ __launch_bounds__(kBmThreads) void k_bm25_tail_scan(BmArgs a, int nblk) {
@@ -369,7 +400,7 @@ __global__ __launch_bounds__(kBmThreads) void k_bm25_tail_scan(BmArgs a, int nbl
 }
 
 // ... and the rows themselves, in ascending order, at ranks nsel + (untouched rows before them), while < k
-template <bool kFilt>
+template <bool kFilt, bool kSlot = false>
 __device__ __forceinline__ void bm_tail_write(const BmArgs& a, const u32* allow) {
     const int s = blockIdx.y, tid = threadIdx.x;
     const long long nsel = a.st[s].nsel;
@@ -377,7 +408,7 @@ __device__ __forceinline__ void bm_tail_write(const BmArgs& a, const u32* allow)
     const long long start = nsel + a.tblk[s * a.tblk_stride + blockIdx.x];
     if (start >= a.k) return;
     u32 z[4];
-    bm_zero_words<kFilt>(a, s, blockIdx.x, tid, allow, z);
+    bm_zero_words<kFilt, kSlot>(a, s, blockIdx.x, tid, allow, z);
     __shared__ u32 lds[kBmThreads / 64];
     u32 total;
     long long pos = start + block_excl_scan(__popc(z[0]) + __popc(z[1]) + __popc(z[2]) + __popc(z[3]), lds, &total);
@@ -392,11 +423,21 @@ __device__ __forceinline__ void bm_tail_write(const BmArgs& a, const u32* allow)
 
 __global__ __launch_bounds__(kBmThreads) void k_bm25_tail_write(BmArgs a) { bm_tail_write<false>(a, nullptr); }
 __global__ __launch_bounds__(kBmThreads) void k_bm25_tail_write_f(BmArgs a, const u32* allow) { bm_tail_write<true>(a, allow); }
+__global__ __launch_bounds__(kBmThreads) void k_bm25_tail_write_m(BmArgs a, const Bm25Desc* __restrict__ desc) { bm_tail_write<true, true>(a, bm_desc(a, desc).allow); }
 
 // a filter that allows fewer than k rows: ranks from .. k - 1 of every slot are padding, written before the sort and the tail write theirs
 __global__ __launch_bounds__(kBmThreads) void k_bm25_pad_out(BmArgs a, long long from) {
     const int s = blockIdx.y;
     for (long long i = from + (long long)blockIdx.x * kBmThreads + threadIdx.x; i < a.k; i += (long long)gridDim.x * kBmThreads) {
+        a.out_ids[s * a.out_stride + i] = -1;
+        a.out_scores[s * a.out_stride + i] = -FLT_MAX;
+    }
+}
+
+// ... and where every slot has its own filter, from its own rank: the grid covers the group's longest span, a slot without padding starts at k
+__global__ __launch_bounds__(kBmThreads) void k_bm25_pad_out_m(BmArgs a, const Bm25Desc* __restrict__ desc) {
+    const int s = blockIdx.y;
+    for (long long i = bm_desc(a, desc).pad_from + (long long)blockIdx.x * kBmThreads + threadIdx.x; i < a.k; i += (long long)gridDim.x * kBmThreads) {
         a.out_ids[s * a.out_stride + i] = -1;
         a.out_scores[s * a.out_stride + i] = -FLT_MAX;
     }
@@ -676,7 +717,9 @@ __global__ __launch_bounds__(kBmThreads) void k_bm25_live_append(LiveArgs a) {
 //   the mode of a call     vf_bm25_call.h: bm25c_decode turns `nq`'s flag bits and the struct's phase into one of eight kinds or a
 //                          refusal, bm25c_plan turns (kind, k, nq, slots, words, m) into the kernels of the group loop.  vf_bm25_search
 //                          is decode, the checks every kind shares, the filter resolved into a BmFilter (bm_filter_check, then
-//                          bm_filter_bind once the slots exist), one group loop.
+//                          bm_filter_bind once the slots exist), one group loop.  A prepared search whose mode is
+//                          VF_BM25_PREPARED_PER_QUERY resolves one filter per query instead (bm_multi_check): vf_bm25_multi.h holds its
+//                          descriptors and its plan, bm_multi_launch_plan puts that plan into the group loop's terms.
 //   the checks             each written once: bm_check_allow (a caller's bitmap), bm_check_scoring (idf, avgdl, k1, b), bm_all_padding,
 //                          bm_sub_args (the SubArgs of the stage, the prepare and both scored searches).
 //   device memory          bm_free frees and nulls, bm_alloc makes a list of buffers or none of them, bm_grow serves the buffers that
@@ -752,6 +795,10 @@ struct vf_bm25 {
     // prepared filters (VF_BM25_PREPARED): each owns its device memory; none aliases d_allow
     std::vector<struct BmPrepared*> prepared;
     unsigned long long next_token = 1;
+    // a prepared filter per query (VF_BM25_PREPARED_PER_QUERY) also holds these from the first such call on
+    Bm25Desc* d_desc = nullptr;             // [desc_cap] the descriptors of the call in flight, one per query
+    long long desc_cap = 0;
+    std::vector<Bm25Desc> desc_host;        // what goes up to d_desc: it outlives the copy
     std::mutex mu;
 };
 
@@ -923,7 +970,7 @@ static int bm_destroy(vf_bm25* h) {
     bm_free_big(h);
     bm_drop_stage(h);
     bm_prepared_free_all(h);
-    bm_free(h->d_indptr, h->d_indices, h->d_data, h->d_qoff, h->d_qterms, h->d_tf, h->d_doclen, h->d_sub, h->d_sidf);
+    bm_free(h->d_indptr, h->d_indices, h->d_data, h->d_qoff, h->d_qterms, h->d_tf, h->d_doclen, h->d_sub, h->d_sidf, h->d_desc);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return VF_OK;
@@ -1408,12 +1455,41 @@ struct BmFilter {
     long long m = 0;                  // rows allowed
     const BmPrepared* pf = nullptr;   // kBm25PrepSearch: the filter its token names
     SubArgs sub{};                    // read by the scatters that score from tf (the plan's kBm25ScatterSubPos and kBm25ScatterSubCol)
+    const Bm25Desc* desc = nullptr;   // a filter per query: the call's descriptors on the device (the _m kernels read them; allow, m, pf and sub
+                                      // are then not used) and, host_desc, the same on the host for the padding's grid
+    const Bm25Desc* host_desc = nullptr;
 };
 
 // Every check of the call's filter, in the order of include/veritasfi_hip.h.  A prepared search's filter is found here, under the lock, and with it
 // its mode: c.subset is set for the plan (the decoder cannot know it).
-static int bm_filter_check(vf_bm25* h, Bm25Call& c, const BmCallArg& arg, long long T, BmFilter* f) {
+// A prepared search with a filter per query (mode VF_BM25_PREPARED_PER_QUERY): tokens[i] names query i's filter, 0 none.  Checked in query
+// order, each as the one-token search checks its own; then the descriptors are written into the handle's host table (pointers into the
+// filters' own device memory: nothing of a filter is copied).  A refusal leaves the table unread.
+static int bm_multi_check(vf_bm25* h, const vf_bm25_prepared_query* pq, int nq, int k, BmFilter* f) {
+    if (!pq->tokens) return bm_fail(VF_EINVAL, "vf_bm25_search: VF_BM25_PREPARED_PER_QUERY with a null tokens (one token per query, 0 for a query without a filter)");
+    try {
+        h->desc_host.resize((size_t)nq);
+    } catch (const std::bad_alloc&) {
+        return bm_fail(VF_ENOMEM, "host allocation failed");
+    }
+    for (int i = 0; i < nq; ++i) {
+        const unsigned long long token = pq->tokens[i];
+        if (token == 0) { h->desc_host[(size_t)i] = bm25m_desc_none(k); continue; }
+        const std::string who = "tokens[" + std::to_string(i) + "] = " + std::to_string(token);
+        const BmPrepared* pf = bm_prepared_find(h, token);
+        if (!pf) return bm_fail(VF_EINVAL, "vf_bm25_search: " + who + " names no prepared filter of this handle (unknown or released)");
+        if (pf->stale || pf->gen != h->gen) return bm_prepared_stale(h, pf, ("VF_BM25_PREPARED_SEARCH, " + who).c_str());
+        if (pf->subset && !pf->armed)
+            return bm_fail(VF_EINVAL, "vf_bm25_search: " + who + ": the prepared filter is in subset mode and was never armed (VF_BM25_PREPARED_ARM gives it its idf)");
+        h->desc_host[(size_t)i] = bm25m_desc(pf->d_allow, pf->subset ? pf->d_idf : nullptr, pf->avgdl, pf->k1, pf->b, pf->m, k);
+    }
+    f->host_desc = h->desc_host.data();
+    return VF_OK;
+}
+
+static int bm_filter_check(vf_bm25* h, Bm25Call& c, const BmCallArg& arg, long long T, int k, BmFilter* f) {
     if (c.kind == kBm25Plain) return VF_OK;
+    if (c.kind == kBm25PrepSearch && arg.pq->mode == VF_BM25_PREPARED_PER_QUERY) return bm_multi_check(h, arg.pq, c.nq, k, f);
     if (c.kind == kBm25PrepSearch) {   // the filter's own checks were made when it was prepared: only that it is still this index's is looked at here
         const unsigned long long token = arg.pq->token;
         const BmPrepared* pf = bm_prepared_find(h, token);
@@ -1444,6 +1520,13 @@ static int bm_filter_bind(vf_bm25* h, const Bm25Call& c, const BmCallArg& arg, l
     if (c.kind == kBm25Plain) return VF_OK;
     int rc = bm_ensure_filter(h);   // d_allow, and the tail's scratch over every bitmap block
     if (rc != VF_OK) return rc;
+    if (f->host_desc) {   // a filter per query: c.nq descriptors go up beside the query, nothing of any filter (d_allow is not touched)
+        rc = bm_grow("vf_bm25: query descriptors", h->d_desc, h->desc_cap, c.nq, (size_t)c.nq * sizeof(Bm25Desc));
+        if (rc != VF_OK) return rc;
+        VFS_HIP(hipMemcpyAsync(h->d_desc, f->host_desc, (size_t)c.nq * sizeof(Bm25Desc), hipMemcpyHostToDevice, h->stream));
+        f->desc = h->d_desc;
+        return VF_OK;
+    }
     if (f->pf) {   // nothing goes up: the bitmap is the filter's own (d_allow and what a stage left in it are not touched)
         f->allow = f->pf->d_allow;
         if (c.subset) f->sub = bm_sub_args(h, f->allow, nullptr, f->pf->d_idf, f->pf->avgdl, f->pf->k1, f->pf->b);
@@ -1465,6 +1548,16 @@ static int bm_filter_bind(vf_bm25* h, const Bm25Call& c, const BmCallArg& arg, l
     return VF_OK;
 }
 
+// the plan of a call with a filter per query (vf_bm25_multi.h) in the group loop's terms: the tail's buffers are the filtered call's, the
+// scatter and the padding are chosen per slot on the device (the _m kernels), so `scatter`, `pad_from` and `pad_out` are not read
+static Bm25LaunchPlan bm_multi_launch_plan(const Bm25MultiPlan& mp, long long k) {
+    Bm25LaunchPlan p{};
+    p.no_launch = mp.no_launch; p.small = mp.small; p.S = mp.S;
+    p.scatter = kBm25ScatterFiltered; p.tail_f = true; p.tail_blocks = mp.tail_blocks; p.tblk_stride = mp.tblk_stride;
+    p.pad_from = k; p.pad_out = false;
+    return p;
+}
+
 // the scoring and the radix select of the group's queries (slots 0 .. g-1); sel / tblk / out set by the caller
 static int bm_score_select(vf_bm25* h, BmArgs& a, const int64_t* q_off, int g, const Bm25LaunchPlan& p, const BmFilter& f) {
     hipStream_t st = h->stream;
@@ -1481,7 +1574,8 @@ static int bm_score_select(vf_bm25* h, BmArgs& a, const int64_t* q_off, int g, c
         }
         if (post == 0) continue;
         const dim3 grid(bm_grid(post, kBmThreads, 4096), g), block(kBmThreads);
-        switch (p.scatter) {   // the filtered forms skip the rows outside the set; the two last score each posting from its tf
+        if (f.desc) hipLaunchKernelGGL(k_bm25_accum_m, grid, block, 0, st, a, (int)t, f.desc, (const int*)h->d_tf, (const int*)h->d_doclen);   // each slot its own form
+        else switch (p.scatter) {   // the filtered forms skip the rows outside the set; the two last score each posting from its tf
             case kBm25ScatterPlain: hipLaunchKernelGGL(k_bm25_accum, grid, block, 0, st, a, (int)t); break;
             case kBm25ScatterFiltered: hipLaunchKernelGGL(k_bm25_accum_f, grid, block, 0, st, a, (int)t, f.allow); break;
             case kBm25ScatterSubPos: hipLaunchKernelGGL(k_bm25_accum_s, grid, block, 0, st, a, (int)t, f.sub); break;       // idf per q_terms position
@@ -1522,10 +1616,12 @@ static int bm_sort_deep(vf_bm25* h, BmArgs& a) {
 static int bm_tail_and_reset(vf_bm25* h, BmArgs& a, const int64_t* q_off, int g, const Bm25LaunchPlan& p, const BmFilter& f) {
     hipStream_t st = h->stream;
     const dim3 grid(p.tail_blocks, g), block(kBmThreads);
-    if (p.tail_f) hipLaunchKernelGGL(k_bm25_tail_count_f, grid, block, 0, st, a, f.allow);
+    if (f.desc) hipLaunchKernelGGL(k_bm25_tail_count_m, grid, block, 0, st, a, f.desc);
+    else if (p.tail_f) hipLaunchKernelGGL(k_bm25_tail_count_f, grid, block, 0, st, a, f.allow);
     else hipLaunchKernelGGL(k_bm25_tail_count, grid, block, 0, st, a);
     hipLaunchKernelGGL(k_bm25_tail_scan, dim3(1, g), block, 0, st, a, p.tail_blocks);
-    if (p.tail_f) hipLaunchKernelGGL(k_bm25_tail_write_f, grid, block, 0, st, a, f.allow);
+    if (f.desc) hipLaunchKernelGGL(k_bm25_tail_write_m, grid, block, 0, st, a, f.desc);
+    else if (p.tail_f) hipLaunchKernelGGL(k_bm25_tail_write_f, grid, block, 0, st, a, f.allow);
     else hipLaunchKernelGGL(k_bm25_tail_write, grid, block, 0, st, a);
     long long post = 0;
     for (int s = 0; s < g; ++s)
@@ -1567,9 +1663,10 @@ extern "C" int vf_bm25_search(vf_bm25* h, const int64_t* q_offsets, const int32_
         if (q_terms[t] < 0 || q_terms[t] >= h->V) return bm_fail(VF_EINVAL, "vf_bm25_search: a token column is out of range");
     // 3. the filter, and with its m the plan
     BmFilter f;
-    int rc = bm_filter_check(h, c, arg, T, &f);
+    int rc = bm_filter_check(h, c, arg, T, k, &f);
     if (rc != VF_OK) return rc;
-    const Bm25LaunchPlan p = bm25c_plan(c, k, nq, h->slot_cap, h->words, f.m);
+    Bm25LaunchPlan p = bm25c_plan(c, k, nq, h->slot_cap, h->words, f.m);
+    if (f.host_desc) p = bm_multi_launch_plan(bm25m_plan(f.host_desc, k, nq, h->slot_cap, h->words), k);
     if (p.no_launch) {   // no row is allowed
         bm_all_padding(out_ids, out_scores, nq, k);
         if (stage) {
@@ -1611,6 +1708,8 @@ extern "C" int vf_bm25_search(vf_bm25* h, const int64_t* q_offsets, const int32_
         rc = bm_score_select(h, a, q_offsets, g, p, f);
         if (rc != VF_OK) return rc;
         if (p.pad_out) hipLaunchKernelGGL(k_bm25_pad_out, dim3(pad_grid, g), dim3(kBmThreads), 0, st, a, p.pad_from);
+        const long long span = f.desc ? bm25m_group_pad_span(f.host_desc, q0, g, k) : 0;   // a filter per query: the group's longest padding
+        if (span > 0) hipLaunchKernelGGL(k_bm25_pad_out_m, dim3(bm_grid(span, kBmThreads, 64), g), dim3(kBmThreads), 0, st, a, f.desc);
         if (p.small) hipLaunchKernelGGL(k_bm25_sort_small, dim3(1, g), dim3(512), (size_t)Pk * 8, st, a, Pk);
         else rc = bm_sort_deep(h, a);
         if (rc == VF_OK) rc = bm_tail_and_reset(h, a, q_offsets, g, p, f);
