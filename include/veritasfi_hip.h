@@ -47,7 +47,7 @@ typedef struct vf_index vf_index;
 
 /* counters of the last search on a handle (for tests / benches; not part of the reference surface) */
 typedef struct vf_search_stats {
-    int64_t path;            /* 0 = small-N exact dense, 1 = fused MFMA scan, 2 = chunked exact, 3 = subset scan (VF_SEARCH_SUBSET) */
+    int64_t path;            /* 0 = small-N exact dense, 1 = fused MFMA scan, 2 = chunked exact, 3 = subset scan (VF_SEARCH_SUBSET), 4 = a list per query (VF_SEARCH_SUBSETS) */
     int64_t n_queries;
     int64_t candidates;      /* total candidates appended by the fused scan (all queries) */
     int64_t max_candidates;  /* largest per-query candidate count */
@@ -60,8 +60,9 @@ typedef struct vf_search_stats {
     int64_t scans_overlap;   /* 1 = main scans of consecutive slots were not ordered against each other */
     int64_t scan_kernel;     /* main-scan kernel of the call: 1 k_scan (register loads), 2 k_scan2 (whole-line LDS-DMA), 3 k_scan_wide, 4 k_scan_wide8 (fp8 matrix instruction), 5 k_scan2r (k_scan2, half the query image in registers), 6 k_scan_ksplit (rows of 2560 to 4096 padded elements: option "wide_rows"), 7 k_scan_ksplit8 (the same for e4m3 rows) or its int8 form k_scan_ksplit8i (int8 rows report 7 as the int8 forms of k_scan and k_scan_wide report 1 and 3) */
     int64_t scan_image;      /* 1 = the main scan read the int8 row image (option "scan_image"), 0 = the rows as stored */
-    int64_t subset_rows;     /* path 3 only: rows the list of a subset search named (VF_SEARCH_SUBSET) */
-    int64_t reserved[2];
+    int64_t subset_rows;     /* path 3: rows the list of a subset search named (VF_SEARCH_SUBSET); path 4: the sum over the queries of their own list's length */
+    int64_t subset_tiles;    /* path 4 only: query tiles k_scan_subset_m scored: per pass, the sum over its lists of ceil(queries of the list / 4) */
+    int64_t reserved[1];
 } vf_search_stats;
 
 int vf_version(void);
@@ -230,6 +231,34 @@ typedef struct vf_subset_query {
     const int64_t* ids;     /* [n_ids] global ids, strictly ascending */
     int64_t n_ids;
 } vf_subset_query;
+
+/* ---- a list PER QUERY of a batch -----------------------------------------------------------------------------------------------
+ * A server that batches the requests of many tenants has one list per query, not one per call.  With VF_SEARCH_SUBSETS row i of the
+ * result is, ids and score bits, what the VF_SEARCH_SUBSET call returns for query i alone under lists[list_of[i]]: each query pads with
+ * (-1, -FLT_MAX) from its own min(n_ids, k), ties go to the lower id, a zero score is +0.0.  Queries that name the same entry of
+ * `lists` share one scan of its rows (four queries per tile); the number of launches does not depend on the number of lists.
+ * This mode serves lists of at most 16 384 ids (the lists the one-list form ranks without a merge, at any k); a longer referenced list is
+ * VF_EUNSUPPORTED, naming lists[j] and its length -- send its queries through VF_SEARCH_SUBSET.  n_ids[j] == 0 gives padding, n_ids[j] == n
+ * is scanned like any list.  list_of[i] outside [0, n_lists) is VF_EINVAL naming the query; a referenced list that is out of range, not
+ * ascending or repeats an id is VF_EINVAL naming lists[j], the position and the value (host form: before any HIP call; device form: by
+ * one kernel over all referenced lists whose word is read at the call's one synchronisation, nothing having been written to the
+ * outputs).  Lists no query names are not read.  A group handle is VF_EUNSUPPORTED in both forms, a damaged handle VF_EHIP, both flags
+ * together VF_EINVAL.  Workspace (at most 16 MB of scores per pass of 256 queries) is one lease of the small entry points' pool, under
+ * the handle's mutex: a search pending between _begin and _end is not disturbed, and a refused call changes nothing.
+ * vf_search_stats: path 4, subset_rows = the sum over the queries of their list's length, subset_tiles.
+ *   vf_subsets_query sq = {queries, lists, n_ids, n_lists, list_of};
+ *   vf_index_search(idx, (const float*)&sq, nq | VF_SEARCH_SUBSETS, k, out_ids, out_scores);                       host buffers
+ *   vf_index_search_device(idx, (const float*)&sq, nq | VF_SEARCH_SUBSETS, k, d_out_ids, d_out_scores, stream);    device buffers
+ * `sq`, `lists`, `n_ids` and `list_of` are always host arrays; `queries` and every lists[j] are host pointers in the host form and
+ * device pointers on the index's device in the device form. */
+#define VF_SEARCH_SUBSETS 0x20000000  /* or'ed into `nq` of vf_index_search / vf_index_search_device: `queries` is a vf_subsets_query */
+typedef struct vf_subsets_query {
+    const float* queries;            /* [nq, d] fp32, not normalised */
+    const int64_t* const* lists;     /* [n_lists] pointers to global ids, each list strictly ascending */
+    const int64_t* n_ids;            /* [n_lists] */
+    int32_t n_lists;
+    const int32_t* list_of;          /* [nq]: each in [0, n_lists) */
+} vf_subsets_query;
 
 int vf_index_info(vf_index* idx, int64_t* n, int32_t* d, int32_t* dtype, int32_t* device_id);
 int vf_index_stats(vf_index* idx, vf_search_stats* out);

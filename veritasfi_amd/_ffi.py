@@ -97,6 +97,39 @@ def search_subset_device(L, handle, d_queries_ptr, nq, k, d_ids_ptr, n_ids, d_ou
     return L.vf_index_search_device(handle, ctypes.addressof(sq), int(nq) | VF_SEARCH_SUBSET, k, d_out_ids_ptr, d_out_scores_ptr, stream)
 
 
+VF_SEARCH_SUBSETS = 0x20000000  # or'ed into nq of vf_index_search / vf_index_search_device: `queries` is then a SubsetsQuery
+
+
+class SubsetsQuery(ctypes.Structure):
+    """vf_subsets_query of include/veritasfi_hip.h: a list PER QUERY (host memory; `lists`, `n_ids` and `list_of` are host arrays, the
+    pointers `queries` and lists[j] are host or device pointers by the call's form)."""
+    _fields_ = [("queries", ctypes.c_void_p), ("lists", ctypes.POINTER(ctypes.c_void_p)), ("n_ids", ctypes.POINTER(c_i64)),
+                ("n_lists", c_i32), ("list_of", ctypes.POINTER(c_i32))]
+
+
+def _subsets_query(queries_ptr, list_ptrs, n_ids, list_of):
+    """(SubsetsQuery, the arrays it points into): the caller keeps the second alive for the call."""
+    n = len(list_ptrs)
+    lists = (ctypes.c_void_p * max(n, 1))(*[int(p) if p else None for p in list_ptrs])
+    lens = (c_i64 * max(n, 1))(*[int(v) for v in n_ids])
+    of = (c_i32 * max(len(list_of), 1))(*[int(v) for v in list_of])
+    sq = SubsetsQuery(queries_ptr, ctypes.cast(lists, ctypes.POINTER(ctypes.c_void_p)), ctypes.cast(lens, ctypes.POINTER(c_i64)), n,
+                      ctypes.cast(of, ctypes.POINTER(c_i32)))
+    return sq, (lists, lens, of)
+
+
+def search_subsets(L, handle, queries_ptr, nq, k, list_ptrs, n_ids, list_of, out_ids_ptr, out_scores_ptr) -> int:
+    """vf_index_search with a list per query (host pointers): query i is searched under list_ptrs[list_of[i]]; returns the code."""
+    sq, keep = _subsets_query(queries_ptr, list_ptrs, n_ids, list_of)
+    return L.vf_index_search(handle, ctypes.addressof(sq), int(nq) | VF_SEARCH_SUBSETS, k, out_ids_ptr, out_scores_ptr)
+
+
+def search_subsets_device(L, handle, d_queries_ptr, nq, k, d_list_ptrs, n_ids, list_of, d_out_ids_ptr, d_out_scores_ptr, stream) -> int:
+    """vf_index_search_device with a list per query (device pointers); returns the code."""
+    sq, keep = _subsets_query(d_queries_ptr, d_list_ptrs, n_ids, list_of)
+    return L.vf_index_search_device(handle, ctypes.addressof(sq), int(nq) | VF_SEARCH_SUBSETS, k, d_out_ids_ptr, d_out_scores_ptr, stream)
+
+
 class EncoderConfig(ctypes.Structure):
     _fields_ = [
         ("vocab", c_i32), ("hidden", c_i32), ("layers", c_i32), ("heads", c_i32), ("ffn", c_i32), ("max_pos", c_i32),
@@ -131,7 +164,8 @@ class SearchStats(ctypes.Structure):
     _fields_ = [
         ("path", c_i64), ("n_queries", c_i64), ("candidates", c_i64), ("max_candidates", c_i64),
         ("uncertified", c_i64), ("overflowed", c_i64), ("exact_reruns", c_i64), ("wide_launches", c_i64), ("wide_queries", c_i64),
-        ("aux_cus", c_i64), ("scans_overlap", c_i64), ("scan_kernel", c_i64), ("scan_image", c_i64), ("subset_rows", c_i64), ("reserved", c_i64 * 2),
+        ("aux_cus", c_i64), ("scans_overlap", c_i64), ("scan_kernel", c_i64), ("scan_image", c_i64), ("subset_rows", c_i64), ("subset_tiles", c_i64),
+        ("reserved", c_i64 * 1),
     ]
 
     def as_dict(self):

@@ -24,7 +24,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, os.environ.get("VF_BUILD_LIB", "libveritasfi_hip.so"))   # VF_BUILD_LIB: name of an A/B variant
 SOURCES = ["vf_kernels.hip", "vf_api.hip", "vf_transformer.hip", "vf_sparse.hip"]
-HEADERS = ["vf_internal.h", os.path.join("..", "..", "include", "veritasfi_hip.h"), "vf_ksplit_geom.h", "vf_scan_lds.h", "vf_route.h", "vf_gemm_route.h", "vf_compact.h", "vf_bm25_live.h", "vf_bm25_filter.h", "vf_bm25_substats.h", "vf_bm25_prepared.h", "vf_bm25_call.h", "vf_bm25_multi.h"]
+HEADERS = ["vf_internal.h", os.path.join("..", "..", "include", "veritasfi_hip.h"), "vf_ksplit_geom.h", "vf_scan_lds.h", "vf_route.h", "vf_gemm_route.h", "vf_compact.h", "vf_bm25_live.h", "vf_bm25_filter.h", "vf_bm25_substats.h", "vf_bm25_prepared.h", "vf_bm25_call.h", "vf_bm25_multi.h", "vf_subset.h", "vf_subset_multi.h"]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
 # VF_BUILD_FLAGS="-DVF_EXPERIMENTS" compiles the measured-and-rejected experiment kernels back in

@@ -1775,9 +1775,12 @@ static int search_device_locked(vf_index* ix, const float* d_queries, int nq, in
 // subset search, below
 static int subset_entry_host(vf_index* ix, const vf_subset_query* sq, int32_t nq, int32_t k, int64_t* out_ids, float* out_scores);
 static int subset_entry_device(vf_index* ix, const vf_subset_query* sq, int32_t nq, int32_t k, int64_t* d_out_ids, float* d_out_scores, void* stream);
+// ... and the form with a list per query (VF_SEARCH_SUBSETS, `queries` is a vf_subsets_query); both flags together are refused there
+static int subsets_entry(vf_index* ix, const vf_subsets_query* sq, int32_t nq_flags, int32_t k, int64_t* out_ids, float* out_scores, bool device, void* stream);
 
 extern "C" int vf_index_search_device(vf_index* ix, const float* d_queries, int32_t nq, int32_t k, int64_t* d_ids,
                                       float* d_scores, void* stream) {
+    if (nq >= 0 && (nq & VF_SEARCH_SUBSETS)) return subsets_entry(ix, (const vf_subsets_query*)d_queries, nq, k, d_ids, d_scores, true, stream);
     if (nq >= 0 && (nq & VF_SEARCH_SUBSET)) return subset_entry_device(ix, (const vf_subset_query*)d_queries, nq & ~VF_SEARCH_SUBSET, k, d_ids, d_scores, stream);
     DeviceGuard restore_callers_device;
     VF_TRY(check_search_args(ix, d_queries, nq, k, d_ids, d_scores));
@@ -1805,6 +1808,7 @@ static int search_host_locked(vf_index* ix, const float* queries, int nq, int k,
 
 extern "C" int vf_index_search(vf_index* ix, const float* queries, int32_t nq, int32_t k, int64_t* out_ids,
                                float* out_scores) {
+    if (nq >= 0 && (nq & VF_SEARCH_SUBSETS)) return subsets_entry(ix, (const vf_subsets_query*)queries, nq, k, out_ids, out_scores, false, nullptr);
     if (nq >= 0 && (nq & VF_SEARCH_SUBSET)) return subset_entry_host(ix, (const vf_subset_query*)queries, nq & ~VF_SEARCH_SUBSET, k, out_ids, out_scores);
     DeviceGuard restore_callers_device;
     VF_TRY(check_search_args(ix, queries, nq, k, out_ids, out_scores));
@@ -2392,6 +2396,168 @@ static int subset_entry_device(vf_index* ix, const vf_subset_query* sq, int32_t 
     if (scan) { subset_stats(ix, nq, m); return VF_OK; }
     if (nq == 0 || k == 0) return VF_OK;
     return search_device_locked(ix, d_queries, nq, k, d_out_ids, d_out_scores, st);   // every row is listed: the ordinary search
+}
+
+// ------------------------------------------------------------------------------------------------
+// A list per query of a batch (round 23): vf_index_search / vf_index_search_device with VF_SEARCH_SUBSETS in nq.  Row i is what the
+// one-list call above returns for query i alone under its own list.  The plan -- passes, the permutation, tiles, size classes, the
+// sentinel rule, the limits -- is vf_subset_multi.h; here are the argument checks, the tables' upload and subsets_enqueue_pass.
+// The workspace is ONE lease of the small entry points' pool, as above.
+// ------------------------------------------------------------------------------------------------
+struct SubsetsBuffers {     // what a pass works in (all on the device)
+    float* qn; float* scores; long long* rank_ids; float* rank_sc;
+    const SubmTile* tiles; const SubmQuery* qd;   // of the whole call: a pass uses [tile0, + n_tiles) and [q0, + nb)
+    const u64* flag;                               // the device form's check word, or null
+};
+
+// One pass, enqueued on `st` (nothing is waited for): the query prep, per size class in use one scan and one ranking launch, the map.
+static int subsets_enqueue_pass(vf_index* ix, const SubmConfig& c, const SubmPass& p, int tile0, const float* d_q, int k, const SubsetsBuffers& b,
+                                int64_t* d_out_ids, float* d_out_sc, hipStream_t st) {
+    const int d = ix->d;
+    VF_HIP(launch_prep_queries(d_q + (size_t)p.q0 * d, p.nb, d, d, p.nb, b.qn, nullptr, st));
+    for (int cls = 0; cls < c.n_classes; ++cls) {
+        if (p.class_queries[cls] == 0) continue;
+        const int n_rank = (int)c.class_rows[cls];
+        SubsetMArgs a{};
+        a.rows = ix->rows_orig; a.norm = ix->norm; a.n = ix->n; a.id_base = ix->id_offset; a.qn = b.qn; a.d = d; a.scores = b.scores;
+        a.tiles = b.tiles + tile0 + p.class_tile0[cls]; a.n_rank = n_rank;
+        VF_HIP(launch_scan_subset_m(a, p.class_tiles[cls], ix->dtype, st));
+        const size_t at = (size_t)p.class_first[cls] * k;
+        VF_HIP(launch_sort_rows(b.scores + p.class_base[cls], n_rank, p.class_queries[cls], n_rank, k, 0, b.rank_ids + at, b.rank_sc + at, k, st));
+    }
+    VF_HIP(launch_subset_ids_m(b.rank_ids, b.rank_sc, p.nb, k, b.qd + p.q0, b.flag, (long long*)d_out_ids, d_out_sc, st));
+    return VF_OK;
+}
+
+static int subsets_locked(vf_index* ix, const vf_subsets_query* sq, int nq, int k, int64_t* out_ids, float* out_sc, bool device, hipStream_t st,
+                          const char* who) {
+    if (ix->damaged) return fail(VF_EHIP, std::string(who) + ": " + kDamagedMsg);
+    if (!ix->shards.empty()) return fail(VF_EUNSUPPORTED, std::string(who) + ": a group handle takes one list per call (VF_SEARCH_SUBSET, host buffers), not a list per query");
+    const SubmConfig c = subm_config_default();
+    const long long* m = (const long long*)sq->n_ids;
+    const SubmCall call = subm_call(nq, sq->list_of, sq->n_lists, m, c);
+    if (call.verdict == kSubmBadListOf)
+        return fail(VF_EINVAL, std::string(who) + ": list_of[" + std::to_string(call.at) + "] = " + std::to_string(call.value) + " is outside [0, " + std::to_string(sq->n_lists) + "): query " + std::to_string(call.at) + " names no list");
+    if (call.verdict == kSubmNegativeLength)
+        return fail(VF_EINVAL, std::string(who) + ": lists[" + std::to_string(call.at) + "]: negative n_ids");
+    if (call.verdict == kSubmTooLong)
+        return fail(VF_EUNSUPPORTED, std::string(who) + ": lists[" + std::to_string(call.at) + "] holds " + std::to_string(call.value) + " ids; a list per query serves at most " +
+                                         std::to_string(c.rank_rows) + " (send its queries through VF_SEARCH_SUBSET)");
+    if (call.verdict != kSubmOk) return fail(VF_EINVAL, std::string(who) + ": bad sizes");
+    // the referenced lists, ascending by their number
+    std::vector<char> used((size_t)sq->n_lists, 0);
+    for (int q = 0; q < nq; ++q) used[sq->list_of[q]] = 1;
+    std::vector<int> ref;
+    long long longest = 0, total = 0;
+    for (int j = 0; j < sq->n_lists; ++j) {
+        if (!used[j]) continue;
+        if (m[j] > 0 && !sq->lists[j]) return fail(VF_EINVAL, std::string(who) + ": lists[" + std::to_string(j) + "]: null id list");
+        ref.push_back(j);
+        longest = std::max(longest, m[j]); total += m[j];
+    }
+    const int64_t lo = ix->id_offset, hi = ix->id_offset + ix->n;
+    if (!device)   // before any HIP call
+        for (int j : ref) {
+            const long long bad = subset_first_bad((const long long*)sq->lists[j], m[j], lo, hi);
+            if (bad >= 0) return fail(VF_EINVAL, subset_bad_message((std::string(who) + ": lists[" + std::to_string(j) + "]").c_str(), bad, sq->lists[j][bad], bad > 0,
+                                                                    bad > 0 ? sq->lists[j][bad - 1] : 0, lo, hi));
+        }
+    if (nq == 0 || (k == 0 && !device)) return VF_OK;
+    // the workspace: the largest pass's scores, the ranked positions of a pass, the three tables; the host form's staging
+    long long score_floats = 0;
+    for (int q0 = 0; q0 < nq; q0 += c.pass_queries) {
+        long long f = 0;
+        for (int q = q0; q < std::min(nq, q0 + c.pass_queries); ++q) f += c.class_rows[subm_class_of(c, m[sq->list_of[q]])];
+        score_floats = std::max(score_floats, f);
+    }
+    if (score_floats * 4 > subm_score_bytes_bound(c)) return fail(VF_EINVAL, std::string(who) + ": the plan's score workspace exceeds its bound");
+    const int nbmax = std::min(nq, c.pass_queries);
+    const size_t qe = (size_t)nq * ix->d, oe = (size_t)nq * k, part = (size_t)nbmax * k;
+    const size_t tiles_b = Lease::padded((size_t)nq * sizeof(SubmTile)), qd_b = Lease::padded((size_t)nq * sizeof(SubmQuery)), lists_b = Lease::padded(ref.size() * sizeof(SubmList));
+    size_t bytes = Lease::padded(8) + Lease::padded((size_t)nbmax * ix->d * 4) + Lease::padded((size_t)score_floats * 4) + Lease::padded(part * 8) + Lease::padded(part * 4) +
+                   tiles_b + qd_b + lists_b;
+    if (!device) bytes += Lease::padded(qe * 4) + Lease::padded((size_t)total * 8) + Lease::padded(oe * 8) + Lease::padded(oe * 4);
+    VF_HIP(hipSetDevice(ix->device));
+    Lease ws;
+    VF_TRY(ws.acquire(ix->device, bytes));
+    u64* d_flag = ws.take<u64>(1);
+    SubsetsBuffers b{};
+    b.qn = ws.take<float>((size_t)nbmax * ix->d); b.scores = ws.take<float>((size_t)score_floats);
+    b.rank_ids = ws.take<long long>(part); b.rank_sc = ws.take<float>(part);
+    char* d_tables = ws.take<char>(tiles_b + qd_b + lists_b);
+    b.tiles = (const SubmTile*)d_tables; b.qd = (const SubmQuery*)(d_tables + tiles_b); b.flag = device ? d_flag : nullptr;
+    const SubmList* d_lists = (const SubmList*)(d_tables + tiles_b + qd_b);
+    const float* d_q = sq->queries;
+    int64_t* d_out_ids = out_ids; float* d_out_sc = out_sc;
+    std::vector<const long long*> list_ptr((size_t)sq->n_lists, nullptr);
+    if (device) {
+        for (int j : ref) list_ptr[j] = (const long long*)sq->lists[j];
+    } else {   // the queries and, in ONE copy, every referenced list go up
+        float* dq = ws.take<float>(qe); long long* dl = ws.take<long long>((size_t)total);
+        d_out_ids = ws.take<int64_t>(oe); d_out_sc = ws.take<float>(oe);
+        std::vector<long long> all((size_t)total);
+        size_t at = 0;
+        for (int j : ref) {
+            if (m[j] > 0) memcpy(all.data() + at, sq->lists[j], (size_t)m[j] * 8);
+            list_ptr[j] = dl + at; at += (size_t)m[j];
+        }
+        VF_HIP(hipMemcpy(dq, sq->queries, qe * 4, hipMemcpyHostToDevice));
+        if (total > 0) VF_HIP(hipMemcpy(dl, all.data(), (size_t)total * 8, hipMemcpyHostToDevice));
+        d_q = dq;
+    }
+    // the tables of every pass, built on the host and uploaded in one copy
+    std::vector<char> tables(tiles_b + qd_b + lists_b, 0);
+    SubmTile* h_tiles = (SubmTile*)tables.data(); SubmQuery* h_qd = (SubmQuery*)(tables.data() + tiles_b); SubmList* h_lists = (SubmList*)(tables.data() + tiles_b + qd_b);
+    std::vector<SubmPass> passes;
+    std::vector<int> tile0s, perm((size_t)c.pass_queries);
+    int n_tiles = 0;
+    for (int ps = 0; ps < call.passes && k > 0; ++ps) {
+        passes.push_back(subm_build_pass(ps, nq, sq->list_of, m, list_ptr.data(), c, perm.data(), h_tiles + n_tiles, h_qd + (size_t)ps * c.pass_queries));
+        tile0s.push_back(n_tiles);
+        n_tiles += passes.back().n_tiles;
+    }
+    for (size_t r = 0; r < ref.size(); ++r) h_lists[r] = SubmList{list_ptr[ref[r]], m[ref[r]], ref[r]};
+    VF_HIP(hipMemcpyAsync(d_tables, tables.data(), tables.size(), hipMemcpyHostToDevice, st));   // (`tables` outlives the call's one wait)
+    if (device) {
+        VF_HIP(hipMemsetAsync(d_flag, 0xFF, 8, st));
+        VF_HIP(launch_subset_check_m(d_lists, (int)ref.size(), longest, lo, hi, d_flag, st));
+    }
+    for (size_t ps = 0; ps < passes.size(); ++ps) VF_TRY(subsets_enqueue_pass(ix, c, passes[ps], tile0s[ps], d_q, k, b, d_out_ids, d_out_sc, st));
+    if (device) {
+        u64 first_bad = 0;
+        VF_HIP(hipMemcpyAsync(&first_bad, d_flag, 8, hipMemcpyDeviceToHost, st));
+        VF_HIP(hipStreamSynchronize(st));   // the one wait of the call: the results are final and the check word is here
+        if (first_bad != ~0ull) {
+            const long long j = subm_check_list(first_bad), i = subm_check_pos(first_bad);
+            int64_t v[2] = {0, 0};
+            VF_HIP(hipMemcpy(v, sq->lists[j] + (i > 0 ? i - 1 : 0), (i > 0 ? 2 : 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+            return fail(VF_EINVAL, subset_bad_message((std::string(who) + ": lists[" + std::to_string(j) + "]").c_str(), i, i > 0 ? v[1] : v[0], i > 0, v[0], lo, hi));
+        }
+        if (k == 0) return VF_OK;
+    } else {
+        VF_HIP(hipStreamSynchronize(st));
+        VF_HIP(hipMemcpy(out_ids, d_out_ids, oe * 8, hipMemcpyDeviceToHost));
+        VF_HIP(hipMemcpy(out_sc, d_out_sc, oe * 4, hipMemcpyDeviceToHost));
+    }
+    vf_search_stats stt{};
+    stt.path = 4; stt.n_queries = nq; stt.subset_rows = call.rows; stt.subset_tiles = n_tiles;
+    ix->stats = stt;
+    return VF_OK;
+}
+
+// the argument checks that need no handle come first, in the order of the one-list form
+static int subsets_entry(vf_index* ix, const vf_subsets_query* sq, int32_t nq_flags, int32_t k, int64_t* out_ids, float* out_scores, bool device, void* stream) {
+    const char* who = device ? "vf_index_search_device (VF_SEARCH_SUBSETS)" : "vf_index_search (VF_SEARCH_SUBSETS)";
+    if (nq_flags & VF_SEARCH_SUBSET) return fail(VF_EINVAL, std::string(who) + ": VF_SEARCH_SUBSET and VF_SEARCH_SUBSETS together (one list per call, or one per query)");
+    const int nq = nq_flags & ~VF_SEARCH_SUBSETS;
+    if (!sq) return fail(VF_EINVAL, std::string(who) + ": null vf_subsets_query");
+    if (!ix) return fail(VF_EINVAL, std::string(who) + ": null handle");
+    if (k < 0 || sq->n_lists < 0) return fail(VF_EINVAL, std::string(who) + ": negative k / n_lists");
+    if (nq > 0 && (!sq->list_of || !sq->lists || !sq->n_ids)) return fail(VF_EINVAL, std::string(who) + ": null list table (lists / n_ids / list_of)");
+    if (nq > 0 && k > 0 && (!sq->queries || !out_ids || !out_scores)) return fail(VF_EINVAL, std::string(who) + ": null buffer");
+    DeviceGuard restore_callers_device;
+    std::lock_guard<std::mutex> g(ix->mu);
+    return subsets_locked(ix, sq, nq, k, out_ids, out_scores, device, (hipStream_t)stream, who);
 }
 
 extern "C" int vf_merge_topk_device(const int64_t* d_ids_parts, const float* d_score_parts, int32_t nparts, int32_t nq,

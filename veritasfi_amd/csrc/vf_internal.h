@@ -12,6 +12,7 @@
 #include "vf_ksplit_geom.h"   // + vf_scan_lds.h: the design constants, RowForm and every scan kernel's LDS budget
 #include "vf_compact.h"       // the plan of a removal's row compaction
 #include "vf_subset.h"        // the plan of a search over a chosen subset of rows
+#include "vf_subset_multi.h"  // ... and of a batch whose queries each bring their own list
 
 namespace vf {
 
@@ -198,6 +199,21 @@ hipError_t launch_subset_check(const long long* ids, long long m, long long lo, 
 // ranked positions -> ids through the list (-1 stays), scores copied; nothing is written when *first_bad != ~0 (first_bad may be null)
 hipError_t launch_subset_ids(const long long* pos, const float* sc, long long total, const long long* ids, const u64* first_bad,
                              long long* out_ids, float* out_scores, hipStream_t s);
+// k_scan_subset_m: k_scan_subset's body behind a tile table (VF_SEARCH_SUBSETS; the plan: vf_subset_multi.h).  One launch scores every
+// tile of one size class: `tiles` points at the class's first descriptor, n_rank is the class's row count.
+struct SubsetMArgs {
+    const void* rows; const float* norm; long long n; long long id_base;   // the index, as SubsetArgs names it
+    const float* qn; int d;                                                // canonical queries of the pass, caller order [nb][d]
+    float* scores;                                                         // the pass's scores: subm_score_index
+    const SubmTile* tiles; int n_rank;
+};
+hipError_t launch_scan_subset_m(const SubsetMArgs& a, int n_tiles, int dt /* VF_DTYPE_* */, hipStream_t s);
+// every referenced list checked in one launch: *first_bad (preset to ~0) = the lowest subm_check_key(list, position) refused
+hipError_t launch_subset_check_m(const SubmList* lists, int n_lists, long long longest, long long lo, long long hi, u64* first_bad, hipStream_t s);
+// ranked positions [nb][k] in permuted order -> the caller's rows through each query's own list; sentinels (pos >= m) and padding become
+// (-1, -FLT_MAX); nothing is written when *first_bad != ~0 (first_bad may be null)
+hipError_t launch_subset_ids_m(const long long* pos, const float* sc, int nb, int k, const SubmQuery* qd, const u64* first_bad,
+                               long long* out_ids, float* out_scores, hipStream_t s);
 hipError_t launch_sort_rows(const float* scores, long long score_stride, int nq, int n, int k,
                             long long id_base, long long* out_ids, float* out_scores, int out_stride,
                             hipStream_t s);

@@ -4342,122 +4342,188 @@ tail:
 // last one, a block index to the last whole block, an id to the index's rows (a list the device form has not yet seen refused must
 // not read outside the rows); the contribution is masked instead.
 // ------------------------------------------------------------------------------------------------
+// The body both k_scan_subset and k_scan_subset_m (vf_subset_multi.h) run, in two halves.  subset_lane_rows: the kSubsetR rows of this
+// lane's pair -- position, clamped row, row address, canonical inverse norm -- from the `count` ids at `ids`.  subset_scan_tile: one
+// tile of kSubsetQ queries against those rows; qrow(qi) is the row of qn that query slot qi reads (-1: absent, zeros are staged), and
+// store(r, qi, position, score) is called by lane half 0 of every pair for every slot: what is kept is the caller's business.
 template <int DT>
-__global__ __launch_bounds__(kSubsetThreads, 2) void k_scan_subset(SubsetArgs a) {   // two waves per SIMD: at most 256 registers (the e4m3 form took 258 without the bound)
+struct SubsetLane {
+    long long pos[kSubsetR], row[kSubsetR];
+    const char* base[kSubsetR];
+    float inv[kSubsetR];
+    bool vec;
+};
+
+template <int DT, class Ids>   // Ids: const long long*, or the same in the global address space (k_scan_subset_m's list comes out of a descriptor)
+__device__ __forceinline__ void subset_lane_rows(SubsetLane<DT>& L, const void* rows, const float* norm, long long n, int d, Ids ids,
+                                                 long long id_base, long long count) {
+    constexpr int R = kSubsetR;
+    constexpr int ESZ = DT == VF_DTYPE_F32 ? 4 : (DT == VF_DTYPE_F16 ? 2 : 1);
+    const int p = threadIdx.x >> 1;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        L.pos[r] = (long long)blockIdx.x * kSubsetRowsPerWg + r * (kSubsetThreads / 2) + p;
+        const long long c = L.pos[r] < count ? L.pos[r] : count - 1;
+        long long g = ids[c] - id_base;
+        g = g < 0 ? 0 : (g < n ? g : n - 1);
+        L.row[r] = g;
+        L.base[r] = (const char*)rows + g * (long long)d * ESZ;
+        L.inv[r] = canon_inv(norm[g]);
+    }
+    L.vec = ((((unsigned long long)(uintptr_t)rows) | ((unsigned long long)d * ESZ)) & 15) == 0;
+}
+
+template <int DT, class QRow, class Store>
+__device__ __forceinline__ void subset_scan_tile(const SubsetLane<DT>& L, const void* rows, int d, const float* qn, float* qs, QRow qrow, Store store) {
     constexpr int R = kSubsetR, Q = kSubsetQ;
     constexpr int ESZ = DT == VF_DTYPE_F32 ? 4 : (DT == VF_DTYPE_F16 ? 2 : 1);
     constexpr int kBlk = (DT == VF_DTYPE_F32 || DT == VF_DTYPE_FP8_E4M3) ? 2 : 4;   // 16-element blocks in flight per row and lane (e4m3: four spilled two registers)
     typedef typename RowVec<DT>::type vec_t;
-    __shared__ __attribute__((aligned(16))) float qs[Q * kSubsetSlice];
-    const int lane = threadIdx.x, h = lane & 1, p = lane >> 1;
-    long long pos[R], row[R];
-    const char* base[R];
-    float inv[R];
+    const int lane = threadIdx.x, h = lane & 1;
+    float acc[R][Q][8];
 #pragma unroll
-    for (int r = 0; r < R; ++r) {
-        pos[r] = (long long)blockIdx.x * kSubsetRowsPerWg + r * (kSubsetThreads / 2) + p;
-        const long long c = pos[r] < a.count ? pos[r] : a.count - 1;
-        long long g = a.ids[a.pos0 + c] - a.id_base;
-        g = g < 0 ? 0 : (g < a.n ? g : a.n - 1);
-        row[r] = g;
-        base[r] = (const char*)a.rows + g * (long long)a.d * ESZ;
-        inv[r] = canon_inv(a.norm[g]);
-    }
-    const bool vec = ((((unsigned long long)(uintptr_t)a.rows) | ((unsigned long long)a.d * ESZ)) & 15) == 0;
-    for (int q0 = blockIdx.y * Q; q0 < a.nq; q0 += gridDim.y * Q) {   // (the launcher gives every query tile its own workgroups)
-        float acc[R][Q][8];
+    for (int r = 0; r < R; ++r)
 #pragma unroll
-        for (int r = 0; r < R; ++r)
+        for (int qi = 0; qi < Q; ++qi)
 #pragma unroll
-            for (int qi = 0; qi < Q; ++qi)
+            for (int e = 0; e < 8; ++e) acc[r][qi][e] = 0.0f;
+    for (int k0 = 0; k0 < d; k0 += kSubsetSlice) {
+        const int len = d - k0 < kSubsetSlice ? d - k0 : kSubsetSlice;   // elements of this slice
+        const int len16 = (len + 15) & ~15;                              // ... padded with zeros to whole blocks
+        __syncthreads();
+        for (int i = lane; i < Q * len16; i += kSubsetThreads) {
+            const int qi = i / len16, j = i - qi * len16;
+            const long long qr = qrow(qi);
+            qs[qi * kSubsetSlice + j] = (qr >= 0 && j < len) ? qn[qr * d + k0 + j] : 0.0f;
+        }
+        __syncthreads();
+        const int nfull = len >> 4;
+        // one 16-element block of the R rows (cn: the normalised values) against the Q queries of the tile
+        auto step = [&](const float (&cn)[R][8], int b, bool live, int valid) {
 #pragma unroll
-                for (int e = 0; e < 8; ++e) acc[r][qi][e] = 0.0f;
-        for (int k0 = 0; k0 < a.d; k0 += kSubsetSlice) {
-            const int len = a.d - k0 < kSubsetSlice ? a.d - k0 : kSubsetSlice;   // elements of this slice
-            const int len16 = (len + 15) & ~15;                                  // ... padded with zeros to whole blocks
-            __syncthreads();
-            for (int i = lane; i < Q * len16; i += kSubsetThreads) {
-                const int qi = i / len16, j = i - qi * len16;
-                qs[qi * kSubsetSlice + j] = (q0 + qi < a.nq && j < len) ? a.qn[(long long)(q0 + qi) * a.d + k0 + j] : 0.0f;
+            for (int qi = 0; qi < Q; ++qi) {
+                const float* qp = qs + qi * kSubsetSlice + b * 16 + 8 * h;
+                const float4 q0v = *(const float4*)qp, q1v = *(const float4*)(qp + 4);
+                const float qq[8] = {q0v.x, q0v.y, q0v.z, q0v.w, q1v.x, q1v.y, q1v.z, q1v.w};
+#pragma unroll
+                for (int e = 0; e < 8; ++e)
+#pragma unroll
+                    for (int r = 0; r < R; ++r) {
+                        const float t = __builtin_fmaf(qq[e], cn[r][e], acc[r][qi][e]);
+                        acc[r][qi][e] = (live && e < valid) ? t : acc[r][qi][e];
+                    }
             }
-            __syncthreads();
-            const int nfull = len >> 4;
-            // one 16-element block of the R rows (cn: the normalised values) against the Q queries of the tile
-            auto step = [&](const float (&cn)[R][8], int b, bool live, int valid) {
+        };
+        if (L.vec) {
+            for (int b0 = 0; b0 < nfull; b0 += kBlk) {
+                vec_t v[R][kBlk];
 #pragma unroll
-                for (int qi = 0; qi < Q; ++qi) {
-                    const float* qp = qs + qi * kSubsetSlice + b * 16 + 8 * h;
-                    const float4 q0v = *(const float4*)qp, q1v = *(const float4*)(qp + 4);
-                    const float qq[8] = {q0v.x, q0v.y, q0v.z, q0v.w, q1v.x, q1v.y, q1v.z, q1v.w};
+                for (int u = 0; u < kBlk; ++u) {
+                    const int b = b0 + u < nfull ? b0 + u : nfull - 1;
 #pragma unroll
-                    for (int e = 0; e < 8; ++e)
-#pragma unroll
-                        for (int r = 0; r < R; ++r) {
-                            const float t = __builtin_fmaf(qq[e], cn[r][e], acc[r][qi][e]);
-                            acc[r][qi][e] = (live && e < valid) ? t : acc[r][qi][e];
-                        }
+                    for (int r = 0; r < R; ++r) v[r][u] = *(const vec_t*)(L.base[r] + ((long long)k0 + b * 16 + 8 * h) * ESZ);
                 }
-            };
-            if (vec) {
-                for (int b0 = 0; b0 < nfull; b0 += kBlk) {
-                    vec_t v[R][kBlk];
 #pragma unroll
-                    for (int u = 0; u < kBlk; ++u) {
-                        const int b = b0 + u < nfull ? b0 + u : nfull - 1;
-#pragma unroll
-                        for (int r = 0; r < R; ++r) v[r][u] = *(const vec_t*)(base[r] + ((long long)k0 + b * 16 + 8 * h) * ESZ);
-                    }
-#pragma unroll
-                    for (int u = 0; u < kBlk; ++u) {
-                        const bool live = b0 + u < nfull;
-                        float cn[R][8];
-#pragma unroll
-                        for (int r = 0; r < R; ++r) {
-                            float x[8];
-                            decode8<DT>(v[r][u], x);
-#pragma unroll
-                            for (int e = 0; e < 8; ++e) cn[r][e] = x[e] * inv[r];
-                        }
-                        step(cn, live ? b0 + u : nfull - 1, live, 8);
-                    }
-                }
-            } else {   // rows that are not 16-byte aligned (odd d): element loads, same order
-                for (int b = 0; b < nfull; ++b) {
+                for (int u = 0; u < kBlk; ++u) {
+                    const bool live = b0 + u < nfull;
                     float cn[R][8];
 #pragma unroll
-                    for (int r = 0; r < R; ++r)
+                    for (int r = 0; r < R; ++r) {
+                        float x[8];
+                        decode8<DT>(v[r][u], x);
 #pragma unroll
-                        for (int e = 0; e < 8; ++e) cn[r][e] = load_elem(a.rows, DT, row[r] * (long long)a.d + k0 + b * 16 + 8 * h + e) * inv[r];
-                    step(cn, b, true, 8);
+                        for (int e = 0; e < 8; ++e) cn[r][e] = x[e] * L.inv[r];
+                    }
+                    step(cn, live ? b0 + u : nfull - 1, live, 8);
                 }
             }
-            if (len & 15) {   // the tail block (the last slice alone has one): element j of it exists while j < len
-                const int j0 = nfull * 16 + 8 * h;
-                const int valid = len - j0 < 0 ? 0 : (len - j0 > 8 ? 8 : len - j0);
+        } else {   // rows that are not 16-byte aligned (odd d): element loads, same order
+            for (int b = 0; b < nfull; ++b) {
                 float cn[R][8];
 #pragma unroll
                 for (int r = 0; r < R; ++r)
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        const int j = e < valid ? j0 + e : 0;   // (a clamped, masked read)
-                        cn[r][e] = load_elem(a.rows, DT, row[r] * (long long)a.d + k0 + j) * inv[r];
-                    }
-                step(cn, nfull, true, valid);
+                    for (int e = 0; e < 8; ++e) cn[r][e] = load_elem(rows, DT, L.row[r] * (long long)d + k0 + b * 16 + 8 * h + e) * L.inv[r];
+                step(cn, b, true, 8);
             }
         }
-        // canonical tree: s8[l] = acc[l] + acc[l + 8] needs the partner half's sums; then 4, 2, 1 in-lane
+        if (len & 15) {   // the tail block (the last slice alone has one): element j of it exists while j < len
+            const int j0 = nfull * 16 + 8 * h;
+            const int valid = len - j0 < 0 ? 0 : (len - j0 > 8 ? 8 : len - j0);
+            float cn[R][8];
 #pragma unroll
-        for (int r = 0; r < R; ++r)
+            for (int r = 0; r < R; ++r)
 #pragma unroll
-            for (int qi = 0; qi < Q; ++qi) {
-                float s8[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) s8[e] = acc[r][qi][e] + __shfl_xor(acc[r][qi][e], 1);
-                const float s4[4] = {s8[0] + s8[4], s8[1] + s8[5], s8[2] + s8[6], s8[3] + s8[7]};
-                const float s = (s4[0] + s4[2]) + (s4[1] + s4[3]);
-                if (h == 0 && pos[r] < a.count && q0 + qi < a.nq) a.scores[subset_score_index(pos[r], q0 + qi, a.nq, a.rank_rows)] = s;
-            }
+                for (int e = 0; e < 8; ++e) {
+                    const int j = e < valid ? j0 + e : 0;   // (a clamped, masked read)
+                    cn[r][e] = load_elem(rows, DT, L.row[r] * (long long)d + k0 + j) * L.inv[r];
+                }
+            step(cn, nfull, true, valid);
+        }
     }
+    // canonical tree: s8[l] = acc[l] + acc[l + 8] needs the partner half's sums; then 4, 2, 1 in-lane
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+        for (int qi = 0; qi < Q; ++qi) {
+            float s8[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) s8[e] = acc[r][qi][e] + __shfl_xor(acc[r][qi][e], 1);
+            const float s4[4] = {s8[0] + s8[4], s8[1] + s8[5], s8[2] + s8[6], s8[3] + s8[7]};
+            const float s = (s4[0] + s4[2]) + (s4[1] + s4[3]);
+            if (h == 0) store(r, qi, L.pos[r], s);
+        }
+}
+
+template <int DT>
+__global__ __launch_bounds__(kSubsetThreads, 2) void k_scan_subset(SubsetArgs a) {   // two waves per SIMD: at most 256 registers (the e4m3 form took 258 without the bound)
+    __shared__ __attribute__((aligned(16))) float qs[kSubsetQ * kSubsetSlice];
+    SubsetLane<DT> L;
+    subset_lane_rows<DT>(L, a.rows, a.norm, a.n, a.d, a.ids + a.pos0, a.id_base, a.count);
+    for (int q0 = blockIdx.y * kSubsetQ; q0 < a.nq; q0 += gridDim.y * kSubsetQ)   // (the launcher gives every query tile its own workgroups)
+        subset_scan_tile<DT>(L, a.rows, a.d, a.qn, qs,
+                             [&](int qi) -> long long { return q0 + qi < a.nq ? q0 + qi : -1; },
+                             [&](int, int qi, long long pos, float s) {
+                                 if (pos < a.count && q0 + qi < a.nq) a.scores[subset_score_index(pos, q0 + qi, a.nq, a.rank_rows)] = s;
+                             });
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_scan_subset_m: k_scan_subset's body behind the tile table of a batch whose queries each bring their own list (VF_SEARCH_SUBSETS; the
+// plan: vf_subset_multi.h).  Grid (ceil(n_rank / 64), tiles of the launch's size class); blockIdx.y picks the 64-byte descriptor -- one
+// address per workgroup, read before the first store, so its loads are scalar -- and the list pointer read from it is given its global
+// address space back (a pointer out of memory is a flat one to the compiler, and round 22 saw what flat loads cost a short workgroup).
+// The tile's queries are gathered into the LDS tile by index from qn; an absent slot is zeros and writes nothing.  Positions [m, n_rank)
+// get the sentinel -FLT_MAX (subm_wg_kind: a workgroup wholly inside them writes those alone), so the ranking launch reads no slot
+// that was not written.
+// ------------------------------------------------------------------------------------------------
+typedef const long long __attribute__((address_space(1)))* global_ll_ptr;
+static_assert(kSubsetRowsPerWg == kSubsetThreads && kSubsetQ == 4, "k_scan_subset_m: a sentinel workgroup writes one position per lane; four query slots");
+
+template <int DT>
+__global__ __launch_bounds__(kSubsetThreads, 2) void k_scan_subset_m(SubsetMArgs a) {
+    __shared__ __attribute__((aligned(16))) float qs[kSubsetQ * kSubsetSlice];
+    const SubmTile* __restrict__ tp = a.tiles + blockIdx.y;
+    const long long m = tp->m, score_base = tp->score_base;
+    const int n_rank = tp->n_rank;
+    const int q[kSubsetQ] = {tp->q[0], tp->q[1], tp->q[2], tp->q[3]};
+    const global_ll_ptr ids = (global_ll_ptr)tp->ids;
+    const int kind = subm_wg_kind(m, n_rank, blockIdx.x, kSubsetRowsPerWg);
+    if (kind == kSubmWgNothing) return;
+    if (kind == kSubmWgSentinels) {
+        const long long pos = (long long)blockIdx.x * kSubsetRowsPerWg + threadIdx.x;
+#pragma unroll
+        for (int qi = 0; qi < kSubsetQ; ++qi)
+            if (q[qi] >= 0 && pos < n_rank) a.scores[score_base + (long long)qi * n_rank + pos] = -FLT_MAX;
+        return;
+    }
+    SubsetLane<DT> L;
+    subset_lane_rows<DT>(L, a.rows, a.norm, a.n, a.d, ids, a.id_base, m);
+    subset_scan_tile<DT>(L, a.rows, a.d, a.qn, qs,
+                         [&](int qi) -> long long { return qi == 0 ? q[0] : qi == 1 ? q[1] : qi == 2 ? q[2] : q[3]; },   // (selects: no indexed register array)
+                         [&](int, int qi, long long pos, float s) {
+                             if (q[qi] >= 0 && pos < n_rank) a.scores[score_base + (long long)qi * n_rank + pos] = pos < m ? s : -FLT_MAX;
+                         });
 }
 
 hipError_t launch_scan_subset(const SubsetArgs& a, int dt, hipStream_t s) {
@@ -4526,6 +4592,67 @@ hipError_t launch_subset_ids(const long long* pos, const float* sc, long long to
     long long blocks = (total + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(k_subset_ids, dim3((unsigned)blocks), dim3(256), 0, s, pos, sc, total, ids, first_bad, out_ids, out_scores);
+    return hipGetLastError();
+}
+
+// ---- a list per query (vf_subset_multi.h) --------------------------------------------------------------------------------------------
+hipError_t launch_scan_subset_m(const SubsetMArgs& a, int n_tiles, int dt, hipStream_t s) {
+    if (n_tiles <= 0) return hipSuccess;
+    if (a.n <= 0 || a.d <= 0 || a.n_rank <= 0 || a.n_rank > kSubsetRankRows || n_tiles > 65535) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)subm_scan_blocks(a.n_rank, kSubsetRowsPerWg), (unsigned)n_tiles), block(kSubsetThreads);
+    if (dt == VF_DTYPE_F16) hipLaunchKernelGGL(k_scan_subset_m<VF_DTYPE_F16>, grid, block, 0, s, a);
+    else if (dt == VF_DTYPE_FP8_E4M3) hipLaunchKernelGGL(k_scan_subset_m<VF_DTYPE_FP8_E4M3>, grid, block, 0, s, a);
+    else if (dt == VF_DTYPE_INT8) hipLaunchKernelGGL(k_scan_subset_m<VF_DTYPE_INT8>, grid, block, 0, s, a);
+    else if (dt == VF_DTYPE_F32) hipLaunchKernelGGL(k_scan_subset_m<VF_DTYPE_F32>, grid, block, 0, s, a);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+// the device form's check of every referenced list in one launch (grid.y is the list): the lowest (list << 32 | position) that
+// subset_bad_at refuses, or ~0 (the caller's memset)
+__global__ __launch_bounds__(256) void k_subset_check_m(const SubmList* __restrict__ lists, long long lo, long long hi, u64* first_bad) {
+    const SubmList* __restrict__ lp = lists + blockIdx.y;
+    const long long m = lp->m, list = lp->list;
+    const global_ll_ptr ids = (global_ll_ptr)lp->ids;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < m; i += (long long)gridDim.x * 256)
+        if (subset_bad_value(ids[i], i > 0, i > 0 ? ids[i - 1] : 0, lo, hi)) atomicMin(first_bad, (u64)subm_check_key(list, i));
+}
+
+hipError_t launch_subset_check_m(const SubmList* lists, int n_lists, long long longest, long long lo, long long hi, u64* first_bad, hipStream_t s) {
+    if (n_lists <= 0 || longest <= 0) return hipSuccess;
+    if (longest > kSubsetRankRows) return hipErrorInvalidValue;
+    const unsigned blocks = (unsigned)((longest + 255) / 256);
+    for (int l0 = 0; l0 < n_lists; l0 += 65535) {
+        const int g = n_lists - l0 < 65535 ? n_lists - l0 : 65535;
+        hipLaunchKernelGGL(k_subset_check_m, dim3(blocks, (unsigned)g), dim3(256), 0, s, lists + l0, lo, hi, first_bad);
+    }
+    return hipGetLastError();
+}
+
+// ranked positions (permuted order, [nb][k]) -> the caller's rows: out[row][i] = ids[pos] of the query's own list and its score, or
+// (-1, -FLT_MAX) where pos < 0 (the ranking's own padding) or pos >= m (a sentinel, struck by position).  Nothing at all is written
+// when the check word is not clean.
+__global__ __launch_bounds__(256) void k_subset_ids_m(const long long* pos, const float* sc, int k, const SubmQuery* __restrict__ qd, const u64* first_bad,
+                                                        long long* out_ids, float* out_scores) {
+    if (first_bad && *first_bad != ~0ull) return;
+    const SubmQuery* __restrict__ qp = qd + blockIdx.y;
+    const long long m = qp->m, row = qp->row;
+    const global_ll_ptr ids = (global_ll_ptr)qp->ids;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < k; i += gridDim.x * 256) {
+        const long long p = pos[(long long)blockIdx.y * k + i];
+        const bool real = p >= 0 && p < m;
+        out_ids[row * k + i] = real ? ids[p] : -1;
+        out_scores[row * k + i] = real ? sc[(long long)blockIdx.y * k + i] : -FLT_MAX;
+    }
+}
+
+hipError_t launch_subset_ids_m(const long long* pos, const float* sc, int nb, int k, const SubmQuery* qd, const u64* first_bad,
+                               long long* out_ids, float* out_scores, hipStream_t s) {
+    if (nb <= 0 || k <= 0) return hipSuccess;
+    if (nb > 65535) return hipErrorInvalidValue;
+    int blocks = (k + 255) / 256;
+    if (blocks > 64) blocks = 64;
+    hipLaunchKernelGGL(k_subset_ids_m, dim3((unsigned)blocks, (unsigned)nb), dim3(256), 0, s, pos, sc, k, qd, first_bad, out_ids, out_scores);
     return hipGetLastError();
 }
 

@@ -143,6 +143,8 @@ VF_HD SubsetSpan subset_rank_chunk(const SubsetPlan& p, const SubsetSpan& sup, l
 VF_HD bool subset_bad_at(const long long* ids, long long i, long long lo, long long hi) {
     return ids[i] < lo || ids[i] >= hi || (i > 0 && ids[i] <= ids[i - 1]);
 }
+// the same test on values already read (k_subset_check_m reads its list through a global-address-space pointer)
+VF_HD bool subset_bad_value(long long v, bool has_prev, long long prev, long long lo, long long hi) { return v < lo || v >= hi || (has_prev && v <= prev); }
 VF_HD long long subset_first_bad(const long long* ids, long long m, long long lo, long long hi) {
     for (long long i = 0; i < m; ++i) if (subset_bad_at(ids, i, lo, hi)) return i;
     return -1;

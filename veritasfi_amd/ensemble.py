@@ -435,17 +435,20 @@ class EnsembleRetriever:
         stages.metric("retrieved_chunks", len(out))
         return out
 
+    def _resolve_where(self, where):
+        """(passing, allow, dense filter, BM25 filter) of one request: what the two legs take as subset= is the passing rows, or a
+        PreparedWhere's device-resident filters."""
+        if isinstance(where, PreparedWhere):
+            return where._current(self)
+        passing = None if where is None else self.rows_where(where)
+        allow = None if passing is None else set(passing.tolist())
+        return passing, allow, passing, passing
+
     def _invoke(self, input: str, hyde_chunks: List[str], where=None) -> List[Dict]:
         seen: set = set()
         out: list = []
         bundle_cnt = 0
-        dense_rows = bm25_rows = None   # what the two legs take as subset=: the passing rows, or a PreparedWhere's device-resident filters
-        if isinstance(where, PreparedWhere):
-            passing, allow, dense_rows, bm25_rows = where._current(self)
-        else:
-            passing = None if where is None else self.rows_where(where)
-            allow = None if passing is None else set(passing.tolist())
-            dense_rows = bm25_rows = passing
+        passing, allow, dense_rows, bm25_rows = self._resolve_where(where)
         if passing is not None and passing.size == 0:
             return out
         if self.faiss_k > 0:
@@ -459,15 +462,25 @@ class EnsembleRetriever:
                 bundle_cnt = self._bm25_branch(input, seen, out, bundle_cnt, allow, passing, bm25_rows)
         return out
 
-    def _faiss_branch(self, input, hyde_chunks, seen, out, bundle_cnt, passing=None, allow=None, dense_rows=None):
-        inputs = [input] + list(hyde_chunks)
+    # Each branch is an ASK (what the leg is called with) and a CONSUME (what is emitted from its answer): invoke runs them back to
+    # back, invoke_batch asks once for many requests and consumes per request -- the same consuming code, so the same output.
+    def _faiss_depth(self) -> int:
         # upstream always searches 2048 deep (:64-66) and reads the tail only as the neighbour expansion's score map (:85-107): without
         # enable_expand the first faiss_k entries are all that is looked at, and an exact search's top-k is a prefix of its top-2048
-        depth = SEARCH_DEPTH if self.enable_expand else min(SEARCH_DEPTH, max(1, int(self.faiss_k)))
+        return SEARCH_DEPTH if self.enable_expand else min(SEARCH_DEPTH, max(1, int(self.faiss_k)))
+
+    @staticmethod
+    def _dense_filter(passing, dense_rows):
+        return passing if dense_rows is None else dense_rows
+
+    def _faiss_ask(self, input, hyde_chunks, passing=None, dense_rows=None):
+        inputs = [input] + list(hyde_chunks)
         if passing is None:
-            ids_list, scores_list = self.faiss_retriever.invoke(inputs, depth)
-        else:   # rows are ids here (the retriever's index starts at 0, as upstream's does)
-            ids_list, scores_list = self.faiss_retriever.invoke(inputs, depth, subset=passing if dense_rows is None else dense_rows)
+            return self.faiss_retriever.invoke(inputs, self._faiss_depth())
+        # rows are ids here (the retriever's index starts at 0, as upstream's does)
+        return self.faiss_retriever.invoke(inputs, self._faiss_depth(), subset=self._dense_filter(passing, dense_rows))
+
+    def _faiss_consume(self, ids_list, scores_list, seen, out, bundle_cnt, allow=None):
         for ids, scores in zip(ids_list, scores_list):
             ids = [int(i) for i in ids]
             score_map = dict(zip(ids, scores))
@@ -483,9 +496,12 @@ class EnsembleRetriever:
                 bundle_cnt += 1
         return bundle_cnt
 
-    def _title_branch(self, input, seen, out, bundle_cnt, allow=None):
-        t_ids, t_scores = self.title_summary_faiss_retriever.invoke([input], self.faiss_ts_k)
-        for t, score in zip(t_ids[0], t_scores[0]):
+    def _faiss_branch(self, input, hyde_chunks, seen, out, bundle_cnt, passing=None, allow=None, dense_rows=None):
+        ids_list, scores_list = self._faiss_ask(input, hyde_chunks, passing, dense_rows)
+        return self._faiss_consume(ids_list, scores_list, seen, out, bundle_cnt, allow)
+
+    def _title_consume(self, t_ids, t_scores, seen, out, bundle_cnt, allow=None):
+        for t, score in zip(t_ids, t_scores):
             if t < 0:
                 continue
             for row in self._title_rows.get(self.title_summaries[int(t)], ()):
@@ -496,43 +512,176 @@ class EnsembleRetriever:
                 bundle_cnt += 1
         return bundle_cnt
 
-    def _bm25_branch(self, input, seen, out, bundle_cnt, allow=None, passing=None, bm25_rows=None):
+    def _title_branch(self, input, seen, out, bundle_cnt, allow=None):
+        t_ids, t_scores = self.title_summary_faiss_retriever.invoke([input], self.faiss_ts_k)
+        return self._title_consume(t_ids[0], t_scores[0], seen, out, bundle_cnt, allow)
+
+    def _bm25_depth(self, passing=None) -> int:
+        """Rows a retriever with a total order is asked for: bm25_k, or fewer where fewer exist (or pass)."""
+        return max(1, min(int(self.bm25_k), self.num_chunk if passing is None else len(passing)))
+
+    def _bm25_ask(self, input, allow=None, passing=None, bm25_rows=None):
+        """The (row, score) pairs the branch emits from, at most bm25_k of them."""
         if allow is not None:
             # filtered: the first bm25_k passing rows of the full ranking (whole-corpus statistics: the stated exception) -- from a
             # retriever that filters on its own (filtered_prefix), else from the full ranking, filtered here
             if passing is not None and bm25_rows is not None and bm25_rows is not passing:   # a prepared filter: its mode is its own
-                b_ids, b_scores = self.bm25_retriever.invoke(input, max(1, min(int(self.bm25_k), len(passing))), subset=bm25_rows)
-                kept = [(int(r), s) for r, s in zip(b_ids, b_scores)]
-            elif passing is not None and self.where_statistics == "subset":   # no exception: the passing chunks' own statistics
-                b_ids, b_scores = self.bm25_retriever.invoke(input, max(1, min(int(self.bm25_k), len(passing))), subset=passing, stats="subset")
-                kept = [(int(r), s) for r, s in zip(b_ids, b_scores)]
-            elif passing is not None and getattr(self.bm25_retriever, "filtered_prefix", False) is True:
-                b_ids, b_scores = self.bm25_retriever.invoke(input, max(1, min(int(self.bm25_k), len(passing))), subset=passing)
-                kept = [(int(r), s) for r, s in zip(b_ids, b_scores)]
-            else:
-                b_ids, b_scores = self.bm25_retriever.invoke(input, self.num_chunk)
-                kept = [(int(r), s) for r, s in zip(b_ids, b_scores) if int(r) in allow][:self.bm25_k]
-            for row, score in kept:
-                if row in seen:
-                    continue
-                seen.add(row)
-                self._emit(out, "BM25", score, self._bundle_of(row, seen, allow), bundle_cnt)
-                bundle_cnt += 1
-            return bundle_cnt
+                b_ids, b_scores = self.bm25_retriever.invoke(input, self._bm25_depth(passing), subset=bm25_rows)
+                return [(int(r), s) for r, s in zip(b_ids, b_scores)]
+            if passing is not None and self.where_statistics == "subset":   # no exception: the passing chunks' own statistics
+                b_ids, b_scores = self.bm25_retriever.invoke(input, self._bm25_depth(passing), subset=passing, stats="subset")
+                return [(int(r), s) for r, s in zip(b_ids, b_scores)]
+            if passing is not None and getattr(self.bm25_retriever, "filtered_prefix", False) is True:
+                b_ids, b_scores = self.bm25_retriever.invoke(input, self._bm25_depth(passing), subset=passing)
+                return [(int(r), s) for r, s in zip(b_ids, b_scores)]
+            b_ids, b_scores = self.bm25_retriever.invoke(input, self.num_chunk)
+            return [(int(r), s) for r, s in zip(b_ids, b_scores) if int(r) in allow][:self.bm25_k]
         # upstream ranks every chunk (:188) and reads the first bm25_k; a retriever whose ranking is a total order
         # (exact_prefix, e.g. veritasfi_amd.BM25Retriever) returns exactly that prefix when asked for bm25_k rows -- min_score
         # included, since it keeps a prefix of a descending ranking.  Others keep the upstream call.
         depth = self.num_chunk
         if getattr(self.bm25_retriever, "exact_prefix", False) is True:
-            depth = max(1, min(int(self.bm25_k), self.num_chunk))
+            depth = self._bm25_depth()
         b_ids, b_scores = self.bm25_retriever.invoke(input, depth)
-        for row, score in zip(b_ids[:self.bm25_k], b_scores[:self.bm25_k]):
+        return list(zip(b_ids[:self.bm25_k], b_scores[:self.bm25_k]))
+
+    def _bm25_consume(self, kept, seen, out, bundle_cnt, allow=None):
+        for row, score in kept:
             if row in seen:
                 continue
             seen.add(row)
-            self._emit(out, "BM25", score, self._bundle_of(row, seen), bundle_cnt)
+            self._emit(out, "BM25", score, self._bundle_of(row, seen, allow), bundle_cnt)
             bundle_cnt += 1
         return bundle_cnt
+
+    def _bm25_branch(self, input, seen, out, bundle_cnt, allow=None, passing=None, bm25_rows=None):
+        return self._bm25_consume(self._bm25_ask(input, allow, passing, bm25_rows), seen, out, bundle_cnt, allow)
+
+    # -- many requests at once ------------------------------------------------------------------------
+    def invoke_batch(self, inputs, hyde_chunks_list, wheres=None) -> List[List[Dict]]:
+        """``[invoke(inputs[i], hyde_chunks_list[i], where=wheres[i]) for i]``, equal as Python objects, with each leg asked ONCE for
+        the whole batch where it can be: requests of different tenants share the device calls.
+        wheres: None, or one of None / dict / ``PreparedWhere`` per request.  A dict is prepared for the duration of the call
+        (``prepare_where``) and released after; dicts of equal content share one preparation.
+        Dense leg: one ``invoke(every input and hyde chunk, depth, subsets=[the request's dense filter per string])`` when the retriever
+        declares ``per_query_subsets`` (this package's ``FaissRetriever``), else one call per request, as ``invoke`` makes it.
+        Title-summary leg: one ``invoke(inputs, faiss_ts_k)``.  BM25 leg: one ``invoke_batch(inputs, min(bm25_k, chunks),
+        subsets=[BM25Subset or None])`` when the retriever offers ``prepare_subset``, an ``invoke_batch`` that takes ``subsets=`` and
+        declares ``exact_prefix``; each request keeps its own ``min(bm25_k, passing rows)`` because that call returns
+        ``min(k, rows allowed)`` rows per query.  Else one call per request.  A request whose filter passes nothing yields [] and asks
+        no leg.  ``seen``, the bundle counter and the order of emission are per request, exactly as in ``invoke``.  Stage brackets: one
+        ``"retrieve"`` around the batch; the ``retrieved_chunks`` metric is recorded once per request."""
+        inputs = list(inputs)
+        hyde = [list(h) for h in hyde_chunks_list]
+        if len(hyde) != len(inputs):
+            raise ValueError(f"invoke_batch: {len(hyde)} hyde chunk lists for {len(inputs)} inputs")
+        wheres = [None] * len(inputs) if wheres is None else list(wheres)
+        if len(wheres) != len(inputs):
+            raise ValueError(f"invoke_batch: {len(wheres)} wheres for {len(inputs)} inputs")
+        for w in wheres:
+            if w is not None and not isinstance(w, (dict, PreparedWhere)):
+                raise TypeError("invoke_batch: each entry of `wheres` is None, a dict (rows_where's argument) or a PreparedWhere")
+        with stages.stage("retrieve"):
+            outs = self._invoke_batch(inputs, hyde, wheres)
+        for out in outs:
+            stages.metric("retrieved_chunks", len(out))
+        return outs
+
+    @staticmethod
+    def _where_key(where: dict):
+        """Dicts of equal content share one preparation: the key of a dict's content, or of the object itself where a value cannot
+        be hashed."""
+        def frozen(v):
+            return (type(v).__name__, frozenset(v)) if isinstance(v, (set, frozenset)) else (type(v).__name__, tuple(v)) if isinstance(v, (list, tuple)) else v
+        try:
+            key = frozenset((f, frozen(v)) for f, v in where.items())
+            hash(key)
+            return key
+        except TypeError:
+            return ("object", id(where))
+
+    def _bm25_takes_subsets(self) -> bool:
+        bm = self.bm25_retriever
+        fn = getattr(bm, "invoke_batch", None)
+        if fn is None or not hasattr(bm, "prepare_subset") or getattr(bm, "exact_prefix", False) is not True:
+            return False
+        import inspect
+        try:
+            params = inspect.signature(fn).parameters
+        except (TypeError, ValueError):
+            return False
+        return "subsets" in params or any(p.kind is inspect.Parameter.VAR_KEYWORD for p in params.values())
+
+    def _invoke_batch(self, inputs, hyde, wheres) -> List[List[Dict]]:
+        temps = {}   # the dicts of this call, prepared once per content
+        try:
+            state = []
+            for w in wheres:
+                if isinstance(w, dict):
+                    key = self._where_key(w)
+                    if key not in temps:
+                        temps[key] = PreparedWhere(self, w)
+                    w = temps[key]
+                state.append(self._resolve_where(w))
+            n = len(inputs)
+            outs = [[] for _ in range(n)]
+            seen = [set() for _ in range(n)]
+            cnt = [0] * n
+            live = [i for i in range(n) if state[i][0] is None or state[i][0].size > 0]   # the others yield [] and ask no leg
+            if not live:
+                return outs
+            if self.faiss_k > 0:
+                with stages.stage("retrieve_faiss"):
+                    answers = self._faiss_ask_batch(live, inputs, hyde, state)
+                    for i in live:
+                        cnt[i] = self._faiss_consume(answers[i][0], answers[i][1], seen[i], outs[i], cnt[i], state[i][1])
+            if self.faiss_ts_k > 0:
+                with stages.stage("retrieve_faiss_ts"):
+                    t_ids, t_scores = self.title_summary_faiss_retriever.invoke([inputs[i] for i in live], self.faiss_ts_k)
+                    for j, i in enumerate(live):
+                        cnt[i] = self._title_consume(t_ids[j], t_scores[j], seen[i], outs[i], cnt[i], state[i][1])
+            if self.bm25_k > 0:
+                with stages.stage("retrieve_bm25"):
+                    kept = self._bm25_ask_batch(live, inputs, state)
+                    for i in live:
+                        cnt[i] = self._bm25_consume(kept[i], seen[i], outs[i], cnt[i], state[i][1])
+            return outs
+        finally:
+            for pw in temps.values():
+                pw.close()
+
+    def _faiss_ask_batch(self, live, inputs, hyde, state) -> dict:
+        """request -> (ids_list, scores_list), one entry per string of the request ([input] + hyde chunks)."""
+        if getattr(self.faiss_retriever, "per_query_subsets", False) is not True:
+            return {i: self._faiss_ask(inputs[i], hyde[i], state[i][0], state[i][2]) for i in live}
+        strings, subsets, spans = [], [], {}
+        for i in live:
+            mine = [inputs[i]] + hyde[i]
+            passing, _, dense_rows, _ = state[i]
+            spans[i] = (len(strings), len(strings) + len(mine))
+            strings += mine
+            subsets += [None if passing is None else self._dense_filter(passing, dense_rows)] * len(mine)   # the same object: one list
+        ids, scores = self.faiss_retriever.invoke(strings, self._faiss_depth(), subsets=subsets)
+        return {i: (ids[a:b], scores[a:b]) for i, (a, b) in spans.items()}
+
+    def _bm25_ask_batch(self, live, inputs, state) -> dict:
+        """request -> the (row, score) pairs its BM25 branch emits from."""
+        bm = self.bm25_retriever
+        batched = self._bm25_takes_subsets()
+        if batched:   # every filtered request must bring an object the retriever prepared
+            batched = all(state[i][0] is None or (state[i][3] is not None and state[i][3] is not state[i][0]) for i in live)
+        if not batched:
+            return {i: self._bm25_ask(inputs[i], state[i][1], state[i][0], state[i][3]) for i in live}
+        answers = bm.invoke_batch([inputs[i] for i in live], self._bm25_depth(), subsets=[None if state[i][0] is None else state[i][3] for i in live])
+        kept = {}
+        for j, i in enumerate(live):
+            b_ids, b_scores = answers[j]
+            if state[i][0] is None:
+                kept[i] = list(zip(b_ids[:self.bm25_k], b_scores[:self.bm25_k]))
+            else:   # min(bm25_k, passing rows) of them: the call returns min(k, rows allowed) per query
+                want = self._bm25_depth(state[i][0])
+                kept[i] = [(int(r), s) for r, s in zip(b_ids[:want], b_scores[:want])]
+        return kept
 
     # ensembleRetriever.py:235-281
     def compute_similarity(self, chunks, selected_indices, candidate_index):

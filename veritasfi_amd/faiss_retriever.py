@@ -116,17 +116,23 @@ class FaissRetriever:
             raise ValueError("this retriever wraps an index it did not build: pass corpus_dtype to from_index to remove from it")
         return int(self.index.remove(np.asarray(ids, dtype=np.int64).ravel()))
 
-    def invoke(self, querys: list, k: int, subset=None):
+    per_query_subsets = True   # invoke takes subsets=[one filter per query] (EnsembleRetriever.invoke_batch asks for this before it batches)
+
+    def invoke(self, querys: list, k: int, subset=None, subsets=None):
         """(I, D) = ids and cosine scores, best first, shape [len(querys), k]; -1 / -FLT_MAX pad a corpus with fewer than k rows
         (reference :28-38: embed each string, fp32, L2-normalise, IndexFlatIP.search).  An embedder with a batched
         ``embed_queries`` -- ours has one -- gets ONE forward for all strings; any other is called per string, as upstream does.
         subset: search these rows only (ids, a boolean mask or a ``RowSubset``: ``DenseIndex.search``) -- the metadata filtering the
-        reference class announces and does not have."""
+        reference class announces and does not have.
+        subsets: one entry per string -- ids, a mask, a ``RowSubset`` or None -- passed through to ``DenseIndex.search(subsets=)``: row i
+        is what ``invoke([querys[i]], k, subset=subsets[i])`` returns.  Entries that are the same object share one list."""
         texts = list(querys)
         embed_many = getattr(self.embeddings, "embed_queries", None)
         vectors = embed_many(texts) if embed_many is not None else [self.embeddings.embed_query(t) for t in texts]
         q = np.asarray(vectors, dtype=np.float32).reshape(len(texts), -1)
-        if subset is None:
+        if subsets is not None:
+            ids, scores = self.index.search(q, k, subset=subset, subsets=subsets)
+        elif subset is None:
             ids, scores = self.index.search(q, k)      # normalisation happens on the device (k_prep_queries), canonical order
         else:
             ids, scores = self.index.search(q, k, subset=subset)

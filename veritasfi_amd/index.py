@@ -76,6 +76,53 @@ class RowSubset:
         return int(self.ids.size)
 
 
+SUBSETS_MAX_IDS = 16384   # the longest list the library's list-per-query mode serves (kSubsetRankRows, vf_subset_multi.h)
+
+
+def subsets_plan(subsets, nq: int, n: int, id_offset: int = 0, device_id=None, subset=None) -> dict:
+    """How ``DenseIndex.search(queries, k, subsets=[...])`` is served -- a pure function of its arguments (no GPU, no library).
+    ``subsets`` holds one entry per query: ids, a boolean mask, a ``RowSubset`` or None.  Entries that are the SAME OBJECT share one
+    list; equal contents in different objects do not (nothing is compared).  The answer:
+    ``plain``: the queries whose entry is None -- one unfiltered call for all of them;
+    ``long``: ``[{"subset", "queries"}]``, one per distinct object of more than ``SUBSETS_MAX_IDS`` ids -- one ``subset=`` call each;
+    ``multi``: None, or ``{"form", "queries", "lists", "list_of", "first_query"}`` -- ONE list-per-query call for all the rest:
+    ``lists[list_of[i]]`` serves ``queries[i]``, ``first_query[j]`` is the first query of the call's ``subsets`` that uses ``lists[j]``.
+    ``form`` is "device" when every list is a ``RowSubset`` on ``device_id`` (``lists`` then holds those objects), else "host"
+    (``lists`` holds int64 arrays; a ``RowSubset`` gives its host copy)."""
+    if subset is not None:
+        raise ValueError("search: subset= (one list for the whole call) and subsets= (one per query) cannot be given together")
+    entries = list(subsets)
+    if len(entries) != int(nq):
+        raise ValueError(f"subsets: {len(entries)} entries for {int(nq)} queries (one entry per query; None = no filter)")
+    plain, slot_of, groups = [], {}, []
+    for q, e in enumerate(entries):
+        if e is None:
+            plain.append(q)
+            continue
+        g = slot_of.get(id(e))
+        if g is None:
+            is_rs = isinstance(e, RowSubset)
+            ids = e.ids if is_rs else subset_ids(e, n, id_offset)
+            g = slot_of[id(e)] = len(groups)
+            groups.append({"object": e, "ids": ids, "row_subset": is_rs, "queries": []})
+        groups[g]["queries"].append(q)
+    long = [{"subset": g["object"] if g["row_subset"] else g["ids"], "queries": g["queries"]} for g in groups if g["ids"].size > SUBSETS_MAX_IDS]
+    short = [g for g in groups if g["ids"].size <= SUBSETS_MAX_IDS]
+    multi = None
+    if short:
+        on_device = device_id is not None and all(g["row_subset"] and g["object"].device_id == int(device_id) for g in short)
+        pairs = sorted((q, j) for j, g in enumerate(short) for q in g["queries"])
+        multi = {"form": "device" if on_device else "host", "queries": [q for q, _ in pairs], "list_of": [j for _, j in pairs],
+                 "lists": [g["object"] if on_device else g["ids"] for g in short], "first_query": [g["queries"][0] for g in short]}
+    return {"plain": plain, "long": long, "multi": multi}
+
+
+def _name_subsets(message: str, first_query) -> str:
+    """The library names ``lists[j]``; the caller knows ``subsets[i]``: the first query that uses that list."""
+    import re
+    return re.sub(r"lists\[(\d+)\]", lambda mo: f"subsets[{first_query[int(mo.group(1))]}]" if int(mo.group(1)) < len(first_query) else mo.group(0), message)
+
+
 def _dev_array(device_ids):
     ids = [int(x) for x in device_ids]
     if not ids:
@@ -339,9 +386,13 @@ class DenseIndex:
             self._keepalive = None
 
     # -- host buffers ------------------------------------------------------------------------------
-    def search(self, queries, k: int, subset=None):
+    def search(self, queries, k: int, subset=None, subsets=None):
         """queries [nq, d] -> (ids int64 [nq, k], scores float32 [nq, k]); ids first, as
         FaissRetriever.invoke returns them (faissRetriever.py:38).
+        subsets: one entry PER QUERY -- ids, a boolean mask, a ``RowSubset`` or None.  Row i is, ids and score bits, what
+        ``search(queries[i:i+1], k, subset=subsets[i])`` returns (None: the plain search), in one library call for every list of at
+        most 16 384 ids (``subsets_plan`` says how the rest is routed).  Entries that are the same object share a list; equal contents
+        in different objects do not.  Single-device handles only.
         subset: search these rows only -- an int64 array-like of ids, a boolean mask of length n, or a ``RowSubset``.  The result is
         what an index over those rows alone would return, ids mapped back (``vf_index_search`` with ``VF_SEARCH_SUBSET``: only the listed rows are
         read).  An unsorted or repeating list is sorted and made distinct on the host first (``subset_ids``); fewer than k rows pad
@@ -350,6 +401,8 @@ class DenseIndex:
         if q.ndim != 2 or q.shape[1] != self.d:
             raise ValueError(f"queries must be [nq, {self.d}], got {q.shape}")
         k = int(k)
+        if subsets is not None:
+            return self._search_subsets(q, k, subsets, subset)
         ids = np.empty((q.shape[0], k), dtype=np.int64)
         scores = np.empty((q.shape[0], k), dtype=np.float32)
         if isinstance(subset, RowSubset):
@@ -370,6 +423,44 @@ class DenseIndex:
         if self.device_ids is not None:
             raise ValueError("row_subset: a sharded handle takes id lists (search(subset=ids)), not a device-resident subset")
         return RowSubset(subset_ids(ids_or_mask, self.n, self.id_offset), self.device_id)
+
+    def _search_subsets(self, q: np.ndarray, k: int, subsets, subset=None):
+        if self.device_ids is not None:
+            raise ValueError("search: a sharded handle takes one id list per call (search(subset=ids)), not subsets=")
+        nq = q.shape[0]
+        plan = subsets_plan(subsets, nq, self.n, self.id_offset, self.device_id, subset)
+        ids = np.empty((nq, k), dtype=np.int64)
+        scores = np.empty((nq, k), dtype=np.float32)
+        if plan["plain"]:
+            ids[plan["plain"]], scores[plan["plain"]] = self.search(q[plan["plain"]], k)
+        for part in plan["long"]:
+            ids[part["queries"]], scores[part["queries"]] = self.search(q[part["queries"]], k, subset=part["subset"])
+        multi = plan["multi"]
+        if multi is not None:
+            qm = np.ascontiguousarray(q[multi["queries"]])
+            lens = [len(x) for x in multi["lists"]]
+            try:
+                if multi["form"] == "device":
+                    got = self._search_subsets_device(qm, k, multi["lists"], lens, multi["list_of"])
+                else:
+                    got = np.empty((qm.shape[0], k), dtype=np.int64), np.empty((qm.shape[0], k), dtype=np.float32)
+                    _ffi.check(_ffi.search_subsets(_ffi.lib(), self._h, qm.ctypes.data, qm.shape[0], k, [x.ctypes.data for x in multi["lists"]], lens,
+                                                   multi["list_of"], got[0].ctypes.data, got[1].ctypes.data), "vf_index_search (subsets)")
+            except RuntimeError as e:
+                raise RuntimeError(_name_subsets(str(e), multi["first_query"])) from None
+            ids[multi["queries"]], scores[multi["queries"]] = got
+        return ids, scores
+
+    def _search_subsets_device(self, qm: np.ndarray, k: int, row_subsets, lens, list_of):
+        import torch
+        dev = torch.device(f"cuda:{self.device_id}")
+        dq = torch.from_numpy(qm).to(dev)
+        out_ids = torch.empty((qm.shape[0], k), dtype=torch.int64, device=dev)
+        out_scores = torch.empty((qm.shape[0], k), dtype=torch.float32, device=dev)
+        _ffi.check(_ffi.search_subsets_device(_ffi.lib(), self._h, dq.data_ptr(), qm.shape[0], k, [rs.tensor.data_ptr() for rs in row_subsets], lens,
+                                              list_of, out_ids.data_ptr(), out_scores.data_ptr(),
+                                              torch.cuda.current_stream(dev).cuda_stream), "vf_index_search_device (subsets)")
+        return out_ids.cpu().numpy(), out_scores.cpu().numpy()
 
     def _search_row_subset(self, q: np.ndarray, k: int, rs: RowSubset):
         import torch
