@@ -260,6 +260,48 @@ typedef struct vf_subsets_query {
     const int32_t* list_of;          /* [nq]: each in [0, n_lists) */
 } vf_subsets_query;
 
+/* ---- a metadata filter evaluated on the device: range and boolean `where` -----------------------------------------------------------
+ * Both filtered searches above start from a row set; this call MAKES one from a filter, on the device, per request.  The caller keeps
+ * one int64 KEY COLUMN per metadata field on the index's device (order-preserving keys: an int is its own key, a float its bits
+ * folded so that signed compare orders them, a string its rank among the sorted distinct values) with a validity bitmap for rows that
+ * lack the field, and compiles the filter into a postfix PROGRAM (veritasfi_amd/where.py does both; csrc/vf_where.h is the program's
+ * definition, checker and interpreter):
+ *   leaves   kind 0: valid && lo <= key <= hi (lo > hi: passes nothing); kind 1: valid && key is one of the strictly ascending run
+ *            set_values[lo .. lo + hi); kind 2: !valid
+ *   ops      one byte each: a value below 0x80 pushes that leaf's verdict, 0x80 ands and 0x81 ors the two top values, 0x82 negates the top;
+ *            the program leaves exactly one value
+ *   limits   64 leaves, 128 ops, stack depth 32, 16 columns, 65 536 set values
+ * The call writes d_bitmap -- uint32 words, bit r & 31 of word r >> 5 (VF_BM25_FILTER's layout), 2 * ceil(n / 64) words, zero at and past
+ * n -- the number m of passing rows, and, when d_ids is not NULL, their global ids (id_offset + row) in ascending order: exactly the
+ * list VF_SEARCH_SUBSET takes, already on the device.  Three launches (evaluate and ballot per 64 rows, prefix over the per-tile counts,
+ * ids), one synchronisation, at which m is read.  k, d_ids and d_scores of the call itself are not read.
+ * Checked before any device work, VF_EINVAL naming the position: n that is not the handle's row count (columns made before an append or
+ * a removal are stale); a program the checker refuses (an op that is no leaf and no operator, a pop from an empty stack, values left
+ * over, a leaf of unknown kind or naming no column, a run outside set_values or not strictly ascending); a null d_bitmap; ids_cap < n;
+ * a tile_rows that is not 0 or a multiple of 64 in [64, 1024]; the flag together with VF_SEARCH_SUBSET / VF_SEARCH_SUBSETS; count bits
+ * in nq; the flag on vf_index_search (the message names the device form).  VF_EUNSUPPORTED: a group handle, or a program over the
+ * limits -- evaluate those on the host.  VF_EHIP: a damaged handle.  A refused call writes nothing.  n == 0 returns m = 0 without a
+ * launch.  The call runs under the handle's mutex; its descriptor block and tile counts are one lease of the small entry points' pool,
+ * so a search pending between _begin and _end is not disturbed; vf_index_stats is left alone.
+ *   vf_where_query wq = {n, columns, n_columns, leaves, n_leaves, ops, n_ops, set_values, n_set_values, d_bitmap, d_ids, ids_cap, 0, 0};
+ *   vf_index_search_device(idx, (const float*)&wq, VF_SEARCH_WHERE, 0, NULL, NULL, stream);       then wq.m rows pass
+ * `wq`, `columns`, `leaves`, `ops` and `set_values` are host memory; the pointers inside `columns`, d_bitmap and d_ids are device
+ * pointers on the index's device. */
+#define VF_SEARCH_WHERE 0x10000000   /* or'ed into nq of vf_index_search_device: `d_queries` is a vf_where_query; the count bits are 0 */
+typedef struct vf_where_column { const int64_t* keys; const uint32_t* valid; } vf_where_column;   /* device; valid NULL = every row has the field */
+typedef struct vf_where_leaf { int32_t kind, column; int64_t lo, hi; } vf_where_leaf;
+typedef struct vf_where_query {
+    int64_t n;                                   /* rows the columns were made for: must equal the handle's row count */
+    const vf_where_column* columns; int32_t n_columns;      /* host array of device pointers */
+    const vf_where_leaf* leaves;   int32_t n_leaves;        /* host */
+    const uint8_t* ops;            int32_t n_ops;           /* host, postfix */
+    const int64_t* set_values;     int64_t n_set_values;    /* host */
+    uint32_t* d_bitmap;                          /* device out, 2 * ceil(n / 64) words */
+    int64_t*  d_ids; int64_t ids_cap;            /* device out, or NULL: ids_cap >= n */
+    int64_t   m;                                 /* out: rows passing */
+    int32_t   tile_rows;                         /* 0 = 1024; a multiple of 64 in [64, 1024]: tests lower it */
+} vf_where_query;
+
 int vf_index_info(vf_index* idx, int64_t* n, int32_t* d, int32_t* dtype, int32_t* device_id);
 int vf_index_stats(vf_index* idx, vf_search_stats* out);
 /* tuning knobs, by name: every name, its default and its accepted values are the table in veritasfi_amd/csrc/vf_options.h (tests use

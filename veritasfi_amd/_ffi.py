@@ -130,6 +130,51 @@ def search_subsets_device(L, handle, d_queries_ptr, nq, k, d_list_ptrs, n_ids, l
     return L.vf_index_search_device(handle, ctypes.addressof(sq), int(nq) | VF_SEARCH_SUBSETS, k, d_out_ids_ptr, d_out_scores_ptr, stream)
 
 
+VF_SEARCH_WHERE = 0x10000000   # or'ed into nq of vf_index_search_device: `d_queries` is then a WhereQuery; the count bits are 0
+
+
+class WhereColumnPtr(ctypes.Structure):
+    """vf_where_column of include/veritasfi_hip.h: one field's int64 keys and its validity words (device pointers; valid NULL = every
+    row has the field)."""
+    _fields_ = [("keys", ctypes.c_void_p), ("valid", ctypes.c_void_p)]
+
+
+class WhereLeaf(ctypes.Structure):
+    """vf_where_leaf: kind 0 an inclusive key interval [lo, hi] (lo > hi passes nothing), kind 1 membership in the strictly ascending
+    run set_values[lo : lo + hi], kind 2 "the row lacks the field" -- the layout of ``where.LEAF_DTYPE``."""
+    _fields_ = [("kind", c_i32), ("column", c_i32), ("lo", c_i64), ("hi", c_i64)]
+
+
+class WhereQuery(ctypes.Structure):
+    """vf_where_query: a compiled filter (``where.WhereProgram``) and its outputs.  Host memory, as are ``columns``, ``leaves``, ``ops``
+    and ``set_values``; the pointers inside ``columns``, ``d_bitmap`` (2 * ceil(n / 64) uint32 words) and ``d_ids`` (int64, ids_cap >= n, or
+    NULL) are device pointers.  ``m`` is written by the call.  Limits: 64 leaves, 128 ops, stack depth 32, 16 columns, 65 536 set values."""
+    _fields_ = [("n", c_i64), ("columns", ctypes.POINTER(WhereColumnPtr)), ("n_columns", c_i32), ("leaves", ctypes.c_void_p), ("n_leaves", c_i32),
+                ("ops", ctypes.c_void_p), ("n_ops", c_i32), ("set_values", ctypes.c_void_p), ("n_set_values", c_i64),
+                ("d_bitmap", ctypes.c_void_p), ("d_ids", ctypes.c_void_p), ("ids_cap", c_i64), ("m", c_i64), ("tile_rows", c_i32)]
+
+
+def eval_where_device(L, handle, n, column_ptrs, leaves, ops, set_values, d_bitmap_ptr, d_ids_ptr, ids_cap, stream, tile_rows=0, flags=0,
+                      host_form=False):
+    """vf_index_search_device in its VF_SEARCH_WHERE form; returns (code, m).  column_ptrs: [(keys device pointer, valid device pointer
+    or None)]; leaves: a ``where.LEAF_DTYPE`` array; ops: uint8; set_values: int64 (host arrays).  ``flags`` is or'ed into nq and
+    ``host_form`` sends the call to vf_index_search: both exist for the tests of the refusals."""
+    import numpy as np
+    cols = (WhereColumnPtr * max(len(column_ptrs), 1))(*[WhereColumnPtr(int(k) if k else None, int(v) if v else None) for k, v in column_ptrs])
+    leaves = np.ascontiguousarray(leaves)
+    ops = np.ascontiguousarray(ops, dtype=np.uint8)
+    sets = np.ascontiguousarray(set_values, dtype=np.int64)
+    wq = WhereQuery(int(n), ctypes.cast(cols, ctypes.POINTER(WhereColumnPtr)), len(column_ptrs), leaves.ctypes.data if leaves.size else None,
+                    int(leaves.shape[0]), ops.ctypes.data if ops.size else None, int(ops.size), sets.ctypes.data if sets.size else None, int(sets.size),
+                    d_bitmap_ptr, d_ids_ptr, int(ids_cap), -1, int(tile_rows))
+    nq = VF_SEARCH_WHERE | int(flags)
+    if host_form:
+        rc = L.vf_index_search(handle, ctypes.addressof(wq), nq, 0, None, None)
+    else:
+        rc = L.vf_index_search_device(handle, ctypes.addressof(wq), nq, 0, None, None, stream)
+    return rc, int(wq.m)
+
+
 class EncoderConfig(ctypes.Structure):
     _fields_ = [
         ("vocab", c_i32), ("hidden", c_i32), ("layers", c_i32), ("heads", c_i32), ("ffn", c_i32), ("max_pos", c_i32),

@@ -1777,9 +1777,12 @@ static int subset_entry_host(vf_index* ix, const vf_subset_query* sq, int32_t nq
 static int subset_entry_device(vf_index* ix, const vf_subset_query* sq, int32_t nq, int32_t k, int64_t* d_out_ids, float* d_out_scores, void* stream);
 // ... and the form with a list per query (VF_SEARCH_SUBSETS, `queries` is a vf_subsets_query); both flags together are refused there
 static int subsets_entry(vf_index* ix, const vf_subsets_query* sq, int32_t nq_flags, int32_t k, int64_t* out_ids, float* out_scores, bool device, void* stream);
+// ... and a metadata filter evaluated into a bitmap and an id list (VF_SEARCH_WHERE, `queries` is a vf_where_query; the device form only)
+static int where_entry(vf_index* ix, vf_where_query* wq, int32_t nq_flags, bool device, void* stream);
 
 extern "C" int vf_index_search_device(vf_index* ix, const float* d_queries, int32_t nq, int32_t k, int64_t* d_ids,
                                       float* d_scores, void* stream) {
+    if (nq >= 0 && (nq & VF_SEARCH_WHERE)) return where_entry(ix, (vf_where_query*)d_queries, nq, true, stream);
     if (nq >= 0 && (nq & VF_SEARCH_SUBSETS)) return subsets_entry(ix, (const vf_subsets_query*)d_queries, nq, k, d_ids, d_scores, true, stream);
     if (nq >= 0 && (nq & VF_SEARCH_SUBSET)) return subset_entry_device(ix, (const vf_subset_query*)d_queries, nq & ~VF_SEARCH_SUBSET, k, d_ids, d_scores, stream);
     DeviceGuard restore_callers_device;
@@ -1808,6 +1811,7 @@ static int search_host_locked(vf_index* ix, const float* queries, int nq, int k,
 
 extern "C" int vf_index_search(vf_index* ix, const float* queries, int32_t nq, int32_t k, int64_t* out_ids,
                                float* out_scores) {
+    if (nq >= 0 && (nq & VF_SEARCH_WHERE)) return where_entry(ix, (vf_where_query*)queries, nq, false, nullptr);
     if (nq >= 0 && (nq & VF_SEARCH_SUBSETS)) return subsets_entry(ix, (const vf_subsets_query*)queries, nq, k, out_ids, out_scores, false, nullptr);
     if (nq >= 0 && (nq & VF_SEARCH_SUBSET)) return subset_entry_host(ix, (const vf_subset_query*)queries, nq & ~VF_SEARCH_SUBSET, k, out_ids, out_scores);
     DeviceGuard restore_callers_device;
@@ -2558,6 +2562,89 @@ static int subsets_entry(vf_index* ix, const vf_subsets_query* sq, int32_t nq_fl
     DeviceGuard restore_callers_device;
     std::lock_guard<std::mutex> g(ix->mu);
     return subsets_locked(ix, sq, nq, k, out_ids, out_scores, device, (hipStream_t)stream, who);
+}
+
+// ------------------------------------------------------------------------------------------------
+// A metadata filter evaluated on the device (round 24): vf_index_search_device with VF_SEARCH_WHERE in nq.  What turns a filter into a
+// row set used to be host dictionaries and an upload of 8 bytes per passing row; here the program of vf_where.h runs over int64 key
+// columns that live on the device and leaves the bitmap (the BM25 filter's layout) and the ascending id list (what VF_SEARCH_SUBSET
+// takes) where the two legs want them.  Everything is checked before any device work; the descriptor block, the tile counts and
+// their prefix are ONE lease of the small entry points' pool; three launches, one wait, at which m is read.
+// ------------------------------------------------------------------------------------------------
+static_assert(sizeof(vf_where_leaf) == sizeof(WhereLeaf) && sizeof(vf_where_column) == sizeof(WhereColumnPtr), "the public structs are the header's");
+// vf_where.hip is the one kernel TU this file calls that a link of the host side alone leaves out (tests/test_host_sanitized.py links
+// vf_kernels.o and vf_transformer.o): the reference is weak, and a library without the TU refuses the call instead of failing to link.
+namespace vf { hipError_t launch_where(const WhereArgs& a, hipStream_t s) __attribute__((weak)); }
+
+static std::string where_refusal(const WhereVerdict& v, const vf_where_query* wq) {
+    switch (v.verdict) {
+        case kWhereEmpty: return "an empty program (it needs at least one column, one leaf and one op)";
+        case kWhereBadOp: return "ops[" + std::to_string(v.at) + "] = " + std::to_string((int)wq->ops[v.at]) + " is neither one of the " + std::to_string(wq->n_leaves) + " leaves nor an operator";
+        case kWhereUnderflow: return "ops[" + std::to_string(v.at) + "] pops more than the stack holds";
+        case kWhereLeftover: return "the program leaves " + std::to_string(v.at) + " values on the stack, not one";
+        case kWhereBadLeaf: return "leaves[" + std::to_string(v.at) + "] has an unknown kind or names a column outside [0, " + std::to_string(wq->n_columns) + ")";
+        case kWhereBadSetRun: return "leaves[" + std::to_string(v.at) + "]: its run lies outside the " + std::to_string(wq->n_set_values) + " set values";
+        case kWhereSetNotAscending: return "set_values[" + std::to_string(v.at) + "] is not above its predecessor (a set leaf's run must be strictly ascending)";
+        default: return "bad program";
+    }
+}
+
+static int where_entry(vf_index* ix, vf_where_query* wq, int32_t nq_flags, bool device, void* stream) {
+    static const char* who = "vf_index_search_device (VF_SEARCH_WHERE)";
+    if (!device) return fail(VF_EINVAL, "vf_index_search (VF_SEARCH_WHERE): a filter is evaluated by the device form, vf_index_search_device");
+    if (nq_flags & (VF_SEARCH_SUBSET | VF_SEARCH_SUBSETS)) return fail(VF_EINVAL, std::string(who) + ": VF_SEARCH_WHERE together with VF_SEARCH_SUBSET / VF_SEARCH_SUBSETS (a call evaluates a filter or searches, not both)");
+    if (nq_flags & ~VF_SEARCH_WHERE) return fail(VF_EINVAL, std::string(who) + ": the count bits of nq must be 0");
+    if (!wq) return fail(VF_EINVAL, std::string(who) + ": null vf_where_query");
+    if (!ix) return fail(VF_EINVAL, std::string(who) + ": null handle");
+    DeviceGuard restore_callers_device;
+    std::lock_guard<std::mutex> g(ix->mu);
+    if (ix->damaged) return fail(VF_EHIP, std::string(who) + ": " + kDamagedMsg);
+    if (!ix->shards.empty()) return fail(VF_EUNSUPPORTED, std::string(who) + ": a group handle evaluates no filter (evaluate it on the host: WhereProgram.evaluate_numpy)");
+    if (wq->n != ix->n) return fail(VF_EINVAL, std::string(who) + ": n = " + std::to_string(wq->n) + " but the index holds " + std::to_string(ix->n) + " rows (columns made before an append or a removal are stale)");
+    const int tile_rows = wq->tile_rows == 0 ? kWhereTileRows : wq->tile_rows;
+    if (!where_tile_rows_ok(tile_rows)) return fail(VF_EINVAL, std::string(who) + ": tile_rows = " + std::to_string(wq->tile_rows) + " must be 0 or a multiple of 64 in [64, 1024]");
+    if (wq->n_columns < 0 || wq->n_leaves < 0 || wq->n_ops < 0 || wq->n_set_values < 0) return fail(VF_EINVAL, std::string(who) + ": a negative count");
+    if ((wq->n_columns > 0 && !wq->columns) || (wq->n_leaves > 0 && !wq->leaves) || (wq->n_ops > 0 && !wq->ops) || (wq->n_set_values > 0 && !wq->set_values))
+        return fail(VF_EINVAL, std::string(who) + ": null columns / leaves / ops / set_values");
+    const WhereVerdict v = where_validate((const WhereLeaf*)wq->leaves, wq->n_leaves, wq->ops, wq->n_ops, wq->n_columns, wq->set_values, wq->n_set_values);
+    if (v.verdict == kWhereOverLimits) {
+        static const char* what[] = {"leaves", "ops", "columns", "set values", "stack depth"};
+        static const long long cap[] = {kWhereMaxLeaves, kWhereMaxOps, kWhereMaxColumns, kWhereMaxSetValues, kWhereMaxDepth};
+        const std::string got = v.limit == kWhereLimitDepth ? "ops[" + std::to_string(v.at) + "] takes the stack past" : std::to_string(v.at) + " " + what[v.limit] + ", above";
+        return fail(VF_EUNSUPPORTED, std::string(who) + ": " + got + " the limit of " + std::to_string(cap[v.limit]) + (v.limit == kWhereLimitDepth ? " values" : "") + " (evaluate it on the host: WhereProgram.evaluate_numpy)");
+    }
+    if (v.verdict != kWhereOk) return fail(VF_EINVAL, std::string(who) + ": " + where_refusal(v, wq));
+    for (int c = 0; c < wq->n_columns; ++c)
+        if (!wq->columns[c].keys) return fail(VF_EINVAL, std::string(who) + ": columns[" + std::to_string(c) + "]: null keys");
+    if (ix->n > 0 && !wq->d_bitmap) return fail(VF_EINVAL, std::string(who) + ": null d_bitmap");
+    if (wq->d_ids && wq->ids_cap < ix->n) return fail(VF_EINVAL, std::string(who) + ": ids_cap = " + std::to_string(wq->ids_cap) + " is below the index's " + std::to_string(ix->n) + " rows");
+    if (ix->n == 0) { wq->m = 0; return VF_OK; }
+    if (!launch_where) return fail(VF_EINTERNAL, std::string(who) + ": this library was linked without vf_where.hip");
+    hipStream_t st = (hipStream_t)stream;
+    const long long tiles = where_tiles(ix->n, tile_rows);
+    const WhereBlock blk = where_block(wq->n_columns, wq->n_leaves, wq->n_ops, wq->n_set_values);
+    VF_HIP(hipSetDevice(ix->device));
+    Lease ws;
+    VF_TRY(ws.acquire(ix->device, Lease::padded((size_t)blk.bytes) + Lease::padded((size_t)tiles * 4) + Lease::padded((size_t)tiles * 8) + Lease::padded(8)));
+    char* d_blk = ws.take<char>((size_t)blk.bytes);
+    u32* d_counts = ws.take<u32>((size_t)tiles); long long* d_prefix = ws.take<long long>((size_t)tiles); long long* d_m = ws.take<long long>(1);
+    std::vector<char> block((size_t)blk.bytes, 0);
+    memcpy(block.data() + blk.columns_at, wq->columns, (size_t)wq->n_columns * sizeof(WhereColumnPtr));
+    memcpy(block.data() + blk.leaves_at, wq->leaves, (size_t)wq->n_leaves * sizeof(WhereLeaf));
+    memcpy(block.data() + blk.ops_at, wq->ops, (size_t)wq->n_ops);
+    if (wq->n_set_values > 0) memcpy(block.data() + blk.sets_at, wq->set_values, (size_t)wq->n_set_values * 8);
+    VF_HIP(hipMemcpyAsync(d_blk, block.data(), block.size(), hipMemcpyHostToDevice, st));   // (`block` outlives the call's one wait)
+    WhereArgs a{};
+    a.columns = (const WhereColumnPtr*)(d_blk + blk.columns_at); a.leaves = (const WhereLeaf*)(d_blk + blk.leaves_at);
+    a.ops = (const uint8_t*)(d_blk + blk.ops_at); a.n_ops = wq->n_ops; a.sets = (const int64_t*)(d_blk + blk.sets_at);
+    a.n = ix->n; a.tile_rows = tile_rows; a.bitmap = wq->d_bitmap; a.tile_counts = d_counts; a.tile_prefix = d_prefix; a.m_out = d_m;
+    a.ids = (long long*)wq->d_ids; a.id_offset = ix->id_offset;
+    VF_HIP(launch_where(a, st));
+    long long m = 0;
+    VF_HIP(hipMemcpyAsync(&m, d_m, 8, hipMemcpyDeviceToHost, st));
+    VF_HIP(hipStreamSynchronize(st));   // the one wait of the call: the bitmap and the ids are final and m is here
+    wq->m = m;
+    return VF_OK;
 }
 
 extern "C" int vf_merge_topk_device(const int64_t* d_ids_parts, const float* d_score_parts, int32_t nparts, int32_t nq,

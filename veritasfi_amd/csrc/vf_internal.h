@@ -13,6 +13,7 @@
 #include "vf_compact.h"       // the plan of a removal's row compaction
 #include "vf_subset.h"        // the plan of a search over a chosen subset of rows
 #include "vf_subset_multi.h"  // ... and of a batch whose queries each bring their own list
+#include "vf_where.h"         // a metadata filter as a program over key columns: its checks, interpreter and output geometry
 
 namespace vf {
 
@@ -214,6 +215,17 @@ hipError_t launch_subset_check_m(const SubmList* lists, int n_lists, long long l
 // (-1, -FLT_MAX); nothing is written when *first_bad != ~0 (first_bad may be null)
 hipError_t launch_subset_ids_m(const long long* pos, const float* sc, int nb, int k, const SubmQuery* qd, const u64* first_bad,
                                long long* out_ids, float* out_scores, hipStream_t s);
+// k_where_eval, k_where_scan, k_where_ids (vf_where.hip; VF_SEARCH_WHERE; the program and the geometry: vf_where.h): the filter's bitmap,
+// its tile counts and their prefix, the number of passing rows and -- when `ids` is not null -- their ids, ascending.  Everything is on
+// the device; the caller has validated the program (where_validate) and sized bitmap [where_bitmap_words(n)], tile_counts and tile_prefix
+// [where_tiles(n, tile_rows)] and ids [>= n].
+struct WhereArgs {
+    const WhereColumnPtr* columns; const WhereLeaf* leaves; const uint8_t* ops; int n_ops; const int64_t* sets;
+    long long n; int tile_rows;
+    u32* bitmap; u32* tile_counts; long long* tile_prefix; long long* m_out;
+    long long* ids; long long id_offset;
+};
+hipError_t launch_where(const WhereArgs& a, hipStream_t s);
 hipError_t launch_sort_rows(const float* scores, long long score_stride, int nq, int n, int k,
                             long long id_base, long long* out_ids, float* out_scores, int out_stride,
                             hipStream_t s);

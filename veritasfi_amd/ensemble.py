@@ -25,6 +25,7 @@ from typing import Dict, List
 import numpy as np
 
 from . import stages
+from . import where as vf_where
 from .faiss_retriever import FaissRetriever
 from .similarity import _embed_all, compute_similarity, compute_similarity_mtx
 
@@ -100,14 +101,20 @@ class PreparedWhere:
     def _prepare(self) -> None:
         r = self._retriever
         self._release()
-        self.passing = r.rows_where(self.where)
-        self.allow = set(self.passing.tolist())
+        evaluated = None
+        if vf_where.has_operators(self.where):   # the operator grammar: evaluated on the device where the index offers it
+            self.passing, self.allow, evaluated = r._eval_where(self.where)
+        else:
+            self.passing = r.rows_where(self.where)
+            self.allow = set(self.passing.tolist())
         self.dense = self.bm25 = self.passing
         self._epoch = r._epoch
         if self.passing.size == 0:      # invoke returns [] before any leg is asked
             return
         ix = getattr(r.faiss_retriever, "index", None)
-        if r.faiss_k > 0 and hasattr(ix, "row_subset") and getattr(ix, "device_ids", None) is None:
+        if evaluated is not None:       # the evaluation left the ids on the device: nothing to upload
+            self.dense = evaluated
+        elif r.faiss_k > 0 and hasattr(ix, "row_subset") and getattr(ix, "device_ids", None) is None:
             self.dense = ix.row_subset(self.passing)
         bm = r.bm25_retriever
         if r.bm25_k > 0 and hasattr(bm, "prepare_subset"):
@@ -210,6 +217,7 @@ class EnsembleRetriever:
     def _build_maps(self) -> None:
         self.docid2idx, self._bundle_rows, self._title_rows = {}, {}, {}
         self._field_rows = {}   # rows_where's per-field dictionaries: built on first use, dropped whenever the corpus changes
+        self._where_columns = {}   # ... and the operator grammar's typed key columns (where.WhereColumn), under the same rule
         for row, md in enumerate(self.chunk_metadata):
             self.docid2idx[md["doc_id"]] = row
             b = md.get("bundle_id", None)
@@ -287,6 +295,7 @@ class EnsembleRetriever:
         self.chunk_metadata = list(self.chunk_metadata) + metadatas
         self.num_chunk = len(self.chunk_metadata)
         self._field_rows = {}
+        self._where_columns = {}
         if self._documents is not None:
             self._documents = list(self._documents) + texts
         for row, md in enumerate(metadatas, start=first):
@@ -339,9 +348,14 @@ class EnsembleRetriever:
         """Sorted row numbers (int64) of the chunks whose metadata passes ``where``: a dict ``field -> value``, or ``field -> a
         collection of values`` (list, tuple, set, frozenset: any of them passes); several fields must all pass.  A chunk without the
         field passes only a filter that lists ``None``.  Served from one dictionary ``value -> rows`` per field, built on the first
-        use of that field and dropped by ``add_documents`` / ``remove_documents``."""
+        use of that field and dropped by ``add_documents`` / ``remove_documents``.
+        A ``where`` with a ``$`` key anywhere speaks Chroma's operator grammar instead (``$eq $ne $gt $gte $lt $lte $in $nin $and $or``:
+        veritasfi_amd/where.py has the semantics): the rows are those for which ``where.matches(metadata, where)`` holds, found by a
+        compiled program over typed key columns -- on the device when the dense index offers ``eval_where``, else in NumPy."""
         if not isinstance(where, dict):
             raise TypeError("rows_where: `where` is a dict field -> value, or field -> a collection of values")
+        if vf_where.has_operators(where):
+            return self._eval_where(where)[0]
         rows = None
         for field, want in where.items():
             index = self._field_rows.get(field)
@@ -358,6 +372,27 @@ class EnsembleRetriever:
             hit = np.asarray(hit, dtype=np.int64)
             rows = hit if rows is None else np.intersect1d(rows, hit, assume_unique=True)
         return np.arange(self.num_chunk, dtype=np.int64) if rows is None else rows
+
+    def _where_column(self, field):
+        col = self._where_columns.get(field)
+        if col is None:
+            col = self._where_columns[field] = vf_where.build_column([md.get(field) for md in self.chunk_metadata], field)
+        return col
+
+    def _eval_where(self, where):
+        """An operator filter's (passing rows, their ``RowMask``, the device-resident ``RowSubset`` or None).  The kind check is the
+        columns' construction, so every route raises it alike.  The device evaluates when the dense retriever's index is a
+        single-device handle with ``eval_where`` over exactly these chunks and the program fits its limits; NumPy otherwise."""
+        columns = {f: self._where_column(f) for f in vf_where.fields_of(where)}
+        program = vf_where.compile_where(where, columns, n=self.num_chunk)
+        ix = getattr(self.faiss_retriever, "index", None)
+        if (program.fits_device and hasattr(ix, "eval_where") and getattr(ix, "device_ids", None) is None
+                and getattr(ix, "n", None) == self.num_chunk):
+            subset, mask = ix.eval_where(program, columns)
+            offset = int(getattr(ix, "id_offset", 0))
+            return (subset.ids - offset if offset else subset.ids), mask, subset
+        mask = program.evaluate_numpy(columns, self.num_chunk)
+        return np.flatnonzero(mask).astype(np.int64), vf_where.RowMask(mask), None
 
     def prepare_where(self, where) -> PreparedWhere:
         """``where`` (``rows_where``'s argument) prepared once for many ``invoke(..., where=<the returned object>)`` calls: the passing
@@ -440,6 +475,9 @@ class EnsembleRetriever:
         PreparedWhere's device-resident filters."""
         if isinstance(where, PreparedWhere):
             return where._current(self)
+        if isinstance(where, dict) and vf_where.has_operators(where):
+            passing, allow, dense = self._eval_where(where)   # the dense leg takes the ids where the evaluation left them
+            return passing, allow, passing if dense is None else dense, passing
         passing = None if where is None else self.rows_where(where)
         allow = None if passing is None else set(passing.tolist())
         return passing, allow, passing, passing
@@ -591,8 +629,14 @@ class EnsembleRetriever:
     def _where_key(where: dict):
         """Dicts of equal content share one preparation: the key of a dict's content, or of the object itself where a value cannot
         be hashed."""
-        def frozen(v):
-            return (type(v).__name__, frozenset(v)) if isinstance(v, (set, frozenset)) else (type(v).__name__, tuple(v)) if isinstance(v, (list, tuple)) else v
+        def frozen(v, deep=False):   # deep: inside an operator dict or a list, where 1 and True are different filters
+            if isinstance(v, dict):
+                return ("dict", frozenset((f, frozen(x, True)) for f, x in v.items()))
+            if isinstance(v, (set, frozenset)):
+                return (type(v).__name__, frozenset(frozen(x, deep) for x in v))
+            if isinstance(v, (list, tuple)):
+                return (type(v).__name__, tuple(frozen(x, deep or isinstance(x, dict)) for x in v))
+            return (type(v).__name__, v) if deep else v
         try:
             key = frozenset((f, frozen(v)) for f, v in where.items())
             hash(key)

@@ -8,6 +8,7 @@ paths.  PyTorch is plumbing here: device memory and streams only.
 from __future__ import annotations
 
 import ctypes
+import threading
 
 import numpy as np
 
@@ -72,6 +73,14 @@ class RowSubset:
         self.device_id = int(device_id)
         self.tensor = torch.from_numpy(ids).to(f"cuda:{self.device_id}")
 
+    @classmethod
+    def adopt(cls, tensor, ids: np.ndarray, device_id: int) -> "RowSubset":
+        """A RowSubset around ids that are ALREADY on the device (``DenseIndex.eval_where`` leaves them there): ``tensor`` (int64, CUDA,
+        strictly ascending global ids) and its host copy ``ids``; nothing is uploaded."""
+        rs = cls.__new__(cls)
+        rs.ids, rs.device_id, rs.tensor = ids, int(device_id), tensor
+        return rs
+
     def __len__(self) -> int:
         return int(self.ids.size)
 
@@ -131,6 +140,8 @@ def _dev_array(device_ids):
 
 
 class DenseIndex:
+    _where_ids = None   # eval_where's n-sized id scratch (one per index, made on first use)
+
     def __init__(self, rows, device_id: int = 0, id_offset: int = 0, device_ids=None):
         """rows: [n, d] float32 / float16 ndarray (copied to HBM) or a CUDA torch tensor (borrowed).
         FP8: a torch.float8_e4m3fn tensor (CPU or CUDA), or a uint8 ndarray / tensor of OCP e4m3 codes passed with
@@ -423,6 +434,43 @@ class DenseIndex:
         if self.device_ids is not None:
             raise ValueError("row_subset: a sharded handle takes id lists (search(subset=ids)), not a device-resident subset")
         return RowSubset(subset_ids(ids_or_mask, self.n, self.id_offset), self.device_id)
+
+    def eval_where(self, program, columns, tile_rows: int = 0):
+        """A compiled metadata filter (``where.compile_where``) evaluated on the index's device: ``(RowSubset, RowMask)`` of the passing
+        rows.  ``columns``: field -> ``where.WhereColumn``, made for this index's rows as they are NOW (after ``add`` / ``remove`` build
+        them again: stale ones are refused).  Each column's keys and validity words go to the device on first use and stay on the
+        column; the id list is written into ONE n-sized int64 scratch tensor this index keeps (calls take turns on it) and its first
+        m entries are copied out for the ``RowSubset``, which therefore costs no upload.  One library call (``vf_index_search_device``
+        with ``VF_SEARCH_WHERE``).  Single-device handles; a program over the device's limits (``program.fits_device``) raises ValueError:
+        both are served by ``program.evaluate_numpy(columns)``."""
+        import torch
+        from . import where as vf_where
+        if self.device_ids is not None:
+            raise ValueError("eval_where: a sharded handle evaluates no filter on the device; use the numpy route (WhereProgram.evaluate_numpy)")
+        if not program.fits_device:
+            raise ValueError("eval_where: the program exceeds the device evaluator's limits; use the numpy route (WhereProgram.evaluate_numpy)")
+        dev = torch.device(f"cuda:{self.device_id}")
+        ptrs = []
+        for f in program.fields:
+            col = columns[f]
+            held = col._device.get(self.device_id)
+            if held is None:
+                keys = torch.from_numpy(col.keys).to(dev)
+                valid = None if col.valid is None else torch.from_numpy(col.valid_words().view(np.int32)).to(dev)
+                held = col._device[self.device_id] = (keys, valid)
+            ptrs.append((held[0].data_ptr(), None if held[1] is None else held[1].data_ptr()))
+        n = int(program.n)
+        words = torch.empty(2 * ((n + 63) // 64), dtype=torch.int32, device=dev)
+        with self.__dict__.setdefault("_where_lock", threading.Lock()):   # (atomic: every constructor is served without naming it)
+            if self._where_ids is None or int(self._where_ids.shape[0]) < max(n, 1):
+                self._where_ids = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+            scratch = self._where_ids
+            rc, m = _ffi.eval_where_device(_ffi.lib(), self._h, n, ptrs, program.leaves, program.ops, program.set_values, words.data_ptr(),
+                                           scratch.data_ptr(), int(scratch.shape[0]), torch.cuda.current_stream(dev).cuda_stream, tile_rows)
+            _ffi.check(rc, "vf_index_search_device (where)")
+            ids = scratch[:m].clone()
+        mask = vf_where.RowMask.from_words(words.cpu().numpy().view(np.uint32), n, m)
+        return RowSubset.adopt(ids, ids.cpu().numpy(), self.device_id), mask
 
     def _search_subsets(self, q: np.ndarray, k: int, subsets, subset=None):
         if self.device_ids is not None:
